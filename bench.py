@@ -3,7 +3,7 @@
 
 Metric (BASELINE.json): banded pair-HMM DP cells/s (whole job), plus reads/s.
 
-    python bench.py --gpus N --steps K --warmup W [--workload northstar|c2|anchor|c3]
+    python bench.py --gpus N --steps K --warmup W [--workload northstar|c2|anchor|c3] [--full] [--dump-outputs DIR]
 
 Resident workloads (northstar -- the default --, c2, anchor): a "step" is one pass of the hot path over one synthetic
 batch whose inputs are already resident in HBM: npr_batch_run (forward + backward + posterior extraction of every read)
@@ -21,12 +21,21 @@ analyses.utils.realignSamFile runs): every rank maps the SAM + FASTA, parses the
 keeps two batches in flight (stage = band planning + upload, DP, finish = MEA chain + cigar) and writes its block of the
 realigned SAM at its offset of the one output file; the per-read results are gathered to rank 0 (RCCL) inside the timed
 region (utils.py:557-609).  `--resident-arrays` runs the same pipeline from arrays already in host memory (round 2's job).
-value = cells of the whole set / that time; reads_per_s likewise.  The default run (any N) carries this job as an `also`
-entry, so that a --gpus 1/2/4/8 series measures the strong-scaling target next to the weak-scaling headline.
+value = cells of the whole set / that time; reads_per_s likewise.  The default workload with --full (any N) carries this job as
+an `also` entry, so that a --gpus 1/2/4/8 series measures the strong-scaling target next to the weak-scaling headline.
 
 `--workload em` is the Baum-Welch E-step (npr_batch_expectations: what the trainer runs 3 x 100 times per model,
 utils.py:509-523) over one resident batch in the trainer's own band (anchors, splitMatrixBiggerThanThis 300, utils.py:511).  The default
-run at N = 1 carries it as an `also` entry too (seven timed steps, after the reference's own band and the rescore mode).
+run at N = 1 with --full carries it as an `also` entry too (seven timed steps, after the reference's own band and the rescore mode).
+
+A plain run does only what its headline line needs: it builds the inputs, warms up, times the --steps steps and prints the
+line.  `--full` adds everything else the benchmark measures or checks, each in runs of its own: the from-cold rate, the
+CPU oracle baseline and its cigar parity probe, the secondary (`also`) lines named above, the N = 1 point of the strong-
+scaling job and the E-step's CPU baseline, and the results gather of a multi-rank resident run.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step, as a caller of that path receives it, to
+DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed, seeded sample of the reads where the whole would not fit).  The
+inputs are seeded, so two builds can be compared output for output.
 
 Rank 0 prints ONE JSON line.
 """
@@ -287,6 +296,39 @@ def spread(ms):
     return {"n": int(v.size), "median_ms": float(np.median(v)), "min_ms": float(v.min()), "max_ms": float(v.max())}
 
 
+DUMP_BYTES = 64 << 20     # --dump-outputs: the most it writes
+DUMP_CIGAR_READS = 512    # reads whose whole cigar it writes (a seeded sample: all of them would be gigabytes on the north-star batch)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 kept, anything else as float64 (the integer fields are exact there)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
+def per_read_outputs(res, ops_off=None, ops=None):
+    """What a caller of the realign path receives: the per-read results (npr_read_result) of every read -- of a seeded sample of
+    them when they would not fit in DUMP_BYTES / 2 -- and the cigars, (op, length) per row, of DUMP_CIGAR_READS seeded reads."""
+    n = len(res)
+    rows = max(1, (DUMP_BYTES // 2) // (8 * len(res.dtype.names)))
+    pick = np.arange(n) if n <= rows else np.sort(np.random.default_rng(12345).choice(n, size=rows, replace=False))
+    out = {"result_" + k: res[k][pick] for k in res.dtype.names}
+    if n > rows:
+        out["result_read_index"] = pick
+    if ops_off is not None:
+        reads = np.sort(np.random.default_rng(54321).choice(n, size=min(n, DUMP_CIGAR_READS), replace=False))
+        lens = ops_off[reads + 1] - ops_off[reads]
+        out["cigar_read_index"] = reads
+        out["cigar_off"] = np.concatenate([[0], np.cumsum(lens)])
+        out["cigar_ops"] = np.concatenate([ops[ops_off[i]:ops_off[i + 1]] for i in reads]).astype(np.float32)  # (lengths < 2^24: exact)
+    return out
+
+
 def timed_resident(ctx, h, w, W, steps, warmup, sync, options=None):
     """Stages one batch and times `steps` passes of run + finish.  Returns everything the line needs."""
     params = make_params(W)
@@ -365,14 +407,21 @@ def main():
                     "wavefront slot (rounds 1-2: 12288; the launch lasts as long as its longest chain of reads, which two per slot leave "
                     "10 %% above the mean), 1000 c2, 8192 anchor, 6144 em) or in the whole set (c3; default 50000)")
     ap.add_argument("--resident-arrays", action="store_true", help="c3: the job from arrays in host memory instead of from files")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary lines of the default run (the reference's own band; the "
-                    "files -> file strong-scaling job of configs[2]/[3])")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline line (from-cold rate, CPU "
+                    "baselines and the parity probe, the secondary lines, the N = 1 point of the strong-scaling job), in runs of their own")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the timed path computed in its last step to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the secondary lines of the default run (the reference's own "
+                    "band; the files -> file strong-scaling job of configs[2]/[3])")
     ap.add_argument("--ab", default="", help="NAME=a,b: a paired A/B inside ONE process on ONE box -- the steps alternate between the two values of a context "
                     "option (nanopore_amd._lib.OPTIONS, e.g. tile_rs=0,2; resident workloads: one staged batch per value) or of the job's NPR_JOB_OVERLAP "
                     "(job_overlap=1,2 with --workload c3); prints per-value median / min - max and the paired differences with their spread")
     ap.add_argument("--ab-pairs", type=int, default=7)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.ab and args.dump_outputs:
+        ap.error("--dump-outputs writes the outputs of a timed path; --ab times two")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # a plain `python bench.py --gpus N ...`: start the N ranks ourselves (one process per GPU, the launch line the
@@ -426,12 +475,12 @@ def main():
     if args.ab:
         out = ab_run(env)
     elif args.workload == "c3":
-        out = c3_job(env, args.reads or 50000, args.steps, args.warmup, from_files=not args.resident_arrays)
+        out = c3_job(env, args.reads or 50000, args.steps, args.warmup, from_files=not args.resident_arrays, dump=args.dump_outputs)
     elif args.workload == "em":
-        out = em_step(env)
+        out = em_step(env, dump=args.dump_outputs)
     else:
         out = resident(env)
-        if args.workload == "northstar" and not args.no_also:
+        if args.workload == "northstar" and args.full and not args.no_also:
             # collective: the strong-scaling job of configs[2]/[3], files -> file, at this N
             # (NPR_BENCH_ALSO_READS: a smaller set for the shared-GPU test hook, where two ranks' scratch must fit one device)
             entry = c3_job(env, int(os.environ.get("NPR_BENCH_ALSO_READS", 50000)), ALSO_STEPS, 1, from_files=True)
@@ -529,9 +578,12 @@ def resident(env):
     else:
         total_cells, total_reads = cells, n_reads
 
+    if rank == 0 and args.dump_outputs:
+        off, ops = batch.ops()
+        dump_outputs(args.dump_outputs, per_read_outputs(res, off, ops))
     # the one gather the path has (summary to rank 0), outside the timed steps
     gather_ms = None
-    if dist is not None:
+    if dist is not None and args.full:
         from nanopore_amd import dist as npd
         import torch
         off, ops = batch.ops()
@@ -575,10 +627,10 @@ def resident(env):
         "finish_ms": r["finish_ms"],
         "gather_ms": gather_ms,
     }
-    if world == 1:
+    if world == 1 and args.full:
         out["from_cold"] = from_cold(ctx, w, r["params"], cells)
         out["from_cold"]["first_create_s"] = r["first_create_s"]
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         cb, ro = cpu_baseline(h, w, W, res["cells"])
         out["cpu_baseline"] = cb
         # the sample doubles as an end-of-run parity probe: GPU cigars vs the fp64 oracle's
@@ -590,7 +642,7 @@ def resident(env):
         if W < 0:  # rescore mode: the cigars are the guides'; what is computed is the score
             out["max_score_difference_to_builds_own_fp64_oracle"] = float(np.max(np.abs(res["score"][:k] - np.asarray(ro["score"])[:k]))) if k else 0.0
     batch.close()
-    if world == 1 and args.workload == "northstar" and not args.no_also:
+    if world == 1 and args.workload == "northstar" and args.full and not args.no_also:
         # the band the drop-in path actually runs (realignSamFile: the reference's own call parameters), driver-visible
         h2, w2, W2, label2 = build_workload("anchor", 8192, 0)
         r2 = timed_resident(ctx, h2, w2, W2, ALSO_STEPS, 1, sync)
@@ -647,7 +699,7 @@ def c3_inputs(n_reads, rank, dist, from_files):
     return h, w, 200, tmp, sam, fa
 
 
-def c3_job(env, n_reads, steps, warmup, from_files):
+def c3_job(env, n_reads, steps, warmup, from_files, dump=""):
     import shutil
     from nanopore_amd import job
     ctx, rank, world, dist, coll_dev, sync, allreduce, gpu = (env[k] for k in ("ctx", "rank", "world", "dist", "coll_dev", "sync", "allreduce", "gpu"))
@@ -689,7 +741,7 @@ def c3_job(env, n_reads, steps, warmup, from_files):
     if dist is not None:
         elapsed = allreduce([elapsed], dist.ReduceOp.MAX)[0]
         total_cells = int(allreduce([cells_rank], dist.ReduceOp.SUM)[0])
-        if from_files:
+        if from_files and env["args"].full:
             # the SAME job on rank 0 alone (the other ranks wait at the barrier), with the host threads a one-rank launch has:
             # the N = 1 point of the strong-scaling series measured inside the N-rank run, on the same box, so that
             # `speedup_vs_n1` does not depend on a second invocation
@@ -724,6 +776,8 @@ def c3_job(env, n_reads, steps, warmup, from_files):
             sys.stderr.write("[job trace] %-7s %8.1f .. %8.1f ms\n" % (ev[0], (ev[1] - base) * 1e3, (ev[2] - base) * 1e3))
     sam_bytes = os.path.getsize(out_sam)
     res = last["results"]
+    if dump:
+        dump_outputs(dump, per_read_outputs(res))
     ok = int((res["status"] == 0).sum())
     in_bytes = (os.path.getsize(sam) + os.path.getsize(fa)) if from_files else 0
     shutil.rmtree(tmp, ignore_errors=True)
@@ -769,7 +823,7 @@ def c3_job(env, n_reads, steps, warmup, from_files):
     }
 
 
-def em_step(env, steps=None, warmup=None, cpu=True, reads=None):
+def em_step(env, steps=None, warmup=None, cpu=True, reads=None, dump=""):
     """Baum-Welch E-step over one resident batch in the trainer's band: a step = npr_batch_expectations (forward with all five
     states kept, backward with the expected transition / emission counts accumulated, one reduction per model slot)."""
     args, ctx, rank, world, dist, sync, allreduce = (env[k] for k in ("args", "ctx", "rank", "world", "dist", "sync", "allreduce"))
@@ -828,7 +882,9 @@ def em_step(env, steps=None, warmup=None, cpu=True, reads=None):
                      "note": "kernel_ms = HIP-event time of ALL E-step launches of the batch (one per kernel class, concurrent)"},
         "loglik": float(ll[0]),
     }
-    if world == 1 and cpu and not args.no_cpu_baseline:
+    if dump:
+        dump_outputs(dump, {"expected_transitions": T, "expected_emissions": E, "loglik": ll})
+    if world == 1 and cpu and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = em_cpu_baseline(h, w, P)
     b.close()
     return out

@@ -6,8 +6,11 @@ indel / substitution statistics the shipped model (nanopore/mappers/blasr_hmm_0.
 guide alignment handed to the realigner is the true generating path with every indel block slid by up to
 +-`jitter` columns along the neighbouring match runs, so the realigner has real work to do.
 
-Everything is vectorised over reads (numpy); no Python loop per base.
+Everything is vectorised over reads (numpy; the error channel's walk is C, nanopore_amd/csrc/npr_synth.c); no Python loop per base.
 """
+import ctypes as C
+import os
+
 import numpy as np
 
 OP_M, OP_I, OP_D = 0, 1, 2
@@ -19,10 +22,25 @@ def random_reference(rng, length, gc=0.5):
     return rng.choice(4, size=length, p=p).astype(np.uint8)
 
 
-def _sample_rows(rng, cdf_rows, idx):
-    """Draw one category per element of idx from the row cdf_rows[idx]."""
-    u = rng.random(len(idx))
-    return (u[:, None] >= cdf_rows[idx]).sum(axis=1).astype(np.int64)
+_SYNTH_LIB = None
+
+
+def _synth_lib():
+    """libnprsynth.so (nanopore_amd/csrc/npr_synth.c, built with the package by __graft_entry__.build()): the walk of error_channel."""
+    global _SYNTH_LIB
+    if _SYNTH_LIB is None:
+        L = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libnprsynth.so"))
+        p = C.c_void_p
+        L.npr_synth_channel.restype = C.c_int64
+        L.npr_synth_channel.argtypes = [p, p, p, p, C.c_int64, p, p, p, C.c_int64, C.c_int64, p, p, p, p, p, p, p]
+        L.npr_synth_gather.restype = None
+        L.npr_synth_gather.argtypes = [p, p, C.c_int64, C.c_int64, p, p, p, p, p]
+        _SYNTH_LIB = L
+    return _SYNTH_LIB
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
 
 
 def error_channel(rng, ref_codes, ref_off, T, E):
@@ -31,57 +49,43 @@ def error_channel(rng, ref_codes, ref_off, T, E):
     ref_codes: uint8 codes (0..3) of all slices concatenated; ref_off: int64 offsets [n+1].
     Returns (read_codes, read_off, ops_flat, ops_off): ops are per-column codes (0 M, 1 I, 2 D) of the TRUE
     global alignment, concatenated per read.
+
+    The reads walk the chain together, one column per step: at every step each active read draws its next state from
+    `rng` (in read order), then the reads that took a match draw its base, then those that took an insert draw theirs
+    (npr_synth.c walks them in exactly this order).
     """
     T = np.asarray(T, dtype=np.float64).reshape(5, 5)
     E = np.asarray(E, dtype=np.float64).reshape(5, 4, 4)
-    Tc = np.cumsum(T / T.sum(axis=1, keepdims=True), axis=1)[:, :4]
+    Tc = np.ascontiguousarray(np.cumsum(T / T.sum(axis=1, keepdims=True), axis=1)[:, :4])
     match_given_x = E[0] / E[0].sum(axis=1, keepdims=True)
-    Mc = np.cumsum(match_given_x, axis=1)[:, :3]
+    Mc = np.ascontiguousarray(np.cumsum(match_given_x, axis=1)[:, :3])
     ins = E[2].sum(axis=0)
-    Ic = np.cumsum(ins / ins.sum())[:3][None, :]
+    Ic = np.ascontiguousarray(np.cumsum(ins / ins.sum())[:3])
+    ref_codes = np.ascontiguousarray(ref_codes, dtype=np.uint8)
+    ref_off = np.ascontiguousarray(ref_off, dtype=np.int64)
     n = len(ref_off) - 1
-    lens = (ref_off[1:] - ref_off[:-1]).astype(np.int64)
-    cap = int(lens.max() * 1.6) + 64
-    reads = np.zeros((n, cap), dtype=np.uint8)
-    ops = np.zeros((n, 2 * cap), dtype=np.uint8)
-    rlen = np.zeros(n, dtype=np.int64)
-    nops = np.zeros(n, dtype=np.int64)
-    xpos = np.zeros(n, dtype=np.int64)
-    state = np.zeros(n, dtype=np.int64)
-    active = np.nonzero(lens > 0)[0]
-    while len(active):
-        s = _sample_rows(rng, Tc, state[active])
-        state[active] = s
-        is_m, is_x, is_y = s == 0, (s == 1) | (s == 3), (s == 2) | (s == 4)
-        # reads that would overflow their buffers are forced to consume reference
-        full = (rlen[active] >= cap - 1) | (nops[active] >= 2 * cap - 1)
-        is_y &= ~full
-        is_x |= full & ~is_m
-        a_m, a_x, a_y = active[is_m], active[is_x], active[is_y]
-        if len(a_m):
-            xb = ref_codes[ref_off[a_m] + xpos[a_m]]
-            yb = _sample_rows(rng, Mc, xb)
-            reads[a_m, rlen[a_m]] = yb
-            rlen[a_m] += 1
-            ops[a_m, nops[a_m]] = OP_M
-            xpos[a_m] += 1
-        if len(a_x):
-            ops[a_x, nops[a_x]] = OP_D
-            xpos[a_x] += 1
-        if len(a_y):
-            yb = _sample_rows(rng, Ic, np.zeros(len(a_y), dtype=np.int64))
-            reads[a_y, rlen[a_y]] = yb
-            rlen[a_y] += 1
-            ops[a_y, nops[a_y]] = OP_I
-        nops[active] += 1
-        active = active[xpos[active] < lens[active]]
+    lens = ref_off[1:] - ref_off[:-1]
+    cap = int(lens.max() * 1.6) + 64 if n else 64  # a read is at most cap bases and 2 * cap columns long
+    # one row of n bytes per step (np.empty: only the rows of the steps taken are ever touched)
+    op_rows = np.empty((2 * cap, n), dtype=np.uint8)
+    base_rows = np.empty((2 * cap, n), dtype=np.uint8)
+    rlen, nops = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+    scratch = [np.empty(n, dtype=np.int64) for _ in range(3)]
+    L = _synth_lib()
+    bg = rng.bit_generator.ctypes
+    steps = L.npr_synth_channel(C.c_void_p(bg.state_address), C.cast(bg.next_double, C.c_void_p), _ptr(ref_codes), _ptr(ref_off), n,
+                                _ptr(Tc), _ptr(Mc), _ptr(Ic), cap, 2 * cap, _ptr(op_rows), _ptr(base_rows), _ptr(rlen), _ptr(nops),
+                                *(_ptr(a) for a in scratch))
+    if steps < 0 or (n and rlen.max() > cap):
+        raise ValueError("error_channel: a read outgrew %d bases / %d columns" % (cap, 2 * cap))
     read_off = np.zeros(n + 1, dtype=np.int64)
     np.cumsum(rlen, out=read_off[1:])
     ops_off = np.zeros(n + 1, dtype=np.int64)
     np.cumsum(nops, out=ops_off[1:])
-    mask_r = np.arange(cap)[None, :] < rlen[:, None]
-    mask_o = np.arange(2 * cap)[None, :] < nops[:, None]
-    return reads[mask_r], read_off, ops[mask_o], ops_off
+    reads = np.empty(int(read_off[-1]), dtype=np.uint8)
+    ops = np.empty(int(ops_off[-1]), dtype=np.uint8)
+    L.npr_synth_gather(_ptr(op_rows), _ptr(base_rows), n, steps, _ptr(nops), _ptr(ops_off), _ptr(read_off), _ptr(ops), _ptr(reads))
+    return reads, read_off, ops, ops_off
 
 
 def columns_to_runs(ops_flat, ops_off):
@@ -208,7 +212,10 @@ def make_workload(seed, n_reads, read_len, T, E, flank=0, ref_slice_len=None, ge
     np.cumsum(slen, out=ref_off[1:])
     start = None
     if genome is None:
-        ref_codes = rng.integers(0, 4, size=int(ref_off[-1])).astype(np.uint8)
+        # (drawn in chunks: the same draws as one call, without its int64 array of every base)
+        ref_codes = np.empty(int(ref_off[-1]), dtype=np.uint8)
+        for k in range(0, len(ref_codes), 1 << 24):
+            ref_codes[k:k + (1 << 24)] = rng.integers(0, 4, size=min(1 << 24, len(ref_codes) - k))
     else:
         start = rng.integers(0, len(genome) - slen.max(), size=n_reads)
         ref_codes = np.empty(int(ref_off[-1]), dtype=np.uint8)
@@ -223,33 +230,34 @@ def make_workload(seed, n_reads, read_len, T, E, flank=0, ref_slice_len=None, ge
     runs, run_off = columns_to_runs(cols, cols_off)
     true_runs = runs.copy()
     runs = jitter_guide(rng, runs, run_off, jitter)
-    # wrap with the leading / trailing deletions that make the guide global over the slice
-    trail = slen - lead - ilen
-    out_runs = []
-    out_off = np.zeros(n_reads + 1, dtype=np.int64)
-    true_out = []
-    for i in range(n_reads):
-        r = runs[run_off[i]:run_off[i + 1]]
-        tr = true_runs[run_off[i]:run_off[i + 1]]
-        parts, tparts = [], []
-        if lead[i] > 0 and not windowed:
-            parts.append(np.array([[OP_D, lead[i]]], dtype=np.int32))
-        parts.append(r)
-        if trail[i] > 0 and not windowed:
-            parts.append(np.array([[OP_D, trail[i]]], dtype=np.int32))
-        g = np.concatenate(parts) if parts else np.zeros((0, 2), dtype=np.int32)
-        # merge adjacent equal ops created by the wrapping
-        if len(g) > 1:
-            keep = np.ones(len(g), dtype=bool)
-            keep[1:] = g[1:, 0] != g[:-1, 0]
-            grp = np.cumsum(keep) - 1
-            merged = np.zeros((grp[-1] + 1, 2), dtype=np.int32)
-            merged[:, 0] = g[keep, 0]
-            np.add.at(merged[:, 1], grp, g[:, 1])
-            g = merged
-        out_runs.append(g)
-        out_off[i + 1] = out_off[i] + len(g)
-    guide_ops = np.concatenate(out_runs) if out_runs else np.zeros((0, 2), dtype=np.int32)
+    if windowed:
+        # the guide is the jittered runs themselves: maximal runs of one read never hold two adjacent equal ops
+        guide_ops, out_off = runs, run_off.copy()
+    else:
+        # wrap with the leading / trailing deletions that make the guide global over the slice
+        trail = slen - lead - ilen
+        out_runs = []
+        out_off = np.zeros(n_reads + 1, dtype=np.int64)
+        for i in range(n_reads):
+            parts = []
+            if lead[i] > 0:
+                parts.append(np.array([[OP_D, lead[i]]], dtype=np.int32))
+            parts.append(runs[run_off[i]:run_off[i + 1]])
+            if trail[i] > 0:
+                parts.append(np.array([[OP_D, trail[i]]], dtype=np.int32))
+            g = np.concatenate(parts)
+            # merge adjacent equal ops created by the wrapping
+            if len(g) > 1:
+                keep = np.ones(len(g), dtype=bool)
+                keep[1:] = g[1:, 0] != g[:-1, 0]
+                grp = np.cumsum(keep) - 1
+                merged = np.zeros((grp[-1] + 1, 2), dtype=np.int32)
+                merged[:, 0] = g[keep, 0]
+                np.add.at(merged[:, 1], grp, g[:, 1])
+                g = merged
+            out_runs.append(g)
+            out_off[i + 1] = out_off[i] + len(g)
+        guide_ops = np.concatenate(out_runs) if out_runs else np.zeros((0, 2), dtype=np.int32)
     guide_start = None
     if windowed:
         guide_start = np.stack([np.asarray(lead, dtype=np.int64), np.zeros(n_reads, dtype=np.int64)], axis=1)

@@ -138,7 +138,7 @@ def test_job_and_em_collectives_run_on_device_tensors_under_nccl(gpu_ctx, tmp_pa
 @pytest.mark.timeout(1500)
 @pytest.mark.parametrize("ranks,reads", [(2, 1024), (8, 512)], ids=["two_ranks", "eight_ranks"])
 def test_plain_bench_command_line_starts_its_own_ranks(gpu_ctx, tmp_path, ranks, reads):
-    """`python bench.py --gpus N ...` without a launcher (the driver's form): N ranks are spawned, share cuda:0 through the
+    """`python bench.py --gpus N ... --full` without a launcher (the driver's form): N ranks are spawned, share cuda:0 through the
     test hook (gloo collectives), rank 0 prints ONE JSON line with the weak-scaling headline and the strong-scaling job beside
     it, and the exit code is 0.  N = 8: the rehearsal of the node BASELINE.json configs[3] names -- eight processes map one SAM,
     each with 16 // 8 host threads, eight offsets are gathered, eight blocks land in one file."""
@@ -147,7 +147,7 @@ def test_plain_bench_command_line_starts_its_own_ranks(gpu_ctx, tmp_path, ranks,
     env = dict(os.environ, NPR_BENCH_SHARE_GPU="1", NPR_BENCH_ALSO_READS=str(max(1024, 8 * ranks)), TMPDIR=str(tmp_path))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "NPR_HOST_THREADS"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--reads", str(reads)],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--reads", str(reads), "--full"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1400)
     err = p.stderr.decode()
     assert p.returncode == 0, "\n".join([l for l in err.split("\n") if "[rank0]" in l][-25:]) + err[-1500:]

@@ -1,3 +1,5 @@
+import hashlib
+
 import numpy as np
 
 from helpers import load_model_arrays
@@ -41,3 +43,13 @@ def test_north_star_shape_has_50kb_slices():
         assert sx == v["interval_len"][i] and sy == v["read_off"][i + 1] - v["read_off"][i]
         assert v["guide_start"][i, 0] == v["lead"][i] and v["guide_start"][i, 1] == 0
         assert v["guide_start"][i, 0] + sx <= 50000
+
+
+def test_workloads_stay_what_their_seeds_made_them():
+    """The seeded inputs of bench.py and of the tests do not change from build to build (outputs are compared across builds on
+    them): digests of two small batches, the windowed north-star shape and the global-guide c2 shape."""
+    T, E, _ = load_model_arrays()
+    keys = ("ref", "ref_off", "read", "read_off", "guide_ops", "guide_off", "true_runs")
+    for (w, _), want in ((synth.config_north_star(T, E, n_reads=16), "88989508bc6c792c996f3b7bc6a349639597347fa60afbac02e8da3874772ba3"),
+                         (synth.config_c2(T, E, n_reads=16), "659577ee8b5b91ed70880d85fbd439278db604e305337a3d54f0b78c6c71f481")):
+        assert hashlib.sha256(b"".join(np.ascontiguousarray(w[k]).tobytes() for k in keys)).hexdigest() == want

@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 GROUPS_=("SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_WAVES SQ_INSTS_BRANCH" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY GRBM_GUI_ACTIVE")
 i=0
 for g in "${GROUPS_[@]}"; do
-  timeout 400 rocprofv3 --pmc $g --output-format csv -d $R/$OUT/g$i -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline > $R/$OUT/g$i.log 2>&1
+  timeout 400 rocprofv3 --pmc $g --output-format csv -d $R/$OUT/g$i -- python $R/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline > $R/$OUT/g$i.log 2>&1
   i=$((i+1))
 done
 python3 - <<PY
