@@ -83,6 +83,103 @@ def full_matrix_reference(T, E, X, Y, start=None, end=None):
     return total, post, F, B
 
 
+def numpy_expectations(T, E, X, Y, start=None, end=None):
+    """Baum-Welch expected counts (T[25], E[80]) and the total from full_matrix_reference's forward / backward: every term
+    F(from) * t(from, to) * e(to) * B(to) / total, added up cell by cell.  A base N (code 4) is emitted with 1/16 (match) or 1/4
+    (gap) and counted in the transitions, in no emission bin.  A gap state's emission is counted by its own base and spread as
+    a quarter over the other sequence's four bases (the 80-entry layout of a model file)."""
+    tot, _, F, B = full_matrix_reference(T, E, X, Y, start=start, end=end)
+    Tm = np.asarray(T).reshape(5, 5)
+    Em = np.full((5, 5), 1.0 / 16.0)
+    Em[:4, :4] = np.asarray(E[:16]).reshape(4, 4)
+    Ex = {s: np.append(np.asarray(E[16 * s:16 * s + 16]).reshape(4, 4).sum(axis=1), 0.25) for s in range(5)}
+    Ey = {s: np.append(np.asarray(E[16 * s:16 * s + 16]).reshape(4, 4).sum(axis=0), 0.25) for s in range(5)}
+    Texp, Eexp = np.zeros((5, 5)), np.zeros(80)
+    for x in range(len(X) + 1):
+        for y in range(len(Y) + 1):
+            if x > 0 and y > 0:
+                w = F[x - 1, y - 1] * Tm[:, 0] * Em[X[x - 1], Y[y - 1]] * B[x, y, 0] / tot
+                Texp[:, 0] += w
+                if X[x - 1] < 4 and Y[y - 1] < 4:
+                    Eexp[X[x - 1] * 4 + Y[y - 1]] += w.sum()
+            if x > 0:
+                for t in (1, 3):
+                    w = F[x - 1, y] * Tm[:, t] * Ex[t][X[x - 1]] * B[x, y, t] / tot
+                    Texp[:, t] += w
+                    if X[x - 1] < 4:
+                        Eexp[t * 16 + X[x - 1] * 4:t * 16 + X[x - 1] * 4 + 4] += 0.25 * w.sum()
+            if y > 0:
+                for t in (2, 4):
+                    w = F[x, y - 1] * Tm[:, t] * Ey[t][Y[y - 1]] * B[x, y, t] / tot
+                    Texp[:, t] += w
+                    if Y[y - 1] < 4:
+                        Eexp[t * 16 + Y[y - 1]:t * 16 + 16:4] += 0.25 * w.sum()
+    return Texp.reshape(-1), Eexp, tot
+
+
+STATE_NAMES = ("match", "shortGapX", "shortGapY", "longGapX", "longGapY")
+
+
+def count_name(i):
+    """The name of entry i of the 105 counts (T[25] then E[80]): T[3][0], E[match][A][T], E[shortGapX][G][*], E[longGapY][*][C]."""
+    if i < 25:
+        return "T[%d][%d]" % (i // 5, i % 5)
+    s, r = divmod(i - 25, 16)
+    x, y = "ACGT"[r // 4], "ACGT"[r % 4]
+    if s in (1, 3):
+        y = "*"   # (a gap in the read: counted by the reference base, spread over the four read bases)
+    elif s in (2, 4):
+        x = "*"
+    return "E[%s][%s][%s]" % (STATE_NAMES[s], x, y)
+
+
+# Per-bin contract of the E-step counts against the fp64 oracle: |got - want| <= rel * want + floor on every one of the 25 + 80
+# entries, and an entry the reference has at exactly 0 (a transition the model lacks, a bin only N bases would reach) is exactly 0.
+#
+# Why a relative bound per bin holds.  Each count is a sum of positive terms F(from) * t * e * B(to) / P.  The device keeps F, B
+# and P in fp32 with an exponent beside them (per cell, per lane or per row: the kernel's choice), so each factor carries a relative
+# error of a few 2^-24 per operation of its recursion; those errors are shared by F, B and P (P is the sum of F * B over any
+# anti-diagonal) and largely cancel in the quotient.  The one place the precision is lower is the stripe E-step
+# (k_dp_tile_cs<.., EM>), whose four gap-state forward values are kept as 24-bit floats with 15 mantissa bits: relative error
+# at most 2^-16 = 1.5e-5 on the F factor of a gap-state term, once per term (the planes are written once and read once).  A sum
+# of positive terms has a relative error no larger than the largest relative error of its terms, plus the rounding of the sum
+# itself: fp32 per lane (n terms: at most (n - 1) * 2^-24, about sqrt(n) * 2^-24 for roundings of either sign, 4e-6 for the few
+# thousand terms of a lane), then fp64.  So every bin stays within about 2e-5 of its own size on every path.  Measured on the
+# MI355X (test_gpu_em.py's fixtures, every path and model): at most 5.5e-6 against the oracle, 1.3e-5 between two kernels (k_dp_wide
+# against k_dp_generic, bands of 1500), on bins of at least 1 count; rel = 1e-4 is 8x above the worst.  Bins below 1 count -- a
+# transition the band meets in a few cells, an emission a handful of bases make -- differ by at most 1e-6 counts; the floor,
+# 1e-4 counts, is 100x above that and 2e-8 of the totals of these fixtures (5e3 - 2e4 transitions).
+COUNTS_REL, COUNTS_FLOOR = 1e-4, 1e-4
+
+
+def counts_error(got_T, got_E, want_T, want_E):
+    """(worst relative error over the entries whose reference count is at least 1, worst absolute error over the others)."""
+    got = np.concatenate([np.asarray(got_T, dtype=np.float64).reshape(-1), np.asarray(got_E, dtype=np.float64).reshape(-1)])
+    want = np.concatenate([np.asarray(want_T, dtype=np.float64).reshape(-1), np.asarray(want_E, dtype=np.float64).reshape(-1)])
+    big = want >= 1.0
+    d = np.abs(got - want)
+    return (float((d[big] / want[big]).max()) if big.any() else 0.0, float(d[~big].max()) if (~big).any() else 0.0)
+
+
+def assert_counts_match(got_T, got_E, want_T, want_E, rel=COUNTS_REL, floor=COUNTS_FLOOR, what=""):
+    """Every one of the 25 transition and 80 emission counts: finite, |got - want| <= rel * want + floor, and exactly 0 where the
+    reference is exactly 0.  On failure the message names each failing entry with got, want and the relative error."""
+    got = np.concatenate([np.asarray(got_T, dtype=np.float64).reshape(-1), np.asarray(got_E, dtype=np.float64).reshape(-1)])
+    want = np.concatenate([np.asarray(want_T, dtype=np.float64).reshape(-1), np.asarray(want_E, dtype=np.float64).reshape(-1)])
+    assert got.shape == want.shape == (105,), (got.shape, want.shape)
+    bad = []
+    for i in range(105):
+        g, w = got[i], want[i]
+        ok = np.isfinite(g) and (g == 0.0 if w == 0.0 else abs(g - w) <= rel * abs(w) + floor)
+        if not ok:
+            name = count_name(i)
+            if name not in (b[0] for b in bad):
+                bad.append((name, g, w))
+    assert not bad, "%s: %d entries off (rel %.1e + floor %.1e): %s" % (
+        what, len(bad), rel, floor, "; ".join("%s got %.9g want %.9g (rel %.2e)" % (n, g, w, abs(g - w) / abs(w) if w else float("inf"))
+                                              for n, g, w in bad[:12]))
+
+
 def random_pair(rng, lX, sub=0.1, indel=0.1, max_indel=3):
     """Random reference X and a noisy copy Y with the TRUE global alignment as (op,len) list."""
     X = rng.integers(0, 4, size=lX).astype(np.uint8)

@@ -10,7 +10,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import ROOT, cigar_spans, full_matrix_reference, load_model_arrays, oracle_hmm, orc, random_pair
+from helpers import ROOT, cigar_spans, count_name, full_matrix_reference, load_model_arrays, numpy_expectations, oracle_hmm, orc, random_pair
 
 LN2 = np.log(2.0)
 
@@ -205,47 +205,68 @@ def test_unsupported_transition_rejected_by_mirror():
     assert m["rc"] == -4
 
 
-def test_expectations_match_independent_numpy():
-    """Baum-Welch expected counts (SURVEY 8f #2) against counts computed from the independent numpy forward/backward."""
-    rng = np.random.default_rng(31)
+def _model_variant(variant):
+    """The shipped model (blasr_hmm_0), or it with gap emissions that depend on the base, or with shortGapX <-> shortGapY switches."""
     T, E, _ = load_model_arrays()
+    T, E = T.reshape(5, 5).copy(), E.reshape(5, 4, 4).copy()
+    if variant == "gap_emissions_by_base":   # (the construction of test_gpu_em.py's stripe-instance test)
+        g = np.array([0.4, 0.1, 0.2, 0.3]) / 4
+        E[1], E[3] = g[:, None] * np.ones((4, 4)), g[::-1][:, None] * np.ones((4, 4))
+        E[2], E[4] = g[None, :] * np.ones((4, 4)), g[::-1][None, :] * np.ones((4, 4))
+    if variant == "short_gap_switches":
+        T[1, 2], T[2, 1] = 0.03, 0.02
+        T[1, 1] -= 0.03
+        T[2, 2] -= 0.02
+    return T.reshape(-1), E.reshape(-1)
+
+
+@pytest.mark.parametrize("case", ["shipped", "gap_emissions_by_base", "short_gap_switches", "ragged_start", "ragged_end",
+                                  "ragged_both_with_switches", "n_bases_at_the_ends", "n_facing_n"])
+def test_expectations_match_independent_numpy(case):
+    """Baum-Welch expected counts of orc_expectations_f64 against counts computed from the independent numpy
+    forward/backward (helpers.numpy_expectations), per bin to 1e-9 relative: the reference every E-step test on the GPU rests on,
+    with the models and the segment edges the kernels have (ragged starts and ends come from split points: a segment then starts
+    in either long-gap state and ends from any state into its successor's)."""
+    rng = np.random.default_rng(31)
+    model = {"gap_emissions_by_base": "gap_emissions_by_base", "short_gap_switches": "short_gap_switches",
+             "ragged_both_with_switches": "short_gap_switches"}.get(case, "shipped")
+    T, E = _model_variant(model)
+    Tm = T.reshape(5, 5)
     h = orc.make_hmm(T, E)
     X, Y, ops = random_pair(rng, 30)
     X[7] = 4  # an N: contributes to transitions, not to emissions
+    if case == "n_bases_at_the_ends":
+        X[0] = X[-1] = Y[0] = Y[-1] = 4
+    if case == "n_facing_n":   # (a match of N with N, and gap bases that are N next to it)
+        X[12:15] = 4
+        Y[11:15] = 4
+    rs = case in ("ragged_start", "ragged_both_with_switches")
+    re_ = case in ("ragged_end", "ragged_both_with_switches")
     seg = orc.plan(len(X), len(Y), ops, orc.make_params(band_mode=orc.BAND_FIXED, fixed_width=10000))[0]
-    r = orc.expectations(h, X, Y, seg["lo"], seg["n"])
-    tot, _, F, B = full_matrix_reference(T, E, X, Y)
-    Tm = np.asarray(T).reshape(5, 5)
-    Em = np.full((5, 5), 1.0 / 16.0)
-    Em[:4, :4] = np.asarray(E[:16]).reshape(4, 4)
-    Ex = {s: np.append(np.asarray(E[16 * s:16 * s + 16]).reshape(4, 4).sum(axis=1), 0.25) for s in range(5)}
-    Ey = {s: np.append(np.asarray(E[16 * s:16 * s + 16]).reshape(4, 4).sum(axis=0), 0.25) for s in range(5)}
-    Texp, Eexp = np.zeros((5, 5)), np.zeros(80)
-    for x in range(len(X) + 1):
-        for y in range(len(Y) + 1):
-            if x > 0 and y > 0:
-                w = F[x - 1, y - 1] * Tm[:, 0] * Em[X[x - 1], Y[y - 1]] * B[x, y, 0] / tot
-                Texp[:, 0] += w
-                if X[x - 1] < 4 and Y[y - 1] < 4:
-                    Eexp[X[x - 1] * 4 + Y[y - 1]] += w.sum()
-            if x > 0:
-                for t in (1, 3):
-                    w = F[x - 1, y] * Tm[:, t] * Ex[t][X[x - 1]] * B[x, y, t] / tot
-                    Texp[:, t] += w
-                    if X[x - 1] < 4:
-                        Eexp[t * 16 + X[x - 1] * 4:t * 16 + X[x - 1] * 4 + 4] += 0.25 * w.sum()
-            if y > 0:
-                for t in (2, 4):
-                    w = F[x, y - 1] * Tm[:, t] * Ey[t][Y[y - 1]] * B[x, y, t] / tot
-                    Texp[:, t] += w
-                    if Y[y - 1] < 4:
-                        Eexp[t * 16 + Y[y - 1]:t * 16 + 16:4] += 0.25 * w.sum()
+    r = orc.expectations(h, X, Y, seg["lo"], seg["n"], int(rs), int(re_))
+    start = np.array([0, 0, 0, 1.0, 1.0]) if rs else None
+    end = np.array([Tm[0, 3], Tm[0, 3], Tm[0, 4], Tm[3, 3], Tm[4, 4]]) if re_ else None
+    Texp, Eexp, tot = numpy_expectations(T, E, X, Y, start=start, end=end)
     assert r["rc"] == 0
-    assert np.abs(r["T"] - Texp.reshape(-1)).max() < 1e-11
-    assert np.abs(r["E"] - Eexp).max() < 1e-11
     assert r["total_ll"] == pytest.approx(np.log(tot), abs=1e-10)
-    # every path has one transition per alignment column
-    assert max(len(X), len(Y)) <= r["T"].sum() <= len(X) + len(Y)
+    want = np.concatenate([Texp, Eexp])
+    got = np.concatenate([r["T"], r["E"]])
+    assert ((want == 0) == (got == 0)).all(), [count_name(i) for i in np.nonzero((want == 0) != (got == 0))[0]]
+    assert np.abs(r["T"] - Texp).max() < 1e-11
+    assert np.abs(r["E"] - Eexp).max() < 1e-11
+    nz = want > 0
+    worst = np.abs(got[nz] - want[nz]) / want[nz]
+    assert worst.max() < 1e-9, "%s: %s rel %.2e" % (case, count_name(np.nonzero(nz)[0][worst.argmax()]), worst.max())
+    # the structural zeros: transitions the model lacks are never counted
+    for i in np.nonzero(T == 0)[0]:
+        assert r["T"][i] == 0.0, count_name(i)
+    if model == "short_gap_switches":
+        assert r["T"][1 * 5 + 2] > 0 and r["T"][2 * 5 + 1] > 0
+    # every path has one transition per alignment column (a ragged segment starts in a gap state, which has been entered already)
+    if not rs and not re_:
+        assert max(len(X), len(Y)) <= r["T"].sum() <= len(X) + len(Y)
+    if case == "n_bases_at_the_ends":   # the corners hold N on both sides: the emission bins do not see them
+        assert Eexp.sum() < Texp.sum() - 1.5
 
 
 def test_approximate_logadd_mode_is_a_measuring_stick_not_the_norm():
