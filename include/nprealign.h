@@ -146,7 +146,7 @@ const char *npr_last_error(npr_ctx *ctx);
  * compare with each other; a caller of the drop-in path never sets them.  Since round 4 these are context options, not
  * environment variables: what the library runs does not depend on the caller's environment.  (Still read from the environment,
  * and changing no choice of kernel: NPR_TIMING=1 stage times on stderr, NPR_POISON=<byte> device buffers filled when handed
- * out, NPR_TILE_PROF=1 wait cycles of the stripe kernel, NPR_HOST_THREADS=<n> host worker threads.) */
+ * out, NPR_HOST_THREADS=<n> host worker threads.) */
 #define NPR_OPT_KERNEL 3           /* 1: the any-band kernel (k_dp_generic) for every task */
 #define NPR_OPT_ARITH 4            /* 1: one exponent per cell (k_dp_stair) instead of one per row (k_dp_rs / k_dp_mid_rs) */
 #define NPR_OPT_PAIR 5             /* a read's two sweeps on two wavefronts: 0 the default rule (row-scaled arithmetic: every task of 64+ anti-diagonals), 1 never, 2 the tasks longer than a fair share, 3 always */
@@ -154,16 +154,11 @@ const char *npr_last_error(npr_ctx *ctx);
 #define NPR_OPT_NO_WIDE 7          /* 1: no multi-wavefront frame kernel */
 #define NPR_OPT_TILE_RS 8          /* the stripe kernel: 0 / 1 column-scaled arithmetic (k_dp_tile_cs, the default), 2 one exponent per cell (k_dp_tile) */
 #define NPR_OPT_TILE_WAVES 9       /* wavefronts per stripe task (1 .. 8; 0: default 4) */
-#define NPR_OPT_WAVES_PER_CU 10    /* resident wavefronts / workgroups per CU of every DP launch (0: per class) */
-#define NPR_OPT_CLASS_MIN 11       /* smallest frame class considered */
-#define NPR_OPT_VARIABLE_SCRATCH 12 /* scratch regions sized per task: 0 above 32 GB, 1 always, 2 never */
+/* 10, 11, 12, 16, 18 and 19 are retired bring-up switches: npr_ctx_option refuses them as unknown */
 #define NPR_OPT_HOST_MEA 13        /* 1: chain + cigar on the host in realign mode too */
 #define NPR_OPT_MEA_RING_ONLY 14   /* 1: every read through the LDS-ring chain kernel */
 #define NPR_OPT_MEA_GLOBAL_SORT 15 /* 1: the sort's tables in HBM whatever the span */
-#define NPR_OPT_MEA_OWN_SCRATCH 16 /* 1: the MEA tables in buffers of the context's own, not in the forward scratch */
 #define NPR_OPT_EM_GENERIC 17      /* 1: the E-step on the any-band kernel */
-#define NPR_OPT_EM_SERIAL 18       /* 1: the E-step's launches one after the other */
-#define NPR_OPT_EM_WAVES 19        /* wavefronts per CU of k_em_stair (0: per class) */
 #define NPR_OPT_MEA_WIDE_OPS 20    /* 1: the packed cigars cross PCIe as whole words even when every run fits 14 bits */
 #define NPR_OPT_EM_TILE 21         /* the E-step of stripe tasks: 0 column-scaled arithmetic first (k_dp_tile_cs's E-step instance; what its certificate refuses goes to k_em_tile), 1 k_em_tile only, 2 (tests) as 0 with every other task refused */
 #define NPR_OPT_COUNT 22

@@ -77,13 +77,11 @@ int32_t npr_create(int32_t device_id, npr_ctx **out, char *err, size_t errlen) {
     ctx->host_threads = usable_cpus();
     // The side streams carry the SMALL launches of a pass (the classes with few cells beside the one that fills the chip): at the highest priority,
     // so that when all of a pass's launches become ready together the small ones are dispatched first -- a kernel that fills every SIMD's
-    // registers with persistent workgroups leaves no room for a late one until it drains (NPR_SIDE_PRIORITY=0: default priority, A/B)
+    // registers with persistent workgroups leaves no room for a late one until it drains
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    const char *pe = std::getenv("NPR_SIDE_PRIORITY");
-    const int side_prio = (pe && std::atoi(pe) == 0) ? prio_lo : prio_hi;
     for (int i = 0; i < npr_ctx::kSideStreams; ++i)
-        if ((e = hipStreamCreateWithPriority(&ctx->side[i], hipStreamNonBlocking, side_prio)) != hipSuccess ||
+        if ((e = hipStreamCreateWithPriority(&ctx->side[i], hipStreamNonBlocking, prio_hi)) != hipSuccess ||
             (e = hipEventCreateWithFlags(&ctx->side_done[i], hipEventDisableTiming)) != hipSuccess) {
             say("npr_create: side stream allocation", e);
             npr_destroy(ctx);
@@ -166,13 +164,14 @@ int32_t npr_ctx_option(npr_ctx *ctx, int32_t option, int64_t value) {
     switch (option) {
         case NPR_OPT_OVERLAP: ctx->overlap = value == 2 ? 2 : (value != 0 ? 1 : 0); return NPR_OK;
         case NPR_OPT_RELEASE_SCRATCH: return release_scratch(ctx, value == 2);
+        case 10: case 11: case 12: case 16: case 18: case 19: break;  // retired (include/nprealign.h)
         default:
             if (option > NPR_OPT_RELEASE_SCRATCH && option < NPR_OPT_COUNT) {
                 ctx->opt[option] = value;
                 return NPR_OK;
             }
-            return fail(ctx, NPR_ERR_INVALID, "npr_ctx_option: unknown option");
     }
+    return fail(ctx, NPR_ERR_INVALID, "npr_ctx_option: unknown option");
 }
 
 int32_t npr_set_hmm(npr_ctx *ctx, int32_t slot, const double *T25, const double *E80) {

@@ -58,7 +58,7 @@ struct KernelArgs {
     const uint32_t *coff;  // per anti-diagonal: offset of its first cell inside the task (cells padded to x4)
     const Stripe *stripes;  // k_dp_tile: stripe tables (Task::tile_off)
     const uint32_t *rowmask;  // k_dp_tile: lane masks of every row, packed (npr_sched.h tile_row_word; Task::rowmask_off)
-    unsigned long long *prof;  // k_dp_tile, NPR_TILE_PROF=1: wait-cycle counters
+    unsigned long long *prof;  // unused (kept so the fields after it keep their kernarg offsets)
     const int64_t *region;  // k_dp_tile: first scratch cell of each workgroup (regions sized by the workgroup's first task)
     const uint32_t *ctl;   // register kernel: two control words per anti-diagonal (row offset; jlo | n << 13 | (rebase + 1) << 26)
     char *F;               // forward match-state scratch: one region of 8*slot_stride bytes per resident wave.  The
@@ -292,12 +292,8 @@ size_t em_tile_lds_bytes(int nw);
 // anti-diagonal row instead of one per cell.  A task's scratch region (8 bytes per cell of its frame schedule, as for
 // k_dp_stair) holds the forward rows at 4 bytes per cell in its first half and the row exponents, one word per NPR_RS_K
 // anti-diagonals, from byte 4 * rs_half_cells(cells) on.
-#ifndef NPR_RS_K
-#define NPR_RS_K 16
-#endif
-#ifndef NPR_RS_TOP
-#define NPR_RS_TOP 85  // the renormalised maximum of a row pair lies in [2^84, 2^85)
-#endif
+constexpr int NPR_RS_K = 16;
+constexpr int NPR_RS_TOP = 85;  // the renormalised maximum of a row pair lies in [2^84, 2^85)
 // The certificate that one exponent per row was enough.  s = eF + eB - eTot of an anti-diagonal turns a
 // forward-backward product into a posterior; the rows' maxima stay below 2^(NPR_RS_TOP + 6), so no F * 2^s or B * 2^s of that
 // row exceeds 2^(NPR_RS_TOP + 6 + s), and a cell whose other factor fell below fp32's normal range (2^-126 in row units: flushed,
@@ -309,18 +305,16 @@ size_t em_tile_lds_bytes(int nw);
 // TASK_RERUN instead of NPR_OK and npr_batch_run runs it again with the per-cell-exponent kernel (k_dp_stair), which has no
 // such limit.  So does a task whose forward sweep arrives at the end corner with nothing: whether that band really carries
 // no probability (NPR_ERR_ZERO_PROB) is for the kernel without a range limit to say.
-#define NPR_RS_S_LIMIT (126 - 60 - (NPR_RS_TOP + 6) - 1)
+constexpr int NPR_RS_S_LIMIT = 126 - 60 - (NPR_RS_TOP + 6) - 1;
 constexpr int32_t TASK_RERUN = 1;  // TaskOut::status of such a task between the two launches (never leaves npr_batch_run)
 NPR_HD constexpr int64_t rs_half_cells(int64_t cells_pad) { return (cells_pad + 63) & ~int64_t(63); }
 int launch_rs(const KernelArgs &a, int R, int grid, void *stream, bool sw, bool flat);  // sw: a loaded model has short-gap switches; flat: all gap emissions are 2^-2 (npr_rs.h)
 // k_dp_mid_rs (npr_kernel_mid.hip): k_dp_rs's sweeps on two wavefronts that meet in the middle -- the forward one from row 0, the backward one from
 // row D, each going on past the cut against the other's stored rows.  Tasks of fewer than MID_MIN_D anti-diagonals stay with k_dp_rs.
 constexpr int32_t MID_MIN_D = 4 * NPR_RS_K;
-#ifndef NPR_MID_WAVES2
-#define NPR_MID_WAVES2 7  // wavefronts per SIMD k_dp_mid_rs<2> is compiled for
-#endif
+constexpr int MID_WAVES2 = 7;  // wavefronts per SIMD k_dp_mid_rs<2> is compiled for
 // resident wavefronts per CU of k_dp_mid_rs<R> (80 / .. / 124 registers)
-inline int mid_waves_per_cu(int R) { return R == 1 ? 24 : (R == 2 ? 4 * NPR_MID_WAVES2 : 16); }
+inline int mid_waves_per_cu(int R) { return R == 1 ? 24 : (R == 2 ? 4 * MID_WAVES2 : 16); }
 int launch_mid_rs(const KernelArgs &a, int R, int grid, void *stream, bool sw, bool flat);
 // k_dp_tile_cs (npr_kernel_tile_cs.hip): k_dp_tile's stripes in column-scaled arithmetic -- one exponent per lane (pair of lattice columns);
 // sw / flat as for launch_rs

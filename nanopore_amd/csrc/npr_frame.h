@@ -13,9 +13,7 @@ namespace npr {
 namespace {
 
 constexpr int WAVE = 64;
-#ifndef NPR_T_SGPR_MIN_R
-#define NPR_T_SGPR_MIN_R 2  // transitions in SGPRs from this many slots per lane on (below: VGPRs)
-#endif
+constexpr int T_SGPR_MIN_R = 2;  // transitions in SGPRs from this many slots per lane on (below: VGPRs)
 constexpr int MODEL_FLOATS = sizeof(DevModel) / sizeof(float);
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -284,11 +282,7 @@ template <int R>
 __device__ __forceinline__ void emissions(const StepEnv &E, const Bases<R> &bx, const Bases<R> &by, int r, float &em,
                                           float &exs, float &exl, float &eys, float &eyl) {
     constexpr int OFF_EM = offsetof(DevModel, em), OFF_EX = offsetof(DevModel, ex), OFF_EY = offsetof(DevModel, ey);
-#ifdef NPR_EMIDX_MAD24
-    em = *reinterpret_cast<const float *>(E.ltab + OFF_EM + (__umul24(static_cast<unsigned>(bx.b[r]), 5u) + static_cast<unsigned>(by.b[r])));
-#else
     em = *reinterpret_cast<const float *>(E.ltab + OFF_EM + 5 * bx.b[r] + by.b[r]);
-#endif
     exs = *reinterpret_cast<const float *>(E.ltab + OFF_EX + 20 + bx.b[r]);
     exl = *reinterpret_cast<const float *>(E.ltab + OFF_EX + 60 + bx.b[r]);
     eys = *reinterpret_cast<const float *>(E.ltab + OFF_EY + 40 + by.b[r]);

@@ -79,7 +79,7 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
 }
 
 template <int R, bool SW, bool FLAT>
-__global__ void __launch_bounds__(2 * WAVE) __attribute__((amdgpu_waves_per_eu(R == 1 ? 6 : (R == 2 ? NPR_MID_WAVES2 : 4)))) k_dp_mid_rs(KernelArgs a) {
+__global__ void __launch_bounds__(2 * WAVE) __attribute__((amdgpu_waves_per_eu(R == 1 ? 6 : (R == 2 ? MID_WAVES2 : 4)))) k_dp_mid_rs(KernelArgs a) {
     __shared__ __attribute__((aligned(16))) RsTables ltab_s;
     __shared__ __attribute__((aligned(16))) float lmodel[MODEL_FLOATS];
     // [0..1] total (forward, at the end corner), [2..3] total (backward), [4] sum of rebases, [5] / [12] candidates of wavefront 0 / 1,
@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(2 * WAVE) __attribute__((amdgpu_waves_per_eu(R
         __syncthreads();
         {
             Trans tr = load_trans(E.mdl->T);
-            if constexpr (R >= NPR_RS_T_SGPR_MIN_R) {
+            if constexpr (R >= RS_T_SGPR_MIN_R) {
                 tr.mm = unif(tr.mm), tr.sxm = unif(tr.sxm), tr.sym = unif(tr.sym), tr.lxm = unif(tr.lxm), tr.lym = unif(tr.lym);
                 tr.msx = unif(tr.msx), tr.sxsx = unif(tr.sxsx), tr.sysx = unif(tr.sysx);
                 tr.msy = unif(tr.msy), tr.sysy = unif(tr.sysy), tr.sxsy = unif(tr.sxsy);

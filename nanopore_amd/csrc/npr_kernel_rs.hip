@@ -20,7 +20,7 @@ namespace npr {
 namespace {
 
 template <int R, bool SW, bool FLAT>
-__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(R == 2 ? NPR_RS_WAVES2 : 1))) k_dp_rs(KernelArgs a) {
+__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(R == 2 ? RS_WAVES2 : 1))) k_dp_rs(KernelArgs a) {
     // static LDS: the tables' addresses are compile-time constants and fold into the ds_read offsets
     __shared__ __attribute__((aligned(16))) RsTables ltab_s;
     __shared__ __attribute__((aligned(16))) float lmodel[MODEL_FLOATS];
@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(R == 
         E.X = a.seq + x_off, E.Y = a.seq + y_off, E.lX = lX, E.lY = lY, E.lane = lane;
         {
             Trans tr = load_trans(E.mdl->T);
-            if constexpr (R >= NPR_RS_T_SGPR_MIN_R) {
+            if constexpr (R >= RS_T_SGPR_MIN_R) {
                 tr.mm = unif(tr.mm), tr.sxm = unif(tr.sxm), tr.sym = unif(tr.sym), tr.lxm = unif(tr.lxm), tr.lym = unif(tr.lym);
                 tr.msx = unif(tr.msx), tr.sxsx = unif(tr.sxsx), tr.sysx = unif(tr.sysx);
                 tr.msy = unif(tr.msy), tr.sysy = unif(tr.sysy), tr.sxsy = unif(tr.sxsy);

@@ -45,12 +45,7 @@ namespace {
 constexpr int TILE_MAX_NW = 8;  // wavefronts per workgroup (launch bound)
 constexpr int TILE_BLOCK = 16;  // neighbour cells staged / published at a time
 constexpr int EDGE_FLOATS = 8;  // one neighbour cell in memory: m, sx, sy, lx, ly, e, -, -
-#ifndef NPR_EDGE_ST_AUX
-#define NPR_EDGE_ST_AUX 0
-#endif
-#ifndef NPR_EDGE_LD_AUX
-#define NPR_EDGE_LD_AUX 16
-#endif
+constexpr int EDGE_ST_AUX = 0, EDGE_LD_AUX = 16;  // cache policy of the neighbour cells' stores and loads (16: sc1, edge_stage)
 
 typedef const __attribute__((address_space(4))) int32_t *cptr_i32;
 
@@ -104,8 +99,8 @@ __device__ __forceinline__ void tile_load_row(__amdgpu_buffer_rsrc_t rs, int vo,
 __device__ __forceinline__ void edge_store(__amdgpu_buffer_rsrc_t rs, int k, const Cell &c, uint64_t lane_mask) {
     if (__builtin_amdgcn_inverse_ballot_w64(lane_mask)) {
         const int vo = 4 * EDGE_FLOATS * k;
-        __builtin_amdgcn_raw_buffer_store_b128(v4i{fbits(c.m), fbits(c.sx), fbits(c.sy), fbits(c.lx)}, rs, vo, 0, NPR_EDGE_ST_AUX);
-        __builtin_amdgcn_raw_buffer_store_b64(v2i{fbits(c.ly), c.e}, rs, vo + 16, 0, NPR_EDGE_ST_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(v4i{fbits(c.m), fbits(c.sx), fbits(c.sy), fbits(c.lx)}, rs, vo, 0, EDGE_ST_AUX);
+        __builtin_amdgcn_raw_buffer_store_b64(v2i{fbits(c.ly), c.e}, rs, vo + 16, 0, EDGE_ST_AUX);
     }
 }
 // `cnt` neighbour cells starting at row `row` into this wavefront's LDS staging (lane l takes cell l).  The loads bypass
@@ -113,8 +108,8 @@ __device__ __forceinline__ void edge_store(__amdgpu_buffer_rsrc_t rs, int k, con
 __device__ __forceinline__ void edge_stage(char *Eb, uint32_t row, int cnt, float *stage, int lane) {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(Eb + static_cast<int64_t>(row) * (4 * EDGE_FLOATS), 0, -1, 0x00020000);
     if (__builtin_amdgcn_inverse_ballot_w64(low_lanes(cnt))) {
-        const v4i q = __builtin_amdgcn_raw_buffer_load_b128(rs, 32 * lane, 0, NPR_EDGE_LD_AUX);
-        const v2i g = __builtin_amdgcn_raw_buffer_load_b64(rs, 32 * lane + 16, 0, NPR_EDGE_LD_AUX);
+        const v4i q = __builtin_amdgcn_raw_buffer_load_b128(rs, 32 * lane, 0, EDGE_LD_AUX);
+        const v2i g = __builtin_amdgcn_raw_buffer_load_b64(rs, 32 * lane + 16, 0, EDGE_LD_AUX);
         *reinterpret_cast<v4i *>(stage + EDGE_FLOATS * lane) = q;
         *reinterpret_cast<v2i *>(stage + EDGE_FLOATS * lane + 4) = g;
     }
@@ -196,9 +191,7 @@ __device__ __forceinline__ void tile_bwd_step(int d, const StepEnv &E, Diag<R> &
 
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-// PROF (NPR_TILE_PROF=1, bring-up): cycles every wavefront spends waiting -- for a neighbour's cells, for its own stores
-// before it publishes, at the barriers between the sweeps -- summed into a.prof[0..3] next to its total.
-template <int R, bool PROF, bool FLAT>
+template <int R, bool FLAT>
 __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves_per_eu(R == 2 ? 6 : 1))) k_dp_tile(KernelArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *lmodel = reinterpret_cast<float *>(smem);
@@ -216,9 +209,6 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
 #pragma unroll
     for (int r = 0; r < R; ++r) jr[r] = R * lane + r;
 
-    uint64_t pf_spin = 0, pf_vm = 0, pf_bar = 0, pf_t0 = 0, pf_all = 0;
-    auto tick = [&]() -> uint64_t { return PROF ? __builtin_readcyclecounter() : 0; };
-    if constexpr (PROF) pf_t0 = tick();
 
     int t = blockIdx.x;
     while (t < a.ntasks) {
@@ -251,7 +241,7 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
         E.X = a.seq + x_off, E.Y = a.seq + y_off, E.lX = lX, E.lY = lY, E.lane = lane;
         {
             Trans tr = load_trans(E.mdl->T);
-            if constexpr (R >= NPR_T_SGPR_MIN_R) {
+            if constexpr (R >= T_SGPR_MIN_R) {
                 tr.mm = unif(tr.mm), tr.sxm = unif(tr.sxm), tr.sym = unif(tr.sym), tr.lxm = unif(tr.lxm), tr.lym = unif(tr.lym);
                 tr.msx = unif(tr.msx), tr.sxsx = unif(tr.sxsx), tr.sysx = unif(tr.sysx);
                 tr.msy = unif(tr.msy), tr.sysy = unif(tr.sysy), tr.sxsy = unif(tr.sxsy);
@@ -294,7 +284,7 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
                 if (q0 >= 0 && q0 < lenL) {
                     const int hi = min(q0 + TILE_BLOCK, lenL);
                     const int need = static_cast<int>(row0L) + hi;
-                    { const uint64_t c0 = tick(); while (uni(lds_peek(prog + wL)) < need) __builtin_amdgcn_s_sleep(2); pf_spin += tick() - c0; }
+                    while (uni(lds_peek(prog + wL)) < need) __builtin_amdgcn_s_sleep(2);
                     asm volatile("" ::: "memory");
                     edge_stage(Ef, row0L + q0, hi - q0, stage, lane);
                     blk_lo = q0, blk_hi = hi;
@@ -314,7 +304,7 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
                     if (q >= blk_hi) {
                         const int hi = min(q + TILE_BLOCK, lenL);
                         const int need = static_cast<int>(row0L) + hi;
-                        { const uint64_t c0 = tick(); while (uni(lds_peek(prog + wL)) < need) __builtin_amdgcn_s_sleep(2); pf_spin += tick() - c0; }
+                        while (uni(lds_peek(prog + wL)) < need) __builtin_amdgcn_s_sleep(2);
                         asm volatile("" ::: "memory");
                         edge_stage(Ef, row0L + q, hi - q, stage, lane);
                         blk_lo = q, blk_hi = hi;
@@ -335,7 +325,7 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
                 tile_store_row<R>(rsF, voff + k * (K * 8), io, mk);
                 edge_store(rsE, k, io.c[R - 1], out_lane);
                 if ((k & (TILE_BLOCK - 1)) == TILE_BLOCK - 1 || d == st.dl) {
-                    { const uint64_t c0 = tick(); wait_vm(); pf_vm += tick() - c0; }
+                    wait_vm();
                     if (lane == 0) lds_poke(prog + wv, static_cast<int>(st.row0) + k + 1);
                 }
             };
@@ -362,7 +352,7 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
             }
             }
         }
-        { const uint64_t c0 = tick(); __syncthreads(); pf_bar += tick() - c0; }
+        __syncthreads();
         const float tot_m = unif(reinterpret_cast<float *>(lmisc)[0]);
         const int tot_e = uni(lmisc[1]);
 
@@ -417,7 +407,7 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
                     if (q0 >= 0 && q0 < lenR) {
                         const int lo = max(q0 - TILE_BLOCK + 1, 0);
                         const int need = static_cast<int>(row0R) + lo;
-                        { const uint64_t c0 = tick(); while (uni(lds_peek(prog + wR)) > need) __builtin_amdgcn_s_sleep(2); pf_spin += tick() - c0; }
+                        while (uni(lds_peek(prog + wR)) > need) __builtin_amdgcn_s_sleep(2);
                         asm volatile("" ::: "memory");
                         edge_stage(Eb, row0R + lo, q0 - lo + 1, stage, lane);
                         blk_lo = lo, blk_hi = q0 + 1;
@@ -441,7 +431,7 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
                         if (q < blk_lo) {
                             const int lo = max(q - TILE_BLOCK + 1, 0);
                             const int need = static_cast<int>(row0R) + lo;
-                            { const uint64_t c0 = tick(); while (uni(lds_peek(prog + wR)) > need) __builtin_amdgcn_s_sleep(2); pf_spin += tick() - c0; }
+                            while (uni(lds_peek(prog + wR)) > need) __builtin_amdgcn_s_sleep(2);
                             asm volatile("" ::: "memory");
                             edge_stage(Eb, row0R + lo, q - lo + 1, stage, lane);
                             blk_lo = lo, blk_hi = q + 1;
@@ -495,7 +485,7 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
                         }
                     }
                     if (((st.dl - d) & (TILE_BLOCK - 1)) == TILE_BLOCK - 1 || d == st.df) {
-                        { const uint64_t c0 = tick(); wait_vm(); pf_vm += tick() - c0; }
+                        wait_vm();
                         if (lane == 0) lds_poke(prog + wv, static_cast<int>(st.row0) + k);
                     }
                 };
@@ -521,7 +511,7 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
                 }
                 }
             }
-            { const uint64_t c0 = tick(); __syncthreads(); pf_bar += tick() - c0; }
+            __syncthreads();
             out.btot_m = unif(reinterpret_cast<float *>(lmisc)[2]);
             out.btot_e = uni(lmisc[3]);
         }
@@ -534,15 +524,6 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
         }
         __syncthreads();
         t = uni(lmisc[5]) + static_cast<int>(gridDim.x);
-    }
-    if constexpr (PROF) {
-        pf_all = tick() - pf_t0;
-        if (lane == 0) {
-            atomicAdd(a.prof + 0, static_cast<unsigned long long>(pf_spin));
-            atomicAdd(a.prof + 1, static_cast<unsigned long long>(pf_vm));
-            atomicAdd(a.prof + 2, static_cast<unsigned long long>(pf_bar));
-            atomicAdd(a.prof + 3, static_cast<unsigned long long>(pf_all));
-        }
     }
 }
 
@@ -587,10 +568,7 @@ __device__ __forceinline__ Cell edge_load(char *Eb, uint32_t row) {
     return Cell{bitsf(q.x), bitsf(q.y), bitsf(q.z), bitsf(q.w), bitsf(g.x), g.y};
 }
 
-#ifndef NPR_EM_SKIP
-#define NPR_EM_SKIP (-40)
-#endif
-constexpr int EM_SKIP = NPR_EM_SKIP;
+constexpr int EM_SKIP = -40;
 __device__ __forceinline__ int Fm_e_of(const Cell &c) { return c.e; }
 __device__ __forceinline__ float &tile_bin_at(float *lbins, int byte_off) {
     return *reinterpret_cast<float *>(reinterpret_cast<char *>(lbins) + byte_off);
@@ -666,11 +644,9 @@ __device__ __forceinline__ void tile_em_cells(const StepEnv &E, const Diag<R> &i
     }
 }
 
-#ifndef NPR_EM_TILE_WPE
-#define NPR_EM_TILE_WPE 3  // wavefronts per SIMD the register allocation aims at (164 VGPRs unconstrained: 3)
-#endif
+constexpr int EM_TILE_WPE = 3;  // wavefronts per SIMD the register allocation aims at (164 VGPRs unconstrained: 3)
 template <int R>
-__global__ void __launch_bounds__(WAVE *EM_TILE_NW) __attribute__((amdgpu_waves_per_eu(NPR_EM_TILE_WPE))) k_em_tile(KernelArgs a) {
+__global__ void __launch_bounds__(WAVE *EM_TILE_NW) __attribute__((amdgpu_waves_per_eu(EM_TILE_WPE))) k_em_tile(KernelArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *lmodel = reinterpret_cast<float *>(smem);
     int *lmisc = reinterpret_cast<int *>(lmodel + MODEL_FLOATS);  // [0..3] totals, [5] next task
@@ -1016,7 +992,7 @@ size_t tile_lds_bytes(int nw) { return sizeof(float) * (MODEL_FLOATS + 8 + TILE_
 int64_t tile_scratch_cells(int64_t rows, int R) { return rows * (64 * R + 2 * EDGE_FLOATS / 2); }
 
 size_t em_tile_lds_bytes(int nw) { return tile_lds_bytes(nw) + sizeof(float) * static_cast<size_t>(nw) * (EM_BINS + 1) * WAVE; }
-int em_tile_waves_per_cu() { return 4 * NPR_EM_TILE_WPE; }
+int em_tile_waves_per_cu() { return 4 * EM_TILE_WPE; }
 int em_tile_waves() {  // wavefronts per task
     return 2;  // trainer's band 2.24 / 2.53 / 2.40 / 2.16e10 cells/s on 1 / 2 / 3 / 4 wavefronts per task, a 560-cell band 2.6 / 3.3 / 3.1 / 3.3e10
 }
@@ -1032,12 +1008,10 @@ int launch_tile(const KernelArgs &a, int R, int NW, int grid, void *stream, bool
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (NW < 1 || NW > TILE_MAX_NW) return static_cast<int>(hipErrorInvalidValue);
     const size_t lds = tile_lds_bytes(NW);
-    if (R == 2 && a.prof)
-        hipLaunchKernelGGL((k_dp_tile<2, true, false>), dim3(grid), dim3(WAVE * NW), lds, s, a);
-    else if (R == 2 && flat)
-        hipLaunchKernelGGL((k_dp_tile<2, false, true>), dim3(grid), dim3(WAVE * NW), lds, s, a);
+    if (R == 2 && flat)
+        hipLaunchKernelGGL((k_dp_tile<2, true>), dim3(grid), dim3(WAVE * NW), lds, s, a);
     else if (R == 2)
-        hipLaunchKernelGGL((k_dp_tile<2, false, false>), dim3(grid), dim3(WAVE * NW), lds, s, a);
+        hipLaunchKernelGGL((k_dp_tile<2, false>), dim3(grid), dim3(WAVE * NW), lds, s, a);
     else
         return static_cast<int>(hipErrorInvalidValue);
     return static_cast<int>(hipGetLastError());

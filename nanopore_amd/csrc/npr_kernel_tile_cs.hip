@@ -30,7 +30,6 @@
 
 #include <algorithm>
 #include <type_traits>
-#include <cstdlib>
 
 #include "npr_device.h"
 #include "npr_frame.h"
@@ -388,14 +387,7 @@ constexpr int TCS_XROW_BYTES = 1536;
 // The E-step's rows are written once and read once, tens of milliseconds later, by a sweep that moves 39 bytes per cell at 2.9 TB/s: as non-temporal
 // stores and loads (aux 2: nt) they stay out of the way of what the caches can help with -- the records between stripes, the exponents, the tables:
 // 55.2 -> 51.0 ms per step of the bench's batch (four runs, alternating: 55.2 / 56.3 against 51.0 / 50.7); nt on the planes alone 51.5, sc0 | nt 51.2.
-#ifndef NPR_TCS_EM_AUX
-#define NPR_TCS_EM_AUX 2
-#endif
-#ifndef NPR_TCS_EM_ROW_AUX
-#define NPR_TCS_EM_ROW_AUX NPR_TCS_EM_AUX
-#endif
-constexpr int TCS_EM_ROW_AUX = NPR_TCS_EM_ROW_AUX;
-constexpr int TCS_EM_AUX = NPR_TCS_EM_AUX;  // cache policy of the planes' stores and of the backward sweep's row loads
+constexpr int TCS_EM_AUX = 2;  // cache policy of the E-step's row and plane stores and of its backward sweep's loads
 __device__ __forceinline__ void tcs_pack24(const RCell &c, int &d0, int &d1, int &d2) {
     const uint32_t r0 = static_cast<uint32_t>(fbits(c.sx)) + 0x80u, r1 = static_cast<uint32_t>(fbits(c.sy)) + 0x80u, r2 = static_cast<uint32_t>(fbits(c.lx)) + 0x80u,
                    r3 = static_cast<uint32_t>(fbits(c.ly)) + 0x80u;  // (values are finite and not negative: the carry can only reach the exponent)
@@ -410,12 +402,7 @@ __device__ __forceinline__ void tcs_unpack24(int d0, int d1, int d2, float &sx, 
     lx = bitsf(static_cast<int>(__builtin_amdgcn_perm(u2, u1, 0x0403020cu)));
     ly = bitsf(static_cast<int>(u2 & 0xffffff00u));
 }
-// (NPR_TCS_EM_EXP, bring-up builds only -- WRONG counts, for timing: 1 the E-step stops after its forward sweep, 2 its backward sweep loads no forward
-// rows, 3 the forward sweep alone and without these planes.  How DESIGN.md 5.3e's "measured by leaving things out" numbers were taken.)
 __device__ __forceinline__ void tcs_store_planes(__amdgpu_buffer_rsrc_t rsX, int vo_a, int vo_b, const RDiag<2> &io) {
-#ifdef NPR_TCS_EM_EXP
-    if (NPR_TCS_EM_EXP == 3) return;
-#endif
     int d[6];
     tcs_pack24(io.c[0], d[0], d[1], d[2]);
     tcs_pack24(io.c[1], d[3], d[4], d[5]);
@@ -439,48 +426,30 @@ struct __attribute__((aligned(16))) CsLds {
 
 // ... and what the E-step variant adds: per wavefront the emission bins (one column per lane, no atomics in the loop: k_em_tile's) and the block
 // of the LEFT stripe's forward records its lane 0 counts transitions from
-#ifndef NPR_TCS_EM_NW
-#define NPR_TCS_EM_NW 1
-#endif
-constexpr int TCS_EM_NW = NPR_TCS_EM_NW;
+constexpr int TCS_EM_NW = 1;
 constexpr int TCS_EM_ROWS = EM_BINS + 5;  // the bins' rows and a scratch zone for N bases: a short-gap bin's long-gap partner lies 4 rows on, there too
 struct __attribute__((aligned(16))) CsEmLds {
     float stageF[TCS_EM_NW][TCS_BLOCK * TCS_EDGE];
     float bins[TCS_EM_NW][TCS_EM_ROWS * WAVE];
 };
-#ifndef NPR_TCS_EM_WAVES
-#define NPR_TCS_EM_WAVES 2
-#endif
+constexpr int TCS_EM_WAVES = 2;  // wavefronts per SIMD the E-step instances are compiled for
 // a lane whose backward values outgrew 2^(TCS_TOP + this) inside a block (values entering it down a steep exponent gradient) would count its
 // transitions with forward factors scaled further down than fp32 holds exactly: the task is counted by k_em_tile instead
 constexpr int TCS_EM_BOOST = 40;
-#ifndef NPR_TCS_EM_DEAD
-#define NPR_TCS_EM_DEAD (-40)
-#endif
-constexpr int TCS_EM_DEAD = NPR_TCS_EM_DEAD;  // (k_em_tile's EM_SKIP: 2.7e8 terms of 2^-40 each are 2.4e-4 of a count)
-#ifndef NPR_TCS_WAVES
-#define NPR_TCS_WAVES 6
-#endif
-#ifndef NPR_TCS_DP_MASK
-#define NPR_TCS_DP_MASK 1
-#endif
+constexpr int TCS_EM_DEAD = -40;  // (k_em_tile's EM_SKIP: 2.7e8 terms of 2^-40 each are 2.4e-4 of a count)
+constexpr int TCS_WAVES = 6;      // wavefronts per SIMD the DP instances are compiled for
 // (the DP instances' forward rows too are written once and read once, much later: as non-temporal stores and loads 270.9 / 270.0 -> 263.5 / 263.2 ms
 // per launch of the reference's band, 8192 reads, alternating runs)
-#ifndef NPR_TCS_DP_AUX
-#define NPR_TCS_DP_AUX 2
-#endif
-constexpr int TCS_DP_AUX = NPR_TCS_DP_AUX;  // cache policy of the DP instances' row stores and loads (2: nt)
-constexpr bool TCS_DP_MASK = NPR_TCS_DP_MASK != 0;  // the DP instances' row stores and loads in the fast loops only in the lanes that hold a band cell (what halved the E-step's traffic): with plain stores and loads 268.6 / 269.2 -> 272.9 / 273.1 ms per launch of the reference's band, with non-temporal ones 262.1 / 262.2 -> 260.0 / 259.7: on since then
-#ifndef NPR_TCS_T_SGPR
-#define NPR_TCS_T_SGPR 1
-#endif
+constexpr int TCS_DP_AUX = 2;  // cache policy of the DP instances' row stores and loads (2: nt)
+// The DP instances store and load their rows in the fast loops only in the lanes that hold a band cell (what halved the E-step's traffic): with plain
+// stores and loads 268.6 / 269.2 -> 272.9 / 273.1 ms per launch of the reference's band, with non-temporal ones 262.1 / 262.2 -> 260.0 / 259.7.
 // EM: the Baum-Welch E-step on the same sweeps (k_em_tile's job, npr_kernel_tile.hip; nanopore/analyses/utils.py:509-528): the forward sweep also keeps
 // the other four states of every cell, and the backward sweep, instead of emitting posteriors, adds the posterior of every transition into the cells of
 // an anti-diagonal to 15 per-lane accumulators and of every emitted symbol to per-lane bins in LDS.  In this arithmetic a forward row comes back from
 // memory scaled ONCE by 2^(eF + eB - eTot) of its lane and block, so a count is three multiplies and no exponent; cells outside the band are exact
 // zeros on both sides, so there is no mask and no branch in the counting.
 template <bool SW, bool FLAT, bool EM = false>
-__global__ void __launch_bounds__(WAVE *(EM ? TCS_EM_NW : TCS_MAX_NW)) __attribute__((amdgpu_waves_per_eu(EM ? NPR_TCS_EM_WAVES : NPR_TCS_WAVES))) k_dp_tile_cs(KernelArgs a) {
+__global__ void __launch_bounds__(WAVE *(EM ? TCS_EM_NW : TCS_MAX_NW)) __attribute__((amdgpu_waves_per_eu(EM ? TCS_EM_WAVES : TCS_WAVES))) k_dp_tile_cs(KernelArgs a) {
     constexpr int NWMAX = EM ? TCS_EM_NW : TCS_MAX_NW;
     __shared__ CsLds<NWMAX> L;
     float *lbins = nullptr, *stageF = nullptr;
@@ -541,12 +510,10 @@ __global__ void __launch_bounds__(WAVE *(EM ? TCS_EM_NW : TCS_MAX_NW)) __attribu
         E.X = a.seq + x_off, E.Y = a.seq + y_off, E.lX = lX, E.lY = lY, E.lane = lane;
         {
             Trans tr = load_trans(E.mdl->T);
-#if NPR_TCS_T_SGPR
             tr.mm = unif(tr.mm), tr.sxm = unif(tr.sxm), tr.sym = unif(tr.sym), tr.lxm = unif(tr.lxm), tr.lym = unif(tr.lym);
             tr.msx = unif(tr.msx), tr.sxsx = unif(tr.sxsx), tr.sysx = unif(tr.sysx);
             tr.msy = unif(tr.msy), tr.sysy = unif(tr.sysy), tr.sxsy = unif(tr.sxsy);
             tr.mlx = unif(tr.mlx), tr.lxlx = unif(tr.lxlx), tr.mly = unif(tr.mly), tr.lyly = unif(tr.lyly);
-#endif
             E.tr = tr;
         }
         const DevModel *mdl = E.mdl;
@@ -628,7 +595,7 @@ __global__ void __launch_bounds__(WAVE *(EM ? TCS_EM_NW : TCS_MAX_NW)) __attribu
                 }
                 if constexpr (EM) {  // (the lanes that hold a band cell only: the E-step is bound by these bytes)
                     if (lanes_of(mk.lanes)) {
-                        tcs_store_row<TCS_EM_ROW_AUX>(rsF, voff + k * TCS_ROW_BYTES, io);
+                        tcs_store_row<TCS_EM_AUX>(rsF, voff + k * TCS_ROW_BYTES, io);
                         tcs_store_planes(rsX, 2 * voff + k * TCS_XROW_BYTES, 1024 + voff + k * TCS_XROW_BYTES, io);
                     }
                 } else {
@@ -665,22 +632,22 @@ __global__ void __launch_bounds__(WAVE *(EM ? TCS_EM_NW : TCS_MAX_NW)) __attribu
                     tcs_fwd_core<SW, FLAT>(E, Q.A, Q.B, Q.carry, Q.umA, Q.umB, Q.c, m0, er, bx, by, __builtin_amdgcn_readlane(fy.cur, yi));
                     if constexpr (EM) {
                         if (lanes_of(m0.lanes)) {
-                            tcs_store_row<TCS_EM_ROW_AUX>(rsF, vo, Q.A);
+                            tcs_store_row<TCS_EM_AUX>(rsF, vo, Q.A);
                             tcs_store_planes(rsX, 2 * voff + xo, 1024 + voff + xo, Q.A);
                         }
                     } else {
-                        if (!TCS_DP_MASK || lanes_of(m0.lanes)) tcs_store_row<TCS_DP_AUX>(rsF, vo, Q.A);
+                        if (lanes_of(m0.lanes)) tcs_store_row<TCS_DP_AUX>(rsF, vo, Q.A);
                     }
                     if (edge_lane) tcs_store_edge_fwd(rsE, ve, Q.A.c[R - 1], Q.umA, Q.e, Q.eh);
                     const Masks<R> m1 = row_masks(__builtin_amdgcn_readlane(wv16, 2 * i + 1));
                     tcs_fwd_core<SW, FLAT>(E, Q.B, Q.A, Q.carry, Q.umB, Q.umA, Q.c, m1, er + TCS_EDGE, bx, by, __builtin_amdgcn_readlane(fy.cur, yi + 1));
                     if constexpr (EM) {
                         if (lanes_of(m1.lanes)) {
-                            tcs_store_row<TCS_EM_ROW_AUX>(rsF, vo + TCS_ROW_BYTES, Q.B);
+                            tcs_store_row<TCS_EM_AUX>(rsF, vo + TCS_ROW_BYTES, Q.B);
                             tcs_store_planes(rsX, 2 * voff + xo + TCS_XROW_BYTES, 1024 + voff + xo + TCS_XROW_BYTES, Q.B);
                         }
                     } else {
-                        if (!TCS_DP_MASK || lanes_of(m1.lanes)) tcs_store_row<TCS_DP_AUX>(rsF, vo + TCS_ROW_BYTES, Q.B);
+                        if (lanes_of(m1.lanes)) tcs_store_row<TCS_DP_AUX>(rsF, vo + TCS_ROW_BYTES, Q.B);
                     }
                     if (edge_lane) tcs_store_edge_fwd(rsE, ve + 4 * TCS_EDGE, Q.B.c[R - 1], Q.umB, Q.e, Q.eh);
                     yi += 2, vo += 2 * TCS_ROW_BYTES, xo += 2 * TCS_XROW_BYTES, ve += 2 * 4 * TCS_EDGE, er += 2 * TCS_EDGE;
@@ -689,11 +656,11 @@ __global__ void __launch_bounds__(WAVE *(EM ? TCS_EM_NW : TCS_MAX_NW)) __attribu
                 tcs_fwd_core<SW, FLAT>(E, Q.A, Q.B, Q.carry, Q.umA, Q.umB, Q.c, m14, er, bx, by, __builtin_amdgcn_readlane(fy.cur, yi));
                 if constexpr (EM) {
                     if (lanes_of(m14.lanes)) {
-                        tcs_store_row<TCS_EM_ROW_AUX>(rsF, vo, Q.A);
+                        tcs_store_row<TCS_EM_AUX>(rsF, vo, Q.A);
                         tcs_store_planes(rsX, 2 * voff + xo, 1024 + voff + xo, Q.A);
                     }
                 } else {
-                    if (!TCS_DP_MASK || lanes_of(m14.lanes)) tcs_store_row<TCS_DP_AUX>(rsF, vo, Q.A);
+                    if (lanes_of(m14.lanes)) tcs_store_row<TCS_DP_AUX>(rsF, vo, Q.A);
                 }
                 if (edge_lane) tcs_store_edge_fwd(rsE, ve, Q.A.c[R - 1], Q.umA, Q.e, Q.eh);
                 wait_vm();
@@ -735,11 +702,7 @@ __global__ void __launch_bounds__(WAVE *(EM ? TCS_EM_NW : TCS_MAX_NW)) __attribu
 #pragma unroll
         for (int i = 0; i < 15; ++i) em_acc[i] = 0.f;
         // =============================== backward + posteriors ===============================
-#ifdef NPR_TCS_EM_EXP
-        if (alive && !(EM && (NPR_TCS_EM_EXP == 1 || NPR_TCS_EM_EXP == 3))) {
-#else
         if (alive) {
-#endif
             const float inv_tot = 1.0f / tot_m;
             const float thr_lo = a.threshold * tot_m * (1.0f - 1.0f / 1024.0f);
             const PairSink sink{a.px, a.py, a.pp, pair_off, pair_cap, xs, ys, a.threshold};
@@ -862,9 +825,6 @@ __global__ void __launch_bounds__(WAVE *(EM ? TCS_EM_NW : TCS_MAX_NW)) __attribu
                     S.f = v2i{0, 0}, S.x0 = v4i{0, 0, 0, 0}, S.x1 = v2i{0, 0};
                     if (row >= st.df && row <= st.dl) {  // uniform
                         const int k = row - st.df;
-#ifdef NPR_TCS_EM_EXP
-                        if (NPR_TCS_EM_EXP != 2)
-#endif
                         if (lanes_of(row_masks(w).lanes)) {
                             S.f = __builtin_amdgcn_raw_buffer_load_b64(rsF, voff + k * TCS_ROW_BYTES, 0, TCS_EM_AUX);
                             S.x0 = __builtin_amdgcn_raw_buffer_load_b128(rsX, 2 * voff + k * TCS_XROW_BYTES, 0, TCS_EM_AUX);
@@ -1119,7 +1079,7 @@ __global__ void __launch_bounds__(WAVE *(EM ? TCS_EM_NW : TCS_MAX_NW)) __attribu
                             em_fetch_w(d - 2 * i - 4, __builtin_amdgcn_readlane(wv16, 2 * i + 4), S0);
                             bases_up<R>(bym, __builtin_amdgcn_readlane(fy.cur, yi + 1));
                         } else {
-                            if (!TCS_DP_MASK || lanes_of(row_masks(__builtin_amdgcn_readlane(wv16, 2 * i + 1)).lanes)) {
+                            if (lanes_of(row_masks(__builtin_amdgcn_readlane(wv16, 2 * i + 1)).lanes)) {
                                 const v2i q = __builtin_amdgcn_raw_buffer_load_b64(rsF, vo, 0, TCS_DP_AUX);
                                 fa.v[0] = bitsf(q.x), fa.v[1] = bitsf(q.y);
                             }
@@ -1134,7 +1094,7 @@ __global__ void __launch_bounds__(WAVE *(EM ? TCS_EM_NW : TCS_MAX_NW)) __attribu
                             bases_up<R>(bym, __builtin_amdgcn_readlane(fy.cur, yi + 2));
                         } else {
                             emit(d - 2 * i, Q.B, fb, m0);
-                            if (!TCS_DP_MASK || lanes_of(row_masks(__builtin_amdgcn_readlane(wv16, 2 * i + 2)).lanes)) {
+                            if (lanes_of(row_masks(__builtin_amdgcn_readlane(wv16, 2 * i + 2)).lanes)) {
                                 const v2i q = __builtin_amdgcn_raw_buffer_load_b64(rsF, vo - TCS_ROW_BYTES, 0, TCS_DP_AUX);
                                 fb.v[0] = bitsf(q.x), fb.v[1] = bitsf(q.y);
                             }
@@ -1155,7 +1115,7 @@ __global__ void __launch_bounds__(WAVE *(EM ? TCS_EM_NW : TCS_MAX_NW)) __attribu
                             em_fetch_w(d - 18, __builtin_amdgcn_readlane(wv16, 18), S0);
                             bases_up<R>(bym, __builtin_amdgcn_readlane(fy.cur, yi + 1));
                         } else {
-                            if (!TCS_DP_MASK || lanes_of(row_masks(__builtin_amdgcn_readlane(wv16, 15)).lanes)) {
+                            if (lanes_of(row_masks(__builtin_amdgcn_readlane(wv16, 15)).lanes)) {
                                 const v2i q = __builtin_amdgcn_raw_buffer_load_b64(rsF, vo, 0, TCS_DP_AUX);
                                 fa.v[0] = bitsf(q.x), fa.v[1] = bitsf(q.y);
                             }
@@ -1265,14 +1225,10 @@ int launch_tile_cs(const KernelArgs &a, int NW, int grid, void *stream, bool sw,
 
 
 // k_dp_tile_cs<.., EM>: the E-step on the same stripes (static LDS; TCS_EM_NW wavefronts per task at most)
-int em_tile_cs_waves() {  // wavefronts per task (NPR_EM_CS_WAVES: bring-up)
-    const char *e = std::getenv("NPR_EM_CS_WAVES");
-    const int n = e ? std::atoi(e) : TCS_EM_NW;
-    return n >= 1 && n <= TCS_EM_NW ? n : TCS_EM_NW;
-}
-int em_tile_cs_waves_per_cu() {  // what the registers (NPR_TCS_EM_WAVES per SIMD) and the workgroups' static LDS leave room for
+int em_tile_cs_waves() { return TCS_EM_NW; }  // wavefronts per task
+int em_tile_cs_waves_per_cu() {  // what the registers (TCS_EM_WAVES per SIMD) and the workgroups' static LDS leave room for
     const int by_lds = static_cast<int>((160 * 1024) / (sizeof(CsLds<TCS_EM_NW>) + sizeof(CsEmLds))) * em_tile_cs_waves();
-    return std::min(4 * NPR_TCS_EM_WAVES, by_lds);
+    return std::min(4 * TCS_EM_WAVES, by_lds);
 }
 int launch_em_tile_cs(const KernelArgs &a, int NW, int grid, void *stream, bool sw, bool flat) {
     if (NW < 1 || NW > TCS_EM_NW) return static_cast<int>(hipErrorInvalidValue);

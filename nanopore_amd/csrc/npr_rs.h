@@ -27,9 +27,7 @@ namespace npr {
 
 namespace {
 
-#ifndef NPR_RS_T_SGPR_MIN_R
-#define NPR_RS_T_SGPR_MIN_R 4  // transitions in SGPRs from this many slots per lane on (below: VGPRs)
-#endif
+constexpr int RS_T_SGPR_MIN_R = 4;  // transitions in SGPRs from this many slots per lane on (below: VGPRs)
 constexpr int RS_K = NPR_RS_K;  // npr_device.h: shared with the host (scratch layout) and restated by the mirror
 static_assert(RS_K >= 2 && (RS_K & (RS_K - 1)) == 0 && (RS_K & 1) == 0, "renormalising rows must be even anti-diagonals");
 
@@ -103,7 +101,7 @@ __device__ __forceinline__ int feed8_get(Feed &f, const uint8_t *seq, int len, i
     }
     return __builtin_amdgcn_readlane(f.cur, off);
 }
-// ... and for the sweeps that run in blocks of RS_K anti-diagonals (NPR_RS_BLOCK): the window is looked after once per block --
+// ... and for the sweeps that run in blocks of RS_K anti-diagonals: the window is looked after once per block --
 // brought to where every base the block can ask for lies in `cur` -- and the steps read it without a test.  A block moves a stream's
 // index by at most RS_K / 2 own steps + RS_K rebases (and the rebase statements look one base further, into `nxt` if need be).
 constexpr int RS_FEED_BACK = 4;                               // bases kept behind the index (a frame that steps back; today's refill keeps none)
@@ -127,7 +125,7 @@ __device__ __forceinline__ int feed8_take(Feed &f, const uint8_t *seq, int len, 
 //   em4[6x + y] (4-byte stride: byte offset bx + by; the 25 entries of real bases and N lie in 25 different banks),
 //   ex2[x] = (shortGapX, longGapX) at byte offset bx (24-byte stride), eys[y] / eyl[y] = shortGapY / longGapY at byte offset by
 //   Code 5 (byte offsets RS_DEAD8 / RS_DEADX) is the base of a slot OUTSIDE the band: all its emissions are 0, so every state of the cell
-//   computed there is an exact zero (two selects per cell instead of an EXEC-mask region per cell row and the clearing of what the band left behind; NPR_RS_DEADCODE_MAX_R).
+//   computed there is an exact zero (two selects per cell instead of an EXEC-mask region per cell row and the clearing of what the band left behind; RS_DEADCODE_MAX_R).
 struct RsTables {
     float em4[36];            // [6 x + y]
     float ex2[6][RS_XS / 4];  // [x][0 .. 1]
@@ -135,11 +133,9 @@ struct RsTables {
 };
 constexpr int RS_DEAD8 = 5 * RS_YS, RS_DEADX = 5 * RS_XS;
 constexpr int RS_ZERO_EM = RS_DEADX;  // byte offset of an entry of em4 that is 0 and shares its bank with no live entry: (x = 5, y = 0), entry 30
-#ifndef NPR_RS_DEADCODE_MAX_R
-#define NPR_RS_DEADCODE_MAX_R 2  // slots per lane up to which it is used: one cell per lane gains 4 % (config 2: 1.75 -> 1.69 ms); two lost 1 % in round 3 and
-                                 // gain since round 4 (no switch terms, seven wavefronts per SIMD): a 1/8 shard of config 3 -- a launch that is its longest read's
-                                 // serial chain -- 44.5 -> 42.1 ms (two lane-mask regions and their branches fewer per step), the headline batch 139.0 -> 138.5
-#endif
+constexpr int RS_DEADCODE_MAX_R = 2;  // slots per lane up to which it is used: one cell per lane gains 4 % (config 2: 1.75 -> 1.69 ms); two lost 1 % in round 3 and
+                                      // gain since round 4 (no switch terms, seven wavefronts per SIMD): a 1/8 shard of config 3 -- a launch that is its longest read's
+                                      // serial chain -- 44.5 -> 42.1 ms (two lane-mask regions and their branches fewer per step), the headline batch 139.0 -> 138.5
 constexpr int RS_TABLE_FLOATS = sizeof(RsTables) / sizeof(float);
 __device__ __forceinline__ void rs_build_tables(RsTables *t, const DevModel *m, int tid, int nthreads) {
     for (int i = tid; i < 36; i += nthreads) {
@@ -159,14 +155,14 @@ __device__ __forceinline__ void rs_emissions(const char *tab, int bx, int by, fl
     eys = *reinterpret_cast<const float *>(tab + OFF_EYS + by), eyl = *reinterpret_cast<const float *>(tab + OFF_EYL + by);
 }
 
-// The emissions of one cell of a step.  Slots outside the band: up to NPR_RS_DEADCODE_MAX_R slots per lane they take the dead base code (every
+// The emissions of one cell of a step.  Slots outside the band: up to RS_DEADCODE_MAX_R slots per lane they take the dead base code (every
 // emission 0: the cell comes out as exact zeros), above that the step runs under the band's lane mask.
 // FLAT: every loaded model emits every base from every gap state with probability exactly 2^-2 (all shipped ones do: blasr_hmm_0 / _20 / _40;
 // a model trained by EM does not).  The four gap emissions then carry one bit -- in the band or not -- and come from a select instead of two
 // 8-byte LDS loads per cell and direction; the same factor 0.25f or 0.f multiplies the same sums, so not a bit changes.
 template <int R, bool FLAT>
 __device__ __forceinline__ void rs_cell_emissions(const char *tab, uint64_t in_band, int bx, int by, float &em, float &exs, float &exl, float &eys, float &eyl) {
-    if constexpr (R <= NPR_RS_DEADCODE_MAX_R) {
+    if constexpr (R <= RS_DEADCODE_MAX_R) {
         if constexpr (FLAT) {
             const int at = bx + by;
             em = *reinterpret_cast<const float *>(tab + (lanes_of(in_band) ? at : RS_ZERO_EM));  // (every slot outside the band reads ONE zero entry: a broadcast)
@@ -574,9 +570,7 @@ __device__ __forceinline__ void rs_rebase_origin(int &x0, int &y0, int dir) {
     x0 = xs, y0 = ys;
 }
 
-#ifndef NPR_RS_ONE_REBASE_MAX_R
-#define NPR_RS_ONE_REBASE_MAX_R 2  // slots per lane up to which rows and streams rebase in ONE asm statement (rs_rebase_all_*)
-#endif
+constexpr int RS_ONE_REBASE_MAX_R = 2;  // slots per lane up to which rows and streams rebase in ONE asm statement (rs_rebase_all_*)
 // A sweep's register state: the even anti-diagonals in A, the odd ones in B, the base streams and the rows' common exponent.
 template <int R>
 struct RsState {
@@ -595,7 +589,7 @@ __device__ __forceinline__ void rs_fwd_rebase(const StepEnv &E, int r, RsState<R
     const int dir = uni(r);
     const int offX = uni((Q.x0 + 64 * R - 1) - Q.S.fx.base);  // up: the X stream takes in X[(x0 + 1) + 64R - 2]
     const int offY = uni(Q.y0 - Q.S.fy.base);                  // down: the Y stream takes in Y[(y0 + 1) - 1]
-    if constexpr (R <= NPR_RS_ONE_REBASE_MAX_R) {  // rows and streams in one statement: one skip test per anti-diagonal
+    if constexpr (R <= RS_ONE_REBASE_MAX_R) {  // rows and streams in one statement: one skip test per anti-diagonal
         rs_rebase_all_fwd(Q.A, Q.B, Q.S.X, Q.S.Y, Q.S.fx, Q.S.fy, dir, offX, offY, uni(Q.S.xcap), uni(Q.S.ycap));
         rs_rebase_origin(Q.x0, Q.y0, dir);
     } else {
@@ -610,7 +604,7 @@ __device__ __forceinline__ void rs_bwd_rebase(const StepEnv &E, int r, RsState<R
     const int dir = uni(-r);
     const int offX = uni(Q.S.fx.base - (Q.x0 - 1));        // down (r > 0): the X stream takes in X[x0 - 1] at slot 0
     const int offY = uni(Q.S.fy.base - (Q.y0 - 64 * R));   // up (r < 0): the Y stream takes in Y[(y0 - 1) - (64R - 1)] on top
-    if constexpr (R <= NPR_RS_ONE_REBASE_MAX_R) {
+    if constexpr (R <= RS_ONE_REBASE_MAX_R) {
         rs_rebase_all_bwd(Q.A, Q.B, Q.S.X, Q.S.Y, Q.S.fx, Q.S.fy, dir, offX, offY, uni(Q.S.xcap), uni(Q.S.ycap));
         rs_rebase_origin(Q.x0, Q.y0, dir);
     } else {
@@ -650,7 +644,7 @@ __device__ __forceinline__ void rs_fwd_x_step(const StepEnv &E, RDiag<R> &io, co
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         float em, exs, exl, eys, eyl;
-        if constexpr (R <= NPR_RS_DEADCODE_MAX_R) {
+        if constexpr (R <= RS_DEADCODE_MAX_R) {
             rs_cell_emissions<R, FLAT>(E.ltab, mk.cell[r], S.X.b[r], S.Y.b[r], em, exs, exl, eys, eyl);
             o.c[r] = rs_fwd_cell<SW>(E.tr, p1.c[r], io.c[r], U.c[r], em, exs, exl, eys, eyl);
         } else {
@@ -658,7 +652,7 @@ __device__ __forceinline__ void rs_fwd_x_step(const StepEnv &E, RDiag<R> &io, co
             rs_put(io.c[r], mk.cell[r], [&] { return rs_fwd_cell<SW>(E.tr, p1.c[r], io.c[r], U.c[r], em, exs, exl, eys, eyl); });
         }
     }
-    if constexpr (R <= NPR_RS_DEADCODE_MAX_R) io = o;
+    if constexpr (R <= RS_DEADCODE_MAX_R) io = o;
     else rs_clear_outside<R>(io, mk, moved);
 }
 template <int R, bool CHK = true, bool SW = true, bool FLAT = false>
@@ -672,7 +666,7 @@ __device__ __forceinline__ void rs_fwd_y_step(const StepEnv &E, RDiag<R> &io, co
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         float em, exs, exl, eys, eyl;
-        if constexpr (R <= NPR_RS_DEADCODE_MAX_R) {
+        if constexpr (R <= RS_DEADCODE_MAX_R) {
             rs_cell_emissions<R, FLAT>(E.ltab, mk.cell[r], S.X.b[r], S.Y.b[r], em, exs, exl, eys, eyl);
             o.c[r] = rs_fwd_cell<SW>(E.tr, L.c[r], io.c[r], p1.c[r], em, exs, exl, eys, eyl);
         } else {
@@ -680,7 +674,7 @@ __device__ __forceinline__ void rs_fwd_y_step(const StepEnv &E, RDiag<R> &io, co
             rs_put(io.c[r], mk.cell[r], [&] { return rs_fwd_cell<SW>(E.tr, L.c[r], io.c[r], p1.c[r], em, exs, exl, eys, eyl); });
         }
     }
-    if constexpr (R <= NPR_RS_DEADCODE_MAX_R) io = o;
+    if constexpr (R <= RS_DEADCODE_MAX_R) io = o;
     else rs_clear_outside<R>(io, mk, moved);
 }
 // One backward anti-diagonal d: `io` holds d+2 on entry and d on exit, `s1` holds d+1.  S.X / S.Y: X[x]*8, Y[y]*8.
@@ -695,7 +689,7 @@ __device__ __forceinline__ void rs_bwd_x_step(const StepEnv &E, RDiag<R> &io, co
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         float em, exs, exl, eys, eyl;
-        if constexpr (R <= NPR_RS_DEADCODE_MAX_R) {
+        if constexpr (R <= RS_DEADCODE_MAX_R) {
             rs_cell_emissions<R, FLAT>(E.ltab, mk.cell[r], S.X.b[r], S.Y.b[r], em, exs, exl, eys, eyl);
             o.c[r] = rs_bwd_cell<SW>(E.tr, io.c[r], s1.c[r], Ys.c[r], em, exs, exl, eys, eyl);
         } else {
@@ -703,7 +697,7 @@ __device__ __forceinline__ void rs_bwd_x_step(const StepEnv &E, RDiag<R> &io, co
             rs_put(io.c[r], mk.cell[r], [&] { return rs_bwd_cell<SW>(E.tr, io.c[r], s1.c[r], Ys.c[r], em, exs, exl, eys, eyl); });
         }
     }
-    if constexpr (R <= NPR_RS_DEADCODE_MAX_R) io = o;
+    if constexpr (R <= RS_DEADCODE_MAX_R) io = o;
     else rs_clear_outside<R>(io, mk, moved);
 }
 template <int R, bool CHK = true, bool SW = true, bool FLAT = false>
@@ -717,7 +711,7 @@ __device__ __forceinline__ void rs_bwd_y_step(const StepEnv &E, RDiag<R> &io, co
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         float em, exs, exl, eys, eyl;
-        if constexpr (R <= NPR_RS_DEADCODE_MAX_R) {
+        if constexpr (R <= RS_DEADCODE_MAX_R) {
             rs_cell_emissions<R, FLAT>(E.ltab, mk.cell[r], S.X.b[r], S.Y.b[r], em, exs, exl, eys, eyl);
             o.c[r] = rs_bwd_cell<SW>(E.tr, io.c[r], Xs.c[r], s1.c[r], em, exs, exl, eys, eyl);
         } else {
@@ -725,7 +719,7 @@ __device__ __forceinline__ void rs_bwd_y_step(const StepEnv &E, RDiag<R> &io, co
             rs_put(io.c[r], mk.cell[r], [&] { return rs_bwd_cell<SW>(E.tr, io.c[r], Xs.c[r], s1.c[r], em, exs, exl, eys, eyl); });
         }
     }
-    if constexpr (R <= NPR_RS_DEADCODE_MAX_R) io = o;
+    if constexpr (R <= RS_DEADCODE_MAX_R) io = o;
     else rs_clear_outside<R>(io, mk, moved);
 }
 
@@ -739,29 +733,17 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rs_task_rsrc(char *F) {
 // cache policy of the forward rows' stores and loads.  Non-temporal (2), which pays in the stripe kernels (npr_kernel_tile_cs.hip), costs here: the headline
 // launch 134.7 / 134.9 -> 139.8 / 139.7 ms, alternating runs (the stores alone 134.1 -> 137.6 / 138.6, the loads alone 136.7 / 136.7) -- a frame kernel's rows are
 // read back by the partner sweep from the L2 they were written to.
-#ifndef NPR_RS_ROW_AUX
-#define NPR_RS_ROW_AUX 0
-#endif
-#ifndef NPR_RS_PAIR_NT
-#define NPR_RS_PAIR_NT 0  // the posterior triples as non-temporal stores (read once, by the finish): nothing on the headline launch (132.6 / 132.6 ms without, 132.9 / 132.9 with)
-#endif
-#ifndef NPR_RS_ROW_ST_AUX
-#define NPR_RS_ROW_ST_AUX NPR_RS_ROW_AUX
-#endif
-#ifndef NPR_RS_ROW_LD_AUX
-#define NPR_RS_ROW_LD_AUX NPR_RS_ROW_AUX
-#endif
-constexpr int RS_ROW_ST_AUX = NPR_RS_ROW_ST_AUX, RS_ROW_LD_AUX = NPR_RS_ROW_LD_AUX;
+constexpr int RS_ROW_AUX = 0;
 template <int R>
 __device__ __forceinline__ void rs_store_row(__amdgpu_buffer_rsrc_t rs, const RDiag<R> &C, const RowCtl<R> &ct, int voff) {
     if (lanes_of(ct.mk.lanes)) {
         const int vo = voff + static_cast<int>(ct.soff >> 1);
         if constexpr (R == 1) {
-            __builtin_amdgcn_raw_buffer_store_b32(fbits(C.c[0].m), rs, vo, 0, RS_ROW_ST_AUX);
+            __builtin_amdgcn_raw_buffer_store_b32(fbits(C.c[0].m), rs, vo, 0, RS_ROW_AUX);
         } else if constexpr (R == 2) {
-            __builtin_amdgcn_raw_buffer_store_b64(v2i{fbits(C.c[0].m), fbits(C.c[1].m)}, rs, vo, 0, RS_ROW_ST_AUX);
+            __builtin_amdgcn_raw_buffer_store_b64(v2i{fbits(C.c[0].m), fbits(C.c[1].m)}, rs, vo, 0, RS_ROW_AUX);
         } else {
-            __builtin_amdgcn_raw_buffer_store_b128(v4i{fbits(C.c[0].m), fbits(C.c[1].m), fbits(C.c[2].m), fbits(C.c[3].m)}, rs, vo, 0, RS_ROW_ST_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(v4i{fbits(C.c[0].m), fbits(C.c[1].m), fbits(C.c[2].m), fbits(C.c[3].m)}, rs, vo, 0, RS_ROW_AUX);
         }
     }
 }
@@ -778,12 +760,12 @@ __device__ __forceinline__ void rs_load_row(__amdgpu_buffer_rsrc_t rs, RFRow<R> 
     {
         const int vo = voff + static_cast<int>(ct.soff >> 1);
         if constexpr (R == 1) {
-            f.v[0] = bitsf(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, 0, RS_ROW_LD_AUX));
+            f.v[0] = bitsf(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, 0, RS_ROW_AUX));
         } else if constexpr (R == 2) {
-            const v2i q = __builtin_amdgcn_raw_buffer_load_b64(rs, vo, 0, RS_ROW_LD_AUX);
+            const v2i q = __builtin_amdgcn_raw_buffer_load_b64(rs, vo, 0, RS_ROW_AUX);
             f.v[0] = bitsf(q.x), f.v[1] = bitsf(q.y);
         } else {
-            const v4i q = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, RS_ROW_LD_AUX);
+            const v4i q = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, RS_ROW_AUX);
             f.v[0] = bitsf(q.x), f.v[1] = bitsf(q.y), f.v[2] = bitsf(q.z), f.v[3] = bitsf(q.w);
         }
     }
@@ -815,15 +797,11 @@ __device__ __forceinline__ void rs_emit_pairs(const PairSink &S, const RDiag<R> 
                 const int slot = cnt + before;
                 if (lanes_of(hit[r]) && slot < S.cap) {  // (S.off is 0: the sink's pointers are the task's; unsigned slots: scalar base + 32-bit offset)
                     const uint32_t u = static_cast<uint32_t>(slot) << 2;  // a byte offset that fits 32 bits (pair_cap < 2^29): one shift, the arrays' addresses stay scalar
-#if NPR_RS_PAIR_NT
-                    __builtin_nontemporal_store(x0 + jr[r] - 1 + S.xs, &rs_at<int32_t>(S.px, u));
-                    __builtin_nontemporal_store(y0 - jr[r] - 1 + S.ys, &rs_at<int32_t>(S.py, u));
-                    __builtin_nontemporal_store(p[r], &rs_at<float>(S.pp, u));
-#else
+                    // (plain stores: as non-temporal stores -- the triples are read once, by the finish -- they measured nothing on the headline
+                    // launch, 132.6 / 132.6 ms without, 132.9 / 132.9 with)
                     rs_at<int32_t>(S.px, u) = x0 + jr[r] - 1 + S.xs;
                     rs_at<int32_t>(S.py, u) = y0 - jr[r] - 1 + S.ys;
                     rs_at<float>(S.pp, u) = p[r];
-#endif
                 }
                 cnt += __popcll(hit[r]);
             }
@@ -856,10 +834,8 @@ template <int R>
 __device__ __forceinline__ int ctl_rebase_of(uint32_t w1) {  // the rebase a control word asks for, whatever the class's word format
     return R == 2 ? static_cast<int>((w1 >> 28) & 3u) - 1 : static_cast<int>((w1 >> 26) & 3u) - 1;
 }
-#ifndef NPR_RS_WAVES2
-#define NPR_RS_WAVES2 7  // wavefronts per SIMD the R = 2 kernel is compiled for: 72 VGPRs, six spilled outside the sweeps' loops (round 4, without the
-                         // short-gap switch terms: 138.1 ms at 7 per SIMD, 140.4 at 6, 138.6 at 8 on the headline batch; round 3, with them: 6 was best)
-#endif
+constexpr int RS_WAVES2 = 7;  // wavefronts per SIMD the R = 2 kernel is compiled for: 72 VGPRs, six spilled outside the sweeps' loops (round 4, without the
+                              // short-gap switch terms: 138.1 ms at 7 per SIMD, 140.4 at 6, 138.6 at 8 on the headline batch; round 3, with them: 6 was best)
 #define RS_FWD_REBASE(r) rs_fwd_rebase<R>(E, (r), Q)
 #define RS_BWD_REBASE(r) rs_bwd_rebase<R>(E, (r), Q)
 

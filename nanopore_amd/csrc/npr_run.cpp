@@ -44,11 +44,6 @@ int32_t npr_batch_run(npr_batch *b, float *kernel_ms) {
     }
     std::lock_guard<std::mutex> arena_lock(ctx->arena->mu);  // until the DP pass has finished
     ++ctx->arena->epoch;
-    DevBuf<unsigned long long> d_prof;  // NPR_TILE_PROF=1 (bring-up): wait cycles of the stripe kernel's wavefronts
-    if (std::getenv("NPR_TILE_PROF")) {
-        if (d_prof.alloc(8) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_batch_run: hipMalloc");
-        HIP_TRY(ctx, hipMemsetAsync(d_prof.p, 0, d_prof.bytes(), ctx->stream));
-    }
     HIP_TRY(ctx, hipMemsetAsync(b->d_queue.p, 0, sizeof(int32_t) * kQueueSlots, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     // all classes at once, the smallest first, each on its own stream; the main stream waits for all of them,
@@ -81,7 +76,6 @@ int32_t npr_batch_run(npr_batch *b, float *kernel_ms) {
         a.wcap = L.wcap;
         a.slot_base = L.slot_base;
         a.region = L.own_regions ? b->d_region.p + L.region_first : nullptr;
-        a.prof = d_prof.p;
         const KClass &kc = kClassTab[L.cls];
         const int rc = kc.kind == K_MID   ? launch_mid_rs(a, kc.R, L.grid, s, sw, flat)
                        : kc.kind == K_RS    ? launch_rs(a, kc.R, L.grid, s, sw, flat)
@@ -97,12 +91,6 @@ int32_t npr_batch_run(npr_batch *b, float *kernel_ms) {
     HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
-    if (d_prof.p) {
-        unsigned long long pf[8];
-        HIP_TRY(ctx, hipMemcpy(pf, d_prof.p, sizeof(pf), hipMemcpyDeviceToHost));
-        std::fprintf(stderr, "[npr tile prof] wavefront cycles: waiting for a neighbour %.3g, for own stores %.3g, at barriers %.3g, total %.3g (k_dp_tile_cs built with -DNPR_TCS_PROF: neighbour, general step, fast loops, total; stripe set-up %.3g, barriers %.3g, task set-up %.3g, own stores %.3g)\n",
-                     (double)pf[0], (double)pf[1], (double)pf[2], (double)pf[3], (double)pf[4], (double)pf[5], (double)pf[6], (double)pf[7]);
-    }
     // The row-scaled kernels report the tasks for which one exponent per row may not have been enough (TASK_RERUN,
     // npr_device.h): those run again here, with the per-cell-exponent kernel of their frame class, on the scratch regions the
     // first launch had.  Rare -- a row of the alignment ~110 binary orders below the product of the row's largest forward and
@@ -226,8 +214,7 @@ int32_t npr_batch_expectations(npr_batch *b, double *T_exp, double *E_exp, doubl
             // 127 / 161 / 223 VGPRs and 9 KiB of LDS bins per wavefront: 16 / 12 / 8 wavefronts per CU
             l.stair_R = kClassTab[dl.cls].R;
             l.lds = em_stair_lds_bytes();
-            int em_waves = l.stair_R == 4 ? 8 : (l.stair_R == 2 ? 12 : 16);
-            if (ctx->opt[NPR_OPT_EM_WAVES] > 0) em_waves = static_cast<int>(std::min<int64_t>(32, ctx->opt[NPR_OPT_EM_WAVES]));  // bring-up
+            const int em_waves = l.stair_R == 4 ? 8 : (l.stair_R == 2 ? 12 : 16);
             l.grid = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(l.count, static_cast<int64_t>(ctx->cu_count) * em_waves)));
             launches.push_back(l);
             continue;
@@ -334,7 +321,7 @@ int32_t npr_batch_expectations(npr_batch *b, double *T_exp, double *E_exp, doubl
     std::vector<const L *> order;
     for (const auto &l : launches) order.push_back(&l);
     std::stable_sort(order.begin(), order.end(), [](const L *x, const L *y) { return x->cells < y->cells; });
-    bool serial = ctx->opt[NPR_OPT_EM_SERIAL] != 0;  // A/B switch: one launch after the other, as before round 3
+    bool serial = false;
     for (const auto &l : launches) serial |= l.uses_others_regions;
     bool sw = false;  // (as npr_batch_run: the column-scaled kernel leaves out the short-gap switch terms no loaded model has)
     for (int sl = 0; sl < NPR_MAX_MODELS; ++sl)

@@ -245,7 +245,6 @@ static int32_t batch_create_at_impl(npr_ctx *ctx, const npr_params *params, int6
     const bool force_generic = ctx->opt[NPR_OPT_KERNEL] == 1;  // no register kernel (A/B runs, tests)
     const int lds_max_w = generic_max_wcap();
     const bool no_wide = ctx->opt[NPR_OPT_NO_WIDE] != 0;  // no multi-wavefront register kernel (A/B runs, tests)
-    const int cmin = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(kSchedClasses, ctx->opt[NPR_OPT_CLASS_MIN])));  // bring-up: smallest register class to use
     const bool use_tile = !force_generic && ctx->opt[NPR_OPT_NO_TILE] == 0;  // (E-step batches too: k_em_tile)
     // E-step batches whose stripe tasks run in column-scaled arithmetic (k_dp_tile_cs's E-step instance, below): the four-slot frame class goes there
     // too -- k_em_stair<4> is one long dependent chain per task.  (Not the two-slot class: bands of 150 / 200 cells gain 19 / 9 % on the stripes, but
@@ -263,7 +262,7 @@ static int32_t batch_create_at_impl(npr_ctx *ctx, const npr_params *params, int6
     int64_t ctl_entries = kCtlFrontPad;
     for (int64_t k = 0; k < ntasks; ++k) {
         if (force_generic) break;
-        for (int c = cmin; c < kSchedClasses; ++c) {
+        for (int c = 0; c < kSchedClasses; ++c) {
             if (kClassTab[c].kind == K_WIDE && (use_tile || no_wide)) continue;
             if (em_stripes_cs && kClassTab[c].kind == K_STAIR && kClassTab[c].R == 4) continue;
             if (kClassTab[c].kind == K_STAIR && !stair_fits(static_cast<int64_t>(pseg[k].lX) + pseg[k].lY + 1, kClassTab[c].slots())) continue;
@@ -553,7 +552,6 @@ static int32_t batch_create_at_impl(npr_ctx *ctx, const npr_params *params, int6
             L.threads = 512;
             waves_per_cu = 2;  // workgroups per CU
         }
-        if (ctx->opt[NPR_OPT_WAVES_PER_CU] > 0) waves_per_cu = static_cast<int>(std::min<int64_t>(64, ctx->opt[NPR_OPT_WAVES_PER_CU]));
         int64_t grid = std::min<int64_t>(L.count, static_cast<int64_t>(ctx->cu_count) * waves_per_cu);
         L.grid = static_cast<int>(std::max<int64_t>(1, grid));
         if (std::getenv("NPR_TIMING"))
@@ -577,9 +575,7 @@ static int32_t batch_create_at_impl(npr_ctx *ctx, const npr_params *params, int6
     int64_t stair_grid = 0;
     for (auto &L : b->launches)
         if (is_one_wave_kind(kClassTab[L.cls].kind)) stair_grid += L.grid;
-    int64_t var_min_bytes = int64_t(32) << 30;  // uniform stair scratch above this goes variable (NPR_OPT_VARIABLE_SCRATCH: 1 always, 2 never; tests)
-    if (ctx->opt[NPR_OPT_VARIABLE_SCRATCH] == 1) var_min_bytes = 0;
-    if (ctx->opt[NPR_OPT_VARIABLE_SCRATCH] == 2) var_min_bytes = int64_t(1) << 60;
+    const int64_t var_min_bytes = int64_t(32) << 30;  // uniform stair scratch above this goes variable
     b->variable_regions = b->params.mode != NPR_MODE_EXPECTATIONS && stair_grid > 0 && stair_grid * b->slot_stride * 8 >= var_min_bytes &&
                           !force_generic;
     if (any_pair) b->variable_regions = true;  // (their regions hold two sets of rows: not a layout the E-step kernels know)

@@ -1,5 +1,5 @@
-"""tools/shard_dp.py tag[:option=value,...]... -- DP launch time of library variants (NPR_LIB) and context options (nanopore_amd/_lib.py
-OPTIONS, e.g. default:pair=2) on a 1/8 shard of configs[3] (6250 reads: the launch lasts as long as its longest read), on config 2
+"""tools/shard_dp.py [option=value,...]... -- DP launch time under context options (nanopore_amd/_lib.py OPTIONS, e.g. pair=2;
+`default`: none) on a 1/8 shard of configs[3] (6250 reads: the launch lasts as long as its longest read), on config 2
 and on the headline batch, each in its own process.  Bring-up tool."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,8 +27,7 @@ b = ctx.stage_csr(R.make_params(band_mode=R.BAND_FIXED, fixed_width=W), w["ref"]
 out["ns_ms"] = round(min(b.run() for _ in range(3)), 2); b.close()
 print(json.dumps(out))
 '''
-for arg in sys.argv[1:]:
-    tag, _, opts = arg.partition(":")
-    lib = os.path.join(ROOT, "nanopore_amd", "libnprealign.so" if tag == "default" else "libnprealign_%s.so" % tag)
-    p = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT, "opts": opts}], env=dict(os.environ, NPR_LIB=lib), capture_output=True, text=True)
+for arg in sys.argv[1:] or ["default"]:
+    opts = "" if arg == "default" else arg
+    p = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT, "opts": opts}], capture_output=True, text=True)
     print(arg, p.stdout.strip().splitlines()[-1] if p.stdout.strip() else p.stderr[-500:], flush=True)
