@@ -279,6 +279,32 @@ int32_t npr_align_stats(npr_ctx *ctx, int64_t n_reads, int64_t n_refs, const uin
                         const int32_t *ref_index, const uint8_t *read, const int64_t *read_off, const int32_t *ops,
                         const int64_t *ops_off, const int64_t *start, int32_t *stats /* [n_reads][NPR_STATS_WORDS] */);
 
+/* ---- k-mer tables on the device (the reference's KmerAnalysis and IndelKmerAnalysis) ----
+ * Base codes are npr_encode_bases': A C G T -> 0..3 in either letter case, anything else -> 4.  A k-mer's bin is its base-4
+ * number, first base most significant; bin 4^k takes the k-mers that hold a code 4.  1 <= k <= 6 (NPR_ERR_INVALID otherwise);
+ * a table has 4^k + 1 int64 counters and is overwritten. */
+
+/* All windows of n_seqs ASCII sequences (sequence i = seq[seq_off[i] .. seq_off[i + 1])), forward strand:
+ * nanopore/analyses/kmerAnalysis.py:16-17 and :24-25 -- s[i - k : i] for i in k .. len(s) - 1, so the last window of a
+ * sequence is left out, as `xrange(kmerSize, len(seq))` leaves it out.  The reverse complements the reference adds
+ * (:20, :28) are a permutation of the bins and are the caller's. */
+int32_t npr_kmer_counts(npr_ctx *ctx, int32_t k, int64_t n_seqs, const uint8_t *seq, const int64_t *seq_off,
+                        int64_t *counts /* [4^k + 1] */);
+/* The k-mers that straddle a gap of an alignment, of the read (read_counts) and of the reference (ref_counts):
+ * nanopore/analyses/indelKmerAnalysis.py:11-19 (indelKmerFinder) over the read side and the reference side of
+ * record.aligned_pairs (:32-40: s = readSeq[start : end + 1], s = refSeq[start : end + 1]); the reversed k-mers the
+ * reference adds (:36, :40) are a permutation of the bins and are the caller's.  Alignments as for npr_align_stats.
+ * Positions are window coordinates: they count from the first base the cigar consumes, where the reference indexes
+ * record.query from the start of SEQ -- the same thing for a record without soft clips.  A record whose cigar runs
+ * past its sequences adds nothing and makes the call return NPR_ERR_INVALID (the tables hold the other records). */
+int32_t npr_align_indel_kmers(npr_ctx *ctx, int32_t k, int64_t n_reads, int64_t n_refs, const uint8_t *ref, const int64_t *ref_off,
+                              const int32_t *ref_index, const uint8_t *read, const int64_t *read_off, const int32_t *ops,
+                              const int64_t *ops_off, const int64_t *start, int64_t *read_counts, int64_t *ref_counts /* [4^k + 1] each */);
+/* ... of the alignments npr_batch_finish just produced, where they lie (indelKmerAnalysis.py:29-40 over the realigned SAM
+ * without writing it first): to npr_align_indel_kmers what npr_batch_align_stats is to npr_align_stats.  Reads that
+ * failed add nothing. */
+int32_t npr_batch_indel_kmers(npr_batch *b, int32_t k, int64_t *read_counts, int64_t *ref_counts /* [4^k + 1] each */);
+
 /* Expected base counts per reference position from the posterior pairs of a finished batch, on the device (SURVEY.md 8f
  * next #4): what marginAlignSnpCaller.py:150-155 collates from the --outputAllPosteriorProbs files, one text line at a time:
  * every pair (refPos, readPos, p) of a selected read adds p to expect[(first row of its reference + refPos) * 4 + base] for

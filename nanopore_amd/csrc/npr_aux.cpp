@@ -1,39 +1,146 @@
-// npr_aux.cpp -- post-alignment statistics on the device, base expectations of the marginAlign SNP caller, the planner cross-check (coverage.py / substitutions.py / indels.py; marginAlignSnpCaller.py:150-155)
+// npr_aux.cpp -- post-alignment statistics and k-mer tables on the device, base expectations of the marginAlign SNP caller, the planner cross-check (coverage.py / substitutions.py / indels.py; kmerAnalysis.py / indelKmerAnalysis.py; marginAlignSnpCaller.py:150-155)
 // (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
 #include "npr_api_internal.h"
+
+#include <functional>
 
 extern "C" {
 
 namespace {
 
-// the kernel over n reads whose cigars are either packed on the device already (d_ops / d_off) or given on the host
+// what StatsArgs points to besides the base codes, uploaded: n reads whose cigars are either packed on the device already (d_ops / d_off) or given on the host
+struct StatsUpload {
+    DevBuf<uint32_t> ops;
+    DevBuf<int64_t> off;
+    DevBuf<int32_t> so;
+    DevBuf<StatsSeg> sg;
+};
+int32_t stage_stats_args(npr_ctx *ctx, int64_t n, const uint32_t *d_ops, const int64_t *d_off, const std::vector<uint32_t> *h_ops,
+                         const std::vector<int64_t> *h_off, const std::vector<int32_t> &seg_off, const std::vector<StatsSeg> &segs,
+                         const uint8_t *d_seq, StatsUpload &up, StatsArgs &a) {
+    if (n >= (int64_t(1) << 31)) return fail(ctx, NPR_ERR_INVALID, "npr_align_stats: too many reads");
+    hipError_t e;
+    if (!d_ops) {
+        if ((e = up.ops.alloc(h_ops->size())) != hipSuccess || (e = up.off.alloc(h_off->size())) != hipSuccess)
+            return fail(ctx, NPR_ERR_NOMEM, "npr_align_stats: hipMalloc", e);
+        if (!h_ops->empty()) HIP_TRY(ctx, hipMemcpyAsync(up.ops.p, h_ops->data(), up.ops.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(up.off.p, h_off->data(), up.off.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        d_ops = up.ops.p, d_off = up.off.p;
+    }
+    if ((e = up.so.alloc(seg_off.size())) != hipSuccess || (e = up.sg.alloc(segs.size())) != hipSuccess)
+        return fail(ctx, NPR_ERR_NOMEM, "npr_align_stats: hipMalloc", e);
+    HIP_TRY(ctx, hipMemcpyAsync(up.so.p, seg_off.data(), up.so.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    if (!segs.empty()) HIP_TRY(ctx, hipMemcpyAsync(up.sg.p, segs.data(), up.sg.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    a = StatsArgs{static_cast<int32_t>(n), d_off, d_ops, up.so.p, up.sg.p, d_seq, nullptr};
+    return NPR_OK;
+}
+
+// k_align_stats over them
 int32_t run_align_stats(npr_ctx *ctx, int64_t n, const uint32_t *d_ops, const int64_t *d_off, const std::vector<uint32_t> *h_ops,
                         const std::vector<int64_t> *h_off, const std::vector<int32_t> &seg_off, const std::vector<StatsSeg> &segs,
                         const uint8_t *d_seq, int32_t *stats) {
-    if (n >= (int64_t(1) << 31)) return fail(ctx, NPR_ERR_INVALID, "npr_align_stats: too many reads");
-    DevBuf<uint32_t> ops;
-    DevBuf<int64_t> off;
-    DevBuf<int32_t> so, out;
-    DevBuf<StatsSeg> sg;
+    StatsUpload up;
+    StatsArgs a;
+    const int32_t rs = stage_stats_args(ctx, n, d_ops, d_off, h_ops, h_off, seg_off, segs, d_seq, up, a);
+    if (rs != NPR_OK) return rs;
+    DevBuf<int32_t> out;
     hipError_t e;
-    if (!d_ops) {
-        if ((e = ops.alloc(h_ops->size())) != hipSuccess || (e = off.alloc(h_off->size())) != hipSuccess)
-            return fail(ctx, NPR_ERR_NOMEM, "npr_align_stats: hipMalloc", e);
-        if (!h_ops->empty()) HIP_TRY(ctx, hipMemcpyAsync(ops.p, h_ops->data(), ops.bytes(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(off.p, h_off->data(), off.bytes(), hipMemcpyHostToDevice, ctx->stream));
-        d_ops = ops.p, d_off = off.p;
-    }
-    if ((e = so.alloc(seg_off.size())) != hipSuccess || (e = sg.alloc(segs.size())) != hipSuccess ||
-        (e = out.alloc(static_cast<size_t>(n) * NPR_STATS_WORDS)) != hipSuccess)
-        return fail(ctx, NPR_ERR_NOMEM, "npr_align_stats: hipMalloc", e);
-    HIP_TRY(ctx, hipMemcpyAsync(so.p, seg_off.data(), so.bytes(), hipMemcpyHostToDevice, ctx->stream));
-    if (!segs.empty()) HIP_TRY(ctx, hipMemcpyAsync(sg.p, segs.data(), sg.bytes(), hipMemcpyHostToDevice, ctx->stream));
-    StatsArgs a{static_cast<int32_t>(n), d_off, d_ops, so.p, sg.p, d_seq, out.p};
+    if ((e = out.alloc(static_cast<size_t>(n) * NPR_STATS_WORDS)) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_align_stats: hipMalloc", e);
+    a.out = out.p;
     const int rc = launch_align_stats(a, ctx->stream);
     if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_align_stats launch", static_cast<hipError_t>(rc));
     HIP_TRY(ctx, hipMemcpyAsync(stats, out.p, out.bytes(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NPR_OK;
+}
+
+// k_indel_kmers over them (every read with one piece, its whole window, or none); *bad: some cigar ran past its piece
+int32_t run_indel_kmers(npr_ctx *ctx, int32_t k, int64_t n, const uint32_t *d_ops, const int64_t *d_off, const std::vector<uint32_t> *h_ops,
+                        const std::vector<int64_t> *h_off, const std::vector<int32_t> &seg_off, const std::vector<StatsSeg> &segs,
+                        const uint8_t *d_seq, int64_t *read_counts, int64_t *ref_counts, int32_t *bad) {
+    StatsUpload up;
+    IndelKmerArgs a{};
+    const int32_t rs = stage_stats_args(ctx, n, d_ops, d_off, h_ops, h_off, seg_off, segs, d_seq, up, a.s);
+    if (rs != NPR_OK) return rs;
+    const size_t nb = static_cast<size_t>(kmer_bins(k));
+    DevBuf<unsigned long long> tab;  // read-side table, reference-side table, the flag
+    hipError_t e;
+    if ((e = tab.alloc(2 * nb + 1)) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_align_indel_kmers: hipMalloc", e);
+    HIP_TRY(ctx, hipMemsetAsync(tab.p, 0, tab.bytes(), ctx->stream));
+    a.k = k, a.read_counts = tab.p, a.ref_counts = tab.p + nb, a.bad = reinterpret_cast<int32_t *>(tab.p + 2 * nb);
+    const int rc = launch_indel_kmers(a, ctx->stream);
+    if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_indel_kmers launch", static_cast<hipError_t>(rc));
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the tables leave the device as int64");
+    HIP_TRY(ctx, hipMemcpyAsync(read_counts, a.read_counts, nb * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ref_counts, a.ref_counts, nb * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(bad, a.bad, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return NPR_OK;
+}
+
+// the cigars npr_batch_finish produced, where they lie (packed on the device after the device MEA stage) or uploaded: run(d_ops, d_off, h_ops, h_off)
+using CigarFn = std::function<int32_t(const uint32_t *, const int64_t *, const std::vector<uint32_t> *, const std::vector<int64_t> *)>;
+int32_t with_batch_cigars(npr_batch *b, const CigarFn &run) {
+    npr_ctx *ctx = b->ctx;
+    const int64_t n = b->n_reads;
+    std::unique_lock<std::mutex> arena_lock(ctx->arena->mu);  // the resident cigars lie in the arena
+    if (b->dev_ops && b->dev_ops_epoch == ctx->arena->epoch) return run(b->dev_ops, b->dev_od, nullptr, nullptr);
+    arena_lock.unlock();
+    ensure_packed_form(b);
+    std::vector<uint32_t> packed(b->packed.get(), b->packed.get() + b->ops_off[n]);
+    return run(nullptr, nullptr, &packed, &b->ops_off);
+}
+
+// alignments given on the host (npr_align_stats, npr_align_indel_kmers): every read's window -- the reference / read bases its cigar consumes --
+// encoded into one code buffer, one piece per read, the cigars packed; bad[i]: the cigar is malformed or runs past its sequences (it is emptied)
+struct Windows {
+    std::vector<int64_t> off;
+    std::vector<int32_t> seg_off, bad;
+    std::vector<StatsSeg> segs;
+    std::unique_ptr<uint8_t[]> codes;
+    int64_t code_bytes = 0;
+    std::vector<uint32_t> packed;
+};
+void encode_windows(npr_ctx *ctx, int64_t n, int64_t n_refs, const uint8_t *ref, const int64_t *ref_off, const int32_t *ref_index, const uint8_t *read,
+                    const int64_t *read_off, const int32_t *ops, const int64_t *ops_off, const int64_t *start, Windows &w) {
+    std::vector<int64_t> woff(n + 1, 0);
+    w.off.assign(ops_off, ops_off + n + 1);
+    w.seg_off.resize(n + 1), w.bad.assign(n, 0), w.segs.resize(n);
+    std::vector<int32_t> &bad = w.bad;
+    std::vector<int64_t> cx(n), cy(n);
+    parallel_for(n, ctx->host_threads, [&](int64_t i) {
+        int64_t x = 0, y = 0;
+        for (int64_t q = ops_off[i]; q < ops_off[i + 1]; ++q) {
+            const int32_t op = ops[2 * q], len = ops[2 * q + 1];
+            if (op < 0 || op > 2 || len < 0) bad[i] = 1;
+            if (op != NPR_OP_I) x += len;
+            if (op != NPR_OP_D) y += len;
+        }
+        const int64_t k = ref_index ? ref_index[i] : i;
+        const int64_t sx = start ? start[2 * i] : 0, sy = start ? start[2 * i + 1] : 0;
+        if (k < 0 || k >= n_refs || sx < 0 || sy < 0 || sx + x > ref_off[k + 1] - ref_off[k] || sy + y > read_off[i + 1] - read_off[i] ||
+            x >= (int64_t(1) << 30) || y >= (int64_t(1) << 30))
+            bad[i] = 1;
+        cx[i] = bad[i] ? 0 : x, cy[i] = bad[i] ? 0 : y;
+    });
+    for (int64_t i = 0; i < n; ++i) woff[i + 1] = woff[i] + cx[i] + cy[i], w.seg_off[i] = static_cast<int32_t>(i);
+    w.seg_off[n] = static_cast<int32_t>(n);
+    w.code_bytes = woff[n] + 1;
+    w.codes.reset(new uint8_t[w.code_bytes]);
+    w.packed.resize(ops_off[n]);
+    parallel_for(n, ctx->host_threads, [&](int64_t i) {
+        const int64_t k = ref_index ? ref_index[i] : i;
+        const int64_t sx = start ? start[2 * i] : 0, sy = start ? start[2 * i + 1] : 0;
+        uint8_t *c = w.codes.get() + woff[i];
+        if (!bad[i]) {
+            const uint8_t *xs = ref + ref_off[k] + sx, *ys = read + read_off[i] + sy;
+            for (int64_t q = 0; q < cx[i]; ++q) c[q] = encode_base(xs[q]);
+            for (int64_t q = 0; q < cy[i]; ++q) c[cx[i] + q] = encode_base(ys[q]);
+        }
+        w.segs[i] = StatsSeg{0, static_cast<int32_t>(cx[i]), 0, static_cast<int32_t>(cy[i]), woff[i], woff[i] + cx[i]};
+        for (int64_t q = ops_off[i]; q < ops_off[i + 1]; ++q)
+            w.packed[q] = bad[i] ? 0u : (static_cast<uint32_t>(ops[2 * q + 1]) << 2 | static_cast<uint32_t>(ops[2 * q]));
+    });
 }
 
 }  // namespace
@@ -55,17 +162,9 @@ int32_t npr_batch_align_stats(npr_batch *b, int32_t *stats) {
                 const Task &t = b->tasks[b->task_of[b->read_first_task[i] + s]];
                 segs[seg_off[i] + s] = StatsSeg{t.xs, t.xs + t.lX, t.ys, t.ys + t.lY, t.x_off, t.y_off};
             }
-        int32_t rc;
-        std::unique_lock<std::mutex> arena_lock(ctx->arena->mu);  // the resident cigars lie in the arena
-        if (b->dev_ops && b->dev_ops_epoch == ctx->arena->epoch) {
-            rc = run_align_stats(ctx, n, b->dev_ops, b->dev_od, nullptr, nullptr, seg_off, segs, b->d_seq.p, stats);
-            arena_lock.unlock();
-        } else {
-            arena_lock.unlock();
-            ensure_packed_form(b);
-            std::vector<uint32_t> packed(b->packed.get(), b->packed.get() + b->ops_off[n]);
-            rc = run_align_stats(ctx, n, nullptr, nullptr, &packed, &b->ops_off, seg_off, segs, b->d_seq.p, stats);
-        }
+        const int32_t rc = with_batch_cigars(b, [&](const uint32_t *d_ops, const int64_t *d_off, const std::vector<uint32_t> *h_ops, const std::vector<int64_t> *h_off) {
+            return run_align_stats(ctx, n, d_ops, d_off, h_ops, h_off, seg_off, segs, b->d_seq.p, stats);
+        });
         if (rc != NPR_OK) return rc;
         for (int64_t i = 0; i < n; ++i)
             if (b->results[i].status != NPR_OK) std::fill(stats + i * NPR_STATS_WORDS, stats + (i + 1) * NPR_STATS_WORDS, 0), stats[i * NPR_STATS_WORDS + 14] = b->results[i].status;
@@ -83,53 +182,112 @@ int32_t npr_align_stats(npr_ctx *ctx, int64_t n, int64_t n_refs, const uint8_t *
     if (n == 0) return NPR_OK;
     try {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        // every read's window (the reference / read bases its cigar consumes) encoded into one code buffer
-        std::vector<int64_t> woff(n + 1, 0), off(ops_off, ops_off + n + 1);
-        std::vector<int32_t> seg_off(n + 1), bad(n, 0);
-        std::vector<StatsSeg> segs(n);
-        std::vector<int64_t> cx(n), cy(n);
-        parallel_for(n, ctx->host_threads, [&](int64_t i) {
-            int64_t x = 0, y = 0;
-            for (int64_t q = ops_off[i]; q < ops_off[i + 1]; ++q) {
-                const int32_t op = ops[2 * q], len = ops[2 * q + 1];
-                if (op < 0 || op > 2 || len < 0) bad[i] = 1;
-                if (op != NPR_OP_I) x += len;
-                if (op != NPR_OP_D) y += len;
-            }
-            const int64_t k = ref_index ? ref_index[i] : i;
-            const int64_t sx = start ? start[2 * i] : 0, sy = start ? start[2 * i + 1] : 0;
-            if (k < 0 || k >= n_refs || sx < 0 || sy < 0 || sx + x > ref_off[k + 1] - ref_off[k] || sy + y > read_off[i + 1] - read_off[i] ||
-                x >= (int64_t(1) << 30) || y >= (int64_t(1) << 30))
-                bad[i] = 1;
-            cx[i] = bad[i] ? 0 : x, cy[i] = bad[i] ? 0 : y;
-        });
-        for (int64_t i = 0; i < n; ++i) woff[i + 1] = woff[i] + cx[i] + cy[i], seg_off[i] = static_cast<int32_t>(i);
-        seg_off[n] = static_cast<int32_t>(n);
-        const std::unique_ptr<uint8_t[]> codes(new uint8_t[woff[n] + 1]);
-        std::vector<uint32_t> packed(ops_off[n]);
-        parallel_for(n, ctx->host_threads, [&](int64_t i) {
-            const int64_t k = ref_index ? ref_index[i] : i;
-            const int64_t sx = start ? start[2 * i] : 0, sy = start ? start[2 * i + 1] : 0;
-            uint8_t *w = codes.get() + woff[i];
-            if (!bad[i]) {
-                const uint8_t *xs = ref + ref_off[k] + sx, *ys = read + read_off[i] + sy;
-                for (int64_t q = 0; q < cx[i]; ++q) w[q] = encode_base(xs[q]);
-                for (int64_t q = 0; q < cy[i]; ++q) w[cx[i] + q] = encode_base(ys[q]);
-            }
-            segs[i] = StatsSeg{0, static_cast<int32_t>(cx[i]), 0, static_cast<int32_t>(cy[i]), woff[i], woff[i] + cx[i]};
-            for (int64_t q = ops_off[i]; q < ops_off[i + 1]; ++q)
-                packed[q] = bad[i] ? 0u : (static_cast<uint32_t>(ops[2 * q + 1]) << 2 | static_cast<uint32_t>(ops[2 * q]));
-        });
+        Windows w;
+        encode_windows(ctx, n, n_refs, ref, ref_off, ref_index, read, read_off, ops, ops_off, start, w);
         DevBuf<uint8_t> d_codes;
-        if (d_codes.alloc(woff[n] + 1) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_align_stats: hipMalloc");
-        HIP_TRY(ctx, hipMemcpyAsync(d_codes.p, codes.get(), woff[n] + 1, hipMemcpyHostToDevice, ctx->stream));
-        const int32_t rc = run_align_stats(ctx, n, nullptr, nullptr, &packed, &off, seg_off, segs, d_codes.p, stats);
+        if (d_codes.alloc(w.code_bytes) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_align_stats: hipMalloc");
+        HIP_TRY(ctx, hipMemcpyAsync(d_codes.p, w.codes.get(), w.code_bytes, hipMemcpyHostToDevice, ctx->stream));
+        const int32_t rc = run_align_stats(ctx, n, nullptr, nullptr, &w.packed, &w.off, w.seg_off, w.segs, d_codes.p, stats);
         if (rc != NPR_OK) return rc;
         for (int64_t i = 0; i < n; ++i)
-            if (bad[i]) std::fill(stats + i * NPR_STATS_WORDS, stats + (i + 1) * NPR_STATS_WORDS, 0), stats[i * NPR_STATS_WORDS + 14] = NPR_ERR_INVALID;
+            if (w.bad[i]) std::fill(stats + i * NPR_STATS_WORDS, stats + (i + 1) * NPR_STATS_WORDS, 0), stats[i * NPR_STATS_WORDS + 14] = NPR_ERR_INVALID;
         return NPR_OK;
     } catch (const std::exception &) {
         return fail(ctx, NPR_ERR_NOMEM, "npr_align_stats: out of host memory");
+    }
+}
+
+int32_t npr_kmer_counts(npr_ctx *ctx, int32_t k, int64_t n_seqs, const uint8_t *seq, const int64_t *seq_off, int64_t *counts) {
+    if (!ctx || k < 1 || k > NPR_KMER_MAX_K || n_seqs < 0 || !counts || (n_seqs && !seq_off)) return NPR_ERR_INVALID;
+    const size_t nb = static_cast<size_t>(kmer_bins(k));
+    std::fill(counts, counts + nb, int64_t(0));
+    if (n_seqs == 0) return NPR_OK;
+    try {
+        std::vector<int64_t> off(n_seqs + 1);
+        for (int64_t i = 0; i <= n_seqs; ++i) {
+            off[i] = seq_off[i] - seq_off[0];
+            if (i && off[i] < off[i - 1]) return fail(ctx, NPR_ERR_INVALID, "npr_kmer_counts: sequence offsets decrease");
+        }
+        const int64_t total = off[n_seqs];
+        if (total == 0) return NPR_OK;
+        if (!seq) return NPR_ERR_INVALID;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        DevBuf<uint8_t> d_seq;
+        DevBuf<int64_t> d_off;
+        DevBuf<unsigned long long> d_counts;
+        hipError_t e;
+        if ((e = d_seq.alloc(static_cast<size_t>(total) + NPR_KMER_PAD)) != hipSuccess || (e = d_off.alloc(off.size())) != hipSuccess || (e = d_counts.alloc(nb)) != hipSuccess)
+            return fail(ctx, NPR_ERR_NOMEM, "npr_kmer_counts: hipMalloc", e);
+        HIP_TRY(ctx, hipMemcpyAsync(d_seq.p, seq + seq_off[0], static_cast<size_t>(total), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(d_seq.p + total, 0, NPR_KMER_PAD, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_off.p, off.data(), d_off.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(d_counts.p, 0, d_counts.bytes(), ctx->stream));
+        const KmerArgs a{d_seq.p, total, d_off.p, n_seqs, k, d_counts.p};
+        const int rc = launch_kmer_spectrum(a, ctx->stream);
+        if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_kmer_spectrum launch", static_cast<hipError_t>(rc));
+        HIP_TRY(ctx, hipMemcpyAsync(counts, d_counts.p, nb * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return NPR_OK;
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_kmer_counts: out of host memory");
+    }
+}
+
+int32_t npr_align_indel_kmers(npr_ctx *ctx, int32_t k, int64_t n, int64_t n_refs, const uint8_t *ref, const int64_t *ref_off, const int32_t *ref_index,
+                              const uint8_t *read, const int64_t *read_off, const int32_t *ops, const int64_t *ops_off, const int64_t *start,
+                              int64_t *read_counts, int64_t *ref_counts) {
+    if (!ctx || k < 1 || k > NPR_KMER_MAX_K || n < 0 || n_refs < 0 || !read_counts || !ref_counts || (n && (!ref_off || !read_off || !ops_off)))
+        return NPR_ERR_INVALID;
+    if (!ref_index && n_refs != n) return fail(ctx, NPR_ERR_INVALID, "npr_align_indel_kmers: without ref_index, n_refs must equal n_reads");
+    std::fill(read_counts, read_counts + kmer_bins(k), int64_t(0));
+    std::fill(ref_counts, ref_counts + kmer_bins(k), int64_t(0));
+    if (n == 0) return NPR_OK;
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        Windows w;
+        encode_windows(ctx, n, n_refs, ref, ref_off, ref_index, read, read_off, ops, ops_off, start, w);
+        DevBuf<uint8_t> d_codes;
+        if (d_codes.alloc(w.code_bytes) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_align_indel_kmers: hipMalloc");
+        HIP_TRY(ctx, hipMemcpyAsync(d_codes.p, w.codes.get(), w.code_bytes, hipMemcpyHostToDevice, ctx->stream));
+        int32_t bad = 0;
+        const int32_t rc = run_indel_kmers(ctx, k, n, nullptr, nullptr, &w.packed, &w.off, w.seg_off, w.segs, d_codes.p, read_counts, ref_counts, &bad);
+        if (rc != NPR_OK) return rc;
+        for (int64_t i = 0; i < n; ++i) bad |= w.bad[i];
+        return bad ? fail(ctx, NPR_ERR_INVALID, "npr_align_indel_kmers: a cigar runs past its sequences (the record was left out)") : NPR_OK;
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_align_indel_kmers: out of host memory");
+    }
+}
+
+int32_t npr_batch_indel_kmers(npr_batch *b, int32_t k, int64_t *read_counts, int64_t *ref_counts) {
+    if (!b || k < 1 || k > NPR_KMER_MAX_K || !read_counts || !ref_counts) return NPR_ERR_INVALID;
+    if (!b->finished) return NPR_ERR_STATE;
+    npr_ctx *ctx = b->ctx;
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const int64_t n = b->n_reads;
+        std::fill(read_counts, read_counts + kmer_bins(k), int64_t(0));
+        std::fill(ref_counts, ref_counts + kmer_bins(k), int64_t(0));
+        if (n == 0) return NPR_OK;
+        // one piece per read, its whole window (the batch holds every window whole: reference part, then read part, from the first base of
+        // the read's first task back to position 0); a read that failed has none and adds nothing
+        std::vector<int32_t> seg_off(n + 1, 0);
+        std::vector<StatsSeg> segs;
+        for (int64_t i = 0; i < n; ++i) {
+            if (b->results[i].status == NPR_OK && b->read_ntasks[i] > 0) {
+                const Task &t = b->tasks[b->task_of[b->read_first_task[i]]];
+                segs.push_back(StatsSeg{0, static_cast<int32_t>(b->ref_len[i]), 0, static_cast<int32_t>(b->read_len[i]), t.x_off - t.xs, t.y_off - t.ys});
+            }
+            seg_off[i + 1] = static_cast<int32_t>(segs.size());
+        }
+        int32_t bad = 0;
+        const int32_t rc = with_batch_cigars(b, [&](const uint32_t *d_ops, const int64_t *d_off, const std::vector<uint32_t> *h_ops, const std::vector<int64_t> *h_off) {
+            return run_indel_kmers(ctx, k, n, d_ops, d_off, h_ops, h_off, seg_off, segs, b->d_seq.p, read_counts, ref_counts, &bad);
+        });
+        if (rc != NPR_OK) return rc;
+        return bad ? fail(ctx, NPR_ERR_INVALID, "npr_batch_indel_kmers: a cigar runs past its window (the record was left out)") : NPR_OK;
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_batch_indel_kmers: out of host memory");
     }
 }
 

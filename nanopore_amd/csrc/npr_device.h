@@ -246,6 +246,26 @@ struct StatsArgs {
     int32_t *out;            // [n_reads][NPR_STATS_WORDS]
 };
 int launch_align_stats(const StatsArgs &a, void *stream);
+// k-mer tables (npr_kmer.hip).  A k-mer's bin is its base-4 number, first base most significant; bin 4^k takes the k-mers with a code 4.
+constexpr int NPR_KMER_MAX_K = 6;
+constexpr int NPR_KMER_PAD = 64;  // bytes readable past the last base of KmerArgs::seq (a lane loads its run and the halo in 16-byte pieces)
+NPR_HD constexpr int kmer_bins(int k) { return (1 << (2 * k)) + 1; }
+struct KmerArgs {  // k_kmer_spectrum
+    const uint8_t *seq;      // ASCII, the sequences back to back, 16-byte aligned
+    int64_t n;               // bases
+    const int64_t *seq_off;  // [n_seqs + 1], seq_off[0] = 0, seq_off[n_seqs] = n
+    int64_t n_seqs;
+    int32_t k;
+    unsigned long long *counts;  // [kmer_bins(k)], added to
+};
+int launch_kmer_spectrum(const KmerArgs &a, void *stream);
+struct IndelKmerArgs {  // k_indel_kmers: `s` as for k_align_stats, but every record has ONE piece, its whole window (none: the record is skipped); s.out unused
+    StatsArgs s;
+    int32_t k;
+    unsigned long long *read_counts, *ref_counts;  // [kmer_bins(k)] each, added to
+    int32_t *bad;            // set to 1 when a record's cigar runs past its piece (the record adds nothing)
+};
+int launch_indel_kmers(const IndelKmerArgs &a, void *stream);
 constexpr float EXPECT_FIXED_ONE = 1099511627776.0f;  // 2^40
 struct ExpectArgs {
     const Task *tasks;

@@ -204,6 +204,16 @@ class Batch(object):
             raise NprError(rc, "npr_batch_align_stats", self.ctx.last_error())
         return out
 
+    def indel_kmers(self, k=5):
+        """The k-mers that straddle a gap of the cigars finish() produced, counted where they lie (include/nprealign.h:
+        npr_batch_indel_kmers): (read-side table, reference-side table), int64 [4^k + 1] each."""
+        nb = 4 ** k + 1 if 1 <= k <= _lib.KMER_MAX_K else 1
+        rd, rf = np.zeros(nb, dtype=np.int64), np.zeros(nb, dtype=np.int64)
+        rc = self._L.npr_batch_indel_kmers(self._h, int(k), ptr(rd), ptr(rf))
+        if rc != _lib.OK:
+            raise NprError(rc, "npr_batch_indel_kmers", self.ctx.last_error())
+        return rd, rf
+
     def expectations(self):
         """Baum-Welch E-step with the installed models: (T_exp[slots,25], E_exp[slots,80], loglik[slots], kernel ms)."""
         T = np.zeros((_lib.MAX_MODELS, 25))
@@ -361,6 +371,33 @@ class Context(object):
         if rc != _lib.OK:
             raise NprError(rc, "npr_align_stats", self.last_error())
         return out
+
+    def kmer_counts(self, seqs, k=5):
+        """All windows s[i - k : i], i in k .. len(s) - 1, of the ASCII sequences `seqs`, forward strand, counted on the device
+        (include/nprealign.h: npr_kmer_counts): int64 [4^k + 1]; bin = base-4 number of the k-mer (A C G T = 0..3, first base
+        most significant), the last bin for k-mers with a base outside ACGT."""
+        seq, off = _csr(seqs)
+        out = np.zeros(4 ** k + 1 if 1 <= k <= _lib.KMER_MAX_K else 1, dtype=np.int64)
+        rc = self._L.npr_kmer_counts(self._h, int(k), len(off) - 1, ptr(seq), ptr(off), ptr(out))
+        if rc != _lib.OK:
+            raise NprError(rc, "npr_kmer_counts", self.last_error())
+        return out
+
+    def align_indel_kmers(self, refs, reads, cigars, k=5, ref_index=None, start=None):
+        """The k-mers that straddle a gap of arbitrary alignments (arguments as for align_stats), counted on the device
+        (include/nprealign.h: npr_align_indel_kmers): (read-side table, reference-side table), int64 [4^k + 1] each."""
+        ref, ref_off = _csr(refs)
+        read, read_off = _csr(reads)
+        ops, ops_off = _csr_ops(cigars)
+        ri = None if ref_index is None else np.ascontiguousarray(ref_index, dtype=np.int32)
+        st = None if start is None else np.ascontiguousarray(start, dtype=np.int64).reshape(-1, 2)
+        nb = 4 ** k + 1 if 1 <= k <= _lib.KMER_MAX_K else 1
+        rd, rf = np.zeros(nb, dtype=np.int64), np.zeros(nb, dtype=np.int64)
+        rc = self._L.npr_align_indel_kmers(self._h, int(k), len(read_off) - 1, len(ref_off) - 1, ptr(ref), ptr(ref_off), ptr(ri), ptr(read),
+                                           ptr(read_off), ptr(ops), ptr(ops_off), ptr(st), ptr(rd), ptr(rf))
+        if rc != _lib.OK:
+            raise NprError(rc, "npr_align_indel_kmers", self.last_error())
+        return rd, rf
 
     def _realign_once(self, params, refs, reads, guides, model_slot, want_pairs, ref_index, guide_start=None):
         b = self.stage(params, refs, reads, guides, model_slot, ref_index, guide_start)
