@@ -305,6 +305,51 @@ int32_t npr_align_indel_kmers(npr_ctx *ctx, int32_t k, int64_t n_reads, int64_t 
  * failed add nothing. */
 int32_t npr_batch_indel_kmers(npr_batch *b, int32_t k, int64_t *read_counts, int64_t *ref_counts /* [4^k + 1] each */);
 
+/* ---- the device pileup: per-position depth and base counts of a set of alignments ----
+ * What the reference gets from samtools after writing the realigned SAM, converting it to BAM, sorting and indexing it:
+ * `samtools depth` (nanopore/metaAnalyses/coverageDepth.py:49-65) and `samtools mpileup` (analyses/consensus.py).  A table of
+ * NPR_PILEUP_WORDS int32 counters per reference position, rows in the order of the n_refs reference sequences given to
+ * npr_pileup_create (first row of a sequence + position, as for npr_batch_base_expectations), over the selected records:
+ *   [0..3] aligned (M) columns whose READ base is A, C, G, T (either letter case)     [4] M columns with any other read base
+ *   [5] deletion columns: the position lies inside a D run of the record
+ *   [6] insertion runs attached to the position: an I run is attached to the last reference column (M or D) the record consumed
+ *       before it; an I run before the record's first column is attached to nothing; I runs not separated by a column count once
+ *       (mpileup's `+<n>` marker: a leading 2I is dropped, 2I3I shows one marker, a trailing I is shown)
+ *   [7] records whose first reference column (M or D) is the position (mpileup's `^`)
+ * `samtools depth` prints the sum of words 0-4 and gives a line to every position where the sum of words 0-5 is not zero.
+ * Counts are integers: the table is the same from run to run.  A record costs its cigar runs and its M columns, not its
+ * reference span: the D runs of a global alignment (a chained or realigned record spans its whole contig) go through a
+ * difference array that is summed up when the counts are read.
+ * NOT reproduced: samtools 0.1.19 admits at most 8000 records to a position's pileup (bam_pileup.c, maxcnt), which depends on
+ * the order of the file; this table has no cap.
+ * A pileup is an object because it outlives a batch: a file is realigned in several chunks and the table accumulates.  It
+ * belongs to its context and must be destroyed before it; calls on it count as calls on the context. */
+#define NPR_PILEUP_WORDS 8
+typedef struct npr_pileup npr_pileup;
+/* a zeroed table on the device for n_refs reference sequences of ref_len[k] positions */
+int32_t npr_pileup_create(npr_ctx *ctx, int64_t n_refs, const int64_t *ref_len, npr_pileup **out);
+void npr_pileup_destroy(npr_pileup *pl);
+/* Adds the alignments npr_batch_finish just produced, where they lie (the packed cigars and the base codes are still in HBM
+ * after the device MEA stage; otherwise the cigars are uploaded): read i against the reference sequence and from the window
+ * start it was staged with.  use[i] != 0 selects read i (NULL: all); reads that failed add nothing.  The batch must be of the
+ * pileup's context.  A selected read whose window does not fit its reference sequence in the pileup's table, or whose cigar
+ * runs past its window, adds nothing and makes the call return NPR_ERR_INVALID (the other reads are counted). */
+int32_t npr_pileup_add_batch(npr_pileup *pl, npr_batch *b, const uint8_t *use /* [n_reads] or NULL */);
+/* Adds any alignments, e.g. the records of a mapper's SAM file; arguments as for npr_align_stats, without reference bases:
+ * record i = cigar ops[2 * ops_off[i] ..) of read bases read[read_begin[i] .. read_end[i]) against reference sequence
+ * ref_index[i], starting at reference position start[2 * i] and read position start[2 * i + 1] (start == NULL: 0, 0).
+ * read_end == NULL: read_begin has n_reads + 1 entries and read i ends where read i + 1 begins.  use as above.  A selected
+ * record that is malformed (an operation outside M I D, a negative length, a reference index or start outside its sequences)
+ * or whose cigar runs past its read or its reference sequence adds NOTHING -- every cigar is checked before its first add --
+ * and makes the call return NPR_ERR_INVALID; the other records are counted. */
+int32_t npr_pileup_add(npr_pileup *pl, int64_t n_reads, const int32_t *ref_index, const uint8_t *read, const int64_t *read_begin,
+                       const int64_t *read_end, const int32_t *ops, const int64_t *ops_off, const int64_t *start, const uint8_t *use);
+/* The table so far (the difference array summed on the device, then copied); more records may be added afterwards. */
+int32_t npr_pileup_counts(npr_pileup *pl, int32_t *counts /* [sum ref_len][NPR_PILEUP_WORDS] */);
+/* ... or only depth[r] = words 0-4 summed and covered[r] = (words 0-5 summed != 0), made on the device: 5 bytes per position
+ * cross PCIe instead of 32. */
+int32_t npr_pileup_depth(npr_pileup *pl, int32_t *depth /* [sum ref_len] */, uint8_t *covered /* [sum ref_len] */);
+
 /* Expected base counts per reference position from the posterior pairs of a finished batch, on the device (SURVEY.md 8f
  * next #4): what marginAlignSnpCaller.py:150-155 collates from the --outputAllPosteriorProbs files, one text line at a time:
  * every pair (refPos, readPos, p) of a selected read adds p to expect[(first row of its reference + refPos) * 4 + base] for

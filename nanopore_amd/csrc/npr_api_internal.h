@@ -4,7 +4,7 @@
 //   npr_stage.cpp   npr_batch_create*: plan points, packing, H2D, the device planner, kernel classes and launch geometry
 //   npr_run.cpp     npr_batch_run (launch policy, second pass of tasks without a range certificate), the E-step, the dense dumps
 //   npr_finish.cpp  npr_batch_finish and what reads its results: the device MEA stage, the rescore sums, the host stage, ops / pairs
-//   npr_aux.cpp     post-alignment statistics, base expectations, the planner cross-check
+//   npr_aux.cpp     post-alignment statistics, k-mer tables, base expectations, the device pileup, the planner cross-check
 //   npr_text.cpp    cigar and SAM record text (the transport forms a job ships)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -339,6 +339,19 @@ struct npr_batch {
     uint64_t dev_ops_epoch = 0;
 };
 
+// the device pileup (npr_aux.cpp, npr_pileup.hip): the table and the difference array of its deletion columns live on the device from
+// npr_pileup_create to npr_pileup_destroy and are added to by every npr_pileup_add / npr_pileup_add_batch
+struct npr_pileup {
+    npr_ctx *ctx = nullptr;
+    std::vector<int64_t> len;    // positions of every reference sequence
+    std::vector<int64_t> base;   // [n_refs + 1] first row of every sequence
+    int64_t rows = 0;
+    DevBuf<int32_t> tab;         // [rows][NPR_PILEUP_WORDS]; word 5 is written by the scan
+    DevBuf<int32_t> diff;        // [rows + n_refs]: sequence k's slots start at base[k] + k, the last one is spare
+    DevBuf<int32_t> tile;        // the scan's tile sums
+    DevBuf<int64_t> dbase;       // [n_refs + 1] first slot of every sequence
+    DevBuf<int32_t> bad;         // one word: a record of the current call ran past what it has
+};
 
 // --------------------------------------------------------------------------------------------------
 // Frame schedule of the register kernel (npr_kernel_stair.hip).  The wavefront holds a frame of C = 64*R slots of the

@@ -1,4 +1,4 @@
-// npr_aux.cpp -- post-alignment statistics and k-mer tables on the device, base expectations of the marginAlign SNP caller, the planner cross-check (coverage.py / substitutions.py / indels.py; kmerAnalysis.py / indelKmerAnalysis.py; marginAlignSnpCaller.py:150-155)
+// npr_aux.cpp -- post-alignment statistics and k-mer tables on the device, base expectations of the marginAlign SNP caller, the device pileup, the planner cross-check (coverage.py / substitutions.py / indels.py; kmerAnalysis.py / indelKmerAnalysis.py; marginAlignSnpCaller.py:150-155)
 // (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
 #include "npr_api_internal.h"
 
@@ -440,6 +440,223 @@ int32_t npr_batch_base_expectations(npr_batch *b, const uint8_t *use, int64_t n_
     } catch (const std::exception &) {
         return fail(ctx, NPR_ERR_NOMEM, "npr_batch_base_expectations: out of host memory");
     }
+}
+
+// ---- the device pileup (npr_pileup.hip) ----
+namespace {
+
+// k_pileup_add over n records whose cigars are packed on the device already or given on the host (as for run_align_stats); *bad: some
+// record's cigar ran past what it has
+int32_t run_pileup_add(npr_pileup *pl, int64_t n, const uint32_t *d_ops, const int64_t *d_off, const std::vector<uint32_t> *h_ops,
+                       const std::vector<int64_t> *h_off, const std::vector<PileupRec> &recs, const uint8_t *d_seq, bool ascii, int32_t *bad) {
+    npr_ctx *ctx = pl->ctx;
+    DevBuf<uint32_t> ops;
+    DevBuf<int64_t> off;
+    DevBuf<PileupRec> rc;
+    hipError_t e;
+    if (!d_ops) {
+        if ((e = ops.alloc(h_ops->size())) != hipSuccess || (e = off.alloc(h_off->size())) != hipSuccess)
+            return fail(ctx, NPR_ERR_NOMEM, "npr_pileup_add: hipMalloc", e);
+        if (!h_ops->empty()) HIP_TRY(ctx, hipMemcpyAsync(ops.p, h_ops->data(), ops.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(off.p, h_off->data(), off.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        d_ops = ops.p, d_off = off.p;
+    }
+    if ((e = rc.alloc(recs.size())) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_pileup_add: hipMalloc", e);
+    HIP_TRY(ctx, hipMemcpyAsync(rc.p, recs.data(), rc.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(pl->bad.p, 0, sizeof(int32_t), ctx->stream));
+    const PileupArgs a{n, d_off, d_ops, rc.p, d_seq, ascii ? 1 : 0, pl->tab.p, pl->diff.p, pl->bad.p};
+    const int r = launch_pileup_add(a, ctx->stream);
+    if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_pileup_add launch", static_cast<hipError_t>(r));
+    HIP_TRY(ctx, hipMemcpyAsync(bad, pl->bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the cigars may lie in the arena, whose lock the caller holds until here)
+    return NPR_OK;
+}
+
+// word 5 of the table from the difference array
+int32_t pileup_scan(npr_pileup *pl) {
+    npr_ctx *ctx = pl->ctx;
+    const int64_t n_refs = static_cast<int64_t>(pl->len.size()), n_slots = pl->rows + n_refs;
+    const PileupScanArgs a{n_slots, n_refs, pileup_scan_tiles(n_slots), pl->dbase.p, pl->diff.p, pl->tile.p, pl->tab.p};
+    const int r = launch_pileup_scan(a, ctx->stream);
+    if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_pileup_scan launch", static_cast<hipError_t>(r));
+    return NPR_OK;
+}
+
+}  // namespace
+
+int32_t npr_pileup_create(npr_ctx *ctx, int64_t n_refs, const int64_t *ref_len, npr_pileup **out) {
+    if (!ctx || !out || n_refs < 0 || (n_refs && !ref_len)) return NPR_ERR_INVALID;
+    *out = nullptr;
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        std::unique_ptr<npr_pileup> pl(new npr_pileup);
+        pl->ctx = ctx;
+        pl->len.assign(ref_len, ref_len + n_refs);
+        pl->base.assign(n_refs + 1, 0);
+        std::vector<int64_t> dbase(n_refs + 1, 0);
+        for (int64_t k = 0; k < n_refs; ++k) {
+            if (ref_len[k] < 0 || ref_len[k] >= (int64_t(1) << 31) - 1) return fail(ctx, NPR_ERR_INVALID, "npr_pileup_create: a reference length is negative or 2^31 and more");
+            pl->base[k + 1] = pl->base[k] + ref_len[k];
+            dbase[k + 1] = pl->base[k + 1] + k + 1;
+        }
+        pl->rows = pl->base[n_refs];
+        const int64_t n_slots = pl->rows + n_refs;
+        hipError_t e;
+        if ((e = pl->tab.alloc(static_cast<size_t>(pl->rows) * NPR_PILEUP_WORDS)) != hipSuccess || (e = pl->diff.alloc(static_cast<size_t>(n_slots))) != hipSuccess ||
+            (e = pl->tile.alloc(static_cast<size_t>(pileup_scan_tiles(n_slots)))) != hipSuccess || (e = pl->dbase.alloc(dbase.size())) != hipSuccess ||
+            (e = pl->bad.alloc(1)) != hipSuccess)
+            return fail(ctx, NPR_ERR_NOMEM, "npr_pileup_create: hipMalloc", e);
+        if (pl->rows) HIP_TRY(ctx, hipMemsetAsync(pl->tab.p, 0, pl->tab.bytes(), ctx->stream));
+        if (n_slots) HIP_TRY(ctx, hipMemsetAsync(pl->diff.p, 0, pl->diff.bytes(), ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(pl->dbase.p, dbase.data(), pl->dbase.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        *out = pl.release();
+        return NPR_OK;
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_pileup_create: out of host memory");
+    }
+}
+
+void npr_pileup_destroy(npr_pileup *pl) {
+    if (!pl) return;
+    (void)hipSetDevice(pl->ctx->device);
+    delete pl;
+}
+
+int32_t npr_pileup_add_batch(npr_pileup *pl, npr_batch *b, const uint8_t *use) {
+    if (!pl || !b || b->ctx != pl->ctx) return NPR_ERR_INVALID;
+    if (!b->finished) return NPR_ERR_STATE;
+    npr_ctx *ctx = pl->ctx;
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const int64_t n = b->n_reads, n_refs = static_cast<int64_t>(pl->len.size());
+        if (n == 0) return NPR_OK;
+        // a read's window: the batch holds its base codes whole (reference part, then read part, from the first base of the read's first
+        // task back to position 0, as npr_batch_indel_kmers uses them); its first reference position is the window start it was staged with
+        std::vector<PileupRec> recs(n, PileupRec{0, 0, 0, -1, 0});
+        int32_t unfit = 0, bad = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            if ((use && !use[i]) || b->results[i].status != NPR_OK || b->read_ntasks[i] <= 0) continue;
+            const int64_t k = b->ref_id[i], gx = b->gstart[2 * i];
+            if (k < 0 || k >= n_refs || gx < 0 || gx + b->ref_len[i] > pl->len[k]) {
+                unfit = 1;
+                continue;
+            }
+            const Task &t = b->tasks[b->task_of[b->read_first_task[i]]];
+            recs[i] = PileupRec{pl->base[k] + gx, pl->base[k] + k + gx, t.y_off - t.ys, static_cast<int32_t>(b->ref_len[i]), static_cast<int32_t>(b->read_len[i])};
+        }
+        const int32_t rc = with_batch_cigars(b, [&](const uint32_t *d_ops, const int64_t *d_off, const std::vector<uint32_t> *h_ops, const std::vector<int64_t> *h_off) {
+            return run_pileup_add(pl, n, d_ops, d_off, h_ops, h_off, recs, b->d_seq.p, false, &bad);
+        });
+        if (rc != NPR_OK) return rc;
+        if (unfit) return fail(ctx, NPR_ERR_INVALID, "npr_pileup_add_batch: a read's window does not fit its reference in the pileup (the read was left out)");
+        return bad ? fail(ctx, NPR_ERR_INVALID, "npr_pileup_add_batch: a cigar runs past its window (the read was left out)") : NPR_OK;
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_pileup_add_batch: out of host memory");
+    }
+}
+
+int32_t npr_pileup_add(npr_pileup *pl, int64_t n, const int32_t *ref_index, const uint8_t *read, const int64_t *read_begin, const int64_t *read_end,
+                       const int32_t *ops, const int64_t *ops_off, const int64_t *start, const uint8_t *use) {
+    if (!pl || n < 0 || (n && (!ref_index || !read_begin || !ops_off))) return NPR_ERR_INVALID;
+    npr_ctx *ctx = pl->ctx;
+    if (n == 0) return NPR_OK;
+    if (n >= (int64_t(1) << 31)) return fail(ctx, NPR_ERR_INVALID, "npr_pileup_add: too many records");
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const int64_t n_refs = static_cast<int64_t>(pl->len.size()), o0 = ops_off[0], n_ops = ops_off[n] - o0;
+        if (n_ops < 0 || (n_ops && !ops)) return fail(ctx, NPR_ERR_INVALID, "npr_pileup_add: operation offsets decrease");
+        std::vector<PileupRec> recs(n, PileupRec{0, 0, 0, -1, 0});
+        std::vector<int64_t> off(n + 1), ylen(n, 0);
+        std::vector<uint8_t> malformed(n, 0);
+        std::vector<uint32_t> packed(static_cast<size_t>(n_ops));
+        for (int64_t i = 0; i <= n; ++i) {
+            off[i] = ops_off[i] - o0;
+            if (i && off[i] < off[i - 1]) return fail(ctx, NPR_ERR_INVALID, "npr_pileup_add: operation offsets decrease");
+        }
+        parallel_for(n, ctx->host_threads, [&](int64_t i) {
+            const bool selected = !use || use[i];
+            const int64_t k = ref_index[i], sx = start ? start[2 * i] : 0, sy = start ? start[2 * i + 1] : 0;
+            const int64_t len = (read_end ? read_end[i] : read_begin[i + 1]) - read_begin[i];
+            bool ok = k >= 0 && k < n_refs && len >= 0 && len < (int64_t(1) << 31) && sx >= 0 && sy >= 0 && sy <= len;
+            ok = ok && sx <= pl->len[k];
+            for (int64_t q = off[i]; ok && q < off[i + 1]; ++q) {
+                const int32_t op = ops[2 * (o0 + q)], ln = ops[2 * (o0 + q) + 1];
+                ok = op >= 0 && op <= 2 && ln >= 0 && ln < (1 << 30);
+                packed[q] = static_cast<uint32_t>(ln) << 2 | static_cast<uint32_t>(op);
+            }
+            if (!ok) std::fill(packed.begin() + off[i], packed.begin() + off[i + 1], 0u);
+            if (!selected) return;
+            if (!ok) {
+                malformed[i] = 1;
+                return;
+            }
+            ylen[i] = len - sy;
+            recs[i] = PileupRec{pl->base[k] + sx, pl->base[k] + k + sx, 0, static_cast<int32_t>(pl->len[k] - sx), static_cast<int32_t>(len - sy)};
+        });
+        // the read bases the selected records' cigars start at: uploaded as they are when the reads lie back to back, else gathered first
+        DevBuf<uint8_t> d_seq;
+        hipError_t e;
+        std::unique_ptr<uint8_t[]> gathered;
+        if (!read_end) {
+            const int64_t bytes = read_begin[n] - read_begin[0];
+            if (bytes < 0 || (bytes && !read)) return NPR_ERR_INVALID;
+            if ((e = d_seq.alloc(static_cast<size_t>(bytes) + 1)) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_pileup_add: hipMalloc", e);
+            if (bytes) HIP_TRY(ctx, hipMemcpyAsync(d_seq.p, read + read_begin[0], static_cast<size_t>(bytes), hipMemcpyHostToDevice, ctx->stream));
+            for (int64_t i = 0; i < n; ++i)
+                if (recs[i].xlen >= 0) recs[i].y_off = read_begin[i] - read_begin[0] + (start ? start[2 * i + 1] : 0);
+        } else {
+            int64_t bytes = 0;
+            for (int64_t i = 0; i < n; ++i)
+                if (recs[i].xlen >= 0) recs[i].y_off = bytes, bytes += ylen[i];
+            if (bytes && !read) return NPR_ERR_INVALID;
+            gathered.reset(new uint8_t[bytes + 1]);
+            parallel_for(n, ctx->host_threads, [&](int64_t i) {
+                if (recs[i].xlen >= 0 && ylen[i]) std::memcpy(gathered.get() + recs[i].y_off, read + read_begin[i] + (start ? start[2 * i + 1] : 0), static_cast<size_t>(ylen[i]));
+            });
+            if ((e = d_seq.alloc(static_cast<size_t>(bytes) + 1)) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_pileup_add: hipMalloc", e);
+            if (bytes) HIP_TRY(ctx, hipMemcpyAsync(d_seq.p, gathered.get(), static_cast<size_t>(bytes), hipMemcpyHostToDevice, ctx->stream));
+        }
+        int32_t bad = 0;
+        const int32_t rc = run_pileup_add(pl, n, nullptr, nullptr, &packed, &off, recs, d_seq.p, true, &bad);
+        if (rc != NPR_OK) return rc;
+        for (int64_t i = 0; i < n; ++i) bad |= malformed[i];
+        return bad ? fail(ctx, NPR_ERR_INVALID, "npr_pileup_add: a record is malformed or its cigar runs past its sequences (the record was left out)") : NPR_OK;
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_pileup_add: out of host memory");
+    }
+}
+
+int32_t npr_pileup_counts(npr_pileup *pl, int32_t *counts) {
+    if (!pl || (pl->rows && !counts)) return NPR_ERR_INVALID;
+    npr_ctx *ctx = pl->ctx;
+    if (pl->rows == 0) return NPR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int32_t rc = pileup_scan(pl);
+    if (rc != NPR_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(counts, pl->tab.p, pl->tab.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return NPR_OK;
+}
+
+int32_t npr_pileup_depth(npr_pileup *pl, int32_t *depth, uint8_t *covered) {
+    if (!pl || (pl->rows && (!depth || !covered))) return NPR_ERR_INVALID;
+    npr_ctx *ctx = pl->ctx;
+    if (pl->rows == 0) return NPR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int32_t rc = pileup_scan(pl);
+    if (rc != NPR_OK) return rc;
+    DevBuf<int32_t> d_depth;
+    DevBuf<uint8_t> d_cov;
+    hipError_t e;
+    if ((e = d_depth.alloc(static_cast<size_t>(pl->rows))) != hipSuccess || (e = d_cov.alloc(static_cast<size_t>(pl->rows))) != hipSuccess)
+        return fail(ctx, NPR_ERR_NOMEM, "npr_pileup_depth: hipMalloc", e);
+    const int r = launch_pileup_depth(pl->tab.p, pl->rows, d_depth.p, d_cov.p, ctx->stream);
+    if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_pileup_depth launch", static_cast<hipError_t>(r));
+    HIP_TRY(ctx, hipMemcpyAsync(depth, d_depth.p, d_depth.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(covered, d_cov.p, d_cov.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return NPR_OK;
 }
 
 

@@ -266,6 +266,36 @@ struct IndelKmerArgs {  // k_indel_kmers: `s` as for k_align_stats, but every re
     int32_t *bad;            // set to 1 when a record's cigar runs past its piece (the record adds nothing)
 };
 int launch_indel_kmers(const IndelKmerArgs &a, void *stream);
+// the device pileup (npr_pileup.hip): NPR_PILEUP_WORDS int32 per reference position, a difference array for the deletion columns
+struct PileupRec {
+    int64_t row0;    // table row of the record's first reference position
+    int64_t d0;      // slot of that position in the difference array (row0 + index of the reference sequence)
+    int64_t y_off;   // the record's first read base in PileupArgs::seq
+    int32_t xlen;    // reference positions from there to the end of what the record may cover; < 0: the record is not selected
+    int32_t ylen;    // read bases there
+};
+struct PileupArgs {  // k_pileup_add
+    int64_t n;
+    const int64_t *ops_off;  // [n + 1]
+    const uint32_t *ops;     // one word per cigar op: length << 2 | op
+    const PileupRec *recs;
+    const uint8_t *seq;      // read bases: ASCII (ascii != 0) or base codes 0..4
+    int32_t ascii;
+    int32_t *tab;            // [rows][NPR_PILEUP_WORDS], added to
+    int32_t *diff;           // [rows + n_refs], added to
+    int32_t *bad;            // set to 1 when a record's cigar runs past what it has (the record adds nothing)
+};
+struct PileupScanArgs {  // the running sum of diff into word 5 of tab
+    int64_t n_slots, n_refs, n_tiles;  // n_slots = rows + n_refs, n_tiles = pileup_scan_tiles(n_slots)
+    const int64_t *dbase;    // [n_refs + 1]: first slot of every sequence (first row + index)
+    const int32_t *diff;
+    int32_t *tile;           // [n_tiles] scratch
+    int32_t *tab;
+};
+int launch_pileup_add(const PileupArgs &a, void *stream);
+int64_t pileup_scan_tiles(int64_t n_slots);
+int launch_pileup_scan(const PileupScanArgs &a, void *stream);
+int launch_pileup_depth(const int32_t *tab, int64_t rows, int32_t *depth, uint8_t *covered, void *stream);
 constexpr float EXPECT_FIXED_ONE = 1099511627776.0f;  // 2^40
 struct ExpectArgs {
     const Task *tasks;

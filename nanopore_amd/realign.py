@@ -256,6 +256,89 @@ class Batch(object):
             pass
 
 
+class Pileup(object):
+    """A per-position table on the device (include/nprealign.h: npr_pileup_*; csrc/npr_pileup.hip): PILEUP_WORDS int32 counters per
+    position of the reference sequences whose lengths it was made with, rows in their order.  It accumulates over add_batch() / add()
+    calls -- a file realigned in several chunks is one table -- and may be read in between."""
+
+    def __init__(self, ctx, ref_lengths):
+        self._L = _lib.load()
+        self.ctx = ctx
+        self.ref_lengths = np.ascontiguousarray(ref_lengths, dtype=np.int64).reshape(-1)
+        self.rows = int(self.ref_lengths.sum())
+        h = C.c_void_p()
+        rc = self._L.npr_pileup_create(ctx._h, len(self.ref_lengths), ptr(self.ref_lengths), C.byref(h))
+        if rc != _lib.OK:
+            raise NprError(rc, "npr_pileup_create", ctx.last_error())
+        self._h = h
+        ctx._open.add(self)
+
+    def add_batch(self, batch, use=None):
+        """The alignments batch.finish() just produced, where they lie; use[i] != 0 selects read i (None: all); reads that failed add
+        nothing."""
+        u = None if use is None else np.ascontiguousarray(use, dtype=np.uint8)
+        if u is not None and len(u) != batch.n_reads:
+            raise ValueError("use must have one entry per read of the batch")
+        rc = self._L.npr_pileup_add_batch(self._h, batch._h, ptr(u))
+        if rc != _lib.OK:
+            raise NprError(rc, "npr_pileup_add_batch", self.ctx.last_error())
+
+    def add(self, reads, cigars, ref_index, start=None, use=None):
+        """Any alignments: reads = ASCII sequences, cigars = [(op, len)] lists with ops M/I/D (0/1/2), ref_index[i] = the reference
+        sequence of record i, start[i] = (first reference position, first read position) of cigar i (None: 0, 0)."""
+        read, read_off = _csr(reads)
+        ops, ops_off = _csr_ops(cigars)
+        self.add_csr(read, read_off, None, ops, ops_off, ref_index, start, use)
+
+    def add_csr(self, read, read_begin, read_end, ops, ops_off, ref_index, start=None, use=None):
+        """add() on arrays: read i = read[read_begin[i] : read_end[i]] (read_end None: read_begin has n + 1 entries, the reads lie back
+        to back), cigar i = ops[ops_off[i] : ops_off[i + 1]] (rows of (op, len))."""
+        read = np.ascontiguousarray(read, dtype=np.uint8)
+        read_begin = np.ascontiguousarray(read_begin, dtype=np.int64)
+        read_end = None if read_end is None else np.ascontiguousarray(read_end, dtype=np.int64)
+        ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 2)
+        ops_off = np.ascontiguousarray(ops_off, dtype=np.int64)
+        n = len(ops_off) - 1
+        ri = np.ascontiguousarray(ref_index, dtype=np.int32)
+        st = None if start is None else np.ascontiguousarray(start, dtype=np.int64).reshape(-1, 2)
+        u = None if use is None else np.ascontiguousarray(use, dtype=np.uint8)
+        if len(ri) != n or len(read_begin) != (n + 1 if read_end is None else n) or (read_end is not None and len(read_end) != n) or \
+                (st is not None and len(st) != n) or (u is not None and len(u) != n):
+            raise ValueError("one reference index, read, start and use entry per cigar")
+        rc = self._L.npr_pileup_add(self._h, n, ptr(ri), ptr(read), ptr(read_begin), ptr(read_end), ptr(ops), ptr(ops_off), ptr(st), ptr(u))
+        if rc != _lib.OK:
+            raise NprError(rc, "npr_pileup_add", self.ctx.last_error())
+
+    def counts(self):
+        """The table so far: int32 [rows, PILEUP_WORDS]."""
+        out = np.zeros((self.rows, _lib.PILEUP_WORDS), dtype=np.int32)
+        rc = self._L.npr_pileup_counts(self._h, ptr(out))
+        if rc != _lib.OK:
+            raise NprError(rc, "npr_pileup_counts", self.ctx.last_error())
+        return out
+
+    def depth(self):
+        """(depth int32 [rows], covered bool [rows]): what `samtools depth` prints (M columns) and which positions it prints a line for
+        (M or deletion columns), summed on the device."""
+        depth = np.zeros(self.rows, dtype=np.int32)
+        covered = np.zeros(self.rows, dtype=np.uint8)
+        rc = self._L.npr_pileup_depth(self._h, ptr(depth), ptr(covered))
+        if rc != _lib.OK:
+            raise NprError(rc, "npr_pileup_depth", self.ctx.last_error())
+        return depth, covered.astype(bool)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.npr_pileup_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context(object):
     """One realigner context = one GPU + one HIP stream.  Raises if no gfx950 device is usable."""
 
@@ -269,7 +352,7 @@ class Context(object):
         self._h = h
         self.device = device
         self._models = {}  # slot -> (T, E) or None, as installed: what another context on the same GPU copies
-        self._open = weakref.WeakSet()  # the batches staged on this context and not closed yet: close() closes them first
+        self._open = weakref.WeakSet()  # the batches staged and the pileups made on this context and not closed yet: close() closes them first
 
     def set_option(self, option, value):
         """include/nprealign.h: npr_ctx_option (e.g. _lib.OPT_OVERLAP for a context of a pipelined job)."""
@@ -399,6 +482,10 @@ class Context(object):
             raise NprError(rc, "npr_align_indel_kmers", self.last_error())
         return rd, rf
 
+    def pileup(self, ref_lengths):
+        """A zeroed per-position table for reference sequences of these lengths (Pileup; include/nprealign.h: npr_pileup_create)."""
+        return Pileup(self, ref_lengths)
+
     def _realign_once(self, params, refs, reads, guides, model_slot, want_pairs, ref_index, guide_start=None):
         b = self.stage(params, refs, reads, guides, model_slot, ref_index, guide_start)
         try:
@@ -453,8 +540,8 @@ class Context(object):
 
     def close(self):
         if getattr(self, "_h", None):
-            # a batch that outlives its context (a test that failed with one open, at interpreter exit) would hand npr_batch_destroy
-            # a batch whose context is gone: the library has no way to know
+            # a batch or pileup that outlives its context (a test that failed with one open, at interpreter exit) would hand
+            # npr_batch_destroy / npr_pileup_destroy an object whose context is gone: the library has no way to know
             for b in list(getattr(self, "_open", ())):
                 b.close()
             self._L.npr_destroy(self._h)
