@@ -290,6 +290,16 @@ int32_t npr_align_stats(npr_ctx *ctx, int64_t n_reads, int64_t n_refs, const uin
  * (:20, :28) are a permutation of the bins and are the caller's. */
 int32_t npr_kmer_counts(npr_ctx *ctx, int32_t k, int64_t n_seqs, const uint8_t *seq, const int64_t *seq_off,
                         int64_t *counts /* [4^k + 1] */);
+/* The same windows, bins and letter rules, into one table per group in one pass: what the unmapped-read meta-analyses count
+ * (nanopore/metaAnalyses/unmappedKmerAnalysis.py:12-27: read type x mapped / unmapped).  Sequence i is
+ * text[seq_begin[i] .. seq_end[i]), a span inside a larger text as npr_batch_create_spans takes reads (columns 2-3 of
+ * npr_fastq_index fit directly); group[i] in [0, n_groups) picks its table, -1 leaves it out.  1 <= n_groups <= 64.  A group
+ * outside that range, a span that ends before it begins, a bad k or n_groups: NPR_ERR_INVALID, nothing counted, no table
+ * touched.  Empty sequences, sequences shorter than k + 1 and n_seqs == 0 are legal and add nothing.  Counts are exact and
+ * the same from run to run. */
+int32_t npr_kmer_counts_groups(npr_ctx *ctx, int32_t k, int64_t n_seqs, const uint8_t *text, const int64_t *seq_begin,
+                               const int64_t *seq_end, const int32_t *group, int32_t n_groups,
+                               int64_t *counts /* [n_groups][4^k + 1] */);
 /* The k-mers that straddle a gap of an alignment, of the read (read_counts) and of the reference (ref_counts):
  * nanopore/analyses/indelKmerAnalysis.py:11-19 (indelKmerFinder) over the read side and the reference side of
  * record.aligned_pairs (:32-40: s = readSeq[start : end + 1], s = refSeq[start : end + 1]); the reversed k-mers the
@@ -525,6 +535,14 @@ int32_t npr_fasta_pack(const char *text, const int64_t *rec, int64_t n, const in
  * word after '@') and [start, end) of the sequence line.  rec == NULL: only count.  NPR_ERR_INVALID for a record that does
  * not start with '@' or whose third line does not start with '+'. */
 int64_t npr_fastq_index(const char *text, int64_t len, int64_t *rec, int64_t cap);
+/* Which of n names a SAM file maps (abstractUnmappedAnalysis.py:39-43: samIterator, then `not record.is_unmapped`): name i is
+ * names_text[name_span[2 * i] .. name_span[2 * i + 1]); span / fields are the m alignment lines as npr_sam_index and
+ * npr_sam_parse give them.  mark[i] is set to 1 when some line has QNAME bytes equal to name i (case-sensitive), column 15
+ * NPR_OK and FLAG & 4 == 0; every name equal to the QNAME is marked, and nothing is ever cleared: marks of several files OR
+ * together.  Returns the number of such lines whose QNAME is none of the names, or NPR_ERR_INVALID (nothing marked) when a
+ * line's column 15 is NPR_ERR_INVALID or NPR_SAM_UNKNOWN_REFERENCE.  Host code, threaded over the lines. */
+int64_t npr_names_mark(const char *names_text, const int64_t *name_span /* [2 n] */, int64_t n, const char *sam_text,
+                       const int64_t *span, const int64_t *fields, int64_t m, uint8_t *mark /* [n], OR-ed into */);
 
 /* npr_batch_create_at for reads that are NOT contiguous in memory: read i = read[read_begin[i] .. read_end[i]) -- e.g. the
  * aligned part of each record's SEQ inside the mapped SAM text (columns 11, 12 of npr_sam_parse), so the sequences go from

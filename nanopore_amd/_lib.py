@@ -46,6 +46,8 @@ OPTIONS = dict(kernel=3, arith=4, pair=5, no_tile=6, no_wide=7, tile_rs=8, tile_
 KERNEL_GENERIC, ARITH_CELL, PAIR_NEVER, PAIR_LONG, PAIR_ALL = 1, 1, 1, 2, 3
 STATS_WORDS = 40  # NPR_STATS_WORDS
 KMER_MAX_K = 6    # the k-mer tables: 4^k + 1 bins, the last one for k-mers with a base outside ACGT
+KMER_MAX_GROUPS = 64  # npr_kmer_counts_groups: tables of one call
+SAM_COLS = 16     # NPR_SAM_COLS
 PILEUP_WORDS = 8  # NPR_PILEUP_WORDS: M columns by read base A C G T other, deletion columns, insertion runs, record starts
 MAX_MODELS = 8
 E_DEAD = -(1 << 28)
@@ -112,12 +114,12 @@ EXPORTS = [
     "npr_batch_create", "npr_batch_create_at", "npr_batch_run", "npr_batch_finish", "npr_batch_destroy", "npr_batch_get_stats", "npr_batch_class_stats",
     "npr_batch_results", "npr_batch_ops", "npr_batch_ops_packed", "npr_batch_pairs", "npr_batch_debug_set_pairs", "npr_batch_dense", "npr_batch_rs_forward", "npr_batch_expectations",
     "npr_batch_align_stats", "npr_align_stats", "npr_batch_plan_check", "npr_batch_base_expectations",
-    "npr_kmer_counts", "npr_align_indel_kmers", "npr_batch_indel_kmers",
+    "npr_kmer_counts", "npr_kmer_counts_groups", "npr_align_indel_kmers", "npr_batch_indel_kmers",
     "npr_pileup_create", "npr_pileup_destroy", "npr_pileup_add_batch", "npr_pileup_add", "npr_pileup_counts", "npr_pileup_depth",
     "npr_realign_batch",
     "npr_plan_create", "npr_plan_destroy", "npr_plan_segments", "npr_plan_segment_info",
     "npr_plan_segment_band", "npr_plan_frame_schedule", "npr_plan_stripes", "npr_format_cigars", "npr_format_cigars_packed", "npr_format_sam_records", "npr_chain_hits", "npr_mea_cigar", "npr_rescore", "npr_encode_bases",
-    "npr_sam_index", "npr_sam_parse", "npr_sam_guides", "npr_sam_splice", "npr_fasta_index", "npr_fasta_pack", "npr_fastq_index",
+    "npr_sam_index", "npr_sam_parse", "npr_sam_guides", "npr_sam_splice", "npr_fasta_index", "npr_fasta_pack", "npr_fastq_index", "npr_names_mark",
     "npr_batch_create_spans", "npr_chain_merge", "npr_ctx_option", "npr_batch_segment_arith",
 ]
 
@@ -189,6 +191,8 @@ def load():
     L.npr_align_stats.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.npr_kmer_counts.restype = i32
     L.npr_kmer_counts.argtypes = [vp, i32, i64, vp, vp, vp]
+    L.npr_kmer_counts_groups.restype = i32
+    L.npr_kmer_counts_groups.argtypes = [vp, i32, i64, vp, vp, vp, vp, i32, vp]
     L.npr_align_indel_kmers.restype = i32
     L.npr_align_indel_kmers.argtypes = [vp, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.npr_batch_indel_kmers.restype = i32
@@ -253,6 +257,8 @@ def load():
     L.npr_fasta_pack.argtypes = [vp, vp, i64, vp, vp]
     L.npr_fastq_index.restype = i64
     L.npr_fastq_index.argtypes = [vp, i64, vp, i64]
+    L.npr_names_mark.restype = i64
+    L.npr_names_mark.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp]
     L.npr_batch_create_spans.restype = i32
     L.npr_batch_create_spans.argtypes = [vp, C.POINTER(Params), i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
     _lib = L

@@ -233,6 +233,84 @@ int32_t npr_kmer_counts(npr_ctx *ctx, int32_t k, int64_t n_seqs, const uint8_t *
     }
 }
 
+int32_t npr_kmer_counts_groups(npr_ctx *ctx, int32_t k, int64_t n_seqs, const uint8_t *text, const int64_t *seq_begin, const int64_t *seq_end,
+                               const int32_t *group, int32_t n_groups, int64_t *counts) {
+    if (!ctx || k < 1 || k > NPR_KMER_MAX_K || n_seqs < 0 || n_groups < 1 || n_groups > NPR_KMER_MAX_GROUPS || !counts ||
+        (n_seqs && (!seq_begin || !seq_end || !group)))
+        return NPR_ERR_INVALID;
+    const size_t nb = static_cast<size_t>(kmer_bins(k));
+    try {
+        // sequences and bases of every group; nothing is counted and no table touched when an argument is wrong
+        std::vector<int64_t> seqs_of(n_groups, 0), bases_of(n_groups, 0);
+        for (int64_t i = 0; i < n_seqs; ++i) {
+            if (group[i] < -1 || group[i] >= n_groups) return fail(ctx, NPR_ERR_INVALID, "npr_kmer_counts_groups: a group outside -1 .. n_groups - 1");
+            if (seq_end[i] < seq_begin[i] || seq_begin[i] < 0) return fail(ctx, NPR_ERR_INVALID, "npr_kmer_counts_groups: a span that ends before it begins");
+            if (group[i] >= 0) ++seqs_of[group[i]], bases_of[group[i]] += seq_end[i] - seq_begin[i];
+        }
+        std::fill(counts, counts + nb * static_cast<size_t>(n_groups), int64_t(0));
+        // the layout KmerGroupArgs describes: one int64 table {tile0 | seq_first | seq_off}, the bases ordered by group in the pinned staging
+        const size_t G = static_cast<size_t>(n_groups);
+        const int64_t slots = std::accumulate(seqs_of.begin(), seqs_of.end(), int64_t(0)) + n_groups;  // one offset per sequence and every group's end
+        std::vector<int64_t> tab(2 * (G + 1) + static_cast<size_t>(slots), 0);
+        int64_t *const tile0 = tab.data(), *const seq_first = tab.data() + G + 1, *const seq_off = tab.data() + 2 * (G + 1);
+        for (size_t g = 0; g < G; ++g) {
+            tile0[g + 1] = tile0[g] + (bases_of[g] + NPR_KMER_TILE - 1) / NPR_KMER_TILE;
+            seq_first[g + 1] = seq_first[g] + seqs_of[g] + 1;
+        }
+        const int64_t tiles = tile0[G];
+        if (tiles == 0) return NPR_OK;
+        if (!text) return NPR_ERR_INVALID;
+        std::vector<int64_t> src(static_cast<size_t>(slots), -1);  // where the sequence behind seq_off[s] begins in text (-1: a group's end)
+        {
+            std::vector<int64_t> at(G), pos(G);
+            for (size_t g = 0; g < G; ++g) at[g] = seq_first[g], pos[g] = tile0[g] * NPR_KMER_TILE;
+            for (int64_t i = 0; i < n_seqs; ++i) {
+                if (group[i] < 0) continue;
+                const size_t g = static_cast<size_t>(group[i]);
+                seq_off[at[g]] = pos[g], src[at[g]++] = seq_begin[i];
+                pos[g] += seq_end[i] - seq_begin[i];
+            }
+            for (size_t g = 0; g < G; ++g) seq_off[at[g]] = pos[g];
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t stage_need = static_cast<size_t>(tiles) * NPR_KMER_TILE + NPR_KMER_PAD;
+        hipError_t e;
+        if (stage_need > ctx->pin_stage_bytes) {
+            if (ctx->pin_stage) (void)hipHostFree(ctx->pin_stage);
+            ctx->pin_stage = nullptr, ctx->pin_stage_bytes = 0;
+            if ((e = hipHostMalloc(&ctx->pin_stage, stage_need + stage_need / 4, hipHostMallocDefault)) != hipSuccess)
+                return fail(ctx, NPR_ERR_NOMEM, "npr_kmer_counts_groups: hipHostMalloc", e);
+            ctx->pin_stage_bytes = stage_need + stage_need / 4;
+        }
+        uint8_t *const h_seq = static_cast<uint8_t *>(ctx->pin_stage);
+        parallel_for((slots + 255) / 256, ctx->host_threads, [&](int64_t c) {
+            for (int64_t s = c * 256, hi = std::min(slots, (c + 1) * 256); s < hi; ++s)
+                if (src[s] >= 0) std::memcpy(h_seq + seq_off[s], text + src[s], static_cast<size_t>(seq_off[s + 1] - seq_off[s]));
+        });
+        for (size_t g = 0; g < G; ++g) {  // what a group leaves of its last tile (read as a lane's halo, never counted)
+            const int64_t end = seq_off[seq_first[g + 1] - 1];
+            std::memset(h_seq + end, 0, static_cast<size_t>(tile0[g + 1] * NPR_KMER_TILE - end));
+        }
+        std::memset(h_seq + stage_need - NPR_KMER_PAD, 0, NPR_KMER_PAD);
+        DevBuf<uint8_t> d_seq;
+        DevBuf<int64_t> d_tab;
+        DevBuf<unsigned long long> d_counts;
+        if ((e = d_seq.alloc(stage_need)) != hipSuccess || (e = d_tab.alloc(tab.size())) != hipSuccess || (e = d_counts.alloc(nb * G)) != hipSuccess)
+            return fail(ctx, NPR_ERR_NOMEM, "npr_kmer_counts_groups: hipMalloc", e);
+        HIP_TRY(ctx, hipMemcpyAsync(d_seq.p, h_seq, stage_need, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_tab.p, tab.data(), d_tab.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(d_counts.p, 0, d_counts.bytes(), ctx->stream));
+        const KmerGroupArgs a{d_seq.p, d_tab.p, d_tab.p + G + 1, d_tab.p + 2 * (G + 1), n_groups, k, d_counts.p};
+        const int rc = launch_kmer_spectrum_groups(a, tiles, ctx->stream);
+        if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_kmer_spectrum_groups launch", static_cast<hipError_t>(rc));
+        HIP_TRY(ctx, hipMemcpyAsync(counts, d_counts.p, d_counts.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return NPR_OK;
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_kmer_counts_groups: out of host memory");
+    }
+}
+
 int32_t npr_align_indel_kmers(npr_ctx *ctx, int32_t k, int64_t n, int64_t n_refs, const uint8_t *ref, const int64_t *ref_off, const int32_t *ref_index,
                               const uint8_t *read, const int64_t *read_off, const int32_t *ops, const int64_t *ops_off, const int64_t *start,
                               int64_t *read_counts, int64_t *ref_counts) {

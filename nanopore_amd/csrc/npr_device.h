@@ -259,6 +259,18 @@ struct KmerArgs {  // k_kmer_spectrum
     unsigned long long *counts;  // [kmer_bins(k)], added to
 };
 int launch_kmer_spectrum(const KmerArgs &a, void *stream);
+constexpr int NPR_KMER_TILE = 8192;  // bases per workgroup and step of the two k_kmer_spectrum kernels
+constexpr int NPR_KMER_MAX_GROUPS = 64;
+struct KmerGroupArgs {  // k_kmer_spectrum_groups: the sequences ordered by group, group g's bases back to back from seq[tile0[g] * NPR_KMER_TILE] on
+    const uint8_t *seq;        // ASCII, NPR_KMER_PAD readable bytes past the last tile
+    const int64_t *tile0;      // [n_groups + 1] first tile of every group (a group without bases has none)
+    const int64_t *seq_first;  // [n_groups + 1] group g's offsets are seq_off[seq_first[g] .. seq_first[g + 1]): one per sequence and the group's end
+    const int64_t *seq_off;    // positions in seq; a group's first = tile0[g] * NPR_KMER_TILE
+    int32_t n_groups;
+    int32_t k;
+    unsigned long long *counts;  // [n_groups][kmer_bins(k)], added to
+};
+int launch_kmer_spectrum_groups(const KmerGroupArgs &a, int64_t tiles, void *stream);
 struct IndelKmerArgs {  // k_indel_kmers: `s` as for k_align_stats, but every record has ONE piece, its whole window (none: the record is skipped); s.out unused
     StatsArgs s;
     int32_t k;

@@ -1,7 +1,9 @@
 // npr_io.cpp -- bulk text ingest and splice for the file side of the realign path (include/nprealign.h, "bulk text
 // ingest"): the record loop of realignSamFile2TargetFn / realignSamFile3TargetFn (nanopore/analyses/utils.py:557-609) and the
-// FASTA / FASTQ dictionaries (utils.py:233-245) over the whole text of a file at once.  Host code, threaded, no HIP.
+// FASTA / FASTQ dictionaries (utils.py:233-245) over the whole text of a file at once, and the join of FASTQ names with SAM QNAMEs that
+// the unmapped-read meta-analyses make through Python dicts (metaAnalyses/abstractUnmappedAnalysis.py:37-43).  Host code, threaded, no HIP.
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -395,6 +397,45 @@ int64_t npr_fastq_index(const char *text, int64_t len, int64_t *rec, int64_t cap
         }
     }
     return n;
+}
+
+int64_t npr_names_mark(const char *names_text, const int64_t *name_span, int64_t n, const char *sam_text, const int64_t *span, const int64_t *fields,
+                       int64_t m, uint8_t *mark) {
+    if (n < 0 || m < 0 || (n && (!names_text || !name_span || !mark)) || (m && (!sam_text || !span || !fields))) return NPR_ERR_INVALID;
+    try {
+        for (int64_t j = 0; j < m; ++j) {  // (before anything is marked)
+            const int64_t status = fields[j * NPR_SAM_COLS + 15];
+            if (status == NPR_ERR_INVALID || status == NPR_SAM_UNKNOWN_REFERENCE) return NPR_ERR_INVALID;
+        }
+        // names -> the first record that carries them; records of the same name are chained in file order
+        std::unordered_map<std::string_view, int64_t> first;
+        first.reserve(static_cast<size_t>(n) * 2);
+        std::vector<int64_t> next(static_cast<size_t>(n), -1), last(static_cast<size_t>(n));
+        for (int64_t i = 0; i < n; ++i) {
+            if (name_span[2 * i + 1] < name_span[2 * i]) return NPR_ERR_INVALID;
+            const auto at = first.emplace(std::string_view(names_text + name_span[2 * i], static_cast<size_t>(name_span[2 * i + 1] - name_span[2 * i])), i);
+            if (!at.second) next[last[at.first->second]] = i;
+            last[at.first->second] = i;
+        }
+        std::atomic<int64_t> strangers{0};
+        parallel_for((m + 255) / 256, usable_cpus(), [&](int64_t c) {
+            int64_t mine = 0;
+            for (int64_t j = c * 256, hi = std::min(m, (c + 1) * 256); j < hi; ++j) {
+                const int64_t *f = fields + j * NPR_SAM_COLS;
+                if (f[15] != NPR_OK || (f[7] & 4)) continue;
+                const auto it = first.find(std::string_view(sam_text + span[2 * j], static_cast<size_t>(f[0] - span[2 * j])));
+                if (it == first.end()) {
+                    ++mine;
+                    continue;
+                }
+                for (int64_t i = it->second; i >= 0; i = next[i]) __atomic_store_n(&mark[i], uint8_t(1), __ATOMIC_RELAXED);  // (several lines may name one read)
+            }
+            strangers += mine;
+        });
+        return strangers;
+    } catch (const std::exception &) {
+        return NPR_ERR_NOMEM;
+    }
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// npr_kmer.hip -- k_kmer_spectrum, k_indel_kmers: the k-mer tables of the reference's KmerAnalysis and IndelKmerAnalysis, counted on the device.
+// npr_kmer.hip -- k_kmer_spectrum, k_kmer_spectrum_groups, k_indel_kmers: the k-mer tables of the reference's KmerAnalysis, UnmappedKmerAnalysis and
+// IndelKmerAnalysis, counted on the device.
 //
 // nanopore/analyses/kmerAnalysis.py:15-28 slices every window of every reference and read sequence in Python, and
 // indelKmerAnalysis.py:11-19, :29-40 walks every alignment column of every SAM record through an ordered set to find the k-mers that
@@ -11,6 +12,18 @@
 // First numbers (rocprofv3 --kernel-trace --stats, tools/kmer_time.py: 50 000 reads of ~8 kb, k = 5, one MI355X): k_kmer_spectrum 0.67 ms for
 // 394 MB of bases (0.59 TB/s: the LDS adds, not HBM, set the pace); k_indel_kmers 10.5 ms for 98.8 M cigar words read twice (0.79 GB) and
 // 160 M k-mers counted -- the wave-uniform walk over the operations is what it waits for.  Neither shape has been tuned.
+// k_kmer_spectrum_groups (the same windows into one table per group, below), same bases dealt round-robin into groups, same box and session
+// (tools/kmer_groups_time.py, medians of seven launches, range in brackets; profiles/kmer_groups_time.json): k_kmer_spectrum 0.667 ms
+// (0.666 - 0.668; the parent commit's build 0.666, 0.665 - 0.667), two groups 0.688 ms (0.687 - 0.690: + 3.3 %), eight groups 0.706 ms
+// (0.702 - 0.706: + 5.9 %) -- outside the 0.3 % the launches scatter by.  What it does more: a flush per group a workgroup meets (each
+// of the 2304 workgroups strides over the whole text and so meets every group: G x 1025 64-bit atomics per workgroup instead of 1 x), and per
+// tile four dependent loads from the group tables (tile0, seq_first twice, the group's end) before the tile's own search can start; the
+// step from one table to two groups (one more flush) costs more than each further group, which points at the per-tile loads.  Keeping
+// them in registers until the group changes is the obvious next step and has not been measured.  The whole call (stage the spans into
+// the pinned buffer ordered by group, one H2D, kernel, D2H): 13.6 ms (12.6 - 26.8) for two groups and 12.6 ms (11.9 - 13.1) for eight,
+// against 8.2 / 9.9 ms for npr_kmer_counts once per group on bases that ALREADY lie contiguous per group (all bases as one table: 8.1 ms)
+// and ~1 000 ms when numpy has to gather each group first: the staging copy of 394 MB on the host is the difference, and it is serial
+// with the H2D it feeds.
 // Block shape (chosen before any measurement; the reasons are arithmetic):
 //   Both kernels keep their histogram in LDS as 32-bit counters (4 bytes x 4097 bins = 16 KB per table at k = 6) and flush it to the 64-bit
 //   table in global memory with one atomic per non-empty bin and workgroup -- the per-base traffic never leaves the CU.  256 threads per
@@ -30,6 +43,7 @@ constexpr int WAVE = 64;
 constexpr int THREADS = 256;
 constexpr int RUN = 32;               // window starts per lane and tile of k_kmer_spectrum: two 16-byte loads, the halo in a third
 constexpr int TILE = THREADS * RUN;
+static_assert(TILE == NPR_KMER_TILE, "the host lays the groups of k_kmer_spectrum_groups out in tiles of this size");
 static_assert(RUN + 16 <= NPR_KMER_PAD, "a lane whose run starts at the last base reads RUN + 16 bytes");
 
 __device__ __forceinline__ uint32_t code_of(uint32_t c) {
@@ -51,6 +65,41 @@ __device__ __forceinline__ void flush(uint32_t *h, int nb, unsigned long long *o
 // short of the end, and so does this.  The bases of all sequences lie back to back; a lane owns RUN consecutive window starts, reads its
 // run and a halo of k - 1 bases, keeps the code of the last k bases and the number of bases since the last one outside ACGT, and adds a
 // window when it lies inside one sequence (the sequence of a lane's first start: a search per wavefront, then a walk along seq_off).
+// One tile of one lane: the window starts j0 .. j0 + RUN of bases that end at n, which seq_off[0 .. n_seqs] cuts into sequences
+// (seq_off[0] <= the tile's first base, seq_off[n_seqs] = n).
+__device__ __forceinline__ void count_run(uint32_t *hist, const uint8_t *seq, int64_t tile0, int64_t n, const int64_t *seq_off, int64_t n_seqs, int k, int nb,
+                                          uint32_t mask) {
+    const int64_t j0 = tile0 + static_cast<int64_t>(threadIdx.x) * RUN;
+    if (j0 < n) {
+        // last sequence that starts at or before the wavefront's first base
+        const int64_t jw = tile0 + static_cast<int64_t>(threadIdx.x & ~(WAVE - 1)) * RUN;
+        int64_t lo = 0, hi = n_seqs - 1;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if (seq_off[mid] <= jw) lo = mid; else hi = mid - 1;
+        }
+        int64_t si = lo, end = seq_off[si + 1];
+        const uint4 *p = reinterpret_cast<const uint4 *>(seq + j0);
+        const uint4 v0 = p[0], v1 = p[1], v2 = p[2];
+        const uint32_t w[12] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w};
+        uint32_t code = 0;
+        int good = 0;
+#pragma unroll
+        for (int i = 0; i < RUN + NPR_KMER_MAX_K - 1; ++i) {
+            if (i < RUN + k - 1) {
+                const uint32_t c = code_of((w[i >> 2] >> (8 * (i & 3))) & 0xffu);
+                code = ((code << 2) | (c & 3u)) & mask;
+                good = c < 4u ? good + 1 : 0;
+                const int64_t j = j0 + i - (k - 1);  // start of the window that ends with this base
+                if (i >= k - 1 && j < n) {
+                    while (j >= end) end = seq_off[++si + 1];  // (seq_off[n_seqs] = n > j: the walk ends)
+                    if (j + k < end) atomicAdd(&hist[good >= k ? code : static_cast<uint32_t>(nb - 1)], 1u);
+                }
+            }
+        }
+    }
+}
+
 __global__ void __launch_bounds__(THREADS) k_kmer_spectrum(KmerArgs a) {
     extern __shared__ uint32_t hist[];
     const int k = a.k, nb = kmer_bins(k);
@@ -60,38 +109,37 @@ __global__ void __launch_bounds__(THREADS) k_kmer_spectrum(KmerArgs a) {
     const int64_t tiles = (a.n + TILE - 1) / TILE;
     int since_flush = 0;
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int64_t j0 = tile * TILE + static_cast<int64_t>(threadIdx.x) * RUN;
-        if (j0 < a.n) {
-            // last sequence that starts at or before the wavefront's first base
-            const int64_t jw = tile * TILE + static_cast<int64_t>(threadIdx.x & ~(WAVE - 1)) * RUN;
-            int64_t lo = 0, hi = a.n_seqs - 1;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if (a.seq_off[mid] <= jw) lo = mid; else hi = mid - 1;
-            }
-            int64_t si = lo, end = a.seq_off[si + 1];
-            const uint4 *p = reinterpret_cast<const uint4 *>(a.seq + j0);
-            const uint4 v0 = p[0], v1 = p[1], v2 = p[2];
-            const uint32_t w[12] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w};
-            uint32_t code = 0;
-            int good = 0;
-#pragma unroll
-            for (int i = 0; i < RUN + NPR_KMER_MAX_K - 1; ++i) {
-                if (i < RUN + k - 1) {
-                    const uint32_t c = code_of((w[i >> 2] >> (8 * (i & 3))) & 0xffu);
-                    code = ((code << 2) | (c & 3u)) & mask;
-                    good = c < 4u ? good + 1 : 0;
-                    const int64_t j = j0 + i - (k - 1);  // start of the window that ends with this base
-                    if (i >= k - 1 && j < a.n) {
-                        while (j >= end) end = a.seq_off[++si + 1];  // (seq_off[n_seqs] = n > j: the walk ends)
-                        if (j + k < end) atomicAdd(&hist[good >= k ? code : static_cast<uint32_t>(nb - 1)], 1u);
-                    }
-                }
-            }
-        }
+        count_run(hist, a.seq, tile * TILE, a.n, a.seq_off, a.n_seqs, k, nb, mask);
         if (++since_flush == (1 << 18)) flush(hist, nb, a.counts), since_flush = 0;
     }
     flush(hist, nb, a.counts);
+}
+
+// The same windows into one table per group (the unmapped-read meta-analyses: read type x mapped / unmapped).  The host has laid the
+// sequences out ordered by group, every group's bases from a tile boundary on (KmerGroupArgs), so a tile belongs to one group and is
+// counted exactly as k_kmer_spectrum counts it, with the group's own end and its own stretch of seq_off.  A workgroup still keeps ONE
+// histogram: its tiles come in ascending order, so their groups do too, and it flushes to the table of the group it leaves -- at most one
+// flush per group a workgroup touches (4 atomics per thread at k = 5), the LDS budget above unchanged for any number of groups.
+__global__ void __launch_bounds__(THREADS) k_kmer_spectrum_groups(KmerGroupArgs a) {
+    extern __shared__ uint32_t hist[];
+    const int k = a.k, nb = kmer_bins(k);
+    const uint32_t mask = static_cast<uint32_t>(nb - 2);
+    for (int q = threadIdx.x; q < nb; q += THREADS) hist[q] = 0;
+    __syncthreads();
+    const int64_t tiles = a.tile0[a.n_groups];
+    int since_flush = 0, g = 0, cur = -1;
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        while (tile >= a.tile0[g + 1]) ++g;  // (tile < tile0[n_groups]: the walk ends; a group without bases has no tile)
+        if (g != cur) {
+            if (cur >= 0) flush(hist, nb, a.counts + static_cast<int64_t>(cur) * nb), since_flush = 0;
+            cur = g;
+        }
+        const int64_t first = a.seq_first[g], n_seqs = a.seq_first[g + 1] - first - 1;
+        const int64_t *seq_off = a.seq_off + first;
+        count_run(hist, a.seq, tile * TILE, seq_off[n_seqs], seq_off, n_seqs, k, nb, mask);
+        if (++since_flush == (1 << 18)) flush(hist, nb, a.counts + static_cast<int64_t>(cur) * nb), since_flush = 0;
+    }
+    if (cur >= 0) flush(hist, nb, a.counts + static_cast<int64_t>(cur) * nb);
 }
 
 // ---- k_indel_kmers ----
@@ -221,6 +269,13 @@ int launch_kmer_spectrum(const KmerArgs &a, void *stream) {
     const int64_t tiles = (a.n + TILE - 1) / TILE;
     const int grid = static_cast<int>(tiles < 2304 ? tiles : 2304);  // 256 CUs x 9 resident workgroups
     hipLaunchKernelGGL(k_kmer_spectrum, dim3(grid), dim3(THREADS), sizeof(uint32_t) * kmer_bins(a.k), static_cast<hipStream_t>(stream), a);
+    return static_cast<int>(hipGetLastError());
+}
+
+int launch_kmer_spectrum_groups(const KmerGroupArgs &a, int64_t tiles, void *stream) {
+    if (tiles <= 0) return 0;
+    const int grid = static_cast<int>(tiles < 2304 ? tiles : 2304);  // as k_kmer_spectrum
+    hipLaunchKernelGGL(k_kmer_spectrum_groups, dim3(grid), dim3(THREADS), sizeof(uint32_t) * kmer_bins(a.k), static_cast<hipStream_t>(stream), a);
     return static_cast<int>(hipGetLastError());
 }
 

@@ -178,6 +178,34 @@ class FastaTable(object):
         return bytes(self.seq[self.off[k]:self.off[k + 1]]).decode("ascii")
 
 
+class FastqTable(object):
+    """A FASTQ file as text + record index, beside FastaTable: `text` (the mapped file, uint8), `name_span` / `seq_span`
+    (int64 [n, 2]: [start, end) of each record's name -- the first word after '@', what a mapper writes as QNAME -- and of its
+    sequence line inside `text`), `lengths` (bases per record).  Records in file order; no object per record.  The spans are
+    what npr_names_mark and npr_kmer_counts_groups take as they are."""
+
+    def __init__(self, path):
+        L = _lib.load()
+        self.path = path
+        self.text = _map(path)
+        n = _check(L.npr_fastq_index(ptr(self.text), len(self.text), None, 0), "npr_fastq_index")
+        rec = np.zeros((n, 4), dtype=np.int64)
+        if n:
+            _check(L.npr_fastq_index(ptr(self.text), len(self.text), ptr(rec), n), "npr_fastq_index")
+        self.name_span = np.ascontiguousarray(rec[:, 0:2])
+        self.seq_span = np.ascontiguousarray(rec[:, 2:4])
+        self.lengths = self.seq_span[:, 1] - self.seq_span[:, 0]
+
+    def __len__(self):
+        return len(self.lengths)
+
+    def name(self, i):
+        return bytes(self.text[self.name_span[i, 0]:self.name_span[i, 1]]).decode("ascii", errors="replace")
+
+    def sequence(self, i):
+        return bytes(self.text[self.seq_span[i, 0]:self.seq_span[i, 1]]).decode("ascii", errors="replace")
+
+
 def fastq_table(path):
     """getFastqDictionary (utils.py:240-245) without a Python loop over the lines: (names, text, seq spans [n, 2])."""
     L = _lib.load()

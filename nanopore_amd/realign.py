@@ -466,6 +466,22 @@ class Context(object):
             raise NprError(rc, "npr_kmer_counts", self.last_error())
         return out
 
+    def kmer_counts_groups(self, text, begin, end, group, n_groups, k=5):
+        """kmer_counts into one table per group in one pass (include/nprealign.h: npr_kmer_counts_groups): sequence i is
+        text[begin[i]:end[i]] -- spans inside a larger uint8 text, e.g. FastqTable.text / .seq_span --, group[i] in 0 .. n_groups - 1 picks
+        its table and -1 leaves it out: int64 [n_groups, 4^k + 1]."""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        begin, end = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        if not (len(begin) == len(end) == len(group)) or (len(begin) and (int(begin.min()) < 0 or int(end.max()) > len(text))):
+            raise NprError(_lib.ERR_INVALID, "npr_kmer_counts_groups", "spans and groups differ in number, or a span lies outside the text")
+        ok = 1 <= k <= _lib.KMER_MAX_K and 1 <= n_groups <= _lib.KMER_MAX_GROUPS
+        out = np.zeros((n_groups, 4 ** k + 1) if ok else (1, 1), dtype=np.int64)
+        rc = self._L.npr_kmer_counts_groups(self._h, int(k), len(begin), ptr(text), ptr(begin), ptr(end), ptr(group), int(n_groups), ptr(out))
+        if rc != _lib.OK:
+            raise NprError(rc, "npr_kmer_counts_groups", self.last_error())
+        return out
+
     def align_indel_kmers(self, refs, reads, cigars, k=5, ref_index=None, start=None):
         """The k-mers that straddle a gap of arbitrary alignments (arguments as for align_stats), counted on the device
         (include/nprealign.h: npr_align_indel_kmers): (read-side table, reference-side table), int64 [4^k + 1] each."""
@@ -733,6 +749,23 @@ def rescore(guide, x, y, p):
     if rc != _lib.OK:
         raise NprError(rc, "npr_rescore")
     return score.value
+
+
+def names_mark(names_text, name_span, sam_text, span, fields, mark):
+    """Which names a SAM file maps (include/nprealign.h: npr_names_mark; host code, no device needed): sets mark[i] = 1 for every
+    name i = names_text[name_span[i, 0]:name_span[i, 1]] that is the QNAME of an alignment line with a reference and without
+    FLAG 4 -- span / fields as SamText.span / SamText.parse() give them; marks already set stay set.  `mark`: uint8 [n],
+    written in place.  Returns the number of such lines whose QNAME is none of the names."""
+    names_text, sam_text = np.ascontiguousarray(names_text, dtype=np.uint8), np.ascontiguousarray(sam_text, dtype=np.uint8)
+    name_span = np.ascontiguousarray(name_span, dtype=np.int64).reshape(-1, 2)
+    span = np.ascontiguousarray(span, dtype=np.int64).reshape(-1, 2)
+    fields = np.ascontiguousarray(fields, dtype=np.int64).reshape(-1, _lib.SAM_COLS)
+    if not (isinstance(mark, np.ndarray) and mark.dtype == np.uint8 and mark.flags.c_contiguous and mark.shape == (len(name_span),)) or len(span) != len(fields):
+        raise NprError(_lib.ERR_INVALID, "npr_names_mark", "mark must be a contiguous uint8 array with one entry per name, span and fields one row per line")
+    rc = _lib.load().npr_names_mark(ptr(names_text), ptr(name_span), len(name_span), ptr(sam_text), ptr(span), ptr(fields), len(span), ptr(mark))
+    if rc < 0:
+        raise NprError(int(rc), "npr_names_mark")
+    return int(rc)
 
 
 def encode(seq):
