@@ -161,7 +161,14 @@ const char *npr_last_error(npr_ctx *ctx);
 #define NPR_OPT_EM_GENERIC 17      /* 1: the E-step on the any-band kernel */
 #define NPR_OPT_MEA_WIDE_OPS 20    /* 1: the packed cigars cross PCIe as whole words even when every run fits 14 bits */
 #define NPR_OPT_EM_TILE 21         /* the E-step of stripe tasks: 0 column-scaled arithmetic first (k_dp_tile_cs's E-step instance; what its certificate refuses goes to k_em_tile), 1 k_em_tile only, 2 (tests) as 0 with every other task refused */
-#define NPR_OPT_COUNT 22
+/* NPR_OPT_FINISH_TEXT (not a bring-up switch; 0 by default, value 1): npr_batch_finish's device MEA stage formats the cigars as SAM text on the
+ * device (csrc/npr_cigtext.hip) right after it has gathered them, and the TEXT and its offsets cross PCIe through the pinned staging
+ * instead of the packed words; npr_batch_cigar_text then copies from the host.  npr_batch_ops / npr_batch_ops_packed (and the batch
+ * statistics, k-mer and pileup entry points) on such a batch fetch the words from the device on demand while the stage's tables are still
+ * there, and return NPR_ERR_STATE with a message once another batch's finish has overwritten them.  Results do not change; batches that take the
+ * host stage are not affected. */
+#define NPR_OPT_FINISH_TEXT 22
+#define NPR_OPT_COUNT 23
 int32_t npr_ctx_option(npr_ctx *ctx, int32_t option, int64_t value);
 
 /* --loadHmm=<file> (utils.py:586-587): the 25 transition and 80 emission PROBABILITIES exactly as they
@@ -464,6 +471,20 @@ int64_t npr_format_cigars(int64_t n, const int64_t *ops_off, const int32_t *ops,
  * anywhere in `words`, so the gathered payloads need no merge copy before the SAM is written. */
 int64_t npr_format_cigars_packed(int64_t n, const int64_t *word_off, const int64_t *n_ops, const uint32_t *words, int64_t *str_off,
                                  char *out, int64_t cap);
+/* The same text made ON THE DEVICE (csrc/npr_cigtext.hip): host arrays in, host arrays out, the words uploaded, counted, scanned and
+ * formatted by kernels in between.  The contract of npr_format_cigars_packed word for word -- out == NULL: only the offsets; returns the
+ * total length; NPR_ERR_CAPACITY when cap is smaller (the offsets are written); NPR_ERR_INVALID for an op outside M/I/D or a negative
+ * n_ops, and then neither out nor str_off is written.  It exists so that the kernels can be tested on lists no batch produces; a caller
+ * with cigars on the host wants npr_format_cigars_packed. */
+int64_t npr_cigar_text_packed(npr_ctx *ctx, int64_t n, const int64_t *word_off, const int64_t *n_ops, const uint32_t *words, int64_t *str_off,
+                              char *out, int64_t cap);
+/* The cigars npr_batch_ops_packed would return, as that text: string i = cigar of read i ("*" for a read that failed), str_off[n_reads + 1];
+ * out == NULL: only the offsets; returns the total length, NPR_ERR_CAPACITY when cap is smaller, NPR_ERR_STATE before npr_batch_finish.
+ * After npr_batch_finish in every mode.  The packed words are formatted where they lie while the copy the device MEA stage left on the
+ * device is still valid (no other batch finished on the device since) and uploaded from the batch's host form otherwise (the host stage,
+ * NPR_MODE_RESCORE_ORIGINAL, a later finish in between); under NPR_OPT_FINISH_TEXT the text is on the host already.  The first call makes
+ * the text and keeps it with the batch: the sizing call and the fetching call cost one formatting. */
+int64_t npr_batch_cigar_text(npr_batch *b, int64_t *str_off, char *out, int64_t cap);
 /* The realigned SAM records themselves, as text: what realignSamFile3TargetFn's writer puts out for every record after
  * assigning the new cigar (nanopore/analyses/utils.py:591-609; pysam's AlignmentFile.write there), for a job that writes
  * 50 k records per rank at once.  Record i = QNAME \t FLAG \t RNAME \t POS \t MAPQ \t CIGAR \t * \t 0 \t 0 \t SEQ \t * \n with
@@ -523,6 +544,12 @@ int32_t npr_sam_guides(const char *text, const int64_t *fields, int64_t n, const
  * NPR_ERR_CAPACITY when cap is smaller, NPR_ERR_INVALID for an operation outside M / I / D.  Threaded. */
 int64_t npr_sam_splice(const char *text, const int64_t *span, const int64_t *fields, int64_t n, const int64_t *word_off,
                        const int64_t *n_ops, const uint32_t *words, int64_t *rec_off, char *out, int64_t cap);
+
+/* npr_sam_splice for cigars that are text already (npr_batch_cigar_text, npr_cigar_text_packed, npr_format_cigars_packed): line i with its
+ * CIGAR field replaced by cigar_text[str_off[i] .. str_off[i + 1]), every other byte copied, each record ending in "\n".  Same return and
+ * errors as npr_sam_splice, without the check of the operations (NPR_ERR_INVALID: offsets that decrease).  Threaded host code. */
+int64_t npr_sam_splice_text(const char *text, const int64_t *span, const int64_t *fields, int64_t n, const int64_t *str_off,
+                            const char *cigar_text, int64_t *rec_off, char *out, int64_t cap);
 
 /* FASTA text (getFastaDictionary, utils.py:233-238): returns the number of records; rec[4 * k ..] = [start, end) of the
  * record's name (first word of the header line) and [start, end) of its sequence lines in the text, seq_len[k] = bases

@@ -42,7 +42,8 @@ OPT_OVERLAP = 1
 OPT_RELEASE_SCRATCH = 2
 # test / bring-up switches (include/nprealign.h: NPR_OPT_*; none changes a result)
 OPTIONS = dict(kernel=3, arith=4, pair=5, no_tile=6, no_wide=7, tile_rs=8, tile_waves=9, host_mea=13, mea_ring_only=14,
-               mea_global_sort=15, em_generic=17, mea_wide_ops=20, em_tile=21)
+               mea_global_sort=15, em_generic=17, mea_wide_ops=20, em_tile=21, finish_text=22)
+OPT_FINISH_TEXT = 22  # NPR_OPT_FINISH_TEXT: the device MEA stage hands over the cigars as SAM text (0 by default; no result changes)
 KERNEL_GENERIC, ARITH_CELL, PAIR_NEVER, PAIR_LONG, PAIR_ALL = 1, 1, 1, 2, 3
 STATS_WORDS = 40  # NPR_STATS_WORDS
 KMER_MAX_K = 6    # the k-mer tables: 4^k + 1 bins, the last one for k-mers with a base outside ACGT
@@ -121,6 +122,7 @@ EXPORTS = [
     "npr_plan_segment_band", "npr_plan_frame_schedule", "npr_plan_stripes", "npr_format_cigars", "npr_format_cigars_packed", "npr_format_sam_records", "npr_chain_hits", "npr_mea_cigar", "npr_rescore", "npr_encode_bases",
     "npr_sam_index", "npr_sam_parse", "npr_sam_guides", "npr_sam_splice", "npr_fasta_index", "npr_fasta_pack", "npr_fastq_index", "npr_names_mark",
     "npr_batch_create_spans", "npr_chain_merge", "npr_ctx_option", "npr_batch_segment_arith",
+    "npr_cigar_text_packed", "npr_batch_cigar_text", "npr_sam_splice_text",
 ]
 
 _lib = None
@@ -251,6 +253,12 @@ def load():
     L.npr_sam_guides.argtypes = [vp, vp, i64, vp, vp]
     L.npr_sam_splice.restype = i64
     L.npr_sam_splice.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, i64]
+    L.npr_sam_splice_text.restype = i64
+    L.npr_sam_splice_text.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, i64]
+    L.npr_cigar_text_packed.restype = i64
+    L.npr_cigar_text_packed.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64]
+    L.npr_batch_cigar_text.restype = i64
+    L.npr_batch_cigar_text.argtypes = [vp, vp, vp, i64]
     L.npr_fasta_index.restype = i64
     L.npr_fasta_index.argtypes = [vp, i64, vp, vp, i64]
     L.npr_fasta_pack.restype = i32

@@ -6,6 +6,7 @@
 //   npr_finish.cpp  npr_batch_finish and what reads its results: the device MEA stage, the rescore sums, the host stage, ops / pairs
 //   npr_aux.cpp     post-alignment statistics, k-mer tables, base expectations, the device pileup, the planner cross-check
 //   npr_text.cpp    cigar and SAM record text (the transport forms a job ships)
+//   npr_cigtext_api.cpp  cigar text made on the device (npr_cigtext.hip): npr_cigar_text_packed, npr_batch_cigar_text, NPR_OPT_FINISH_TEXT
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -337,6 +338,12 @@ struct npr_batch {
     const uint32_t *dev_ops = nullptr;
     const int64_t *dev_od = nullptr;
     uint64_t dev_ops_epoch = 0;
+    // the cigars as SAM text on the host (npr_cigtext_api.cpp): made by npr_batch_finish under NPR_OPT_FINISH_TEXT, else the first time
+    // npr_batch_cigar_text asks.  words_on_device: such a finish left the packed words on the device only (fetch_device_words)
+    std::unique_ptr<char[]> text;
+    int64_t text_cap = 0;
+    std::vector<int64_t> text_off;
+    bool text_ready = false, words_on_device = false;
 };
 
 // the device pileup (npr_aux.cpp, npr_pileup.hip): the table and the difference array of its deletion columns live on the device from
@@ -477,4 +484,6 @@ KernelArgs make_args(npr_batch *b);                        // npr_run.cpp: the k
 int32_t ensure_coff(npr_batch *b);                         // npr_stage.cpp: the generic kernel's row offsets, made on demand
 int32_t release_scratch(npr_ctx *ctx, bool caches_only);   // npr_api.cpp
 void ensure_packed_form(npr_batch *b);                     // npr_finish.cpp: the batch's cigars as one word per operation
+int32_t device_mea_text(npr_batch *b, MeaArgs &a, const std::vector<int64_t> &od, StageTimer &tm);  // npr_cigtext_api.cpp: the end of device_mea under NPR_OPT_FINISH_TEXT
+int32_t fetch_device_words(npr_batch *b);                  // npr_cigtext_api.cpp: the packed words such a finish left on the device, while they are there
 }  // namespace npr_impl

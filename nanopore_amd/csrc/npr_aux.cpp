@@ -86,6 +86,10 @@ int32_t with_batch_cigars(npr_batch *b, const CigarFn &run) {
     std::unique_lock<std::mutex> arena_lock(ctx->arena->mu);  // the resident cigars lie in the arena
     if (b->dev_ops && b->dev_ops_epoch == ctx->arena->epoch) return run(b->dev_ops, b->dev_od, nullptr, nullptr);
     arena_lock.unlock();
+    if (b->words_on_device && !b->have_packed_form) {  // (finished with NPR_OPT_FINISH_TEXT: the words were on the device only)
+        const int32_t rc = fetch_device_words(b);
+        if (rc != NPR_OK) return rc;
+    }
     ensure_packed_form(b);
     std::vector<uint32_t> packed(b->packed.get(), b->packed.get() + b->ops_off[n]);
     return run(nullptr, nullptr, &packed, &b->ops_off);

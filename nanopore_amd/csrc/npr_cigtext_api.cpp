@@ -1,0 +1,246 @@
+// npr_cigtext_api.cpp -- cigar text made on the device (npr_cigtext.hip): npr_cigar_text_packed, npr_batch_cigar_text, and what
+// NPR_OPT_FINISH_TEXT makes of the end of the device MEA stage (utils.py:597-605: the writer loop's `aR.cigar = ...`)
+// (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
+#include "npr_api_internal.h"
+
+namespace npr_impl {
+namespace {
+
+// what the text kernels need besides the words: offsets, the scan's scratch, the flag; and the text when nobody lends a buffer
+struct TextBufs {
+    DevBuf<int64_t> off, tile;
+    DevBuf<int32_t> bad;
+    DevBuf<char> text;
+    char *text_p = nullptr;
+};
+
+// Lengths, offsets and (want_text) the text of n lists whose words are on the device.  str_off[n + 1] on the host when the call returns
+// NPR_OK; the text stays on the device at bufs.text_p -- in `lend` (lend_bytes) when it fits there.  NPR_ERR_INVALID: an op outside M I D,
+// NPR_ERR_CAPACITY: want_text and the total is above cap (the offsets are valid then); nothing is written in either case.
+int32_t run_cigtext(npr_ctx *ctx, int64_t n, const int64_t *d_word_off, const int64_t *d_n_ops, const uint32_t *d_words, bool want_text,
+                    int64_t cap, char *lend, size_t lend_bytes, TextBufs &bufs, int64_t *str_off) {
+    hipError_t e;
+    if ((e = bufs.off.alloc_from(ctx, n + 1)) != hipSuccess || (e = bufs.tile.alloc_from(ctx, cigtext_scan_tiles(n + 1))) != hipSuccess ||
+        (e = bufs.bad.alloc_from(ctx, 1)) != hipSuccess)
+        return fail(ctx, NPR_ERR_NOMEM, "cigar text: hipMalloc", e);
+    HIP_TRY(ctx, hipMemsetAsync(bufs.bad.p, 0, sizeof(int32_t), ctx->stream));
+    CigTextArgs a{n, d_word_off, d_n_ops, d_words, bufs.off.p, bufs.tile.p, bufs.bad.p, nullptr};
+    int rc = launch_cigtext_offsets(a, ctx->stream);
+    if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_cigtext_len / scan launch", static_cast<hipError_t>(rc));
+    int32_t bad = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(str_off, bufs.off.p, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, bufs.bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (bad) return fail(ctx, NPR_ERR_INVALID, "cigar text: an operation outside M / I / D");
+    if (!want_text) return NPR_OK;
+    const int64_t total = str_off[n];
+    if (cap < total) return NPR_ERR_CAPACITY;
+    if (static_cast<size_t>(total) <= lend_bytes) {
+        bufs.text_p = lend;
+    } else {
+        if ((e = bufs.text.alloc_from(ctx, total)) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "cigar text: hipMalloc", e);
+        bufs.text_p = bufs.text.p;
+    }
+    a.out = bufs.text_p;
+    if ((rc = launch_cigtext_write(a, ctx->stream)) != 0) return fail(ctx, NPR_ERR_HIP, "k_cigtext_write launch", static_cast<hipError_t>(rc));
+    return NPR_OK;
+}
+
+// `bytes` from the device to pageable host memory through the context's pinned staging, in pieces: the host threads move a piece out of
+// the staging buffer while the next ones cross (what device_mea does with the packed words)
+int32_t fetch_through_pin(npr_ctx *ctx, const char *dev, int64_t bytes, char *dst) {
+    if (bytes <= 0) return NPR_OK;
+    hipError_t e;
+    const size_t need = static_cast<size_t>(bytes);
+    if (need > ctx->pin_pairs_bytes) {
+        if (ctx->pin_pairs) (void)hipHostFree(ctx->pin_pairs);
+        ctx->pin_pairs = nullptr, ctx->pin_pairs_bytes = 0;
+        if ((e = hipHostMalloc(&ctx->pin_pairs, need + need / 4, hipHostMallocDefault)) != hipSuccess)
+            return fail(ctx, NPR_ERR_NOMEM, "cigar text: hipHostMalloc", e);
+        ctx->pin_pairs_bytes = need + need / 4;
+    }
+    constexpr int64_t kPieces = 48;
+    const int64_t pieces = std::min<int64_t>(kPieces, (bytes + (4 << 20) - 1) >> 22);
+    const int64_t piece = ((bytes + pieces - 1) / pieces + 255) & ~int64_t(255);
+    while (static_cast<int64_t>(ctx->ops_events.size()) < pieces) {
+        hipEvent_t ev;
+        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return fail(ctx, NPR_ERR_HIP, "hipEventCreate", e);
+        ctx->ops_events.push_back(ev);
+    }
+    char *pin = static_cast<char *>(ctx->pin_pairs);
+    for (int64_t c = 0; c < pieces; ++c) {
+        const int64_t lo = std::min(bytes, c * piece), hi = std::min(bytes, lo + piece);
+        if (hi > lo) HIP_TRY(ctx, hipMemcpyAsync(pin + lo, dev + lo, static_cast<size_t>(hi - lo), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ops_events[c], ctx->stream));
+    }
+    std::atomic<int> failed{0};
+    parallel_for(pieces, ctx->host_threads, [&](int64_t c) {  // (the items are handed out in order)
+        if (hipSetDevice(ctx->device) != hipSuccess || hipEventSynchronize(ctx->ops_events[c]) != hipSuccess) {  // (a worker thread starts on device 0)
+            failed = 1;
+            return;
+        }
+        const int64_t lo = std::min(bytes, c * piece), hi = std::min(bytes, lo + piece);
+        std::memcpy(dst + lo, pin + lo, static_cast<size_t>(hi - lo));
+    });
+    if (failed) return fail(ctx, NPR_ERR_HIP, "cigar text: D2H", hipGetLastError());
+    return NPR_OK;
+}
+
+int32_t keep_text(npr_batch *b, const TextBufs &bufs, std::vector<int64_t> &off) {
+    const int64_t total = off[b->n_reads];
+    if (total > b->text_cap) b->text.reset(new char[total + total / 8]), b->text_cap = total + total / 8;
+    const int32_t rc = fetch_through_pin(b->ctx, bufs.text_p, total, b->text.get());
+    if (rc != NPR_OK) return rc;
+    b->text_off.swap(off);
+    b->text_ready = true;
+    return NPR_OK;
+}
+
+// the text of a finished batch on the host (b->text, b->text_off), made once: from the packed words where the device MEA stage left them
+// while they are still there, else from the batch's host form, uploaded
+int32_t ensure_text(npr_batch *b) {
+    if (b->text_ready) return NPR_OK;
+    npr_ctx *ctx = b->ctx;
+    const int64_t n = b->n_reads;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<int64_t> off(n + 1, 0);
+    TextBufs bufs;
+    if (n == 0) return keep_text(b, bufs, off);
+    {
+        std::unique_lock<std::mutex> arena_lock(ctx->arena->mu);  // the resident cigars lie in the arena
+        if (b->dev_ops && b->dev_ops_epoch == ctx->arena->epoch) {
+            const int32_t rc = run_cigtext(ctx, n, b->dev_od, nullptr, b->dev_ops, true, INT64_MAX, nullptr, 0, bufs, off.data());
+            return rc != NPR_OK ? rc : keep_text(b, bufs, off);  // (keep_text ends with the stream drained: the lock goes after it)
+        }
+    }
+    if (b->words_on_device && !b->have_packed_form) {
+        const int32_t rc = fetch_device_words(b);  // (fails: the words are gone)
+        if (rc != NPR_OK) return rc;
+    }
+    ensure_packed_form(b);
+    const int64_t words = b->ops_off[n];
+    DevBuf<uint32_t> d_words;
+    DevBuf<int64_t> d_off;
+    hipError_t e;
+    if ((e = d_words.alloc_from(ctx, std::max<int64_t>(words, 1))) != hipSuccess || (e = d_off.alloc_from(ctx, n + 1)) != hipSuccess)
+        return fail(ctx, NPR_ERR_NOMEM, "npr_batch_cigar_text: hipMalloc", e);
+    if (words) HIP_TRY(ctx, hipMemcpyAsync(d_words.p, b->packed.get(), sizeof(uint32_t) * static_cast<size_t>(words), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_off.p, b->ops_off.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
+    const int32_t rc = run_cigtext(ctx, n, d_off.p, nullptr, d_words.p, true, INT64_MAX, nullptr, 0, bufs, off.data());
+    return rc != NPR_OK ? rc : keep_text(b, bufs, off);
+}
+
+}  // namespace
+
+// NPR_OPT_FINISH_TEXT: the end of device_mea (npr_finish.cpp) from the point where the reads' results are known -- the gather, then the
+// text kernels over the words the gather left in m.dense, and the TEXT and its offsets through the pinned staging instead of the words.
+// The words stay on the device for npr_batch_ops / npr_batch_ops_packed (fetch_device_words) while the stage's tables are not overwritten.
+int32_t device_mea_text(npr_batch *b, MeaArgs &a, const std::vector<int64_t> &od, StageTimer &tm) {
+    npr_ctx *ctx = b->ctx;
+    MeaScratch &m = *ctx->mea;
+    const int64_t n = b->n_reads;
+    b->have_pairs_form = false, b->have_packed_form = false, b->words_on_device = true;
+    HIP_TRY(ctx, hipMemcpyAsync(m.od.p, od.data(), m.od.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    if (od[n]) {
+        a.ops_dense = m.dense.p;  // (sized for the bound ot[n] >= od[n])
+        a.ops_dense16 = nullptr;
+        const int rc = launch_mea_gather(a, ctx->stream);
+        if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_mea_gather launch", static_cast<hipError_t>(rc));
+    }
+    std::vector<int64_t> off(n + 1, 0);
+    TextBufs bufs;
+    // (the sorted pairs are done with: the text goes where the default path puts the 16-bit words)
+    int32_t rc = run_cigtext(ctx, n, m.od.p, nullptr, m.dense.p, true, INT64_MAX, reinterpret_cast<char *>(m.sorted.p), m.sorted.bytes(), bufs, off.data());
+    if (rc == NPR_OK) rc = keep_text(b, bufs, off);
+    if (rc != NPR_OK) return rc;
+    tm.lap("gather + D2H of the ops");
+    b->dev_ops = m.dense.p, b->dev_od = m.od.p, b->dev_ops_epoch = ctx->arena->epoch;
+    return NPR_OK;
+}
+
+// a batch finished with NPR_OPT_FINISH_TEXT has its packed words on the device only: to the host while they are still there
+int32_t fetch_device_words(npr_batch *b) {
+    npr_ctx *ctx = b->ctx;
+    const int64_t total = b->ops_off[b->n_reads];
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::unique_lock<std::mutex> arena_lock(ctx->arena->mu);
+    if (!(b->dev_ops && b->dev_ops_epoch == ctx->arena->epoch))
+        return fail(ctx, NPR_ERR_STATE, "the batch was finished with NPR_OPT_FINISH_TEXT and its packed cigars have since been overwritten on the device: "
+                                        "fetch them before the next batch is finished, or use npr_batch_cigar_text");
+    if (total > b->packed_cap) b->packed.reset(new uint32_t[total]), b->packed_cap = total;
+    if (total) HIP_TRY(ctx, hipMemcpyAsync(b->packed.get(), b->dev_ops, sizeof(uint32_t) * static_cast<size_t>(total), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    b->have_packed_form = true;
+    return NPR_OK;
+}
+
+}  // namespace npr_impl
+
+extern "C" {
+
+int64_t npr_cigar_text_packed(npr_ctx *ctx, int64_t n, const int64_t *word_off, const int64_t *n_ops, const uint32_t *words, int64_t *str_off,
+                              char *out, int64_t cap) {
+    if (!ctx) return NPR_ERR_INVALID;
+    if (n < 0 || (n && (!word_off || !n_ops || !str_off || !words))) return fail(ctx, NPR_ERR_INVALID, "npr_cigar_text_packed: bad argument");
+    try {
+        if (n == 0) {
+            if (str_off) str_off[0] = 0;
+            return 0;
+        }
+        // the part of `words` the lists cover goes up, the offsets relative to it
+        int64_t lo = INT64_MAX, hi = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            if (n_ops[i] < 0 || (n_ops[i] && word_off[i] < 0)) return fail(ctx, NPR_ERR_INVALID, "npr_cigar_text_packed: a negative count or offset");
+            if (n_ops[i]) lo = std::min(lo, word_off[i]), hi = std::max(hi, word_off[i] + n_ops[i]);
+        }
+        if (hi == 0) lo = 0;
+        std::vector<int64_t> rel(n);
+        for (int64_t i = 0; i < n; ++i) rel[i] = n_ops[i] ? word_off[i] - lo : 0;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        DevBuf<uint32_t> d_words;
+        DevBuf<int64_t> d_off, d_nops;
+        hipError_t e;
+        if ((e = d_words.alloc_from(ctx, std::max<int64_t>(hi - lo, 1))) != hipSuccess || (e = d_off.alloc_from(ctx, n)) != hipSuccess ||
+            (e = d_nops.alloc_from(ctx, n)) != hipSuccess)
+            return fail(ctx, NPR_ERR_NOMEM, "npr_cigar_text_packed: hipMalloc", e);
+        if (hi > lo) HIP_TRY(ctx, hipMemcpyAsync(d_words.p, words + lo, sizeof(uint32_t) * static_cast<size_t>(hi - lo), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_off.p, rel.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_nops.p, n_ops, sizeof(int64_t) * n, hipMemcpyHostToDevice, ctx->stream));
+        std::vector<int64_t> off(n + 1, 0);
+        TextBufs bufs;
+        const int32_t rc = run_cigtext(ctx, n, d_off.p, d_nops.p, d_words.p, out != nullptr, cap, nullptr, 0, bufs, off.data());
+        if (rc != NPR_OK && rc != NPR_ERR_CAPACITY) return rc;  // (an op outside M I D: str_off is not written either)
+        std::copy(off.begin(), off.end(), str_off);
+        if (rc == NPR_ERR_CAPACITY) return rc;
+        if (out) {
+            if (off[n]) HIP_TRY(ctx, hipMemcpyAsync(out, bufs.text_p, static_cast<size_t>(off[n]), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        return off[n];
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_cigar_text_packed: out of host memory");
+    }
+}
+
+int64_t npr_batch_cigar_text(npr_batch *b, int64_t *str_off, char *out, int64_t cap) {
+    if (!b || !str_off) return NPR_ERR_INVALID;
+    if (!b->finished) return fail(b->ctx, NPR_ERR_STATE, "npr_batch_cigar_text before npr_batch_finish");
+    try {
+        const int32_t rc = ensure_text(b);
+        if (rc != NPR_OK) return rc;
+    } catch (const std::exception &) {
+        return fail(b->ctx, NPR_ERR_NOMEM, "npr_batch_cigar_text: out of host memory");
+    }
+    std::copy(b->text_off.begin(), b->text_off.end(), str_off);
+    const int64_t total = b->text_off[b->n_reads];
+    if (!out) return total;
+    if (cap < total) return NPR_ERR_CAPACITY;
+    const char *src = b->text.get();
+    const int64_t chunk = 4 << 20, nchunks = (total + chunk - 1) / chunk;
+    parallel_for(nchunks, b->ctx->host_threads, [&](int64_t c) {
+        std::memcpy(out + c * chunk, src + c * chunk, static_cast<size_t>(std::min(total, (c + 1) * chunk) - c * chunk));
+    });
+    return total;
+}
+
+}  // extern "C"

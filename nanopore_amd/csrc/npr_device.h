@@ -308,6 +308,20 @@ int launch_pileup_add(const PileupArgs &a, void *stream);
 int64_t pileup_scan_tiles(int64_t n_slots);
 int launch_pileup_scan(const PileupScanArgs &a, void *stream);
 int launch_pileup_depth(const int32_t *tab, int64_t rows, int32_t *depth, uint8_t *covered, void *stream);
+// SAM CIGAR text of packed cigars on the device (npr_cigtext.hip): list i = words[word_off[i] .. word_off[i] + n_ops[i])
+struct CigTextArgs {
+    int64_t n;
+    const int64_t *word_off;  // [n], or [n + 1] when n_ops is null
+    const int64_t *n_ops;     // [n]; null: list i ends where list i + 1 begins
+    const uint32_t *words;    // one word per cigar op: length << 2 | op
+    int64_t *str_off;         // [n + 1]: the lengths pass writes every string's length, the scan turns them into offsets in place
+    int64_t *tile;            // [cigtext_scan_tiles(n + 1)] scratch of the scan
+    int32_t *bad;             // set to 1 when a list holds an operation outside M I D
+    char *out;                // the write pass: string i at out[str_off[i] .. str_off[i + 1])
+};
+int64_t cigtext_scan_tiles(int64_t entries);
+int launch_cigtext_offsets(const CigTextArgs &a, void *stream);  // lengths + exclusive scan: str_off, *bad
+int launch_cigtext_write(const CigTextArgs &a, void *stream);
 constexpr float EXPECT_FIXED_ONE = 1099511627776.0f;  // 2^40
 struct ExpectArgs {
     const Task *tasks;

@@ -360,6 +360,7 @@ int32_t device_mea(npr_batch *b) {
     }
     b->ops_off = od;
     b->ops_words = 2 * od[n];
+    if (ctx->opt[NPR_OPT_FINISH_TEXT] != 0) return device_mea_text(b, a, od, tm);  // the text crosses PCIe instead of the words (npr_cigtext_api.cpp)
     b->have_pairs_form = false, b->have_packed_form = true;
     if (od[n] > b->packed_cap)  // kept when the batch is finished again; else one a destroyed batch left behind, if it is large enough
         for (size_t i = 0; i < ctx->packed_pool.size(); ++i)
@@ -455,6 +456,7 @@ static int32_t batch_finish_impl(npr_batch *b) {
     b->results.assign(n, npr_read_result{});
     b->pair_off.assign(n + 1, 0);
     b->pairs_ready = false;
+    b->text_ready = false, b->words_on_device = false;
     const double LN2 = 0.69314718055994530942;
     for (int64_t i = 0; i < n; ++i) {
         npr_read_result &r = b->results[i];
@@ -628,6 +630,10 @@ int32_t npr_batch_ops(const npr_batch *b, int64_t *ops_off, int32_t *ops, int64_
     if (!ops) return NPR_OK;
     if (cap_pairs < b->ops_off[b->n_reads]) return NPR_ERR_CAPACITY;
     try {
+        if (b->words_on_device && !b->have_packed_form && !b->have_pairs_form) {  // (finished with NPR_OPT_FINISH_TEXT)
+            const int32_t rc = fetch_device_words(const_cast<npr_batch *>(b));
+            if (rc != NPR_OK) return rc;
+        }
         ensure_pairs_form(const_cast<npr_batch *>(b));
     } catch (const std::exception &) {
         return fail(b->ctx, NPR_ERR_NOMEM, "npr_batch_ops: out of host memory");
@@ -644,6 +650,10 @@ int32_t npr_batch_ops_packed(const npr_batch *b, int64_t *ops_off, uint32_t *wor
     const int64_t total = b->ops_off[b->n_reads];
     if (cap_words < total) return NPR_ERR_CAPACITY;
     try {
+        if (b->words_on_device && !b->have_packed_form) {  // (finished with NPR_OPT_FINISH_TEXT)
+            const int32_t rc = fetch_device_words(const_cast<npr_batch *>(b));
+            if (rc != NPR_OK) return rc;
+        }
         ensure_packed_form(const_cast<npr_batch *>(b));
     } catch (const std::exception &) {
         return fail(b->ctx, NPR_ERR_NOMEM, "npr_batch_ops_packed: out of host memory");

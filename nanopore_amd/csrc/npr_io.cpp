@@ -303,6 +303,38 @@ int64_t npr_sam_splice(const char *text, const int64_t *span, const int64_t *fie
     }
 }
 
+int64_t npr_sam_splice_text(const char *text, const int64_t *span, const int64_t *fields, int64_t n, const int64_t *str_off,
+                            const char *cigar_text, int64_t *rec_off, char *out, int64_t cap) {
+    if (n < 0 || (n && (!text || !span || !fields || !str_off || !rec_off))) return NPR_ERR_INVALID;
+    try {
+        const int threads = usable_cpus();
+        rec_off[0] = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t *f = fields + i * NPR_SAM_COLS;
+            const int64_t k = str_off[i + 1] - str_off[i];
+            if (k < 0 || (k && !cigar_text)) return NPR_ERR_INVALID;
+            rec_off[i + 1] = rec_off[i] + (f[3] - span[2 * i]) + k + (span[2 * i + 1] - f[4]) + 1;
+        }
+        if (!out) return rec_off[n];
+        if (cap < rec_off[n]) return NPR_ERR_CAPACITY;
+        parallel_for((n + 63) / 64, threads, [&](int64_t c) {
+            for (int64_t i = c * 64, hi = std::min(n, (c + 1) * 64); i < hi; ++i) {
+                const int64_t *f = fields + i * NPR_SAM_COLS;
+                char *w = out + rec_off[i];
+                const size_t head = static_cast<size_t>(f[3] - span[2 * i]), tail = static_cast<size_t>(span[2 * i + 1] - f[4]),
+                             k = static_cast<size_t>(str_off[i + 1] - str_off[i]);
+                std::memcpy(w, text + span[2 * i], head), w += head;
+                if (k) std::memcpy(w, cigar_text + str_off[i], k), w += k;
+                std::memcpy(w, text + f[4], tail), w += tail;
+                *w = '\n';
+            }
+        });
+        return rec_off[n];
+    } catch (const std::exception &) {
+        return NPR_ERR_NOMEM;
+    }
+}
+
 int64_t npr_fasta_index(const char *text, int64_t len, int64_t *rec, int64_t *seq_len, int64_t cap) {
     if (len < 0 || (len && !text)) return NPR_ERR_INVALID;
     const char *const end = text + len;

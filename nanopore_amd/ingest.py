@@ -143,6 +143,26 @@ class SamText(object):
         _check(L.npr_sam_splice(*args, ptr(out), int(total)), "npr_sam_splice")
         return out[:int(total)]
 
+    def splice_text(self, span, fields, str_off, cigar_text, take=None):
+        """splice() for cigars that are text already -- Batch.cigar_text() (include/nprealign.h: npr_sam_splice_text): line i with its
+        CIGAR replaced by cigar_text[str_off[i]:str_off[i + 1]]."""
+        L = _lib.load()
+        n = len(fields)
+        span = np.ascontiguousarray(span, dtype=np.int64)
+        fields = np.ascontiguousarray(fields, dtype=np.int64)
+        str_off = np.ascontiguousarray(str_off, dtype=np.int64)
+        cigar_text = np.ascontiguousarray(cigar_text, dtype=np.uint8)
+        rec_off = np.zeros(n + 1, dtype=np.int64)
+        args = [ptr(self.text), ptr(span), ptr(fields), n, ptr(str_off), ptr(cigar_text), ptr(rec_off)]
+        if take is not None:  # (the sizes are known without a pass over anything: the bound is exact up to the fields cut out)
+            out = take(int((span[:, 1] - span[:, 0]).sum() + (str_off[-1] - str_off[0] if n else 0) + 2 * n + 1))
+            total = _check(L.npr_sam_splice_text(*args, ptr(out), out.nbytes), "npr_sam_splice_text")
+            return out[:int(total)]
+        total = _check(L.npr_sam_splice_text(*args, None, 0), "npr_sam_splice_text")
+        out = np.empty(max(int(total), 1), dtype=np.uint8)
+        _check(L.npr_sam_splice_text(*args, ptr(out), int(total)), "npr_sam_splice_text")
+        return out[:int(total)]
+
     def field_bytes(self, lo, hi):
         return bytes(self.text[lo:hi])
 

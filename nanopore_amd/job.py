@@ -97,6 +97,10 @@ class ArraySource(object):
     def format_block(self, lo, hi, ops_off, words):
         raise NotImplementedError
 
+    def format_block_text(self, lo, hi, str_off, text):
+        """format_block for cigars that are SAM text already (Batch.cigar_text): only sources that splice records have it."""
+        raise NotImplementedError("device_text: this record source formats its records from packed cigars")
+
 
 class SynthSource(ArraySource):
     """A synthetic workload dict (nanopore_amd.synth): records are made up from the arrays (QNAME read_<i>, POS = where the
@@ -188,6 +192,9 @@ class SamSource(ArraySource):
     def format_block(self, lo, hi, ops_off, words):
         nops = np.asarray(ops_off[1:]) - np.asarray(ops_off[:-1])
         return self.sam.splice(self.span[lo:hi], self.fields[lo:hi], ops_off[:-1], nops, words, take=_take)  # (run_pipeline gives it back)
+
+    def format_block_text(self, lo, hi, str_off, text):
+        return self.sam.splice_text(self.span[lo:hi], self.fields[lo:hi], str_off, text, take=_take)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -324,10 +331,20 @@ def _fetch(b, want_stats, buffer=None):
     return buffer, res, off, words, stats
 
 
-def _rerun_overflowed(ctx, src, params, lo, res, off, words, stats, want_stats, tm):
+def _fetch_text(b, want_stats, buffer=None):
+    """_fetch for a job that takes the cigars as SAM text made on the device (NPR_OPT_FINISH_TEXT; Batch.cigar_text): the same tuple with the
+    strings' offsets and bytes in the place of the operations' offsets and words."""
+    res = b.results()
+    text, off = b.cigar_text(buffer)  # (a view of `buffer` when it is large enough, else of a new array: that one is kept for the next chunk)
+    return (text.base if text.base is not None else text), res, off, text, None
+
+
+def _rerun_overflowed(ctx, src, params, lo, res, off, words, stats, want_stats, tm, fetch=None):
     """Reads whose sparse posterior list overflowed its capacity (NPR_ERR_CAPACITY: a diffuse model can put up to
     1 / threshold pairs on a base) run again with a four times larger `max_pairs_per_base` until they fit, as
-    Context.realign does; their results and cigars replace the failed ones."""
+    Context.realign does; their results and cigars replace the failed ones.  `fetch`: _fetch (the default) or _fetch_text -- `off` and
+    `words` are then the strings' offsets and bytes."""
+    fetch = fetch or _fetch
     from . import realign
     per_base = params.max_pairs_per_base if params.max_pairs_per_base > 0 else 6
     limit = int(1.0 / max(params.posterior_threshold, 1e-6)) + 1
@@ -342,7 +359,7 @@ def _rerun_overflowed(ctx, src, params, lo, res, off, words, stats, want_stats, 
         try:
             tm["kernel_ms"] += b.run()
             b.finish()
-            _, r2, o2, w2, s2 = _fetch(b, want_stats)
+            _, r2, o2, w2, s2 = fetch(b, want_stats)
         finally:
             b.close()
         res[again] = r2
@@ -360,7 +377,7 @@ def _rerun_overflowed(ctx, src, params, lo, res, off, words, stats, want_stats, 
     return res, off, words, stats
 
 
-def run_pipeline(src, params, lo, hi, ctxs, sink, want_stats=False, chunk_bases=None):
+def run_pipeline(src, params, lo, hi, ctxs, sink, want_stats=False, chunk_bases=None, device_text=False):
     """Records lo .. hi of `src` as a pipeline of chunks over the contexts `ctxs`, one thread per phase:
 
         stager (band planning + pack + H2D + device planner)  ->  DP pass  ->  finish (MEA chain + cigar on the device)
@@ -372,8 +389,12 @@ def run_pipeline(src, params, lo, hi, ctxs, sink, want_stats=False, chunk_bases=
     runs that far ahead of the DP; the DP passes and MEA stages of different chunks take turns on the device's shared
     scratch (its mutex), everything else overlaps them.  A chunk the device cannot hold (NPR_ERR_NOMEM: the reference's
     per-read jobs have no such limit) is halved and staged again.  Returns (results[hi - lo], n_ops[hi - lo], stats or None,
-    timings)."""
+    timings).  device_text: the contexts run with NPR_OPT_FINISH_TEXT (the caller has set it) -- the fetch phase takes the cigars as SAM
+    text made on the device and the source splices them in as they are (format_block_text); n_ops is then what the results say."""
     from . import realign
+    if device_text and want_stats:
+        raise ValueError("device_text: the statistics are reduced from the packed cigars, which such a job does not fetch")
+    fetch, format_block = (_fetch_text, src.format_block_text) if device_text else (_fetch, src.format_block)
     pending = list(reversed(chunk_bounds(src.lengths(), lo, hi, chunk_bases, len(ctxs))))  # a stack: splits go back on top
     # NPR_OPT_OVERLAP = 2: the MEA tables of a chunk off the device's shared scratch, so that the next chunk's DP pass starts when it
     # is staged and not when this chunk's MEA stage has given the scratch back (a kernel trace showed 10-15 ms per chunk of exactly
@@ -540,21 +561,21 @@ def run_pipeline(src, params, lo, hi, ctxs, sink, want_stats=False, chunk_bases=
                 try:
                     if stop.is_set():
                         continue
-                    words_buf[0], res, off, words, stats = _fetch(batch, want_stats, words_buf[0])
+                    words_buf[0], res, off, words, stats = fetch(batch, want_stats, words_buf[0])
                     tm["cells"] += int(batch.stats()["cells"])
                     if (res["status"] == realign.ERR_CAPACITY).any():
                         batch.close(), open_batch.clear()  # (the reads that overflowed run again on this context)
-                        res, off, words, stats = _rerun_overflowed(ctxs[j], src, params, a, res, off, words, stats, want_stats, tm)
+                        res, off, words, stats = _rerun_overflowed(ctxs[j], src, params, a, res, off, words, stats, want_stats, tm, fetch)
                     t1 = time.perf_counter()
                     note("fetch", t0, t1)
                     # the records in two halves: the first is being written while the second is formatted (a job of one chunk -- a rank's
                     # share of a sharded set -- has nothing else to overlap its 8 ms of pwrite with)
                     m = (b_ - a) // 2
-                    block = src.format_block(a, a + m, off[:m + 1], words[:int(off[m])])
+                    block = format_block(a, a + m, off[:m + 1], words[:int(off[m])])
                     done.put((block, None, None, None))
-                    block = src.format_block(a + m, b_, off[m:] - off[m], words[int(off[m]):])
+                    block = format_block(a + m, b_, off[m:] - off[m], words[int(off[m]):])
                     note("format", t1, time.perf_counter())
-                    done.put((block, res, off[1:] - off[:-1], stats))
+                    done.put((block, res, res["n_ops"].astype(np.int64) if device_text else off[1:] - off[:-1], stats))
                     del block, res, off, words, stats
                 finally:
                     # the batch goes after its block is on its way (releasing its host buffers takes 13 ms); the context after the batch
@@ -677,7 +698,7 @@ def write_summary_xml(path, status, score, nops, cells=None):
 
 
 def run_source(src, params, bounds, out_path, ctxs=None, gpu=None, group=None, want_stats=False, chunk_bases=None, workers=None,
-               coll_device=None):
+               coll_device=None, device_text=False):
     """The job on this rank (collective: every rank of the process group calls it; without torch.distributed initialised it
     is the one-GPU job).  `src` holds this rank's view of the records, `bounds[r] .. bounds[r + 1]` the range of rank r in
     `src`'s numbering.  Output: `out_path` = src.header + every rank's block in rank order.
@@ -713,7 +734,8 @@ def run_source(src, params, bounds, out_path, ctxs=None, gpu=None, group=None, w
         kept.append(block)  # (written after the all_gather of the sizes: the block stays this rank's)
 
     try:
-        results, n_ops, stats, tm = run_pipeline(src, params, lo, hi, ctxs, sink, want_stats=want_stats, chunk_bases=chunk_bases)
+        results, n_ops, stats, tm = run_pipeline(src, params, lo, hi, ctxs, sink, want_stats=want_stats, chunk_bases=chunk_bases,
+                                                 device_text=device_text)
         t0 = time.perf_counter()
         if out_path is not None and dist is not None:
             mine = state["off"] - len(header) if rank == 0 else sum(len(b) for b in kept)
@@ -765,16 +787,25 @@ def run_source(src, params, bounds, out_path, ctxs=None, gpu=None, group=None, w
 
 
 def realign_sam_file(samFile, outputSamFile, referenceFastaFile, hmm=None, gapGamma=0.5, matchGamma=0.0, params=None, group=None,
-                     gpu=None, want_stats=False, model_slot=0, chunk_bases=None, workers=None, coll_device=None, set_models=True):
+                     gpu=None, want_stats=False, model_slot=0, chunk_bases=None, workers=None, coll_device=None, set_models=True,
+                     device_text=False):
     """Files -> file: every record of `samFile` that has a reference realigned against `referenceFastaFile`, written to
     `outputSamFile` with only its CIGAR replaced, same order, header copied (realignSamFile2TargetFn + realignCigarTargetFn +
     realignSamFile3TargetFn, utils.py:557-609).  Under an initialised torch.distributed process group the records shard over
     the ranks (collective call).  `hmm`: a nanopore_amd.hmm.Hmm, a model file path, or None for the stock model;
     `params`: npr_params overriding the reference's call parameters (anchors +- 10, trim 14, split 3000) -- the bench's
-    fixed-band configs.  Returns run_source's dict, plus `records` = the number of records kept (rank 0)."""
+    fixed-band configs.  Returns run_source's dict, plus `records` = the number of records kept (rank 0).
+    device_text (off by default): the cigars are formatted as SAM text on the device (NPR_OPT_FINISH_TEXT on every context of the job,
+    csrc/npr_cigtext.hip) and spliced in as they are (npr_sam_splice_text); the file is the same byte for byte.  One process only: under a
+    process group the job keeps the packed words (what the ranks' payloads are made of) and refuses the keyword; and not with want_stats,
+    whose table is reduced from the packed words."""
     from . import ingest, realign
     from .hmm import Hmm
     dist, world, rank = _dist_state(group)
+    if device_text and dist is not None:
+        raise ValueError("device_text=True is for the single-process job: a job sharded over a process group keeps the packed cigars")
+    if device_text and want_stats:
+        raise ValueError("device_text=True: the statistics are reduced from the packed cigars, which such a job does not fetch")
     gpu = default_gpu() if gpu is None else gpu
     t0 = time.perf_counter()
     sam = ingest.SamText(samFile)
@@ -800,8 +831,14 @@ def realign_sam_file(samFile, outputSamFile, referenceFastaFile, hmm=None, gapGa
         params = realign.make_params(band_mode=realign.BAND_ANCHOR, diagonal_expansion=10, constraint_trim=14, split_threshold=3000,
                                      gap_gamma=gapGamma, match_gamma=matchGamma, mode=realign.MODE_REALIGN)
     local = np.array([0] * (rank + 1) + [len(fields)] * (world - rank), dtype=np.int64)  # src holds this rank's records only
-    out = run_source(src, params, local, outputSamFile, ctxs=ctxs, gpu=gpu, group=group, want_stats=want_stats, chunk_bases=chunk_bases,
-                     coll_device=coll_device)
+    for c in ctxs if device_text else ():
+        c.set_option(_lib.OPT_FINISH_TEXT, 1)
+    try:
+        out = run_source(src, params, local, outputSamFile, ctxs=ctxs, gpu=gpu, group=group, want_stats=want_stats, chunk_bases=chunk_bases,
+                         coll_device=coll_device, device_text=device_text)
+    finally:
+        for c in ctxs if device_text else ():  # (the contexts are the process's: the next job finds them as this one did)
+            c.set_option(_lib.OPT_FINISH_TEXT, 0)
     out["timings"].update(index_s=t1 - t0, parse_s=t2 - t1)
     out["timings"]["wall_s"] += t2 - t0
     if TRACE:

@@ -150,6 +150,21 @@ class Batch(object):
             raise NprError(rc, "npr_batch_ops_packed", self.ctx.last_error())
         return off, buffer[:total], buffer
 
+    def cigar_text(self, buffer=None):
+        """Output cigars as SAM CIGAR text, formatted on the device (include/nprealign.h: npr_batch_cigar_text): (uint8 buffer, offsets[n+1]);
+        string i = buffer[offsets[i]:offsets[i + 1]], "*" for a read that failed.  `buffer`: a uint8 array the text may be written into (a view
+        of it is returned when it is large enough)."""
+        off = np.zeros(self.n_reads + 1, dtype=np.int64)
+        total = self._L.npr_batch_cigar_text(self._h, ptr(off), None, 0)
+        if total < 0:
+            raise NprError(int(total), "npr_batch_cigar_text", self.ctx.last_error())
+        if buffer is None or buffer.size < max(int(total), 1):
+            buffer = np.empty(max(int(total), 1), dtype=np.uint8)
+        rc = self._L.npr_batch_cigar_text(self._h, ptr(off), ptr(buffer), int(total))
+        if rc < 0:
+            raise NprError(int(rc), "npr_batch_cigar_text", self.ctx.last_error())
+        return buffer[:int(total)], off
+
     def debug_set_pairs(self, read, x, y, p, task_status=0):
         """TEST HOOK (include/nprealign.h npr_batch_debug_set_pairs): replaces on the device the posterior pairs the DP pass left for `read`."""
         x = np.ascontiguousarray(x, np.int32)
@@ -682,6 +697,25 @@ def format_cigars_packed(word_off, n_ops, words):
     rc = L.npr_format_cigars_packed(n, ptr(word_off), ptr(n_ops), ptr(words), ptr(str_off), ptr(buf), int(total))
     if rc < 0:
         raise NprError(int(rc), "npr_format_cigars_packed")
+    return buf[:int(total)], str_off
+
+
+def cigar_text_packed(ctx, word_off, n_ops, words):
+    """format_cigars_packed with the text made on the device of `ctx` (include/nprealign.h: npr_cigar_text_packed; the kernels of
+    csrc/npr_cigtext.hip on lists given on the host): (bytes buffer, offsets[n+1])."""
+    L = _lib.load()
+    word_off = np.ascontiguousarray(word_off, dtype=np.int64)
+    n_ops = np.ascontiguousarray(n_ops, dtype=np.int64)
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    n = len(n_ops)
+    str_off = np.zeros(n + 1, dtype=np.int64)
+    total = L.npr_cigar_text_packed(ctx._h, n, ptr(word_off), ptr(n_ops), ptr(words), ptr(str_off), None, 0)
+    if total < 0:
+        raise NprError(int(total), "npr_cigar_text_packed", ctx.last_error())
+    buf = np.empty(max(int(total), 1), dtype=np.uint8)
+    rc = L.npr_cigar_text_packed(ctx._h, n, ptr(word_off), ptr(n_ops), ptr(words), ptr(str_off), ptr(buf), int(total))
+    if rc < 0:
+        raise NprError(int(rc), "npr_cigar_text_packed", ctx.last_error())
     return buf[:int(total)], str_off
 
 
