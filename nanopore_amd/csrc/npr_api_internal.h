@@ -380,9 +380,11 @@ inline bool build_stair_schedule(const Segment &s, int R, int NW, uint32_t *ctl,
 }  // namespace npr_impl
 using namespace npr_impl;
 
-// Kernel classes of a batch, each launched on its own: the register kernel with one wavefront per task (R slots per
-// lane), the register kernel with NW wavefronts per task (k_dp_wide), the generic kernel with an LDS ring in three
-// width classes, the generic kernel with its ring in HBM.
+// Kernel classes of a batch, each launched on its own.  On the frame schedule, R slots per lane: k_dp_stair (K_STAIR,
+// one wavefront per task, one exponent per cell), k_dp_wide (K_WIDE, NW wavefronts per task), k_dp_rs (K_RS, K_STAIR's
+// classes in row-scaled arithmetic), k_dp_mid_rs (K_MID, the same with the two sweeps on two wavefronts).  On column
+// stripes: k_dp_tile (K_TILE, one exponent per cell), k_dp_tile_cs (K_TILE_RS, one per lane).  Everything else:
+// k_dp_generic with its ring in LDS (K_GENERIC_LDS, three width classes) or in HBM (K_GENERIC_GLOBAL).
 namespace npr_impl {
 enum { K_STAIR = 0, K_WIDE = 1, K_GENERIC_LDS = 2, K_GENERIC_GLOBAL = 3, K_TILE = 4, K_MID = 5, K_RS = 6, K_TILE_RS = 7 };
 struct KClass {
@@ -401,8 +403,8 @@ constexpr KClass kClassTab[kClasses] = {{K_STAIR, 1, 1}, {K_STAIR, 2, 1}, {K_STA
                                         {K_TILE_RS, 2, 0}};
 constexpr int kFirstGeneric = 7, kTileClass = 11, kFirstPair = 12, kFirstRs = 15, kTileRsClass = 18, kQueueSlots = 24;
 inline bool is_register_class(int c) { return kClassTab[c].kind <= K_WIDE || kClassTab[c].kind == K_MID || kClassTab[c].kind == K_RS; }
-inline bool is_one_wave_kind(int kind) { return kind == K_STAIR || kind == K_RS; }
-inline bool is_tile_kind(int kind) { return kind == K_TILE || kind == K_TILE_RS; }  // column stripes, NW wavefronts per task  // one wavefront per task on the frame schedule
+inline bool is_one_wave_kind(int kind) { return kind == K_STAIR || kind == K_RS; }  // one wavefront per task on the frame schedule
+inline bool is_tile_kind(int kind) { return kind == K_TILE || kind == K_TILE_RS; }  // column stripes, NW wavefronts per task
 // resident wavefronts per CU of the one-wavefront frame kernels (VGPR-limited: 71 / 80 / 162 registers: 7 / 6 / 3 per SIMD)
 inline int stair_waves_per_cu(int R) { return R == 1 ? 28 : (R == 2 ? 24 : 12); }
 // ... and of k_dp_rs<R> (72 / 72 / 105 registers: 7 / 7 / 4 per SIMD; R = 2 measured at 6 / 7 / 8 per SIMD in round 4: 7 is best)
@@ -440,16 +442,23 @@ inline bool rs_model_ok(const DevModel &m) {
     return grow <= std::exp2(6.0 / NPR_RS_K);
 }
 
-// Whether every loaded model emits every base from every gap state with probability exactly 2^-2 (N included: make_dev_model gives it 1/4): the
-// row-scaled kernels then take the gap emissions from a select instead of their LDS tables (npr_rs.h rs_cell_emissions; same bits).
-inline bool flat_gap_emissions(const npr_ctx *ctx) {
+// What the launches ask of the loaded models.  flat_gaps: every one emits every base from every gap state with probability exactly 2^-2 (N included:
+// make_dev_model gives it 1/4): the row-scaled kernels then take the gap emissions from a select instead of their LDS tables (npr_rs.h rs_cell_emissions;
+// same bits).  sw: one has a short-gap switch (shortGapX <-> shortGapY); the row- / column-scaled kernels leave out the two switch terms of a cell when
+// none has (the shipped ones have none): exact zeros either way (npr_rs.h).  flat: no switch, and flat_gaps.  rs_ok: rs_model_ok for every one.
+struct ModelShape { bool sw, flat_gaps, flat, rs_ok; };
+inline ModelShape model_shape(const npr_ctx *ctx) {
+    ModelShape s{false, true, false, true};
     for (int sl = 0; sl < NPR_MAX_MODELS; ++sl) {
         if (!ctx->model_set[sl]) continue;
         const DevModel &m = ctx->models[sl];
+        if (m.T[1 * 5 + 2] != 0.f || m.T[2 * 5 + 1] != 0.f) s.sw = true;
+        if (!rs_model_ok(m)) s.rs_ok = false;
         for (int b2 = 0; b2 < 5; ++b2)
-            if (m.ex[5 + b2] != 0.25f || m.ex[15 + b2] != 0.25f || m.ey[10 + b2] != 0.25f || m.ey[20 + b2] != 0.25f) return false;
+            if (m.ex[5 + b2] != 0.25f || m.ex[15 + b2] != 0.25f || m.ey[10 + b2] != 0.25f || m.ey[20 + b2] != 0.25f) s.flat_gaps = false;
     }
-    return true;
+    s.flat = !s.sw && s.flat_gaps;
+    return s;
 }
 
 // Stripe table of k_dp_tile for one segment (npr_kernel_tile.hip): the lattice columns 0..lX cut into stripes of 64*R

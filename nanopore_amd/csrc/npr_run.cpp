@@ -2,9 +2,6 @@
 // (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
 #include "npr_api_internal.h"
 
-extern "C" {
-
-}  // extern "C"
 namespace npr_impl {
 KernelArgs make_args(npr_batch *b) {
     KernelArgs a{};
@@ -31,6 +28,215 @@ KernelArgs make_args(npr_batch *b) {
     return a;
 }
 }  // namespace npr_impl
+
+namespace {
+// The arguments of one launch over the tasks [first, first + count) of the batch: its counter of the work queue, its ring capacity, its first
+// uniform scratch region and (a class laid out in regions of its own, own_regions) its entries of the region table.
+KernelArgs launch_args(npr_batch *b, int first, int count, int queue_slot, int wcap, int slot_base, const int64_t *region) {
+    KernelArgs a = make_args(b);
+    a.tasks += first, a.outs += first, a.ntasks = count;
+    a.queue += queue_slot, a.wcap = wcap, a.slot_base = slot_base, a.region = region;
+    return a;
+}
+
+// Streams and events of a pass of n launches that run side by side: all but the last on the context's side streams, each behind ev0; the last (every
+// one of a serial pass) on the main stream, which then waits for the others, so that ev0 -> ev1 brackets the whole pass.  The caller records ev0.
+struct FanOut {
+    npr_ctx *ctx;
+    size_t n;  // launches of the pass
+    bool serial;
+    bool on_main(size_t i) const { return serial || i + 1 == n; }
+    hipStream_t stream(size_t i) const { return on_main(i) ? ctx->stream : ctx->side[i % npr_ctx::kSideStreams]; }
+    int32_t before(size_t i) const {
+        if (!on_main(i)) HIP_TRY(ctx, hipStreamWaitEvent(stream(i), ctx->ev0, 0));
+        return NPR_OK;
+    }
+    int32_t after(size_t i) const {
+        if (!on_main(i)) HIP_TRY(ctx, hipEventRecord(ctx->side_done[i % npr_ctx::kSideStreams], stream(i)));
+        return NPR_OK;
+    }
+    int32_t join(float *kernel_ms) const {
+        for (size_t i = 0; !serial && i + 1 < n; ++i) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_done[i % npr_ctx::kSideStreams], 0));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
+        return NPR_OK;
+    }
+};
+
+// The second pass of a launch: the tasks its row- / column-scaled kernel reported as TASK_RERUN (npr_device.h), gathered for the per-cell-exponent kernel
+// of their class, which runs them on the scratch regions (task j of `again` is no larger than the j-th task of the class) and queue counter of the first.
+struct Rerun {
+    std::vector<int32_t> again;  // their indices in b->tasks
+    DevBuf<Task> d_tasks;        // ... the tasks themselves
+    DevBuf<TaskOut> d_outs;      // ... and where their results go
+    int32_t ntasks() const { return static_cast<int32_t>(again.size()); }
+};
+
+// collects them among [first, first + count) of b->outs; if there are any, uploads them (buffers from the context's cache if `cached`) and resets the launch's queue counter
+int32_t stage_rerun(npr_batch *b, int first, int count, int queue_slot, bool cached, const char *nomem, Rerun *r) {
+    npr_ctx *ctx = b->ctx;
+    for (int k = first; k < first + count; ++k)
+        if (b->outs[k].status == TASK_RERUN) r->again.push_back(k);
+    if (r->again.empty()) return NPR_OK;
+    const size_t n = r->again.size();
+    std::vector<Task> sub(n);
+    for (size_t j = 0; j < n; ++j) sub[j] = b->tasks[r->again[j]];
+    const bool ok = cached ? r->d_tasks.alloc_from(ctx, n) == hipSuccess && r->d_outs.alloc_from(ctx, n) == hipSuccess
+                           : r->d_tasks.alloc(n) == hipSuccess && r->d_outs.alloc(n) == hipSuccess;
+    if (!ok) return fail(ctx, NPR_ERR_NOMEM, nomem);
+    HIP_TRY(ctx, hipMemcpy(r->d_tasks.p, sub.data(), sizeof(Task) * n, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemsetAsync(b->d_queue.p + queue_slot, 0, sizeof(int32_t), ctx->stream));
+    return NPR_OK;
+}
+
+// ... and once the kernel has finished: their results take the place of the first pass's in b->outs
+int32_t merge_rerun(npr_batch *b, const Rerun &r) {
+    std::vector<TaskOut> subout(r.again.size());
+    HIP_TRY(b->ctx, hipMemcpy(subout.data(), r.d_outs.p, sizeof(TaskOut) * subout.size(), hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < r.again.size(); ++j) b->outs[r.again[j]] = subout[j];
+    return NPR_OK;
+}
+const int64_t *own_region(const npr_batch *b, const npr_batch::Launch &L) { return L.own_regions ? b->d_region.p + L.region_first : nullptr; }
+
+// One E-step launch per kernel class of the batch (tasks are grouped by class): which kernel counts the class, and where.
+enum class EmKind {
+    generic,  // k_dp_generic<.., EM> (LDS ring while the band fits, global ring beyond): what has no E-step kernel of its own, and everything under NPR_OPT_EM_GENERIC
+    stair,    // k_em_stair<R>: the one-wavefront frame classes
+    wide,     // k_dp_wide<R, NW, EM>: R slots per lane on NW wavefronts per task
+    tile,     // k_em_tile<R>: the stripe class, scratch regions per workgroup as in the DP launch
+    tile_cs   // k_dp_tile_cs<.., EM>: ... in column-scaled arithmetic first; what its certificate refuses goes to k_em_tile
+};
+struct EmLaunch {
+    const npr_batch::Launch *dp;  // the DP launch of the class: its tasks, its cells and (stripe class) its scratch regions in the batch's table
+    EmKind kind;
+    int R, NW;  // stair / wide / tile / tile_cs: slots per lane; wide: wavefronts per task
+    int grid, wcap;  // wcap: ring capacity of the generic kernel
+    size_t lds;      // ... and its LDS
+    bool global_ring;
+    bool uses_others_regions;  // a generic launch over a class without uniform regions: not beside the others
+    int slot_base;    // first uniform forward-scratch region: the one its class had in the DP launch (the classes run concurrently)
+    int dp_grid;      // ... and how many of them that launch owned
+    size_t fx_off, ring_off;  // where its planes of the other four states / its HBM ring start (floats)
+    bool stripes() const { return kind == EmKind::tile || kind == EmKind::tile_cs; }
+};
+
+// The kernel and launch geometry that count the class of one DP launch.  The launches run concurrently, like the DP launches of
+// npr_batch_run (serialised, a batch in the trainer's band spent 63 ms where its longest class takes 38: profiles/r03_em_*): each
+// class keeps the forward-scratch regions its DP launch owned (so at most that many workgroups) and gets its own planes and ring.
+EmLaunch plan_em_launch(const npr_batch *b, const npr_batch::Launch &dl, const ModelShape &shape) {
+    const npr_ctx *ctx = b->ctx;
+    const KClass &kc = kClassTab[dl.cls];
+    const bool own_kernels = ctx->opt[NPR_OPT_EM_GENERIC] == 0;
+    int64_t per_cu;  // workgroups
+    EmLaunch l{};
+    l.dp = &dl, l.slot_base = dl.slot_base, l.dp_grid = dl.grid;
+    if (is_one_wave_kind(kc.kind) && own_kernels) {
+        // 127 / 161 / 223 VGPRs and 9 KiB of LDS bins per wavefront: 16 / 12 / 8 wavefronts per CU
+        l.kind = EmKind::stair, l.R = kc.R;
+        per_cu = l.R == 4 ? 8 : (l.R == 2 ? 12 : 16);
+    } else if (is_tile_kind(kc.kind) && kc.R == 2 && own_kernels) {
+        // 164 VGPRs: 3 wavefronts per SIMD, 12 per CU -> 3 workgroups of 4; the workgroups keep the scratch regions the DP
+        // launch gave them (region i is sized for task i, and everything the queue hands out later is smaller)
+        const bool cs = kc.kind == K_TILE_RS && ctx->opt[NPR_OPT_TILE_RS] != 2 && ctx->opt[NPR_OPT_EM_TILE] != 1;
+        // (a model that is not rs_model_ok takes k_em_tile on the workgroups the column-scaled kernel would have had)
+        l.kind = cs && shape.rs_ok ? EmKind::tile_cs : EmKind::tile, l.R = 2;
+        per_cu = cs ? em_tile_cs_waves_per_cu() / em_tile_cs_waves() : em_tile_waves_per_cu() / em_tile_waves();
+    } else if (kc.kind == K_WIDE && kc.R == 2 && own_kernels) {
+        // 157 VGPRs: 3 wavefronts per SIMD, 12 per CU -> 3 / 1 tasks per CU on 4 / 8 wavefronts each
+        l.kind = EmKind::wide, l.R = 2, l.NW = kc.NW;
+        per_cu = 12 / l.NW;
+    } else {
+        l.kind = EmKind::generic;
+        l.wcap = static_cast<int>((std::max<int64_t>(dl.width, 64) + 3) & ~int64_t(3));
+        l.lds = generic_lds_bytes(l.wcap) + em_extra_lds_bytes();
+        l.global_ring = l.lds > 160 * 1024;  // the bins take 12 KiB of the LDS the ring would otherwise have
+        if (l.global_ring) l.lds = generic_lds_bytes(0) + em_extra_lds_bytes();
+        per_cu = l.global_ring ? 8 : std::min<int>(12, static_cast<int>(std::max<size_t>(1, (160 * 1024) / (l.lds + 256))));
+    }
+    l.grid = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(dl.count, static_cast<int64_t>(ctx->cu_count) * per_cu)));
+    if (l.kind == EmKind::generic && dl.own_regions) {
+        // A class laid out in scratch regions of its own (the stripe class under NPR_OPT_EM_GENERIC) has no uniform regions: the generic kernel
+        // counts it in regions 0, 1, .. of the arena, which belong to the other classes' launches -- so one launch after the other then, and no
+        // more workgroups than the arena has room for.  (Until round 6 the launches ran side by side there: NaN counts on a batch of four classes.)
+        l.uses_others_regions = true, l.slot_base = 0;
+        const int64_t arena_cells = b->region_end.empty() ? b->slot_stride : b->region_end.back();
+        l.grid = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(l.grid, arena_cells / std::max<int64_t>(b->slot_stride, 1))));
+        l.dp_grid = l.grid;
+    }
+    l.grid = std::max(1, std::min(l.grid, l.dp_grid));  // (uniform regions or the stripe class's own: those of the DP launch's workgroups)
+    return l;
+}
+
+// The planes of the other four states: 16 bytes per cell of forward scratch in use.  The stripe kernel's mirror its regions
+// of the forward scratch, but only those of the workgroups the E-step launches (far fewer than the DP launch had): when
+// the device has no room for them, fewer workgroups yet.  Sets fx_off / ring_off (and may halve grid) of every launch and grows ctx->arena_Fx.
+int32_t lay_out_planes(npr_batch *b, std::vector<EmLaunch> &launches, size_t *ring_floats) {
+    npr_ctx *ctx = b->ctx;
+    for (;;) {
+        // uniform classes: planes packed one class after the other; the stripe class: a mirror of its scratch regions, which
+        // lie behind all uniform regions of the arena (so behind the packed planes too)
+        size_t fx_cells = 0;
+        *ring_floats = 0;
+        for (auto &l : launches) {
+            if (l.stripes()) continue;
+            l.fx_off = fx_cells;
+            fx_cells += static_cast<size_t>(l.grid) * 4 * static_cast<size_t>(b->slot_stride);
+            l.ring_off = *ring_floats;
+            if (l.global_ring) *ring_floats += static_cast<size_t>(l.grid) * 18 * l.wcap;
+        }
+        for (auto &l : launches)
+            if (l.stripes() && !b->region_end.empty()) {
+                l.fx_off = 0;
+                fx_cells = std::max(fx_cells, 4 * static_cast<size_t>(b->region_end[std::min<size_t>(static_cast<size_t>(l.grid), b->region_end.size()) - 1]));
+            }
+        if (fx_cells <= ctx->arena_fx_cells) return NPR_OK;
+        if (ctx->arena_Fx) (void)hipFree(reinterpret_cast<char *>(ctx->arena_Fx) - npr_ctx::kArenaPad);
+        ctx->arena_Fx = nullptr, ctx->arena_fx_cells = 0;
+        char *raw = nullptr;
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&raw), fx_cells * sizeof(float) + 2 * npr_ctx::kArenaPad);
+        if (e != hipSuccess && !ctx->cache.empty()) {  // the buffers kept from closed batches are in the way
+            (void)hipGetLastError();
+            ctx->cache_flush();
+            e = hipMalloc(reinterpret_cast<void **>(&raw), fx_cells * sizeof(float) + 2 * npr_ctx::kArenaPad);
+        }
+        if (e == hipSuccess) {
+            ctx->arena_Fx = reinterpret_cast<float *>(raw + npr_ctx::kArenaPad), ctx->arena_fx_cells = fx_cells;
+            return NPR_OK;
+        }
+        (void)hipGetLastError();
+        bool shrunk = false;
+        for (auto &l : launches)
+            if (l.grid > 1) l.grid = (l.grid + 1) / 2, shrunk = true;
+        if (!shrunk) return fail(ctx, NPR_ERR_NOMEM, "npr_batch_expectations: hipMalloc of the forward planes", e);
+    }
+}
+
+// the arguments of an E-step launch (either pass): its tasks, its planes (indexed from a.Fx by workgroup; by scratch region in the stripe kernel), the sums it adds to
+KernelArgs em_args(npr_batch *b, const EmLaunch &l, int queue_slot, double *em_T, double *em_E) {
+    KernelArgs a = launch_args(b, l.dp->first, l.dp->count, queue_slot, l.wcap, l.slot_base, own_region(b, *l.dp));
+    a.Fx = b->ctx->arena_Fx + l.fx_off;
+    a.em_T = em_T, a.em_E = em_E;
+    return a;
+}
+
+// the kernels' compact emission bins (EM_BINS per model, npr_device.h) as the 80-entry table of a model: a gap state's count per base goes evenly to its 4 entries
+void unpack_bins(const double *bins, double *E_exp) {
+    for (int m = 0; m < NPR_MAX_MODELS; ++m) {
+        const double *s = bins + m * EM_BINS;
+        double *d = E_exp + m * 80;
+        for (int i = 0; i < 16; ++i) d[i] = s[i];
+        for (int x = 0; x < 4; ++x)
+            for (int y = 0; y < 4; ++y) {
+                d[16 + x * 4 + y] = 0.25 * s[16 + x];  // shortGapX: count of reference base x
+                d[48 + x * 4 + y] = 0.25 * s[20 + x];  // longGapX
+                d[32 + x * 4 + y] = 0.25 * s[24 + y];  // shortGapY: count of read base y
+                d[64 + x * 4 + y] = 0.25 * s[28 + y];  // longGapY
+            }
+    }
+}
+}  // namespace
+
 extern "C" {
 
 int32_t npr_batch_run(npr_batch *b, float *kernel_ms) {
@@ -46,51 +252,34 @@ int32_t npr_batch_run(npr_batch *b, float *kernel_ms) {
     ++ctx->arena->epoch;
     HIP_TRY(ctx, hipMemsetAsync(b->d_queue.p, 0, sizeof(int32_t) * kQueueSlots, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    // all classes at once, the smallest first, each on its own stream; the main stream waits for all of them,
-    // so ev0 -> ev1 brackets the whole DP pass
+    // all classes at once, the smallest first, each on its own stream (FanOut)
     std::vector<const npr_batch::Launch *> order;
     for (const auto &L : b->launches) order.push_back(&L);
     std::sort(order.begin(), order.end(), [](const npr_batch::Launch *x, const npr_batch::Launch *y) { return x->cells < y->cells; });
     bool scaled = b->pair_rs;  // (staged for the row- / column-scaled kernels under the models of that moment)
     for (const auto &L : b->launches) scaled |= kClassTab[L.cls].kind == K_TILE_RS;
-    if (scaled)
-        for (int sl = 0; sl < NPR_MAX_MODELS; ++sl)
-            if (ctx->model_set[sl] && !rs_model_ok(ctx->models[sl]))
-                return fail(ctx, NPR_ERR_MODEL, "npr_batch_run: a model loaded after the batch was staged grows faster than the row-scaled kernels allow: stage the batch again");
-    // the row-scaled kernels leave out the two short-gap switch terms of a cell when no loaded model has such a transition (the
-    // shipped ones have none): exact zeros either way (npr_rs.h)
-    bool sw = false;
-    for (int sl = 0; sl < NPR_MAX_MODELS; ++sl)
-        if (ctx->model_set[sl] && (ctx->models[sl].T[1 * 5 + 2] != 0.f || ctx->models[sl].T[2 * 5 + 1] != 0.f)) sw = true;
-    const bool flat = !sw && flat_gap_emissions(ctx);
+    const ModelShape shape = model_shape(ctx);
+    if (scaled && !shape.rs_ok)
+        return fail(ctx, NPR_ERR_MODEL, "npr_batch_run: a model loaded after the batch was staged grows faster than the row-scaled kernels allow: stage the batch again");
+    const FanOut fan{ctx, order.size(), false};
+    int32_t rc;
     for (size_t i = 0; i < order.size(); ++i) {
         const npr_batch::Launch &L = *order[i];
-        const bool last = i + 1 == order.size();
-        hipStream_t s = last ? ctx->stream : ctx->side[i % npr_ctx::kSideStreams];
-        if (!last) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev0, 0));
-        KernelArgs a = make_args(b);
-        a.tasks += L.first;
-        a.outs += L.first;
-        a.ntasks = L.count;
-        a.queue += L.cls;
-        a.wcap = L.wcap;
-        a.slot_base = L.slot_base;
-        a.region = L.own_regions ? b->d_region.p + L.region_first : nullptr;
+        hipStream_t s = fan.stream(i);
+        if ((rc = fan.before(i)) != NPR_OK) return rc;
+        const KernelArgs a = launch_args(b, L.first, L.count, L.cls, L.wcap, L.slot_base, own_region(b, L));
         const KClass &kc = kClassTab[L.cls];
-        const int rc = kc.kind == K_MID   ? launch_mid_rs(a, kc.R, L.grid, s, sw, flat)
-                       : kc.kind == K_RS    ? launch_rs(a, kc.R, L.grid, s, sw, flat)
-                       : kc.kind == K_STAIR ? launch_stair(a, kc.R, L.grid, s)
-                       : kc.kind == K_TILE ? launch_tile(a, kc.R, L.wcap, L.grid, s, flat_gap_emissions(ctx))
-                       : kc.kind == K_TILE_RS ? launch_tile_cs(a, L.wcap, L.grid, s, sw, flat)
-                       : kc.kind == K_WIDE ? launch_wide(a, kc.R, kc.NW, L.grid, s)
-                                           : launch_generic(a, L.grid, L.threads, L.lds, false, kc.kind == K_GENERIC_GLOBAL, s);
-        if (rc != 0) return fail(ctx, NPR_ERR_HIP, "DP kernel launch", static_cast<hipError_t>(rc));
-        if (!last) HIP_TRY(ctx, hipEventRecord(ctx->side_done[i % npr_ctx::kSideStreams], s));
+        const int lrc = kc.kind == K_MID   ? launch_mid_rs(a, kc.R, L.grid, s, shape.sw, shape.flat)
+                        : kc.kind == K_RS    ? launch_rs(a, kc.R, L.grid, s, shape.sw, shape.flat)
+                        : kc.kind == K_STAIR ? launch_stair(a, kc.R, L.grid, s)
+                        : kc.kind == K_TILE ? launch_tile(a, kc.R, L.wcap, L.grid, s, shape.flat_gaps)
+                        : kc.kind == K_TILE_RS ? launch_tile_cs(a, L.wcap, L.grid, s, shape.sw, shape.flat)
+                        : kc.kind == K_WIDE ? launch_wide(a, kc.R, kc.NW, L.grid, s)
+                                            : launch_generic(a, L.grid, L.threads, L.lds, false, kc.kind == K_GENERIC_GLOBAL, s);
+        if (lrc != 0) return fail(ctx, NPR_ERR_HIP, "DP kernel launch", static_cast<hipError_t>(lrc));
+        if ((rc = fan.after(i)) != NPR_OK) return rc;
     }
-    for (size_t i = 0; i + 1 < order.size(); ++i) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_done[i % npr_ctx::kSideStreams], 0));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
+    if ((rc = fan.join(kernel_ms)) != NPR_OK) return rc;
     // The row-scaled kernels report the tasks for which one exponent per row may not have been enough (TASK_RERUN,
     // npr_device.h): those run again here, with the per-cell-exponent kernel of their frame class, on the scratch regions the
     // first launch had.  Rare -- a row of the alignment ~110 binary orders below the product of the row's largest forward and
@@ -98,40 +287,27 @@ int32_t npr_batch_run(npr_batch *b, float *kernel_ms) {
     b->outs.resize(b->tasks.size());
     b->task_rerun.assign(b->tasks.size(), 0);
     for (const auto &L : b->launches) {
-        if (kClassTab[L.cls].kind != K_RS && kClassTab[L.cls].kind != K_TILE_RS && kClassTab[L.cls].kind != K_MID) continue;
+        const KClass &kc = kClassTab[L.cls];
+        if (kc.kind != K_RS && kc.kind != K_TILE_RS && kc.kind != K_MID) continue;
         HIP_TRY(ctx, hipMemcpy(b->outs.data() + L.first, b->d_outs.p + L.first, sizeof(TaskOut) * L.count, hipMemcpyDeviceToHost));
-        std::vector<int32_t> again;
-        for (int k = L.first; k < L.first + L.count; ++k)
-            if (b->outs[k].status == TASK_RERUN) {
-                again.push_back(k);
-                if (std::getenv("NPR_TIMING")) std::fprintf(stderr, "[npr] task %d (D %d) runs again; the first pass left in its result: npairs (k_dp_mid_rs: why, 1 nothing at the cut / 2 no total / 3 exponents apart / 4 totals apart / 5 range certificate; k_dp_tile_cs: its certificate value) %d, btot_m (k_dp_mid_rs: total' / total) %.9g, btot_e (k_dp_mid_rs: exponent difference) %d, total %g x 2^%d\n", k, b->tasks[k].D, b->outs[k].npairs, b->outs[k].btot_m, b->outs[k].btot_e, b->outs[k].tot_m, b->outs[k].tot_e);
-            }
-        if (again.empty()) continue;
-        std::vector<Task> sub(again.size());
-        for (size_t j = 0; j < again.size(); ++j) sub[j] = b->tasks[again[j]];
-        DevBuf<Task> d_sub;
-        DevBuf<TaskOut> d_subout;
-        if (d_sub.alloc(sub.size()) != hipSuccess || d_subout.alloc(sub.size()) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_batch_run: hipMalloc");
-        HIP_TRY(ctx, hipMemcpy(d_sub.p, sub.data(), sizeof(Task) * sub.size(), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemsetAsync(b->d_queue.p + L.cls, 0, sizeof(int32_t), ctx->stream));
-        KernelArgs a = make_args(b);
-        a.tasks = d_sub.p, a.outs = d_subout.p, a.ntasks = static_cast<int32_t>(sub.size());
-        a.queue += L.cls;
-        a.slot_base = L.slot_base;
-        a.region = L.own_regions ? b->d_region.p + L.region_first : nullptr;  // (task j of `again` is no larger than the j-th task of the class)
-        const int grid = static_cast<int>(std::min<size_t>(sub.size(), static_cast<size_t>(L.grid)));
-        a.wcap = L.wcap;
-        const int rc = kClassTab[L.cls].kind == K_TILE_RS ? launch_tile(a, 2, L.wcap, grid, ctx->stream) : launch_stair(a, kClassTab[L.cls].R, grid, ctx->stream);
-        if (rc != 0) return fail(ctx, NPR_ERR_HIP, "DP kernel launch (second pass)", static_cast<hipError_t>(rc));
+        Rerun r;
+        if ((rc = stage_rerun(b, L.first, L.count, L.cls, false, "npr_batch_run: hipMalloc", &r)) != NPR_OK) return rc;
+        if (r.again.empty()) continue;
+        if (std::getenv("NPR_TIMING"))
+            for (const int32_t k : r.again)
+                std::fprintf(stderr, "[npr] task %d (D %d) runs again; the first pass left in its result: npairs (k_dp_mid_rs: why, 1 nothing at the cut / 2 no total / 3 exponents apart / 4 totals apart / 5 range certificate; k_dp_tile_cs: its certificate value) %d, btot_m (k_dp_mid_rs: total' / total) %.9g, btot_e (k_dp_mid_rs: exponent difference) %d, total %g x 2^%d\n", k, b->tasks[k].D, b->outs[k].npairs, b->outs[k].btot_m, b->outs[k].btot_e, b->outs[k].tot_m, b->outs[k].tot_e);
+        KernelArgs a = launch_args(b, L.first, L.count, L.cls, L.wcap, L.slot_base, own_region(b, L));
+        a.tasks = r.d_tasks.p, a.outs = r.d_outs.p, a.ntasks = r.ntasks();
+        const int grid = std::min(r.ntasks(), L.grid);
+        const int lrc = kc.kind == K_TILE_RS ? launch_tile(a, 2, L.wcap, grid, ctx->stream) : launch_stair(a, kc.R, grid, ctx->stream);
+        if (lrc != 0) return fail(ctx, NPR_ERR_HIP, "DP kernel launch (second pass)", static_cast<hipError_t>(lrc));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<TaskOut> subout(sub.size());
-        HIP_TRY(ctx, hipMemcpy(subout.data(), d_subout.p, sizeof(TaskOut) * sub.size(), hipMemcpyDeviceToHost));
-        for (size_t j = 0; j < again.size(); ++j) {
-            b->outs[again[j]] = subout[j];
-            b->task_rerun[again[j]] = 1;
-            HIP_TRY(ctx, hipMemcpy(b->d_outs.p + again[j], &subout[j], sizeof(TaskOut), hipMemcpyHostToDevice));
+        if ((rc = merge_rerun(b, r)) != NPR_OK) return rc;
+        for (const int32_t k : r.again) {  // (the finish reads the results on the device)
+            b->task_rerun[k] = 1;
+            HIP_TRY(ctx, hipMemcpy(b->d_outs.p + k, &b->outs[k], sizeof(TaskOut), hipMemcpyHostToDevice));
         }
-        if (std::getenv("NPR_TIMING")) std::fprintf(stderr, "[npr] class %d: %zu of %d tasks run again with a per-cell exponent\n", L.cls, again.size(), L.count);
+        if (std::getenv("NPR_TIMING")) std::fprintf(stderr, "[npr] class %d: %zu of %d tasks run again with a per-cell exponent\n", L.cls, r.again.size(), L.count);
     }
     b->ran = true;
     b->finished = false;
@@ -168,7 +344,6 @@ int32_t npr_batch_segment_arith(const npr_batch *b, int64_t *seg_off, int32_t *a
     return NPR_OK;
 }
 
-
 int32_t npr_batch_expectations(npr_batch *b, double *T_exp, double *E_exp, double *loglik, float *kernel_ms) {
     if (!b || !T_exp || !E_exp || !loglik) return NPR_ERR_INVALID;
     npr_ctx *ctx = b->ctx;
@@ -184,130 +359,16 @@ int32_t npr_batch_expectations(npr_batch *b, double *T_exp, double *E_exp, doubl
     if (b->variable_regions)
         return fail(ctx, NPR_ERR_STATE, "npr_batch_expectations: this batch was laid out for realignment only (scratch regions of their own size); "
                                         "stage it with NPR_MODE_EXPECTATIONS");
-    {
-        const int32_t rc = ensure_coff(b);  // classes without a register E-step take the generic kernel
-        if (rc != NPR_OK) return rc;
-    }
-    // launch geometry: everything goes through the generic kernel (LDS ring while the band fits, global ring beyond)
-    struct L {
-        int first, count, wcap, grid;
-        size_t lds;
-        bool global_ring;
-        int stair_R;  // > 0: the register-kernel E-step (k_em_stair<R>), else the generic kernel
-        int wide_NW;  // > 0: stair_R slots per lane on wide_NW wavefronts per task (k_dp_wide<R, NW, EM>)
-        bool tile;    // the stripe-kernel E-step (k_em_tile<stair_R>): scratch regions per workgroup, as in the DP launch
-        bool uses_others_regions;  // a generic launch over a class without uniform regions: not beside the others
-        bool tile_cs;  // ... in column-scaled arithmetic first (k_dp_tile_cs<.., EM>); what its certificate refuses goes to k_em_tile
-        int slot_base;    // first uniform forward-scratch region: the one its class had in the DP launch (the classes run concurrently)
-        int dp_grid;      // ... and how many of them that launch owned
-        int64_t cells;
-        int region_first;  // stripe class: its scratch regions in the batch's table
-        size_t fx_off, ring_off;  // where its planes of the other four states / its HBM ring start (floats)
-    };
-    std::vector<L> launches;
-    int64_t max_grid = 1;
-    for (const auto &dl : b->launches) {  // one E-step launch per kernel class of the batch (tasks are grouped by class)
-        L l{};
-        l.first = dl.first, l.count = dl.count;
-        l.slot_base = dl.slot_base, l.dp_grid = dl.grid, l.cells = dl.cells, l.region_first = dl.own_regions ? dl.region_first : -1;
-        if (is_one_wave_kind(kClassTab[dl.cls].kind) && ctx->opt[NPR_OPT_EM_GENERIC] == 0) {
-            // 127 / 161 / 223 VGPRs and 9 KiB of LDS bins per wavefront: 16 / 12 / 8 wavefronts per CU
-            l.stair_R = kClassTab[dl.cls].R;
-            l.lds = em_stair_lds_bytes();
-            const int em_waves = l.stair_R == 4 ? 8 : (l.stair_R == 2 ? 12 : 16);
-            l.grid = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(l.count, static_cast<int64_t>(ctx->cu_count) * em_waves)));
-            launches.push_back(l);
-            continue;
-        }
-        if (is_tile_kind(kClassTab[dl.cls].kind) && kClassTab[dl.cls].R == 2 && ctx->opt[NPR_OPT_EM_GENERIC] == 0) {
-            // 164 VGPRs: 3 wavefronts per SIMD, 12 per CU -> 3 workgroups of 4; the workgroups keep the scratch regions the DP
-            // launch gave them (region i is sized for task i, and everything the queue hands out later is smaller)
-            l.stair_R = 2, l.tile = true;
-            l.lds = em_tile_lds_bytes(em_tile_waves());
-            l.tile_cs = kClassTab[dl.cls].kind == K_TILE_RS && ctx->opt[NPR_OPT_TILE_RS] != 2 && ctx->opt[NPR_OPT_EM_TILE] != 1;
-            const int per_cu = l.tile_cs ? em_tile_cs_waves_per_cu() / em_tile_cs_waves() : em_tile_waves_per_cu() / em_tile_waves();
-            l.grid = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(l.count, dl.grid), static_cast<int64_t>(ctx->cu_count) * per_cu)));
-            launches.push_back(l);
-            continue;
-        }
-        if (kClassTab[dl.cls].kind == K_WIDE && kClassTab[dl.cls].R == 2 && ctx->opt[NPR_OPT_EM_GENERIC] == 0) {
-            // 157 VGPRs: 3 wavefronts per SIMD, 12 per CU -> 3 / 1 tasks per CU on 4 / 8 wavefronts each
-            l.stair_R = 2, l.wide_NW = kClassTab[dl.cls].NW;
-            const int per_cu = 12 / l.wide_NW;
-            l.lds = em_wide_lds_bytes(l.wide_NW);
-            l.grid = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(l.count, static_cast<int64_t>(ctx->cu_count) * per_cu)));
-            launches.push_back(l);
-            continue;
-        }
-        l.wcap = static_cast<int>((std::max<int64_t>(dl.width, 64) + 3) & ~int64_t(3));
-        l.lds = generic_lds_bytes(l.wcap) + em_extra_lds_bytes();
-        l.global_ring = l.lds > 160 * 1024;  // the bins take 12 KiB of the LDS the ring would otherwise have
-        if (l.global_ring) l.lds = generic_lds_bytes(0) + em_extra_lds_bytes();
-        const int waves = l.global_ring ? 8 : std::min<int>(12, static_cast<int>(std::max<size_t>(1, (160 * 1024) / (l.lds + 256))));
-        l.grid = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(l.count, static_cast<int64_t>(ctx->cu_count) * waves)));
-        if (dl.own_regions) {
-            // A class laid out in scratch regions of its own (the stripe class under NPR_OPT_EM_GENERIC) has no uniform regions: the generic kernel
-            // counts it in regions 0, 1, .. of the arena, which belong to the other classes' launches -- so one launch after the other then, and no
-            // more workgroups than the arena has room for.  (Until round 6 the launches ran side by side there: NaN counts on a batch of four classes.)
-            l.uses_others_regions = true;
-            l.slot_base = 0;
-            const int64_t arena_cells = b->region_end.empty() ? b->slot_stride : b->region_end.back();
-            l.grid = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(l.grid, arena_cells / std::max<int64_t>(b->slot_stride, 1))));
-            l.dp_grid = l.grid;
-        }
-        launches.push_back(l);
-    }
-    // The launches run concurrently, like the DP launches of npr_batch_run (serialised, a batch in the trainer's band spent
-    // 63 ms where its longest class takes 38: profiles/r03_em_*): each class keeps the forward-scratch regions its DP launch
-    // owned (so at most that many workgroups) and gets its own planes and ring.
-    for (auto &l : launches)
-        if (!l.tile) l.grid = std::max(1, std::min(l.grid, l.dp_grid));
-    (void)max_grid;
-    // The planes of the other four states: 16 bytes per cell of forward scratch in use.  The stripe kernel's mirror its regions
-    // of the forward scratch, but only those of the workgroups the E-step launches (far fewer than the DP launch had): when
-    // the device has no room for them, fewer workgroups yet.
-    hipError_t e;
+    int32_t rc = ensure_coff(b);  // classes without a register E-step take the generic kernel
+    if (rc != NPR_OK) return rc;
+    const ModelShape shape = model_shape(ctx);
+    std::vector<EmLaunch> launches;
+    for (const auto &dl : b->launches) launches.push_back(plan_em_launch(b, dl, shape));
     size_t ring_floats = 0;
-    for (;;) {
-        // uniform classes: planes packed one class after the other; the stripe class: a mirror of its scratch regions, which
-        // lie behind all uniform regions of the arena (so behind the packed planes too)
-        size_t fx_cells = 0;
-        ring_floats = 0;
-        for (auto &l : launches) {
-            if (l.tile) continue;
-            l.fx_off = fx_cells;
-            fx_cells += static_cast<size_t>(l.grid) * 4 * static_cast<size_t>(b->slot_stride);
-            l.ring_off = ring_floats;
-            if (l.global_ring) ring_floats += static_cast<size_t>(l.grid) * 18 * l.wcap;
-        }
-        for (auto &l : launches)
-            if (l.tile && !b->region_end.empty()) {
-                l.fx_off = 0;
-                fx_cells = std::max(fx_cells, 4 * static_cast<size_t>(b->region_end[std::min<size_t>(static_cast<size_t>(l.grid), b->region_end.size()) - 1]));
-            }
-        if (fx_cells <= ctx->arena_fx_cells) break;
-        if (ctx->arena_Fx) (void)hipFree(reinterpret_cast<char *>(ctx->arena_Fx) - npr_ctx::kArenaPad);
-        ctx->arena_Fx = nullptr, ctx->arena_fx_cells = 0;
-        char *raw = nullptr;
-        e = hipMalloc(reinterpret_cast<void **>(&raw), fx_cells * sizeof(float) + 2 * npr_ctx::kArenaPad);
-        if (e != hipSuccess && !ctx->cache.empty()) {  // the buffers kept from closed batches are in the way
-            (void)hipGetLastError();
-            ctx->cache_flush();
-            e = hipMalloc(reinterpret_cast<void **>(&raw), fx_cells * sizeof(float) + 2 * npr_ctx::kArenaPad);
-        }
-        if (e == hipSuccess) {
-            ctx->arena_Fx = reinterpret_cast<float *>(raw + npr_ctx::kArenaPad);
-            ctx->arena_fx_cells = fx_cells;
-            break;
-        }
-        (void)hipGetLastError();
-        bool shrunk = false;
-        for (auto &l : launches)
-            if (l.grid > 1) l.grid = (l.grid + 1) / 2, shrunk = true;
-        if (!shrunk) return fail(ctx, NPR_ERR_NOMEM, "npr_batch_expectations: hipMalloc of the forward planes", e);
-    }
+    if ((rc = lay_out_planes(b, launches, &ring_floats)) != NPR_OK) return rc;
     DevBuf<float> ring;
     DevBuf<double> d_T, d_E;
+    hipError_t e;
     // (from the context's cache of released buffers: the trainer calls this hundreds of times on one staged batch -- no hipMalloc / hipFree per call)
     if ((e = ring.alloc_from(ctx, ring_floats)) != hipSuccess || (e = d_T.alloc_from(ctx, NPR_MAX_MODELS * 25)) != hipSuccess ||
         (e = d_E.alloc_from(ctx, NPR_MAX_MODELS * EM_BINS)) != hipSuccess)
@@ -316,83 +377,44 @@ int32_t npr_batch_expectations(npr_batch *b, double *T_exp, double *E_exp, doubl
     HIP_TRY(ctx, hipMemsetAsync(d_E.p, 0, d_E.bytes(), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(b->d_queue.p, 0, sizeof(int32_t) * kQueueSlots, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    // all classes at once, the smallest first, each on its own stream; the main stream waits for all of them, so
-    // ev0 -> ev1 brackets the whole E-step
-    std::vector<const L *> order;
-    for (const auto &l : launches) order.push_back(&l);
-    std::stable_sort(order.begin(), order.end(), [](const L *x, const L *y) { return x->cells < y->cells; });
+    // all classes at once, the smallest first, each on its own stream (FanOut); launch i has counter i of the work queue (at most
+    // kClasses launches, kQueueSlots counters)
+    std::stable_sort(launches.begin(), launches.end(), [](const EmLaunch &x, const EmLaunch &y) { return x.dp->cells < y.dp->cells; });
     bool serial = false;
     for (const auto &l : launches) serial |= l.uses_others_regions;
-    bool sw = false;  // (as npr_batch_run: the column-scaled kernel leaves out the short-gap switch terms no loaded model has)
-    for (int sl = 0; sl < NPR_MAX_MODELS; ++sl)
-        if (ctx->model_set[sl] && (ctx->models[sl].T[1 * 5 + 2] != 0.f || ctx->models[sl].T[2 * 5 + 1] != 0.f)) sw = true;
-    const bool flat = !sw && flat_gap_emissions(ctx);
-    for (auto &l : launches)
-        if (l.tile_cs)
-            for (int sl = 0; sl < NPR_MAX_MODELS; ++sl)
-                if (ctx->model_set[sl] && !rs_model_ok(ctx->models[sl])) l.tile_cs = false;
-    for (size_t i = 0; i < order.size(); ++i) {
-        const L &l = *order[i];
-        const bool last = serial || i + 1 == order.size();
-        hipStream_t st = last ? ctx->stream : ctx->side[i % npr_ctx::kSideStreams];
-        if (!last) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev0, 0));
-        KernelArgs a = make_args(b);
-        a.tasks += l.first;
-        a.outs += l.first;
-        a.ntasks = l.count;
-        a.queue += static_cast<int>(i);  // at most kClasses launches, kQueueSlots counters
-        a.wcap = l.wcap;
-        a.slot_base = l.slot_base;
-        a.region = l.region_first >= 0 ? b->d_region.p + l.region_first : nullptr;
+    const FanOut fan{ctx, launches.size(), serial};
+    for (size_t i = 0; i < launches.size(); ++i) {
+        const EmLaunch &l = launches[i];
+        hipStream_t st = fan.stream(i);
+        if ((rc = fan.before(i)) != NPR_OK) return rc;
+        KernelArgs a = em_args(b, l, static_cast<int>(i), d_T.p, d_E.p);
         a.ring = ring.p ? ring.p + l.ring_off : nullptr;
-        // stair / wide / generic kernels index their planes by workgroup from a.Fx; the stripe kernel by its scratch region
-        a.Fx = ctx->arena_Fx + l.fx_off;
-        a.em_T = d_T.p;
-        a.em_E = d_E.p;
-        if (l.tile_cs) a.wcap = ctx->opt[NPR_OPT_EM_TILE] == 2 ? 1 : 0;  // (the column-scaled kernel has no ring: the field carries the test switch)
-        const int rc = l.tile_cs   ? launch_em_tile_cs(a, em_tile_cs_waves(), l.grid, st, sw, flat)
-                       : l.tile    ? launch_em_tile(a, l.stair_R, l.grid, st)
-                       : l.wide_NW ? launch_em_wide(a, l.stair_R, l.wide_NW, l.grid, st)
-                       : l.stair_R ? launch_em_stair(a, l.stair_R, l.grid, st)
-                                   : launch_em(a, l.grid, l.lds, l.global_ring, st);
-        if (rc != 0) return fail(ctx, NPR_ERR_HIP, "E-step kernel launch", static_cast<hipError_t>(rc));
-        if (!last) HIP_TRY(ctx, hipEventRecord(ctx->side_done[i % npr_ctx::kSideStreams], st));
+        if (l.kind == EmKind::tile_cs) a.wcap = ctx->opt[NPR_OPT_EM_TILE] == 2 ? 1 : 0;  // (the column-scaled kernel has no ring: the field carries the test switch)
+        const int lrc = l.kind == EmKind::tile_cs ? launch_em_tile_cs(a, em_tile_cs_waves(), l.grid, st, shape.sw, shape.flat)
+                        : l.kind == EmKind::tile  ? launch_em_tile(a, l.R, l.grid, st)
+                        : l.kind == EmKind::wide  ? launch_em_wide(a, l.R, l.NW, l.grid, st)
+                        : l.kind == EmKind::stair ? launch_em_stair(a, l.R, l.grid, st)
+                                                  : launch_em(a, l.grid, l.lds, l.global_ring, st);
+        if (lrc != 0) return fail(ctx, NPR_ERR_HIP, "E-step kernel launch", static_cast<hipError_t>(lrc));
+        if ((rc = fan.after(i)) != NPR_OK) return rc;
     }
-    if (!serial)
-        for (size_t i = 0; i + 1 < order.size(); ++i) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_done[i % npr_ctx::kSideStreams], 0));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
+    if ((rc = fan.join(kernel_ms)) != NPR_OK) return rc;
     b->outs.resize(b->tasks.size());
     HIP_TRY(ctx, hipMemcpy(b->outs.data(), b->d_outs.p, b->d_outs.bytes(), hipMemcpyDeviceToHost));
     // The tasks the column-scaled kernel did not count (TASK_RERUN: its range certificate, or backward values far above a lane's scale) are counted
     // here by k_em_tile, on the scratch regions and planes the first launch had, into the same sums.
-    for (size_t i = 0; i < order.size(); ++i) {
-        const L &l = *order[i];
-        if (!l.tile_cs) continue;
-        std::vector<int32_t> again;
-        for (int k = l.first; k < l.first + l.count; ++k)
-            if (b->outs[k].status == TASK_RERUN) again.push_back(k);
-        if (std::getenv("NPR_TIMING")) std::fprintf(stderr, "[npr] E-step: %zu of %d stripe tasks counted again with a per-cell exponent\n", again.size(), l.count);
-        if (again.empty()) continue;
-        std::vector<Task> sub(again.size());
-        for (size_t j = 0; j < again.size(); ++j) sub[j] = b->tasks[again[j]];
-        DevBuf<Task> d_sub;
-        DevBuf<TaskOut> d_subout;
-        if (d_sub.alloc_from(ctx, sub.size()) != hipSuccess || d_subout.alloc_from(ctx, sub.size()) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_batch_expectations: hipMalloc");
-        HIP_TRY(ctx, hipMemcpy(d_sub.p, sub.data(), sizeof(Task) * sub.size(), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemsetAsync(b->d_queue.p + static_cast<int>(i), 0, sizeof(int32_t), ctx->stream));
+    for (size_t i = 0; i < launches.size(); ++i) {
+        const EmLaunch &l = launches[i];
+        if (l.kind != EmKind::tile_cs) continue;
+        Rerun r;
+        if ((rc = stage_rerun(b, l.dp->first, l.dp->count, static_cast<int>(i), true, "npr_batch_expectations: hipMalloc", &r)) != NPR_OK) return rc;
+        if (std::getenv("NPR_TIMING")) std::fprintf(stderr, "[npr] E-step: %zu of %d stripe tasks counted again with a per-cell exponent\n", r.again.size(), l.dp->count);
+        if (r.again.empty()) continue;
         HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        KernelArgs a = make_args(b);
-        a.tasks = d_sub.p, a.outs = d_subout.p, a.ntasks = static_cast<int32_t>(sub.size());
-        a.queue += static_cast<int>(i);
-        a.slot_base = l.slot_base;
-        a.region = l.region_first >= 0 ? b->d_region.p + l.region_first : nullptr;  // (task j of `again` is no larger than the j-th task of the class)
-        a.Fx = ctx->arena_Fx + l.fx_off;
-        a.em_T = d_T.p, a.em_E = d_E.p;
-        const int grid = static_cast<int>(std::min<size_t>(sub.size(), static_cast<size_t>(l.grid)));
-        const int rc = launch_em_tile(a, l.stair_R, grid, ctx->stream);
-        if (rc != 0) return fail(ctx, NPR_ERR_HIP, "E-step kernel launch (second pass)", static_cast<hipError_t>(rc));
+        KernelArgs a = em_args(b, l, static_cast<int>(i), d_T.p, d_E.p);
+        a.tasks = r.d_tasks.p, a.outs = r.d_outs.p, a.ntasks = r.ntasks();
+        const int lrc = launch_em_tile(a, l.R, std::min(r.ntasks(), l.grid), ctx->stream);
+        if (lrc != 0) return fail(ctx, NPR_ERR_HIP, "E-step kernel launch (second pass)", static_cast<hipError_t>(lrc));
         HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (kernel_ms) {
@@ -400,25 +422,12 @@ int32_t npr_batch_expectations(npr_batch *b, double *T_exp, double *E_exp, doubl
             HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
             *kernel_ms += ms;
         }
-        std::vector<TaskOut> subout(sub.size());
-        HIP_TRY(ctx, hipMemcpy(subout.data(), d_subout.p, sizeof(TaskOut) * sub.size(), hipMemcpyDeviceToHost));
-        for (size_t j = 0; j < again.size(); ++j) b->outs[again[j]] = subout[j];
+        if ((rc = merge_rerun(b, r)) != NPR_OK) return rc;
     }
-    std::vector<double> hE(NPR_MAX_MODELS * EM_BINS);
+    std::vector<double> bins(NPR_MAX_MODELS * EM_BINS);
     HIP_TRY(ctx, hipMemcpy(T_exp, d_T.p, d_T.bytes(), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(hE.data(), d_E.p, d_E.bytes(), hipMemcpyDeviceToHost));
-    for (int m = 0; m < NPR_MAX_MODELS; ++m) {
-        const double *s = hE.data() + m * EM_BINS;
-        double *d = E_exp + m * 80;
-        for (int i = 0; i < 16; ++i) d[i] = s[i];
-        for (int x = 0; x < 4; ++x)
-            for (int y = 0; y < 4; ++y) {
-                d[16 + x * 4 + y] = 0.25 * s[16 + x];  // shortGapX: count of reference base x
-                d[48 + x * 4 + y] = 0.25 * s[20 + x];  // longGapX
-                d[32 + x * 4 + y] = 0.25 * s[24 + y];  // shortGapY: count of read base y
-                d[64 + x * 4 + y] = 0.25 * s[28 + y];  // longGapY
-            }
-    }
+    HIP_TRY(ctx, hipMemcpy(bins.data(), d_E.p, d_E.bytes(), hipMemcpyDeviceToHost));
+    unpack_bins(bins.data(), E_exp);
     const double LN2 = 0.69314718055994530942;
     for (int64_t k = 0; k < ntasks; ++k) {
         const TaskOut &o = b->outs[k];
@@ -428,7 +437,6 @@ int32_t npr_batch_expectations(npr_batch *b, double *T_exp, double *E_exp, doubl
     b->ran = false;  // the task outputs now belong to the E-step
     return NPR_OK;
 }
-
 
 int32_t npr_batch_dense(npr_batch *b, int64_t read_index, float *Fm_v, int32_t *Fm_e, float *Bm_v, int32_t *Bm_e, int64_t cap) {
     if (!b || read_index < 0 || read_index >= b->n_reads || !Fm_v || !Fm_e || !Bm_v || !Bm_e) return NPR_ERR_INVALID;
@@ -452,23 +460,20 @@ int32_t npr_batch_dense(npr_batch *b, int64_t read_index, float *Fm_v, int32_t *
     for (int32_t s = 0; s < b->read_ntasks[read_index]; ++s) {
         const int32_t k = b->task_of[b->read_first_task[read_index] + s];
         const Task &t = b->tasks[k];
-        KernelArgs a = make_args(b);
-        a.tasks = b->d_tasks.p + k;
-        a.ntasks = 1;
-        a.outs = d_out1.p;
-        a.Bv = d_Bv.p;
-        a.Be = d_Be.p;
         // width of this task decides LDS vs global ring
         std::vector<int32_t> wn(t.D + 1);
         HIP_TRY(ctx, hipMemcpy(wn.data(), b->d_n.p + t.band_off, sizeof(int32_t) * (t.D + 1), hipMemcpyDeviceToHost));
         const int w = (*std::max_element(wn.begin(), wn.end()) + 3) & ~3;
         const bool global_ring = w > generic_max_wcap();
+        KernelArgs a = launch_args(b, k, 1, 0, std::max(w, 64), 0, nullptr);
+        a.outs = d_out1.p;
+        a.Bv = d_Bv.p;
+        a.Be = d_Be.p;
         DevBuf<float> ring1;
         if (global_ring) {
             if ((e = ring1.alloc(static_cast<size_t>(18) * w)) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_batch_dense: hipMalloc", e);
             a.ring = ring1.p;
         }
-        a.wcap = std::max(w, 64);
         HIP_TRY(ctx, hipMemsetAsync(b->d_queue.p, 0, sizeof(int32_t) * kQueueSlots, ctx->stream));
         const int rc = launch_generic(a, 1, 256, generic_lds_bytes(global_ring ? 0 : a.wcap), true, global_ring, ctx->stream);
         if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_dp_generic<dense> launch", static_cast<hipError_t>(rc));
@@ -506,10 +511,7 @@ int32_t npr_batch_rs_forward(npr_batch *b, int64_t read_index, float *Fm_v, int3
     ++ctx->arena->epoch;
     DevBuf<TaskOut> d_out1;
     if (d_out1.alloc(1) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_batch_rs_forward: hipMalloc");
-    bool sw = false;
-    for (int sl = 0; sl < NPR_MAX_MODELS; ++sl)
-        if (ctx->model_set[sl] && (ctx->models[sl].T[1 * 5 + 2] != 0.f || ctx->models[sl].T[2 * 5 + 1] != 0.f)) sw = true;
-    const bool flat = !sw && flat_gap_emissions(ctx);
+    const ModelShape shape = model_shape(ctx);
     int64_t written = 0;
     for (int32_t s = 0; s < b->read_ntasks[read_index]; ++s) {
         const int32_t k = b->task_of[b->read_first_task[read_index] + s];
@@ -518,10 +520,10 @@ int32_t npr_batch_rs_forward(npr_batch *b, int64_t read_index, float *Fm_v, int3
         for (const auto &L : b->launches)
             if (k >= L.first && k < L.first + L.count && (kClassTab[L.cls].kind == K_RS || kClassTab[L.cls].kind == K_MID)) R = kClassTab[L.cls].R;
         if (R == 0 || t.ctl_off < 0) return fail(ctx, NPR_ERR_STATE, "npr_batch_rs_forward: the read has a segment that k_dp_rs does not run");
-        KernelArgs a = make_args(b);
-        a.tasks = b->d_tasks.p + k, a.ntasks = 1, a.outs = d_out1.p, a.slot_base = 0, a.region = nullptr;
+        KernelArgs a = launch_args(b, k, 1, 0, 0, 0, nullptr);
+        a.outs = d_out1.p;
         HIP_TRY(ctx, hipMemsetAsync(b->d_queue.p, 0, sizeof(int32_t) * kQueueSlots, ctx->stream));
-        const int rc = launch_rs(a, R, 1, ctx->stream, sw, flat);
+        const int rc = launch_rs(a, R, 1, ctx->stream, shape.sw, shape.flat);
         if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_dp_rs launch", static_cast<hipError_t>(rc));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         const int64_t half = rs_half_cells(static_cast<int64_t>(static_cast<uint32_t>(t.cells_pad)));
@@ -557,6 +559,5 @@ int32_t npr_batch_rs_forward(npr_batch *b, int64_t read_index, float *Fm_v, int3
     b->ran = false;  // the pair buffers of this read were overwritten by the debug launch
     return NPR_OK;
 }
-
 
 }  // extern "C"
