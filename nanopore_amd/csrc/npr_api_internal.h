@@ -3,7 +3,7 @@
 //   npr_api.cpp     context, options, models, the plan-inspection entry points, the small public helpers
 //   npr_stage.cpp   npr_batch_create*: plan points, packing, H2D, the device planner, kernel classes and launch geometry
 //   npr_run.cpp     npr_batch_run (launch policy, second pass of tasks without a range certificate), the E-step, the dense dumps
-//   npr_finish.cpp  npr_batch_finish and what reads its results: the device MEA stage, the rescore sums, the host stage, ops / pairs
+//   npr_finish.cpp  npr_batch_finish and what reads its results: the device MEA stage and its pieced D2H, the rescore sums, the host stage, ops / pairs
 //   npr_aux.cpp     post-alignment statistics, k-mer tables, base expectations, the device pileup, the planner cross-check
 //   npr_text.cpp    cigar and SAM record text (the transport forms a job ships)
 //   npr_cigtext_api.cpp  cigar text made on the device (npr_cigtext.hip): npr_cigar_text_packed, npr_batch_cigar_text, NPR_OPT_FINISH_TEXT
@@ -90,7 +90,7 @@ struct npr_ctx {
     // the D2H rate and the copy is a GB per batch
     void *pin_pairs = nullptr;
     size_t pin_pairs_bytes = 0;
-    std::vector<hipEvent_t> ops_events;  // one per piece of the ops' D2H (device_mea)
+    std::vector<hipEvent_t> ops_events;  // one per piece of a D2H through pin_pairs (fetch_pieced)
     // the packed cigars of the last batch or two that were destroyed: a batch's 75-150 MB, whose pages cost 3 ms to touch when the
     // next batch is finished and 6 ms to give back when it is destroyed (with a caller waiting for the context)
     struct HostWords {
@@ -98,6 +98,25 @@ struct npr_ctx {
         int64_t cap = 0;
     };
     std::vector<HostWords> packed_pool;
+    // a buffer of at least `words` out of the pool into (p, cap), when it has one
+    void take_packed(int64_t words, std::unique_ptr<uint32_t[]> &p, int64_t &cap) {
+        for (size_t i = 0; i < packed_pool.size(); ++i)
+            if (packed_pool[i].cap >= words) {
+                p = std::move(packed_pool[i].p), cap = packed_pool[i].cap;
+                packed_pool.erase(packed_pool.begin() + static_cast<std::ptrdiff_t>(i));
+                return;
+            }
+    }
+    // ... and a destroyed batch's buffer into it: the pool keeps the two largest
+    void give_packed(std::unique_ptr<uint32_t[]> &p, int64_t cap) {
+        if (!p) return;
+        if (packed_pool.size() < 2) {
+            packed_pool.push_back(HostWords{std::move(p), cap});
+            return;
+        }
+        auto &smallest = *std::min_element(packed_pool.begin(), packed_pool.end(), [](const HostWords &x, const HostWords &y) { return x.cap < y.cap; });
+        if (smallest.cap < cap) smallest.p = std::move(p), smallest.cap = cap;
+    }
     // pinned host staging of npr_batch_create (plan points + sequence windows), grow-only
     void *pin_stage = nullptr;
     size_t pin_stage_bytes = 0;
@@ -481,11 +500,6 @@ inline int64_t stripes_of(const Segment &s, int R) { return (s.xe - s.xs) / (64 
 }  // namespace npr_impl
 using namespace npr_impl;
 
-// --------------------------------------------------------------------------------------------------
-// batch
-// --------------------------------------------------------------------------------------------------
-
-
 // ---- functions one translation unit defines and another calls ----
 namespace npr_impl {
 int32_t rescore_stage(npr_batch *b);                       // npr_finish.cpp: NPR_MODE_RESCORE_ORIGINAL, the guide's M columns as a device table (called when a batch is staged)
@@ -493,6 +507,18 @@ KernelArgs make_args(npr_batch *b);                        // npr_run.cpp: the k
 int32_t ensure_coff(npr_batch *b);                         // npr_stage.cpp: the generic kernel's row offsets, made on demand
 int32_t release_scratch(npr_ctx *ctx, bool caches_only);   // npr_api.cpp
 void ensure_packed_form(npr_batch *b);                     // npr_finish.cpp: the batch's cigars as one word per operation
-int32_t device_mea_text(npr_batch *b, MeaArgs &a, const std::vector<int64_t> &od, StageTimer &tm);  // npr_cigtext_api.cpp: the end of device_mea under NPR_OPT_FINISH_TEXT
+int32_t device_words_text(npr_batch *b, const int64_t *d_off, const uint32_t *d_words, char *lend, size_t lend_bytes);  // npr_cigtext_api.cpp: the batch's text from words on the device
+// `count` elements of `elem` bytes from the device to `dst` through the context's pinned staging, in pieces (npr_finish.cpp)
+using PieceMove = void (*)(void *dst, const void *pin, int64_t lo, int64_t hi);  // elements [lo, hi) of the staging buffer to their place in dst
+struct PiecedFetch {
+    const void *dev;
+    void *dst;
+    int64_t count;
+    size_t elem;
+    int64_t per_piece, round_to;  // elements: one piece per `per_piece` of them (48 pieces at most), each rounded up to a multiple of `round_to`
+    PieceMove move;               // what a host thread does with a piece that has crossed
+    const char *what_pin, *what_d2h;  // the caller's error texts
+};
+int32_t fetch_pieced(npr_ctx *ctx, const PiecedFetch &f);
 int32_t fetch_device_words(npr_batch *b);                  // npr_cigtext_api.cpp: the packed words such a finish left on the device, while they are there
 }  // namespace npr_impl

@@ -1,5 +1,5 @@
-// npr_cigtext_api.cpp -- cigar text made on the device (npr_cigtext.hip): npr_cigar_text_packed, npr_batch_cigar_text, and what
-// NPR_OPT_FINISH_TEXT makes of the end of the device MEA stage (utils.py:597-605: the writer loop's `aR.cigar = ...`)
+// npr_cigtext_api.cpp -- cigar text made on the device (npr_cigtext.hip): npr_cigar_text_packed, npr_batch_cigar_text, and the text the
+// device MEA stage hands over under NPR_OPT_FINISH_TEXT (utils.py:597-605: the writer loop's `aR.cigar = ...`)
 // (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
 #include "npr_api_internal.h"
 
@@ -46,55 +46,34 @@ int32_t run_cigtext(npr_ctx *ctx, int64_t n, const int64_t *d_word_off, const in
     return NPR_OK;
 }
 
-// `bytes` from the device to pageable host memory through the context's pinned staging, in pieces: the host threads move a piece out of
-// the staging buffer while the next ones cross (what device_mea does with the packed words)
-int32_t fetch_through_pin(npr_ctx *ctx, const char *dev, int64_t bytes, char *dst) {
-    if (bytes <= 0) return NPR_OK;
-    hipError_t e;
-    const size_t need = static_cast<size_t>(bytes);
-    if (need > ctx->pin_pairs_bytes) {
-        if (ctx->pin_pairs) (void)hipHostFree(ctx->pin_pairs);
-        ctx->pin_pairs = nullptr, ctx->pin_pairs_bytes = 0;
-        if ((e = hipHostMalloc(&ctx->pin_pairs, need + need / 4, hipHostMallocDefault)) != hipSuccess)
-            return fail(ctx, NPR_ERR_NOMEM, "cigar text: hipHostMalloc", e);
-        ctx->pin_pairs_bytes = need + need / 4;
-    }
-    constexpr int64_t kPieces = 48;
-    const int64_t pieces = std::min<int64_t>(kPieces, (bytes + (4 << 20) - 1) >> 22);
-    const int64_t piece = ((bytes + pieces - 1) / pieces + 255) & ~int64_t(255);
-    while (static_cast<int64_t>(ctx->ops_events.size()) < pieces) {
-        hipEvent_t ev;
-        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return fail(ctx, NPR_ERR_HIP, "hipEventCreate", e);
-        ctx->ops_events.push_back(ev);
-    }
-    char *pin = static_cast<char *>(ctx->pin_pairs);
-    for (int64_t c = 0; c < pieces; ++c) {
-        const int64_t lo = std::min(bytes, c * piece), hi = std::min(bytes, lo + piece);
-        if (hi > lo) HIP_TRY(ctx, hipMemcpyAsync(pin + lo, dev + lo, static_cast<size_t>(hi - lo), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(ctx->ops_events[c], ctx->stream));
-    }
-    std::atomic<int> failed{0};
-    parallel_for(pieces, ctx->host_threads, [&](int64_t c) {  // (the items are handed out in order)
-        if (hipSetDevice(ctx->device) != hipSuccess || hipEventSynchronize(ctx->ops_events[c]) != hipSuccess) {  // (a worker thread starts on device 0)
-            failed = 1;
-            return;
-        }
-        const int64_t lo = std::min(bytes, c * piece), hi = std::min(bytes, lo + piece);
-        std::memcpy(dst + lo, pin + lo, static_cast<size_t>(hi - lo));
-    });
-    if (failed) return fail(ctx, NPR_ERR_HIP, "cigar text: D2H", hipGetLastError());
-    return NPR_OK;
-}
-
 int32_t keep_text(npr_batch *b, const TextBufs &bufs, std::vector<int64_t> &off) {
     const int64_t total = off[b->n_reads];
     if (total > b->text_cap) b->text.reset(new char[total + total / 8]), b->text_cap = total + total / 8;
-    const int32_t rc = fetch_through_pin(b->ctx, bufs.text_p, total, b->text.get());
+    // through the context's pinned staging in pieces of 4 MiB
+    const PiecedFetch fetch{bufs.text_p, b->text.get(), total, 1, 4 << 20, 256,
+                            [](void *dst, const void *pin, int64_t lo, int64_t hi) {
+                                std::memcpy(static_cast<char *>(dst) + lo, static_cast<const char *>(pin) + lo, static_cast<size_t>(hi - lo));
+                            },
+                            "cigar text: hipHostMalloc", "cigar text: D2H"};
+    const int32_t rc = fetch_pieced(b->ctx, fetch);
     if (rc != NPR_OK) return rc;
     b->text_off.swap(off);
     b->text_ready = true;
     return NPR_OK;
 }
+
+}  // namespace
+
+// The text of a batch whose packed words (offsets d_off[n + 1]) are on the device, to b->text and b->text_off.  `lend`: device memory the text
+// may use (lend_bytes).  The stream is drained when it returns.
+int32_t device_words_text(npr_batch *b, const int64_t *d_off, const uint32_t *d_words, char *lend, size_t lend_bytes) {
+    std::vector<int64_t> off(b->n_reads + 1, 0);
+    TextBufs bufs;
+    const int32_t rc = run_cigtext(b->ctx, b->n_reads, d_off, nullptr, d_words, true, INT64_MAX, lend, lend_bytes, bufs, off.data());
+    return rc != NPR_OK ? rc : keep_text(b, bufs, off);
+}
+
+namespace {
 
 // the text of a finished batch on the host (b->text, b->text_off), made once: from the packed words where the device MEA stage left them
 // while they are still there, else from the batch's host form, uploaded
@@ -103,15 +82,13 @@ int32_t ensure_text(npr_batch *b) {
     npr_ctx *ctx = b->ctx;
     const int64_t n = b->n_reads;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<int64_t> off(n + 1, 0);
-    TextBufs bufs;
-    if (n == 0) return keep_text(b, bufs, off);
+    if (n == 0) {
+        std::vector<int64_t> off(1, 0);
+        return keep_text(b, TextBufs{}, off);
+    }
     {
         std::unique_lock<std::mutex> arena_lock(ctx->arena->mu);  // the resident cigars lie in the arena
-        if (b->dev_ops && b->dev_ops_epoch == ctx->arena->epoch) {
-            const int32_t rc = run_cigtext(ctx, n, b->dev_od, nullptr, b->dev_ops, true, INT64_MAX, nullptr, 0, bufs, off.data());
-            return rc != NPR_OK ? rc : keep_text(b, bufs, off);  // (keep_text ends with the stream drained: the lock goes after it)
-        }
+        if (b->dev_ops && b->dev_ops_epoch == ctx->arena->epoch) return device_words_text(b, b->dev_od, b->dev_ops, nullptr, 0);  // (the lock goes after it)
     }
     if (b->words_on_device && !b->have_packed_form) {
         const int32_t rc = fetch_device_words(b);  // (fails: the words are gone)
@@ -126,37 +103,10 @@ int32_t ensure_text(npr_batch *b) {
         return fail(ctx, NPR_ERR_NOMEM, "npr_batch_cigar_text: hipMalloc", e);
     if (words) HIP_TRY(ctx, hipMemcpyAsync(d_words.p, b->packed.get(), sizeof(uint32_t) * static_cast<size_t>(words), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_off.p, b->ops_off.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
-    const int32_t rc = run_cigtext(ctx, n, d_off.p, nullptr, d_words.p, true, INT64_MAX, nullptr, 0, bufs, off.data());
-    return rc != NPR_OK ? rc : keep_text(b, bufs, off);
+    return device_words_text(b, d_off.p, d_words.p, nullptr, 0);
 }
 
 }  // namespace
-
-// NPR_OPT_FINISH_TEXT: the end of device_mea (npr_finish.cpp) from the point where the reads' results are known -- the gather, then the
-// text kernels over the words the gather left in m.dense, and the TEXT and its offsets through the pinned staging instead of the words.
-// The words stay on the device for npr_batch_ops / npr_batch_ops_packed (fetch_device_words) while the stage's tables are not overwritten.
-int32_t device_mea_text(npr_batch *b, MeaArgs &a, const std::vector<int64_t> &od, StageTimer &tm) {
-    npr_ctx *ctx = b->ctx;
-    MeaScratch &m = *ctx->mea;
-    const int64_t n = b->n_reads;
-    b->have_pairs_form = false, b->have_packed_form = false, b->words_on_device = true;
-    HIP_TRY(ctx, hipMemcpyAsync(m.od.p, od.data(), m.od.bytes(), hipMemcpyHostToDevice, ctx->stream));
-    if (od[n]) {
-        a.ops_dense = m.dense.p;  // (sized for the bound ot[n] >= od[n])
-        a.ops_dense16 = nullptr;
-        const int rc = launch_mea_gather(a, ctx->stream);
-        if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_mea_gather launch", static_cast<hipError_t>(rc));
-    }
-    std::vector<int64_t> off(n + 1, 0);
-    TextBufs bufs;
-    // (the sorted pairs are done with: the text goes where the default path puts the 16-bit words)
-    int32_t rc = run_cigtext(ctx, n, m.od.p, nullptr, m.dense.p, true, INT64_MAX, reinterpret_cast<char *>(m.sorted.p), m.sorted.bytes(), bufs, off.data());
-    if (rc == NPR_OK) rc = keep_text(b, bufs, off);
-    if (rc != NPR_OK) return rc;
-    tm.lap("gather + D2H of the ops");
-    b->dev_ops = m.dense.p, b->dev_od = m.od.p, b->dev_ops_epoch = ctx->arena->epoch;
-    return NPR_OK;
-}
 
 // a batch finished with NPR_OPT_FINISH_TEXT has its packed words on the device only: to the host while they are still there
 int32_t fetch_device_words(npr_batch *b) {

@@ -2,10 +2,53 @@
 // (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
 #include "npr_api_internal.h"
 
-extern "C" {
-
-}  // extern "C"
 namespace npr_impl {
+
+// the context's pinned staging (grow-only) of at least `bytes`
+int32_t grow_pin_pairs(npr_ctx *ctx, size_t bytes, const char *what) {
+    if (bytes <= ctx->pin_pairs_bytes) return NPR_OK;
+    if (ctx->pin_pairs) (void)hipHostFree(ctx->pin_pairs);
+    ctx->pin_pairs = nullptr, ctx->pin_pairs_bytes = 0;
+    const hipError_t e = hipHostMalloc(&ctx->pin_pairs, bytes + bytes / 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, what, e);
+    ctx->pin_pairs_bytes = bytes + bytes / 4;
+    return NPR_OK;
+}
+
+// From the device to pageable host memory through the pinned staging, in pieces: the host threads move a piece out of the staging
+// buffer while the next ones cross.
+int32_t fetch_pieced(npr_ctx *ctx, const PiecedFetch &f) {
+    if (f.count <= 0) return NPR_OK;
+    const int32_t grown = grow_pin_pairs(ctx, f.elem * static_cast<size_t>(f.count), f.what_pin);
+    if (grown != NPR_OK) return grown;
+    constexpr int64_t kMaxPieces = 48;
+    const int64_t pieces = std::min(kMaxPieces, (f.count + f.per_piece - 1) / f.per_piece);
+    const int64_t piece = ((f.count + pieces - 1) / pieces + f.round_to - 1) / f.round_to * f.round_to;
+    while (static_cast<int64_t>(ctx->ops_events.size()) < pieces) {
+        hipEvent_t ev;
+        const hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (e != hipSuccess) return fail(ctx, NPR_ERR_HIP, "hipEventCreate", e);
+        ctx->ops_events.push_back(ev);
+    }
+    const char *dev = static_cast<const char *>(f.dev);
+    char *pin = static_cast<char *>(ctx->pin_pairs);
+    for (int64_t c = 0; c < pieces; ++c) {
+        const int64_t lo = std::min(f.count, c * piece), hi = std::min(f.count, lo + piece);
+        if (hi > lo) HIP_TRY(ctx, hipMemcpyAsync(pin + f.elem * lo, dev + f.elem * lo, f.elem * static_cast<size_t>(hi - lo), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ops_events[c], ctx->stream));
+    }
+    std::atomic<int> failed{0};
+    parallel_for(pieces, ctx->host_threads, [&](int64_t c) {  // (the items are handed out in order)
+        if (hipSetDevice(ctx->device) != hipSuccess || hipEventSynchronize(ctx->ops_events[c]) != hipSuccess) {  // (a worker thread starts on device 0)
+            failed = 1;
+            return;
+        }
+        const int64_t lo = std::min(f.count, c * piece), hi = std::min(f.count, lo + piece);
+        f.move(f.dst, pin, lo, hi);
+    });
+    if (failed) return fail(ctx, NPR_ERR_HIP, f.what_d2h, hipGetLastError());
+    return NPR_OK;
+}
 
 // Posterior pairs of every read to the host: one dense D2H, then per read (host threads) its segments' pairs merged
 // and sorted by (x, y).  b->task_dst (prefix of the per-task pair counts) and b->pair_off are already set.
@@ -30,14 +73,8 @@ int32_t fetch_pairs(npr_batch *b) {
         CompactArgs ca{b->d_tasks.p, b->d_outs.p, d_dst.p, static_cast<int32_t>(ntasks), b->d_px.p, b->d_py.p, b->d_pp.p, d_cx.p, d_cy.p, d_cp.p};
         const int rc = launch_compact(ca, ctx->stream);
         if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_compact launch", static_cast<hipError_t>(rc));
-        const size_t need = static_cast<size_t>(total) * 12;
-        if (need > ctx->pin_pairs_bytes) {
-            if (ctx->pin_pairs) (void)hipHostFree(ctx->pin_pairs);
-            ctx->pin_pairs = nullptr, ctx->pin_pairs_bytes = 0;
-            if ((e = hipHostMalloc(&ctx->pin_pairs, need + need / 4, hipHostMallocDefault)) != hipSuccess)
-                return fail(ctx, NPR_ERR_NOMEM, "npr_batch_finish: hipHostMalloc", e);
-            ctx->pin_pairs_bytes = need + need / 4;
-        }
+        const int32_t grown = grow_pin_pairs(ctx, static_cast<size_t>(total) * 12, "npr_batch_finish: hipHostMalloc");
+        if (grown != NPR_OK) return grown;
         int32_t *px_h = static_cast<int32_t *>(ctx->pin_pairs), *py_h = px_h + total;
         float *pp_h = reinterpret_cast<float *>(py_h + total);
         HIP_TRY(ctx, hipMemcpyAsync(px_h, d_cx.p, d_cx.bytes(), hipMemcpyDeviceToHost, ctx->stream));
@@ -193,18 +230,33 @@ int32_t rescore_sum(npr_batch *b, std::vector<double> &score) {
     return NPR_OK;
 }
 
-// MEA chain + cigar of every read on the device (npr_mea.hip): only the ops cross PCIe.  Returns 1 when some read
-// needs the host stage instead (a chain reaching back further than the prefix-maximum ring), NPR_OK or an error.
-int32_t device_mea(npr_batch *b) {
-    npr_ctx *ctx = b->ctx;
-    // the tables are carved out of the arena when they fit -- unless the context runs next to others (NPR_OPT_OVERLAP): then
-    // they live in buffers of its own and the stage need not wait for another batch's DP pass
-    std::unique_lock<std::mutex> arena_lock(ctx->arena->mu, std::defer_lock);
-    if (!ctx->overlap) arena_lock.lock();
-    ++ctx->arena->epoch;
-    StageTimer tm("device_mea");
-    const int64_t n = b->n_reads, ntasks = static_cast<int64_t>(b->tasks.size());
-    std::vector<int64_t> rx(n + 1, 0), ry(n + 1, 0), rp(n + 1, 0), ot(n + 1, 0), od(n + 1, 0);
+// ---- the device MEA stage (npr_mea.hip): chain + cigar of every read on the device, only the ops cross PCIe ----
+
+constexpr int32_t kHostStage = 1;  // what the stage's steps answer besides NPR_OK and errors: the host stage takes the batch
+
+// One batch in the stage's numbers: the per-read offsets, which reads sort through global memory, the pieces of every chain, the reads' order.
+struct MeaPlan {
+    int64_t n = 0, total = 0, n_pieces = 0;  // reads, posterior pairs, chain pieces
+    size_t ntask_map = 0, n_cnt = 1;         // entries of task_of; cells of the global-memory sort's tables
+    int64_t span = 0;                        // the widest table among the reads that sort in LDS
+    bool sort_in_lds = true;
+    // rx | ry | rp | ot | cnt_off as m.off takes them, n + 1 each: reference rows, read columns, pairs, the bound of the ops; first count cell or -1
+    std::vector<int64_t> offs;
+    int64_t stride() const { return n + 1; }
+    int64_t *arr(int k) { return offs.data() + k * stride(); }
+    int64_t cols() const { return offs[2 * stride() - 1]; }     // ry[n]
+    int64_t ops_bound() const { return offs[4 * stride() - 1]; }  // ot[n]
+    std::vector<int32_t> order;        // the reads longest first
+    std::vector<int32_t> pieces_head;  // np[n] | poff[n] | pboff[n] | lane_read[P] | lane_piece[P] as m.pieces takes them
+};
+
+constexpr int64_t kOffArrays = 5, kSortedArrays = 8, kSmallArrays = 6, kVrecWords = 4;
+
+MeaPlan plan_mea(const npr_batch *b) {
+    MeaPlan p;
+    const int64_t n = p.n = b->n_reads;
+    p.offs.assign(kOffArrays * p.stride(), 0);
+    int64_t *const rx = p.arr(0), *const ry = p.arr(1), *const rp = p.arr(2), *const ot = p.arr(3), *const cnt_off = p.arr(4);
     for (int64_t i = 0; i < n; ++i) {  // a read that already failed gets empty tables: its pairs are skipped as out of range
         const bool ok = b->results[i].status == NPR_OK;
         const int64_t lX = ok ? b->ref_len[i] : 0, lY = ok ? b->read_len[i] : 0, np = ok ? b->pair_off[i + 1] - b->pair_off[i] : 0;
@@ -213,240 +265,279 @@ int32_t device_mea(npr_batch *b) {
         rp[i + 1] = rp[i] + np;
         ot[i + 1] = ot[i] + 3 * std::min({np, lX, lY}) + 2;  // (D, I, M) per chain pair, one trailing (D, I)
     }
-    // the LDS-ring kernel takes the few reads the register window gives up on: as many read positions as the LDS
-    // holds with one workgroup per CU; a read whose pairs reach back further than that is reported and the batch takes
-    // the host stage
-    const int ring = 8192;
-    const int64_t total = rp[n];
+    p.total = rp[n];
+    // per-position tables of one read in LDS (count + scan + scatter in one kernel) when the longest span fits
+    // ... read by read (round 4: one read of more than 16 k bases used to send its whole batch through the global-memory kernels)
+    const int64_t lds_span = b->ctx->opt[NPR_OPT_MEA_GLOBAL_SORT] != 0 ? 0 : 16 * 1024;
+    int64_t cnt_total = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t sp = std::max(rx[i + 1] - rx[i], ry[i + 1] - ry[i]);
+        cnt_off[i] = -1;
+        if (sp <= lds_span) p.span = std::max(p.span, sp);
+        else cnt_off[i] = cnt_total, cnt_total += rx[i + 1] - rx[i];
+    }
+    cnt_off[n] = -1;
+    p.sort_in_lds = cnt_total == 0;
+    p.n_cnt = p.sort_in_lds ? 1 : static_cast<size_t>(cnt_total);
+    p.ntask_map = b->task_of.size();
+    p.order.resize(n);  // longest first: the per-read kernels end together instead of waiting for a late long read
+    std::iota(p.order.begin(), p.order.end(), 0);
+    std::stable_sort(p.order.begin(), p.order.end(), [&](int32_t x, int32_t y) { return rp[x + 1] - rp[x] > rp[y + 1] - rp[y]; });
     // the pieces the chain of every read is cut into (npr_mea.hip k_mea_cuts): about 2000 posterior pairs (1200 kept) each
     // ... fewer in a small batch, so that the pieces (one lane each, a serial walk) still fill the chip: 1000 reads of 1 kb as 1000
     // pieces of 1100 kept pairs took 0.9 ms where 14 000 pieces of 80 take 0.1
     constexpr int64_t kMaxPieces = 64, kLanesWanted = 64 * 5 * 256;
-    const int64_t kPiecePairs = std::min<int64_t>(2048, std::max<int64_t>(128, total / kLanesWanted));
+    const int64_t kPiecePairs = std::min<int64_t>(2048, std::max<int64_t>(128, p.total / kLanesWanted));
     std::vector<int32_t> np(n);
-    int64_t n_pieces = 0;
-    for (int64_t i = 0; i < n; ++i) np[i] = static_cast<int32_t>(std::min(kMaxPieces, std::max<int64_t>(1, (rp[i + 1] - rp[i] + kPiecePairs - 1) / kPiecePairs))), n_pieces += np[i];
-    if (!ctx->mea) ctx->mea = new MeaScratch;
-    MeaScratch &m = *ctx->mea;
-    hipError_t e;
-    // per-position tables of one read in LDS (count + scan + scatter in one kernel) when the longest span fits
-    // ... read by read (round 4: one read of more than 16 k bases used to send its whole batch through the global-memory kernels)
-    const int64_t lds_span = ctx->opt[NPR_OPT_MEA_GLOBAL_SORT] != 0 ? 0 : 16 * 1024;
-    int64_t span = 0;  // the widest table among the reads that sort in LDS
-    std::vector<int64_t> cnt_off(n + 1, -1);
-    int64_t cnt_total = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t sp = std::max(rx[i + 1] - rx[i], ry[i + 1] - ry[i]);
-        if (sp <= lds_span) span = std::max(span, sp);
-        else cnt_off[i] = cnt_total, cnt_total += rx[i + 1] - rx[i];
+    for (int64_t i = 0; i < n; ++i) np[i] = static_cast<int32_t>(std::min(kMaxPieces, std::max<int64_t>(1, (rp[i + 1] - rp[i] + kPiecePairs - 1) / kPiecePairs))), p.n_pieces += np[i];
+    p.pieces_head.resize(3 * n + 2 * p.n_pieces);
+    int32_t *const t_np = p.pieces_head.data(), *const t_poff = t_np + n, *const t_pboff = t_poff + n, *const t_lr = t_pboff + n, *const t_lp = t_lr + p.n_pieces;
+    int64_t at = 0;
+    for (int64_t k = 0; k < n; ++k) {  // lanes in the reads' order
+        const int32_t r = p.order[k];
+        t_np[r] = np[r], t_poff[r] = static_cast<int32_t>(at), t_pboff[r] = static_cast<int32_t>(at + k);
+        for (int32_t j = 0; j < np[r]; ++j) t_lr[at + j] = r, t_lp[at + j] = j;
+        at += np[r];
     }
-    const bool sort_in_lds = cnt_total == 0;
-    const size_t ntask_map = b->task_of.size();
-    // The forward scratch of the DP launches is idle now and usually far larger than what this stage needs: carve the
-    // tables out of it (a batch that fills the device's memory leaves nothing to hipMalloc).  Else: grow-only buffers.
-    const size_t n_cnt = sort_in_lds ? 1 : static_cast<size_t>(cnt_total);
-    {
-        auto al = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-        const size_t need = al(8 * 5 * (n + 1)) + al(8 * n) + al(8 * (n + 1)) + 2 * al(4 * n_cnt) + al(4 * (ry[n] + 1)) + al(4 * (12 * total + 16)) +
-                            al(4 * 6 * n) + al(4 * 2 * ot[n]) + al(4 * (3 * n + ntask_map)) + al(4 * ot[n]) + al(4 * (4 * n_pieces + 4 * n));
-        const bool arena_fits = ctx->arena->F && need <= static_cast<size_t>(ctx->arena->cells.load()) * 8;
-        bool in_arena = !ctx->overlap && arena_fits;
-        for (;;) {
-            char *cur = ctx->arena->F;
-            if (in_arena && poison_byte() >= 0) {  // the DP launches are done (their streams feed this one): the tables start from poison
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                poison(ctx->arena->F, need);
-            }
-            auto take = [&](auto &buf, size_t count) -> hipError_t {
-                using T = std::remove_pointer_t<decltype(buf.p)>;
-                if (!in_arena) return buf.reserve(count);
-                buf.borrow(reinterpret_cast<T *>(cur), count);
-                cur += al(sizeof(T) * count);
-                return hipSuccess;
-            };
-            if ((e = take(m.off, 5 * (n + 1))) == hipSuccess && (e = take(m.mass, n)) == hipSuccess && (e = take(m.od, n + 1)) == hipSuccess &&
-                (e = take(m.cnt, n_cnt)) == hipSuccess && (e = take(m.start, n_cnt)) == hipSuccess && (e = take(m.col, ry[n] + 1)) == hipSuccess &&
-                (e = take(m.sorted, 12 * total + 16)) == hipSuccess && (e = take(m.small, 6 * n)) == hipSuccess && (e = take(m.tmp, 2 * ot[n])) == hipSuccess &&
-                (e = take(m.map, 3 * n + ntask_map)) == hipSuccess && (e = take(m.dense, ot[n])) == hipSuccess &&
-                (e = take(m.pieces, 4 * n_pieces + 4 * n)) == hipSuccess)
-                break;
-            (void)hipGetLastError();
-            if (!in_arena && ctx->overlap && arena_fits) {
-                // A pipelined job's context keeps these tables in buffers of its own (NPR_OPT_OVERLAP) so that it need not wait for the batch
-                // that is running in the device's shared scratch -- when they do not fit beside the batches in flight (long reads: 48 bytes per
-                // pair, three chunks on the device) it waits after all, and gives back what it had reserved.
-                m.off.release(), m.mass.release(), m.od.release(), m.cnt.release(), m.start.release(), m.col.release(), m.sorted.release();
-                m.small.release(), m.tmp.release(), m.map.release(), m.dense.release(), m.pieces.release();
-                ctx->cache_flush();
-                arena_lock.lock();
-                // (`arena_fits` was read before the lock: another context may have released or regrown the shared scratch since)
-                if (!(ctx->arena->F && need <= static_cast<size_t>(ctx->arena->cells.load()) * 8)) return 1;
-                ++ctx->arena->epoch;
-                in_arena = true;
-                continue;
-            }
-            return 1;  // no room on the device: the host stage takes the batch
-        }
+    return p;
+}
+
+// The stage's tables.  Five of the buffers hold several arrays one behind the other; what follows is the only place that says how many and how long:
+//   off     rx | ry | rp | ot | cnt_off, n + 1 each
+//   sorted  sx | sy | sq | back | kx | ky | kq | kback, total + 1 each, then total + 2 records of 16 bytes (vrec)
+//   small   best_who | read_flag | n_ops | chain_len | kept | max_run, n each
+//   map     read_first[n] | read_ntasks[n] | task_of[ntask_map] | order[n]
+//   pieces  np[n] | poff[n] | pboff[n] | lane_read[P] | lane_piece[P] | pbest[P] | pb[P + n], P = n_pieces; lanes in the reads' order
+static_assert(kSortedArrays % kVrecWords == 0, "vrec starts on a 16-byte boundary of m.sorted (the arena's tables start 256-byte aligned)");
+inline int64_t sorted_stride(const MeaPlan &p) { return p.total + 1; }
+
+// every buffer of MeaScratch with its element count for the batch: f(buffer, count) until one fails
+template <typename F>
+hipError_t for_each_table(MeaScratch &m, const MeaPlan &p, F &&f) {
+    hipError_t e = hipSuccess;
+    auto one = [&](auto &buf, int64_t count) {
+        if (e == hipSuccess) e = f(buf, static_cast<size_t>(count));
+    };
+    one(m.off, kOffArrays * p.stride());
+    one(m.mass, p.n);
+    one(m.od, p.n + 1);
+    one(m.cnt, p.n_cnt);
+    one(m.start, p.n_cnt);
+    one(m.col, p.cols() + 1);
+    one(m.sorted, kSortedArrays * sorted_stride(p) + kVrecWords * (p.total + 2));
+    one(m.small, kSmallArrays * p.n);
+    one(m.tmp, 2 * p.ops_bound());
+    one(m.map, 3 * p.n + p.ntask_map);
+    one(m.dense, p.ops_bound());  // (the bound ot[n] >= the ops the reads end up with)
+    one(m.pieces, 4 * p.n_pieces + 4 * p.n);
+    return e;
+}
+
+inline size_t table_align(size_t bytes) { return (bytes + 255) & ~size_t(255); }
+
+// the tables as views of the arena's first `need` bytes, one behind the other
+int32_t carve_tables(npr_ctx *ctx, MeaScratch &m, const MeaPlan &p, size_t need) {
+    if (poison_byte() >= 0) {  // the DP launches are done (their streams feed this one): the tables start from poison
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        poison(ctx->arena->F, need);
     }
-    HIP_TRY(ctx, hipMemcpyAsync(m.map.p, b->read_first_task.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(m.map.p + n, b->read_ntasks.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(m.map.p + 2 * n, b->task_of.data(), sizeof(int32_t) * ntask_map, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<int32_t> order(n);  // longest first: the per-read kernels end together instead of waiting for a late long read
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return rp[x + 1] - rp[x] > rp[y + 1] - rp[y]; });
-    HIP_TRY(ctx, hipMemcpyAsync(m.map.p + 2 * n + ntask_map, order.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-    {
-        // layout of m.pieces: np[n] | poff[n] | pboff[n] | lane_read[P] | lane_piece[P] | pbest[P] | pb[P + n]; lanes in the reads' order
-        std::vector<int32_t> tab(3 * n + 2 * n_pieces);
-        int32_t *const t_np = tab.data(), *const t_poff = t_np + n, *const t_pboff = t_poff + n, *const t_lr = t_pboff + n, *const t_lp = t_lr + n_pieces;
-        int64_t at = 0;
-        for (int64_t k = 0; k < n; ++k) {
-            const int32_t r = order[k];
-            t_np[r] = np[r], t_poff[r] = static_cast<int32_t>(at), t_pboff[r] = static_cast<int32_t>(at + k);
-            for (int32_t j = 0; j < np[r]; ++j) t_lr[at + j] = r, t_lp[at + j] = j;
-            at += np[r];
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(m.pieces.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, ctx->stream));
-    }
-    std::vector<int64_t> offs(5 * (n + 1));
-    std::copy(cnt_off.begin(), cnt_off.end(), offs.begin() + 4 * (n + 1));
-    std::copy(rx.begin(), rx.end(), offs.begin());
-    std::copy(ry.begin(), ry.end(), offs.begin() + (n + 1));
-    std::copy(rp.begin(), rp.end(), offs.begin() + 2 * (n + 1));
-    std::copy(ot.begin(), ot.end(), offs.begin() + 3 * (n + 1));
-    HIP_TRY(ctx, hipMemcpyAsync(m.off.p, offs.data(), m.off.bytes(), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(m.small.p, 0, m.small.bytes(), ctx->stream));
-    MeaArgs a{};
-    a.tasks = b->d_tasks.p, a.outs = b->d_outs.p, a.ntasks = static_cast<int32_t>(ntasks), a.n_reads = static_cast<int32_t>(n);
+    char *cur = ctx->arena->F;
+    (void)for_each_table(m, p, [&](auto &buf, size_t count) {
+        using T = std::remove_pointer_t<decltype(buf.p)>;
+        buf.borrow(reinterpret_cast<T *>(cur), count);
+        cur += table_align(sizeof(T) * count);
+        return hipSuccess;
+    });
+    return NPR_OK;
+}
+
+// The forward scratch of the DP launches is idle now and usually far larger than what this stage needs: the tables are carved out of it when
+// they fit (a batch that fills the device's memory leaves nothing to hipMalloc) -- unless the context runs next to others (NPR_OPT_OVERLAP):
+// then they live in grow-only buffers of its own and the stage need not wait for another batch's DP pass.
+int32_t obtain_tables(npr_ctx *ctx, MeaScratch &m, const MeaPlan &p, std::unique_lock<std::mutex> &arena_lock) {
+    size_t need = 0;
+    (void)for_each_table(m, p, [&](auto &buf, size_t count) { return need += table_align(sizeof(*buf.p) * count), hipSuccess; });
+    auto arena_fits = [&] { return ctx->arena->F && need <= static_cast<size_t>(ctx->arena->cells.load()) * 8; };
+    const bool fits = arena_fits();
+    if (!ctx->overlap && fits) return carve_tables(ctx, m, p, need);
+    if (for_each_table(m, p, [](auto &buf, size_t count) { return buf.reserve(count); }) == hipSuccess) return NPR_OK;
+    (void)hipGetLastError();
+    if (!(ctx->overlap && fits)) return kHostStage;  // no room on the device
+    // When the own buffers do not fit beside the batches in flight (long reads: 48 bytes per pair, three chunks of a pipelined job on the
+    // device) the context waits for the shared scratch after all, and gives back what it had reserved.
+    (void)for_each_table(m, p, [](auto &buf, size_t) { return buf.release(), hipSuccess; });
+    ctx->cache_flush();
+    arena_lock.lock();
+    // (`fits` was read before the lock: another context may have released or regrown the shared scratch since)
+    if (!arena_fits()) return kHostStage;
+    ++ctx->arena->epoch;
+    return carve_tables(ctx, m, p, need);
+}
+
+// the maps, the pieces and the offsets to the device; `a`: the kernels' view of the tables
+int32_t upload_tables(npr_batch *b, const MeaPlan &p, MeaScratch &m, MeaArgs &a) {
+    npr_ctx *ctx = b->ctx;
+    const int64_t n = p.n, P = p.n_pieces, so = p.stride(), ss = sorted_stride(p);
+    a.tasks = b->d_tasks.p, a.outs = b->d_outs.p, a.ntasks = static_cast<int32_t>(b->tasks.size()), a.n_reads = static_cast<int32_t>(n);
     a.px = b->d_px.p, a.py = b->d_py.p, a.pp = b->d_pp.p;
-    a.rx_off = m.off.p, a.ry_off = m.off.p + (n + 1), a.rp_off = m.off.p + 2 * (n + 1), a.ot_off = m.off.p + 3 * (n + 1);
+    a.rx_off = m.off.p, a.ry_off = m.off.p + so, a.rp_off = m.off.p + 2 * so, a.ot_off = m.off.p + 3 * so, a.cnt_off = m.off.p + 4 * so;
     a.cnt = m.cnt.p, a.start = m.start.p, a.colsum = m.col.p;
-    a.sx = m.sorted.p, a.sy = m.sorted.p + total + 1, a.sq = m.sorted.p + 2 * (total + 1), a.back = m.sorted.p + 3 * (total + 1);
-    a.kx = m.sorted.p + 4 * (total + 1), a.ky = m.sorted.p + 5 * (total + 1), a.kq = m.sorted.p + 6 * (total + 1), a.kback = m.sorted.p + 7 * (total + 1);
-    a.vrec = reinterpret_cast<int4 *>(m.sorted.p + ((8 * (total + 1) + 3) & ~int64_t(3)));  // (16-byte records: the arena's tables start 256-byte aligned)
+    a.sx = m.sorted.p, a.sy = m.sorted.p + ss, a.sq = m.sorted.p + 2 * ss, a.back = m.sorted.p + 3 * ss;
+    a.kx = m.sorted.p + 4 * ss, a.ky = m.sorted.p + 5 * ss, a.kq = m.sorted.p + 6 * ss, a.kback = m.sorted.p + 7 * ss;
+    a.vrec = reinterpret_cast<int4 *>(m.sorted.p + kSortedArrays * ss);
     a.best_who = m.small.p, a.read_flag = m.small.p + n, a.n_ops = m.small.p + 2 * n, a.chain_len = m.small.p + 3 * n, a.kept = m.small.p + 4 * n, a.max_run = m.small.p + 5 * n;
     a.chain_mass = m.mass.p;
-    a.np = m.pieces.p, a.poff = m.pieces.p + n, a.pboff = m.pieces.p + 2 * n, a.lane_read = m.pieces.p + 3 * n, a.lane_piece = m.pieces.p + 3 * n + n_pieces;
-    a.pbest = m.pieces.p + 3 * n + 2 * n_pieces, a.pb = m.pieces.p + 3 * n + 3 * n_pieces, a.n_pieces = static_cast<int32_t>(n_pieces);
-    a.gap_gamma = b->params.gap_gamma, a.match_gamma = b->params.match_gamma, a.ring = ring;
-    a.ring_only = ctx->opt[NPR_OPT_MEA_RING_ONLY] != 0 ? 1 : 0;
-    a.read_first = m.map.p, a.read_ntasks = m.map.p + n, a.task_of = m.map.p + 2 * n, a.order = m.map.p + 2 * n + ntask_map;
-    a.sort_lds_bytes = static_cast<int32_t>(4 * span);
-    a.sort_threads = ctx->overlap == 1 ? 512 : 0;  // (beside a DP pass: workgroups that fit the half it leaves -- 1024 threads: the job 388 ms instead of 353, 256: 361)  // (beside a DP pass that leaves part of every SIMD: a workgroup that fits there)
-    a.any_global_sort = sort_in_lds ? 0 : 1;
-    a.cnt_off = m.off.p + 4 * (n + 1);
+    int32_t *const read_first = m.map.p, *const read_ntasks = read_first + n, *const task_of = read_ntasks + n, *const order = task_of + p.ntask_map;
+    a.read_first = read_first, a.read_ntasks = read_ntasks, a.task_of = task_of, a.order = order;
+    int32_t *const lanes = m.pieces.p + 3 * n;
+    a.np = m.pieces.p, a.poff = m.pieces.p + n, a.pboff = m.pieces.p + 2 * n, a.lane_read = lanes, a.lane_piece = lanes + P, a.pbest = lanes + 2 * P, a.pb = lanes + 3 * P;
+    a.n_pieces = static_cast<int32_t>(P);
     a.ops_tmp = m.tmp.p, a.od_off = m.od.p;
+    a.gap_gamma = b->params.gap_gamma, a.match_gamma = b->params.match_gamma;
+    // the LDS-ring kernel takes the few reads the register window gives up on: as many read positions as the LDS
+    // holds with one workgroup per CU; a read whose pairs reach back further than that is reported and the batch takes
+    // the host stage
+    a.ring = 8192;
+    a.ring_only = ctx->opt[NPR_OPT_MEA_RING_ONLY] != 0 ? 1 : 0;
+    a.sort_lds_bytes = static_cast<int32_t>(4 * p.span);
+    a.sort_threads = ctx->overlap == 1 ? 512 : 0;  // (beside a DP pass: workgroups that fit the half it leaves -- 1024 threads: the job 388 ms instead of 353, 256: 361)
+    a.any_global_sort = p.sort_in_lds ? 0 : 1;
+    HIP_TRY(ctx, hipMemcpyAsync(read_first, b->read_first_task.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(read_ntasks, b->read_ntasks.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(task_of, b->task_of.data(), sizeof(int32_t) * p.ntask_map, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(order, p.order.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(m.pieces.p, p.pieces_head.data(), sizeof(int32_t) * p.pieces_head.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(m.off.p, p.offs.data(), m.off.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(m.small.p, 0, m.small.bytes(), ctx->stream));
+    return NPR_OK;
+}
+
+// sort and chain; then the per-read words (m.small) and chain masses on the host
+int32_t run_chain(npr_ctx *ctx, const MeaArgs &a, MeaScratch &m, std::vector<int32_t> &small, std::vector<int64_t> &mass) {
     int rc = launch_mea_sort(a, ctx->stream);
     if (rc == 0) rc = launch_mea_chain(a, ctx->stream);
     if (rc != 0) return fail(ctx, NPR_ERR_HIP, "MEA kernel launch", static_cast<hipError_t>(rc));
-    std::vector<int32_t> small(6 * n);
-    std::vector<int64_t> mass(n);
+    small.resize(m.small.count), mass.resize(m.mass.count);
     HIP_TRY(ctx, hipMemcpyAsync(small.data(), m.small.p, m.small.bytes(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(mass.data(), m.mass.p, m.mass.bytes(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    tm.lap("sort + chain + trace");
-    const int32_t *flag = small.data() + n, *nops = small.data() + 2 * n, *clen = small.data() + 3 * n;
-    int32_t longest = 0;  // run of the batch's cigars
+    return NPR_OK;
+}
+
+// Per read its status, number of ops and score; b->ops_off.  kHostStage when a read's chain reached back further than the prefix-maximum
+// ring (nothing of the batch is touched then).  `longest`: the longest run of the batch's cigars.
+int32_t collect_results(npr_batch *b, const std::vector<int32_t> &small, const std::vector<int64_t> &mass, int32_t &longest) {
+    const int64_t n = b->n_reads;
+    const int32_t *flag = small.data() + n, *nops = small.data() + 2 * n, *clen = small.data() + 3 * n, *max_run = small.data() + 5 * n;
     for (int64_t i = 0; i < n; ++i)
-        if (b->results[i].status == NPR_OK && flag[i] == NPR_ERR_CAPACITY) return 1;
+        if (b->results[i].status == NPR_OK && flag[i] == NPR_ERR_CAPACITY) return kHostStage;
+    std::vector<int64_t> &od = b->ops_off;
+    od.assign(n + 1, 0);
+    longest = 0;
     for (int64_t i = 0; i < n; ++i) {
         npr_read_result &r = b->results[i];
         if (r.status == NPR_OK && flag[i] != 0) r.status = flag[i];
         const int64_t k = r.status == NPR_OK ? nops[i] : 0;
         od[i + 1] = od[i] + k;
-        if (k) longest = std::max(longest, small[5 * n + i]);
+        if (k) longest = std::max(longest, max_run[i]);
         r.n_ops = k;
         r.score = (r.status == NPR_OK && clen[i] > 0) ? static_cast<double>(mass[i]) / (static_cast<double>(clen[i]) * PROB_ONE) : 0.0;
     }
-    b->ops_off = od;
     b->ops_words = 2 * od[n];
-    if (ctx->opt[NPR_OPT_FINISH_TEXT] != 0) return device_mea_text(b, a, od, tm);  // the text crosses PCIe instead of the words (npr_cigtext_api.cpp)
-    b->have_pairs_form = false, b->have_packed_form = true;
-    if (od[n] > b->packed_cap)  // kept when the batch is finished again; else one a destroyed batch left behind, if it is large enough
-        for (size_t i = 0; i < ctx->packed_pool.size(); ++i)
-            if (ctx->packed_pool[i].cap >= od[n]) {
-                b->packed = std::move(ctx->packed_pool[i].p), b->packed_cap = ctx->packed_pool[i].cap;
-                ctx->packed_pool.erase(ctx->packed_pool.begin() + static_cast<std::ptrdiff_t>(i));
-                break;
-            }
-    if (od[n] > b->packed_cap) {
-        b->packed.reset(new uint32_t[od[n] + od[n] / 8]);  // (some room: the chunks of a job are about the same size, not exactly)
-        b->packed_cap = od[n] + od[n] / 8;
-    }
-    if (od[n]) {
-        // One packed word per op (length << 2 | op), through the pinned staging in pieces: the host threads move a piece into the
-        // batch's buffer while the next ones cross.  When no run of the batch is longer than 14 bits (a deletion of 16 k bases: the rule)
-        // the words cross as their low halves, 147 MB instead of 295 for the bench's 24576 reads, and the move widens them.
-        const bool narrow = longest < (1 << 14) && ctx->opt[NPR_OPT_MEA_WIDE_OPS] == 0 &&
-                            sizeof(uint16_t) * static_cast<size_t>(od[n]) <= m.sorted.bytes();  // (the sorted pairs are done with)
-        a.ops_dense = m.dense.p;  // (sized for the bound ot[n] >= od[n])
-        a.ops_dense16 = narrow ? reinterpret_cast<uint16_t *>(m.sorted.p) : nullptr;
-        HIP_TRY(ctx, hipMemcpyAsync(m.od.p, od.data(), m.od.bytes(), hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = launch_mea_gather(a, ctx->stream)) != 0) return fail(ctx, NPR_ERR_HIP, "k_mea_gather launch", static_cast<hipError_t>(rc));
-        const size_t word = narrow ? sizeof(uint16_t) : sizeof(uint32_t), need = word * static_cast<size_t>(od[n]);
-        if (need > ctx->pin_pairs_bytes) {
-            if (ctx->pin_pairs) (void)hipHostFree(ctx->pin_pairs);
-            ctx->pin_pairs = nullptr, ctx->pin_pairs_bytes = 0;
-            if ((e = hipHostMalloc(&ctx->pin_pairs, need + need / 4, hipHostMallocDefault)) != hipSuccess)
-                return fail(ctx, NPR_ERR_NOMEM, "npr_batch_finish: hipHostMalloc", e);
-            ctx->pin_pairs_bytes = need + need / 4;
-        }
-        constexpr int64_t kOpsPieces = 48;
-        const int64_t nops_all = od[n], pieces = std::min<int64_t>(kOpsPieces, (nops_all + (1 << 20) - 1) >> 20);
-        const int64_t piece = ((nops_all + pieces - 1) / pieces + 63) & ~int64_t(63);
-        while (static_cast<int64_t>(ctx->ops_events.size()) < pieces) {
-            hipEvent_t ev;
-            if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return fail(ctx, NPR_ERR_HIP, "hipEventCreate", e);
-            ctx->ops_events.push_back(ev);
-        }
-        const char *dev = narrow ? reinterpret_cast<const char *>(a.ops_dense16) : reinterpret_cast<const char *>(m.dense.p);
-        char *pin = static_cast<char *>(ctx->pin_pairs);
-        for (int64_t c = 0; c < pieces; ++c) {
-            const int64_t lo = std::min(nops_all, c * piece), hi = std::min(nops_all, lo + piece);
-            if (hi > lo) HIP_TRY(ctx, hipMemcpyAsync(pin + word * lo, dev + word * lo, word * static_cast<size_t>(hi - lo), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipEventRecord(ctx->ops_events[c], ctx->stream));
-        }
-        uint32_t *out = b->packed.get();
-        std::atomic<int> failed{0};
-        parallel_for(pieces, ctx->host_threads, [&](int64_t c) {  // (the items are handed out in order)
-            if (hipSetDevice(ctx->device) != hipSuccess || hipEventSynchronize(ctx->ops_events[c]) != hipSuccess) {  // (a worker thread starts on device 0)
-                failed = 1;
-                return;
-            }
-            const int64_t lo = std::min(nops_all, c * piece), hi = std::min(nops_all, lo + piece);
-            if (narrow) {
-                const uint16_t *src = reinterpret_cast<const uint16_t *>(pin);
-                for (int64_t i = lo; i < hi; ++i) out[i] = src[i];
-            } else {
-                std::memcpy(out + lo, pin + word * lo, word * static_cast<size_t>(hi - lo));
-            }
-        });
-        if (failed) return fail(ctx, NPR_ERR_HIP, "npr_batch_finish: D2H of the ops", hipGetLastError());
-    }
-    tm.lap("gather + D2H of the ops");
-    if (od[n]) b->dev_ops = m.dense.p, b->dev_od = m.od.p, b->dev_ops_epoch = ctx->arena->epoch;
     return NPR_OK;
 }
 
-}  // namespace npr_impl
-extern "C" {
+// What the two endings share: the ops' offsets up and the gather of the reads' ops into m.dense, one packed word per op (length << 2 | op)
+// -- and as their low halves into `dense16` when that is not null.
+int32_t gather_ops(npr_batch *b, MeaScratch &m, MeaArgs &a, uint16_t *dense16) {
+    npr_ctx *ctx = b->ctx;
+    HIP_TRY(ctx, hipMemcpyAsync(m.od.p, b->ops_off.data(), m.od.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    if (b->ops_off[b->n_reads] == 0) return NPR_OK;
+    a.ops_dense = m.dense.p, a.ops_dense16 = dense16;
+    const int rc = launch_mea_gather(a, ctx->stream);
+    return rc == 0 ? NPR_OK : fail(ctx, NPR_ERR_HIP, "k_mea_gather launch", static_cast<hipError_t>(rc));
+}
+// ... and where they lie afterwards, for whoever asks while the stage's tables are not overwritten
+void words_stay_on_device(npr_batch *b, const MeaScratch &m) { b->dev_ops = m.dense.p, b->dev_od = m.od.p, b->dev_ops_epoch = b->ctx->arena->epoch; }
 
-static int32_t batch_finish_impl(npr_batch *b);
-
-int32_t npr_batch_finish(npr_batch *b) {
-    try {
-        return batch_finish_impl(b);
-    } catch (const std::exception &) {
-        return fail(b ? b->ctx : nullptr, NPR_ERR_NOMEM, "npr_batch_finish: out of host memory");
+// The default ending: the packed words to b->packed, through the pinned staging in pieces.  When no run of the batch is longer than 14 bits
+// (a deletion of 16 k bases: the rule) the words cross as their low halves, 147 MB instead of 295 for the bench's 24576 reads, and the move
+// widens them.
+int32_t hand_over_words(npr_batch *b, MeaScratch &m, MeaArgs &a, int32_t longest) {
+    npr_ctx *ctx = b->ctx;
+    const int64_t words = b->ops_off[b->n_reads];
+    b->have_pairs_form = false, b->have_packed_form = true;
+    // kept when the batch is finished again; else one a destroyed batch left behind, if it is large enough
+    if (words > b->packed_cap) ctx->take_packed(words, b->packed, b->packed_cap);
+    if (words > b->packed_cap) {
+        b->packed.reset(new uint32_t[words + words / 8]);  // (some room: the chunks of a job are about the same size, not exactly)
+        b->packed_cap = words + words / 8;
     }
+    if (words == 0) return NPR_OK;
+    const bool narrow = longest < (1 << 14) && ctx->opt[NPR_OPT_MEA_WIDE_OPS] == 0 &&
+                        sizeof(uint16_t) * static_cast<size_t>(words) <= m.sorted.bytes();  // (the sorted pairs are done with)
+    int32_t rc = gather_ops(b, m, a, narrow ? reinterpret_cast<uint16_t *>(m.sorted.p) : nullptr);
+    if (rc != NPR_OK) return rc;
+    PiecedFetch f{m.dense.p, b->packed.get(), words, sizeof(uint32_t), int64_t(1) << 20, 64, nullptr, "npr_batch_finish: hipHostMalloc", "npr_batch_finish: D2H of the ops"};
+    f.move = [](void *dst, const void *pin, int64_t lo, int64_t hi) {
+        std::memcpy(static_cast<uint32_t *>(dst) + lo, static_cast<const uint32_t *>(pin) + lo, sizeof(uint32_t) * static_cast<size_t>(hi - lo));
+    };
+    if (narrow) {
+        f.dev = a.ops_dense16, f.elem = sizeof(uint16_t);
+        f.move = [](void *dst, const void *pin, int64_t lo, int64_t hi) {
+            uint32_t *out = static_cast<uint32_t *>(dst);
+            const uint16_t *src = static_cast<const uint16_t *>(pin);
+            for (int64_t i = lo; i < hi; ++i) out[i] = src[i];
+        };
+    }
+    if ((rc = fetch_pieced(ctx, f)) != NPR_OK) return rc;
+    words_stay_on_device(b, m);
+    return NPR_OK;
 }
 
-static int32_t batch_finish_impl(npr_batch *b) {
-    if (!b) return NPR_ERR_INVALID;
+// NPR_OPT_FINISH_TEXT: the text kernels over the words the gather left in m.dense, and the TEXT and its offsets through the pinned staging
+// instead of the words (npr_cigtext_api.cpp).  The words stay on the device for npr_batch_ops / npr_batch_ops_packed (fetch_device_words).
+int32_t hand_over_text(npr_batch *b, MeaScratch &m, MeaArgs &a) {
+    b->have_pairs_form = false, b->have_packed_form = false, b->words_on_device = true;
+    int32_t rc = gather_ops(b, m, a, nullptr);
+    // (the sorted pairs are done with: the text goes where the default ending puts the 16-bit words)
+    if (rc == NPR_OK) rc = device_words_text(b, m.od.p, m.dense.p, reinterpret_cast<char *>(m.sorted.p), m.sorted.bytes());
+    if (rc == NPR_OK) words_stay_on_device(b, m);
+    return rc;
+}
+
+// MEA chain + cigar of every read on the device: only the ops cross PCIe.  kHostStage when some read needs the host stage instead
+// (a chain reaching back further than the prefix-maximum ring) or the tables find no room, NPR_OK or an error.
+int32_t device_mea(npr_batch *b) {
     npr_ctx *ctx = b->ctx;
-    if (!b->ran) return fail(ctx, NPR_ERR_STATE, "npr_batch_finish before npr_batch_run");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    StageTimer tm("batch_finish");
+    // (a context that runs next to others, NPR_OPT_OVERLAP, takes the arena's lock only when it has to use the arena: obtain_tables)
+    std::unique_lock<std::mutex> arena_lock(ctx->arena->mu, std::defer_lock);
+    if (!ctx->overlap) arena_lock.lock();
+    ++ctx->arena->epoch;
+    StageTimer tm("device_mea");
+    const MeaPlan p = plan_mea(b);
+    if (!ctx->mea) ctx->mea = new MeaScratch;
+    MeaScratch &m = *ctx->mea;
+    MeaArgs a{};
+    std::vector<int32_t> small;
+    std::vector<int64_t> mass;
+    int32_t longest = 0;
+    int32_t rc = obtain_tables(ctx, m, p, arena_lock);
+    if (rc == NPR_OK) rc = upload_tables(b, p, m, a);
+    if (rc == NPR_OK) rc = run_chain(ctx, a, m, small, mass);
+    if (rc != NPR_OK) return rc;
+    tm.lap("sort + chain + trace");
+    if ((rc = collect_results(b, small, mass, longest)) != NPR_OK) return rc;
+    rc = ctx->opt[NPR_OPT_FINISH_TEXT] != 0 ? hand_over_text(b, m, a) : hand_over_words(b, m, a, longest);
+    if (rc == NPR_OK) tm.lap("gather + D2H of the ops");
+    return rc;
+}
+
+// ---- npr_batch_finish ----
+
+// per-read results from the task outputs; b->task_dst, b->pair_off
+int32_t task_results(npr_batch *b) {
+    npr_ctx *ctx = b->ctx;
     const int64_t ntasks = static_cast<int64_t>(b->tasks.size());
     const int64_t n = b->n_reads;
     std::vector<int64_t> &dst = b->task_dst;
@@ -476,60 +567,46 @@ static int32_t batch_finish_impl(npr_batch *b) {
         r.n_pairs = c;
         b->pair_off[i + 1] = b->pair_off[i] + c;
     }
-    tm.lap("task results");
-    // --- rescore mode: the guide's M columns looked up where the pairs lie (round 5) ---
-    std::vector<double> dev_score;
-    bool have_dev_score = false;
-    if (b->params.mode == NPR_MODE_RESCORE_ORIGINAL && n > 0 && ntasks > 0 && b->rs_staged && ctx->opt[NPR_OPT_HOST_MEA] == 0) {
-        const int32_t rc = rescore_sum(b, dev_score);
-        if (rc < 0) return rc;
-        have_dev_score = true;
-        tm.lap("device rescore");
-    }
-    // --- realign and all-posteriors modes: chain and cigar on the device, the pairs stay in HBM until npr_batch_pairs asks for them ---
-    if ((b->params.mode == NPR_MODE_REALIGN || b->params.mode == NPR_MODE_ALL_POSTERIORS) && n > 0 && ntasks > 0 && ctx->opt[NPR_OPT_HOST_MEA] == 0) {
-        int64_t scratch = 0;
-        for (int64_t i = 0; i < n; ++i) scratch += 8 * (b->ref_len[i] + 1) + 4 * b->read_len[i] + 36 * std::min(b->ref_len[i], b->read_len[i]) + 128;
-        scratch += 48 * b->pair_off[n];
-        size_t mem_free = 0, mem_total = 0;
-        const size_t arena_bytes = ctx->arena->cells.load() * 8;
-        if (static_cast<size_t>(scratch) <= arena_bytes ||
-            (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && static_cast<size_t>(scratch) < mem_free / 2)) {
-            const int32_t rc = device_mea(b);
-            if (rc < 0) return rc;
-            if (rc == NPR_OK) {
-                tm.lap("device MEA");
-                b->finished = true;
-                return NPR_OK;
-            }
-        }
-    }
-    // --- host stage: what the device stages could not take (per-position tables that would not fit: records chained across a whole contig;
-    // a fixed-point sum that could not be exact), and NPR_OPT_HOST_MEA ---
-    if (!have_dev_score) {
-        const int32_t rc = fetch_pairs(b);
-        if (rc != NPR_OK) return rc;
-    }
-    if (b->params.mode == NPR_MODE_RESCORE_ORIGINAL) {
-        // --rescoreOriginalAlignment: ops verbatim (alignmentUncertainty.py:51-52), new score.  The guide's operations are not copied here
-        // (10^7-10^8 per batch): npr_batch_ops / npr_batch_ops_packed make the form they are asked for from b->guide_ops
-        b->ops_off.assign(n + 1, 0);
-        parallel_for(n, ctx->host_threads, [&](int64_t i) {
-            npr_read_result &r = b->results[i];
-            if (r.status != NPR_OK) return;
-            r.n_ops = b->rs_kept[i], b->ops_off[i + 1] = b->rs_kept[i];
-            r.score = have_dev_score ? dev_score[i]
-                                     : rescore(b->guide_ops.data() + 2 * b->guide_off[i], b->guide_off[i + 1] - b->guide_off[i], b->pairs.data() + b->pair_off[i], r.n_pairs);
-        });
-        for (int64_t i = 0; i < n; ++i) b->ops_off[i + 1] += b->ops_off[i];
-        b->ops_words = 2 * b->ops_off[n];
-        b->ops_from_guide = true, b->have_pairs_form = false, b->have_packed_form = false;
-        tm.lap("scores");
-        b->finished = true;
-        return NPR_OK;
-    }
+    return NPR_OK;
+}
+
+// the device MEA stage when an estimate of its tables fits the arena or half of the free device memory; kHostStage otherwise
+int32_t gated_device_mea(npr_batch *b) {
+    npr_ctx *ctx = b->ctx;
+    int64_t scratch = 0;
+    for (int64_t i = 0; i < b->n_reads; ++i) scratch += 8 * (b->ref_len[i] + 1) + 4 * b->read_len[i] + 36 * std::min(b->ref_len[i], b->read_len[i]) + 128;
+    scratch += 48 * b->pair_off[b->n_reads];
+    size_t mem_free = 0, mem_total = 0;
+    const size_t arena_bytes = ctx->arena->cells.load() * 8;
+    if (static_cast<size_t>(scratch) <= arena_bytes ||
+        (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && static_cast<size_t>(scratch) < mem_free / 2))
+        return device_mea(b);
+    return kHostStage;
+}
+
+// --rescoreOriginalAlignment on the host: ops verbatim (alignmentUncertainty.py:51-52), new score -- `dev_score` when the device summed it.
+// The guide's operations are not copied here (10^7-10^8 per batch): npr_batch_ops / npr_batch_ops_packed make the form they are asked for
+// from b->guide_ops
+void host_rescore(npr_batch *b, const std::vector<double> *dev_score) {
+    const int64_t n = b->n_reads;
+    b->ops_off.assign(n + 1, 0);
+    parallel_for(n, b->ctx->host_threads, [&](int64_t i) {
+        npr_read_result &r = b->results[i];
+        if (r.status != NPR_OK) return;
+        r.n_ops = b->rs_kept[i], b->ops_off[i + 1] = b->rs_kept[i];
+        r.score = dev_score ? (*dev_score)[i]
+                            : rescore(b->guide_ops.data() + 2 * b->guide_off[i], b->guide_off[i + 1] - b->guide_off[i], b->pairs.data() + b->pair_off[i], r.n_pairs);
+    });
+    for (int64_t i = 0; i < n; ++i) b->ops_off[i + 1] += b->ops_off[i];
+    b->ops_words = 2 * b->ops_off[n];
+    b->ops_from_guide = true, b->have_pairs_form = false, b->have_packed_form = false;
+}
+
+// chain + cigar of every read on the host, from the pairs fetch_pairs left in b->pairs
+void host_mea(npr_batch *b, StageTimer &tm) {
+    const int64_t n = b->n_reads;
     std::vector<std::vector<int32_t>> per_read_ops(n);
-    parallel_for(n, ctx->host_threads, [&](int64_t i) {
+    parallel_for(n, b->ctx->host_threads, [&](int64_t i) {
         npr_read_result &r = b->results[i];
         if (r.status != NPR_OK) return;
         const int32_t rc = mea_cigar(b->ref_len[i], b->read_len[i], b->pairs.data() + b->pair_off[i], r.n_pairs, b->params.gap_gamma, b->params.match_gamma, per_read_ops[i], r.score);
@@ -547,20 +624,108 @@ static int32_t batch_finish_impl(npr_batch *b) {
     for (int64_t i = 0; i < n; ++i) std::copy(per_read_ops[i].begin(), per_read_ops[i].end(), b->ops.get() + 2 * b->ops_off[i]);
     b->have_pairs_form = true, b->have_packed_form = false;
     tm.lap("gather ops");
+}
+
+int32_t batch_finish_impl(npr_batch *b) {
+    if (!b) return NPR_ERR_INVALID;
+    npr_ctx *ctx = b->ctx;
+    if (!b->ran) return fail(ctx, NPR_ERR_STATE, "npr_batch_finish before npr_batch_run");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    StageTimer tm("batch_finish");
+    int32_t rc = task_results(b);
+    if (rc != NPR_OK) return rc;
+    tm.lap("task results");
+    const bool on_device = b->n_reads > 0 && !b->tasks.empty() && ctx->opt[NPR_OPT_HOST_MEA] == 0;
+    // --- rescore mode: the guide's M columns looked up where the pairs lie (round 5) ---
+    std::vector<double> dev_score;
+    bool have_dev_score = false;
+    if (b->params.mode == NPR_MODE_RESCORE_ORIGINAL && on_device && b->rs_staged) {
+        if ((rc = rescore_sum(b, dev_score)) < 0) return rc;
+        have_dev_score = true;
+        tm.lap("device rescore");
+    }
+    // --- realign and all-posteriors modes: chain and cigar on the device, the pairs stay in HBM until npr_batch_pairs asks for them ---
+    if ((b->params.mode == NPR_MODE_REALIGN || b->params.mode == NPR_MODE_ALL_POSTERIORS) && on_device) {
+        if ((rc = gated_device_mea(b)) < 0) return rc;
+        if (rc == NPR_OK) {
+            tm.lap("device MEA");
+            b->finished = true;
+            return NPR_OK;
+        }
+    }
+    // --- host stage: what the device stages could not take (per-position tables that would not fit: records chained across a whole contig;
+    // a fixed-point sum that could not be exact), and NPR_OPT_HOST_MEA ---
+    if (!have_dev_score && (rc = fetch_pairs(b)) != NPR_OK) return rc;
+    if (b->params.mode == NPR_MODE_RESCORE_ORIGINAL) {
+        host_rescore(b, have_dev_score ? &dev_score : nullptr);
+        tm.lap("scores");
+    } else {
+        host_mea(b, tm);
+    }
     b->finished = true;
     return NPR_OK;
+}
+
+// ---- the two host forms of the cigars, each made from the other the first time it is asked for ----
+
+void ops_from_guide(npr_batch *b) {  // rescore mode: the guide's operations of non-zero length, in the pairs form
+    const int64_t total = b->ops_off[b->n_reads];
+    if (2 * total > b->ops_cap) b->ops.reset(new int32_t[2 * total]), b->ops_cap = 2 * total;
+    parallel_for(b->n_reads, b->ctx->host_threads, [&](int64_t i) {
+        if (b->results[i].status != NPR_OK) return;
+        const int32_t *g = b->guide_ops.data() + 2 * b->guide_off[i];
+        const int64_t ng = b->guide_off[i + 1] - b->guide_off[i];
+        int32_t *out = b->ops.get() + 2 * b->ops_off[i];
+        for (int64_t q = 0; q < ng; ++q)
+            if (g[2 * q + 1] > 0) *out++ = g[2 * q], *out++ = g[2 * q + 1];
+    });
+    b->have_pairs_form = true;
+}
+void ensure_pairs_form(npr_batch *b) {
+    if (b->have_pairs_form) return;
+    if (b->ops_from_guide) return ops_from_guide(b);
+    const int64_t total = b->ops_off[b->n_reads];
+    if (2 * total > b->ops_cap) b->ops.reset(new int32_t[2 * total]), b->ops_cap = 2 * total;
+    const uint32_t *src = b->packed.get();
+    int32_t *out = b->ops.get();
+    const int64_t chunk = 1 << 19, nchunks = (total + chunk - 1) / chunk;
+    parallel_for(nchunks, b->ctx->host_threads, [&](int64_t c) {
+        for (int64_t i = c * chunk, hi = std::min(total, (c + 1) * chunk); i < hi; ++i)
+            out[2 * i] = static_cast<int32_t>(src[i] & 3u), out[2 * i + 1] = static_cast<int32_t>(src[i] >> 2);
+    });
+    b->have_pairs_form = true;
+}
+void ensure_packed_form(npr_batch *b) {
+    if (b->have_packed_form) return;
+    if (b->ops_from_guide && !b->have_pairs_form) ops_from_guide(b);
+    const int64_t total = b->ops_off[b->n_reads];
+    if (total > b->packed_cap) b->packed.reset(new uint32_t[total]), b->packed_cap = total;
+    const int32_t *src = b->ops.get();
+    uint32_t *out = b->packed.get();
+    const int64_t chunk = 1 << 19, nchunks = (total + chunk - 1) / chunk;
+    parallel_for(nchunks, b->ctx->host_threads, [&](int64_t c) {
+        for (int64_t i = c * chunk, hi = std::min(total, (c + 1) * chunk); i < hi; ++i)
+            out[i] = static_cast<uint32_t>(src[2 * i + 1]) << 2 | static_cast<uint32_t>(src[2 * i]);
+    });
+    b->have_packed_form = true;
+}
+
+}  // namespace npr_impl
+
+extern "C" {
+
+int32_t npr_batch_finish(npr_batch *b) {
+    try {
+        return batch_finish_impl(b);
+    } catch (const std::exception &) {
+        return fail(b ? b->ctx : nullptr, NPR_ERR_NOMEM, "npr_batch_finish: out of host memory");
+    }
 }
 
 void npr_batch_destroy(npr_batch *b) {
     if (!b) return;
     (void)hipSetDevice(b->ctx->device);
-    if (b->packed && b->ctx->packed_pool.size() < 2) {
-        b->ctx->packed_pool.push_back(npr_ctx::HostWords{std::move(b->packed), b->packed_cap});
-    } else if (b->packed && !b->ctx->packed_pool.empty()) {  // the pool keeps the larger ones
-        auto &smallest = *std::min_element(b->ctx->packed_pool.begin(), b->ctx->packed_pool.end(),
-                                           [](const npr_ctx::HostWords &x, const npr_ctx::HostWords &y) { return x.cap < y.cap; });
-        if (smallest.cap < b->packed_cap) smallest.p = std::move(b->packed), smallest.cap = b->packed_cap;
-    }
+    b->ctx->give_packed(b->packed, b->packed_cap);
     delete b;
 }
 
@@ -576,52 +741,6 @@ int32_t npr_batch_results(const npr_batch *b, npr_read_result *out) {
     std::copy(b->results.begin(), b->results.end(), out);
     return NPR_OK;
 }
-
-static void ops_from_guide(npr_batch *b) {  // rescore mode: the guide's operations of non-zero length, in the pairs form
-    const int64_t total = b->ops_off[b->n_reads];
-    if (2 * total > b->ops_cap) b->ops.reset(new int32_t[2 * total]), b->ops_cap = 2 * total;
-    parallel_for(b->n_reads, b->ctx->host_threads, [&](int64_t i) {
-        if (b->results[i].status != NPR_OK) return;
-        const int32_t *g = b->guide_ops.data() + 2 * b->guide_off[i];
-        const int64_t ng = b->guide_off[i + 1] - b->guide_off[i];
-        int32_t *out = b->ops.get() + 2 * b->ops_off[i];
-        for (int64_t q = 0; q < ng; ++q)
-            if (g[2 * q + 1] > 0) *out++ = g[2 * q], *out++ = g[2 * q + 1];
-    });
-    b->have_pairs_form = true;
-}
-static void ensure_pairs_form(npr_batch *b) {
-    if (b->have_pairs_form) return;
-    if (b->ops_from_guide) return ops_from_guide(b);
-    const int64_t total = b->ops_off[b->n_reads];
-    if (2 * total > b->ops_cap) b->ops.reset(new int32_t[2 * total]), b->ops_cap = 2 * total;
-    const uint32_t *src = b->packed.get();
-    int32_t *out = b->ops.get();
-    const int64_t chunk = 1 << 19, nchunks = (total + chunk - 1) / chunk;
-    parallel_for(nchunks, b->ctx->host_threads, [&](int64_t c) {
-        for (int64_t i = c * chunk, hi = std::min(total, (c + 1) * chunk); i < hi; ++i)
-            out[2 * i] = static_cast<int32_t>(src[i] & 3u), out[2 * i + 1] = static_cast<int32_t>(src[i] >> 2);
-    });
-    b->have_pairs_form = true;
-}
-}  // extern "C"
-namespace npr_impl {
-void ensure_packed_form(npr_batch *b) {
-    if (b->have_packed_form) return;
-    if (b->ops_from_guide && !b->have_pairs_form) ops_from_guide(b);
-    const int64_t total = b->ops_off[b->n_reads];
-    if (total > b->packed_cap) b->packed.reset(new uint32_t[total]), b->packed_cap = total;
-    const int32_t *src = b->ops.get();
-    uint32_t *out = b->packed.get();
-    const int64_t chunk = 1 << 19, nchunks = (total + chunk - 1) / chunk;
-    parallel_for(nchunks, b->ctx->host_threads, [&](int64_t c) {
-        for (int64_t i = c * chunk, hi = std::min(total, (c + 1) * chunk); i < hi; ++i)
-            out[i] = static_cast<uint32_t>(src[2 * i + 1]) << 2 | static_cast<uint32_t>(src[2 * i]);
-    });
-    b->have_packed_form = true;
-}
-}  // namespace npr_impl
-extern "C" {
 
 int32_t npr_batch_ops(const npr_batch *b, int64_t *ops_off, int32_t *ops, int64_t cap_pairs) {
     if (!b || !ops_off) return NPR_ERR_INVALID;
@@ -711,6 +830,5 @@ int32_t npr_batch_debug_set_pairs(npr_batch *b, int64_t read, const int32_t *x, 
     b->finished = false;
     return NPR_OK;
 }
-
 
 }  // extern "C"

@@ -249,6 +249,63 @@ def test_finish_text_option(gpu_ctx, mode):
                 b.close()
 
 
+def _noisy_batch(seed, n_reads, lmin, lmax, indel, max_indel=3, sub=0.1):
+    """CSR buffers for Context.stage_csr: references of lmin .. lmax random bases and noisy copies of them (helpers.random_pair's channel,
+    drawn with numpy: thousands of reads in a second), the true alignments as global guides."""
+    rng = np.random.default_rng(seed)
+    ascii_of = np.frombuffer(b"ACGT", dtype=np.uint8)
+    refs, reads, guides = [], [], []
+    for _ in range(n_reads):
+        L = int(rng.integers(lmin, lmax + 1))
+        r = rng.random(L)                                     # at most L events consume L reference bases
+        kind = np.where(r < indel / 2, 2, np.where(r < indel, 1, 0)).astype(np.int32)
+        klen = np.where(kind == 0, 1, rng.integers(1, max_indel + 1, size=L)).astype(np.int32)
+        m = int(np.searchsorted(np.cumsum(np.where(kind != 1, klen, 0)), L)) + 1   # the events up to the one that reaches L reference bases
+        kind, klen = kind[:m], klen[:m]
+        x_adv, y_adv = np.where(kind != 1, klen, 0), np.where(kind != 2, klen, 0)
+        X = rng.integers(0, 4, size=int(x_adv.sum())).astype(np.uint8)
+        Y = rng.integers(0, 4, size=int(y_adv.sum())).astype(np.uint8)
+        match = kind == 0
+        copied = X[(np.cumsum(x_adv) - x_adv)[match]]
+        copied = np.where(rng.random(copied.size) < sub, (copied + rng.integers(1, 4, size=copied.size)) % 4, copied)
+        Y[(np.cumsum(y_adv) - y_adv)[match]] = copied
+        first = np.flatnonzero(np.concatenate([[True], kind[1:] != kind[:-1]]))   # runs of the same operation, merged
+        refs.append(ascii_of[X]), reads.append(ascii_of[Y])
+        guides.append(np.stack([kind[first], np.add.reduceat(klen, first)], axis=1))
+    off = lambda parts: np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int64)
+    return (np.concatenate(refs), off(refs), np.concatenate(reads), off(reads), np.concatenate(guides).astype(np.int32), off(guides))
+
+
+def test_hand_over_in_several_pieces(gpu_ctx):
+    """A batch whose cigars cross PCIe in more than one piece of the pinned staging, the last piece partial, in the three forms the device
+    MEA stage hands them over in: 16-bit words (the default), whole words (mea_wide_ops), text (finish_text, the words fetched from the device
+    afterwards).  The same words as the host stage's, and the text the host formatter makes of them."""
+    from nanopore_amd import realign as R
+    from nanopore_amd.hmm import Hmm
+    gpu_ctx.set_hmm(Hmm.loadHmm(MODEL_DIR + "/blasr_hmm_0.txt"))
+    csr = _noisy_batch(41, 3600, 2000, 3000, indel=0.3)
+    P = R.make_params(band_mode=R.BAND_FIXED, fixed_width=100)
+    got = {}
+    for name, opts in (("narrow", {}), ("wide", dict(mea_wide_ops=1)), ("text", dict(finish_text=1)), ("host", dict(host_mea=1))):
+        with gpu_ctx.options(**opts):
+            b = gpu_ctx.stage_csr(P, *csr)
+            try:
+                b.run(), b.finish()
+                text = b.cigar_text() if name == "text" else None   # (made by the finish: asked for before the words come over)
+                got[name] = b.ops_packed() + (b.results()["status"].copy(), text)
+            finally:
+                b.close()
+    off, words, status, _ = got["host"]
+    assert (status == 0).all()
+    assert off[-1] > 2 ** 21 and off[-1] % (1 << 20) != 0   # two pieces or more of 2^20 words, the last one partial
+    for name in ("narrow", "wide", "text"):
+        assert np.array_equal(got[name][0], off) and np.array_equal(got[name][1], words) and np.array_equal(got[name][2], status), name
+    want, want_off = R.format_cigars_packed(off[:-1], np.diff(off), words)
+    assert want_off[-1] > 4 << 20                           # two pieces or more of 4 MiB
+    text, str_off = got["text"][3]
+    assert np.array_equal(str_off, want_off) and bytes(text) == bytes(want)
+
+
 def test_job_with_device_text_writes_the_same_file(tmp_path, monkeypatch):
     from test_gpu_job import HMM0, _c3_files
     from nanopore_amd import job

@@ -300,24 +300,30 @@ def test_finish_stages_refuse_malformed_pair_lists_in_bounded_time(gpu_ctx):
             R.mea_cigar(600, 600, x, y, p)
 
 
+def _mea_batch():
+    """40 reads of 30 .. 2500 bases with long indels, N bases in one, a read of one base and one of 3000 with indels of up to 150."""
+    rng = np.random.default_rng(23)
+    cases = [random_pair(rng, int(rng.integers(30, 2500)), indel=0.2, max_indel=40) for _ in range(40)]
+    cases += [random_pair(rng, 1, indel=0.0), random_pair(rng, 3000, indel=0.3, max_indel=150)]
+    cases[1][0][5:40] = 4
+    return ([bytes(b"ACGTN"[c] for c in X) for X, _, _ in cases], [bytes(b"ACGTN"[c] for c in Y) for _, Y, _ in cases], [g for _, _, g in cases])
+
+
+_MEA_PARAMS = (dict(band_mode=1, fixed_width=100), dict(band_mode=1, fixed_width=100, gap_gamma=0.0),
+               dict(band_mode=1, fixed_width=64, gap_gamma=0.9, match_gamma=0.3), dict(band_mode=1, fixed_width=700),
+               dict(band_mode=0, split_threshold=40, constraint_trim=3), dict(band_mode=0, match_gamma=0.95),
+               dict(band_mode=0, gap_gamma=0.2, match_gamma=-0.1))
+
+
 def test_device_mea_matches_host_stage(gpu_ctx, monkeypatch):
     """The chain + cigar stage runs on the device in realign mode (npr_mea.hip) and on the host in the other modes,
     for hand-made pair lists (npr_mea_cigar) and with NPR_OPT_HOST_MEA: same integers, so same ops and same scores --
     over gapGamma / matchGamma settings, reads of several segments, N bases, reads without any pair above matchGamma,
     and with the pairs fetched afterwards."""
     from nanopore_amd import realign as R
-    rng = np.random.default_rng(23)
     gpu_ctx.set_hmm(_hmm_obj("blasr_hmm_0.txt"))
-    cases = [random_pair(rng, int(rng.integers(30, 2500)), indel=0.2, max_indel=40) for _ in range(40)]
-    cases += [random_pair(rng, 1, indel=0.0), random_pair(rng, 3000, indel=0.3, max_indel=150)]
-    cases[1][0][5:40] = 4
-    refs = [bytes(b"ACGTN"[c] for c in X) for X, _, _ in cases]
-    reads = [bytes(b"ACGTN"[c] for c in Y) for _, Y, _ in cases]
-    guides = [g for _, _, g in cases]
-    for kw in (dict(band_mode=1, fixed_width=100), dict(band_mode=1, fixed_width=100, gap_gamma=0.0),
-               dict(band_mode=1, fixed_width=64, gap_gamma=0.9, match_gamma=0.3), dict(band_mode=1, fixed_width=700),
-               dict(band_mode=0, split_threshold=40, constraint_trim=3), dict(band_mode=0, match_gamma=0.95),
-               dict(band_mode=0, gap_gamma=0.2, match_gamma=-0.1)):
+    refs, reads, guides = _mea_batch()
+    for kw in _MEA_PARAMS:
         got = {}
         # device_ring: the general (LDS-ring) chain kernel for every read and the global-memory sort kernels (the
         # variants long spans and far-reaching pairs fall back to)
@@ -337,6 +343,28 @@ def test_device_mea_matches_host_stage(gpu_ctx, monkeypatch):
             assert u["ops"] == v["ops"] and u["score"] == v["score"] and u["n_pairs"] == v["n_pairs"], kw
             assert t["ops"] == v["ops"] and t["score"] == v["score"], kw
             assert len(u["p"]) == u["n_pairs"]
+
+
+def test_device_mea_with_tables_of_its_own(gpu_ctx):
+    """The stage's tables carved out of the device's shared scratch (NPR_OPT_OVERLAP 0) and in buffers of the context's own (2: what the
+    contexts of a pipelined job run with): the same ops, scores and pair counts, and the host stage's."""
+    from nanopore_amd import realign as R
+    gpu_ctx.set_hmm(_hmm_obj("blasr_hmm_0.txt"))
+    refs, reads, guides = _mea_batch()
+    P = R.make_params(**_MEA_PARAMS[0])
+    try:
+        gpu_ctx.set_option(_lib.OPT_OVERLAP, 2)
+        own = gpu_ctx.realign(P, refs, reads, guides)
+        gpu_ctx.set_option(_lib.OPT_OVERLAP, 0)
+        arena = gpu_ctx.realign(P, refs, reads, guides)
+        with gpu_ctx.options(host_mea=1):
+            host = gpu_ctx.realign(P, refs, reads, guides)
+    finally:
+        gpu_ctx.set_option(_lib.OPT_OVERLAP, 0)
+    assert len(own) == len(arena) == len(host) == len(refs)
+    for u, t, v in zip(own, arena, host):
+        assert u["status"] == t["status"] == v["status"] == 0
+        assert u["ops"] == t["ops"] == v["ops"] and u["score"] == t["score"] == v["score"] and u["n_pairs"] == t["n_pairs"] == v["n_pairs"]
 
 
 def test_rescore_and_all_posteriors_modes_finish_on_the_device(gpu_ctx):
