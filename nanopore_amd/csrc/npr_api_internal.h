@@ -507,6 +507,7 @@ KernelArgs make_args(npr_batch *b);                        // npr_run.cpp: the k
 int32_t ensure_coff(npr_batch *b);                         // npr_stage.cpp: the generic kernel's row offsets, made on demand
 int32_t release_scratch(npr_ctx *ctx, bool caches_only);   // npr_api.cpp
 void ensure_packed_form(npr_batch *b);                     // npr_finish.cpp: the batch's cigars as one word per operation
+int32_t grow_pin_stage(npr_ctx *ctx, size_t bytes, const char *what);  // npr_finish.cpp: the context's pinned staging (pin_stage, grow-only) of at least `bytes`
 int32_t device_words_text(npr_batch *b, const int64_t *d_off, const uint32_t *d_words, char *lend, size_t lend_bytes);  // npr_cigtext_api.cpp: the batch's text from words on the device
 // `count` elements of `elem` bytes from the device to `dst` through the context's pinned staging, in pieces (npr_finish.cpp)
 using PieceMove = void (*)(void *dst, const void *pin, int64_t lo, int64_t hi);  // elements [lo, hi) of the staging buffer to their place in dst

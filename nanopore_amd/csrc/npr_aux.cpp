@@ -278,14 +278,9 @@ int32_t npr_kmer_counts_groups(npr_ctx *ctx, int32_t k, int64_t n_seqs, const ui
         }
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         const size_t stage_need = static_cast<size_t>(tiles) * NPR_KMER_TILE + NPR_KMER_PAD;
+        const int32_t grown = grow_pin_stage(ctx, stage_need, "npr_kmer_counts_groups: hipHostMalloc");
+        if (grown != NPR_OK) return grown;
         hipError_t e;
-        if (stage_need > ctx->pin_stage_bytes) {
-            if (ctx->pin_stage) (void)hipHostFree(ctx->pin_stage);
-            ctx->pin_stage = nullptr, ctx->pin_stage_bytes = 0;
-            if ((e = hipHostMalloc(&ctx->pin_stage, stage_need + stage_need / 4, hipHostMallocDefault)) != hipSuccess)
-                return fail(ctx, NPR_ERR_NOMEM, "npr_kmer_counts_groups: hipHostMalloc", e);
-            ctx->pin_stage_bytes = stage_need + stage_need / 4;
-        }
         uint8_t *const h_seq = static_cast<uint8_t *>(ctx->pin_stage);
         parallel_for((slots + 255) / 256, ctx->host_threads, [&](int64_t c) {
             for (int64_t s = c * 256, hi = std::min(slots, (c + 1) * 256); s < hi; ++s)

@@ -4,16 +4,18 @@
 
 namespace npr_impl {
 
-// the context's pinned staging (grow-only) of at least `bytes`
-int32_t grow_pin_pairs(npr_ctx *ctx, size_t bytes, const char *what) {
-    if (bytes <= ctx->pin_pairs_bytes) return NPR_OK;
-    if (ctx->pin_pairs) (void)hipHostFree(ctx->pin_pairs);
-    ctx->pin_pairs = nullptr, ctx->pin_pairs_bytes = 0;
-    const hipError_t e = hipHostMalloc(&ctx->pin_pairs, bytes + bytes / 4, hipHostMallocDefault);
+// one of the context's pinned staging buffers (grow-only) of at least `bytes`
+static int32_t grow_pinned(npr_ctx *ctx, void *&p, size_t &have, size_t bytes, const char *what) {
+    if (bytes <= have) return NPR_OK;
+    if (p) (void)hipHostFree(p);
+    p = nullptr, have = 0;
+    const hipError_t e = hipHostMalloc(&p, bytes + bytes / 4, hipHostMallocDefault);
     if (e != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, what, e);
-    ctx->pin_pairs_bytes = bytes + bytes / 4;
+    have = bytes + bytes / 4;
     return NPR_OK;
 }
+int32_t grow_pin_pairs(npr_ctx *ctx, size_t bytes, const char *what) { return grow_pinned(ctx, ctx->pin_pairs, ctx->pin_pairs_bytes, bytes, what); }
+int32_t grow_pin_stage(npr_ctx *ctx, size_t bytes, const char *what) { return grow_pinned(ctx, ctx->pin_stage, ctx->pin_stage_bytes, bytes, what); }
 
 // From the device to pageable host memory through the pinned staging, in pieces: the host threads move a piece out of the staging
 // buffer while the next ones cross.
