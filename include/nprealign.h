@@ -367,6 +367,45 @@ int32_t npr_pileup_counts(npr_pileup *pl, int32_t *counts /* [sum ref_len][NPR_P
  * cross PCIe instead of 32. */
 int32_t npr_pileup_depth(npr_pileup *pl, int32_t *depth /* [sum ref_len] */, uint8_t *covered /* [sum ref_len] */);
 
+/* ---- exact-match seeding on the device: the local hits a base mapper hands to chainSamFile ----
+ * The reference's base mappers (last, bwa, lastz, blasr) are external binaries and not part of this build; this is the build's own
+ * mapper (nanopore_amd/mappers/seedMapper.py), behind the C ABI like every other stage.  Base codes are npr_encode_bases': A C G T ->
+ * 0..3 in either letter case, anything else -> 4, and a code 4 matches NOTHING, not even another code 4.  For a reference sequence X, a
+ * read Y in one orientation and parameters k <= min_len, a MATCH is (a, b, L) with X[a + t] == Y[b + t] (both codes < 4) for
+ * 0 <= t < L, L >= min_len, that cannot be extended: a == 0 or b == 0 or X[a - 1], Y[b - 1] do not match, and likewise at a + L, b + L.
+ * Matches never cross from one reference sequence into the next.  The forward strand is the read as given, the reverse strand its
+ * reverse complement, and b counts in that orientation (what a FLAG 16 record holds).  The result for a read is the SET of all its
+ * matches against every reference sequence on the strands asked for, as rows of four int32 -- reference index, a, b | strand << 31
+ * (strand 1 = reverse), L -- sorted by (strand, reference index, a, b): the same from run to run.  8 <= k <= 32 and
+ * k <= min_len < 2^31, NPR_ERR_INVALID otherwise.  k decides what the index holds (the positions whose next k bases are all A C G T,
+ * bucketed by the first min(k, 12) of them); which matches exist is decided by min_len alone.  A repeat of the reference is never
+ * masked: a read position inside a homopolymer run meets every position of the run. */
+typedef struct npr_seed_index npr_seed_index;
+/* The index of n_refs ASCII sequences (sequence i = ref[ref_off[i] .. ref_off[i + 1]), as for npr_kmer_counts), built on the device
+ * and kept there until it is destroyed.  It belongs to its context and must be destroyed before it; calls on it count as calls on the
+ * context.  n_refs == 0 and sequences shorter than k are legal and never match.  Fewer than 2^31 - 64 bases and sequences together. */
+int32_t npr_seed_index_create(npr_ctx *ctx, int32_t k, int64_t n_refs, const uint8_t *ref, const int64_t *ref_off, npr_seed_index **out);
+void npr_seed_index_destroy(npr_seed_index *index);
+/* The matches of n_reads reads: read i = text[begin[i] .. end[i]), a span inside a larger text as npr_kmer_counts_groups takes them.
+ * strands: 1 forward, 2 reverse, 3 both.  hit_off[n_reads + 1] is always filled: the rows of read i are hits[4 * hit_off[i] ..
+ * 4 * hit_off[i + 1]).  hits (cap rows of four int32; may be NULL with cap 0) is written only when all rows fit: returns the number of
+ * rows (>= 0), or NPR_ERR_CAPACITY when there are more than cap -- hit_off[n_reads] then says how many, and hits is not touched.
+ * n_reads == 0, empty reads and reads shorter than k are legal and have no rows.  NPR_ERR_INVALID (nothing written): a bad min_len or
+ * strands, a span that ends before it begins, 2^31 - 64 read bases and reads together or more in one call. */
+int64_t npr_seed_matches(npr_seed_index *index, int64_t min_len, int32_t strands, int64_t n_reads, const uint8_t *text, const int64_t *begin,
+                         const int64_t *end, int64_t *hit_off, int32_t *hits, int64_t cap);
+/* The rows npr_seed_matches returned as the SAM records of a base mapper, one per match, in row order: QNAME \t FLAG \t RNAME \t POS \t 255
+ * \t CIGAR \t * \t 0 \t 0 \t SEQ \t * \n with QNAME = text[name_span[2 * i] .. name_span[2 * i + 1]) of the row's read i, FLAG 0 or 16,
+ * RNAME = entry `reference index` of the rnames list (CSR), POS = a + 1, CIGAR = <b>H<L>M<rest>H with rest = read length - b - L and
+ * clips of length 0 left out, SEQ = the L matched bases in the strand's orientation, letters as they stand in the text and
+ * complemented for the reverse strand.  Hard clips keep a record at tens of bytes where soft clips would repeat the whole read in
+ * every one.  Record q lands at out[rec_off[q] .. rec_off[q + 1]), rec_off[hit_off[n_reads] + 1]; out == NULL: only the offsets.
+ * Returns the total length, NPR_ERR_CAPACITY when cap is smaller, NPR_ERR_INVALID for a row outside its read or the reference list.
+ * Threaded host code, no GPU needed. */
+int64_t npr_seed_sam_text(int64_t n_reads, const uint8_t *text, const int64_t *name_span, const int64_t *begin, const int64_t *end,
+                          const char *rnames, const int64_t *rname_off, int64_t n_refs, const int64_t *hit_off, const int32_t *hits,
+                          int64_t *rec_off, char *out, int64_t cap);
+
 /* Expected base counts per reference position from the posterior pairs of a finished batch, on the device (SURVEY.md 8f
  * next #4): what marginAlignSnpCaller.py:150-155 collates from the --outputAllPosteriorProbs files, one text line at a time:
  * every pair (refPos, readPos, p) of a selected read adds p to expect[(first row of its reference + refPos) * 4 + base] for

@@ -49,6 +49,7 @@ STATS_WORDS = 40  # NPR_STATS_WORDS
 KMER_MAX_K = 6    # the k-mer tables: 4^k + 1 bins, the last one for k-mers with a base outside ACGT
 KMER_MAX_GROUPS = 64  # npr_kmer_counts_groups: tables of one call
 SAM_COLS = 16     # NPR_SAM_COLS
+SEED_MIN_K, SEED_MAX_K = 8, 32  # npr_seed_index_create: the k of a seed index
 PILEUP_WORDS = 8  # NPR_PILEUP_WORDS: M columns by read base A C G T other, deletion columns, insertion runs, record starts
 MAX_MODELS = 8
 E_DEAD = -(1 << 28)
@@ -123,6 +124,7 @@ EXPORTS = [
     "npr_sam_index", "npr_sam_parse", "npr_sam_guides", "npr_sam_splice", "npr_fasta_index", "npr_fasta_pack", "npr_fastq_index", "npr_names_mark",
     "npr_batch_create_spans", "npr_chain_merge", "npr_ctx_option", "npr_batch_segment_arith",
     "npr_cigar_text_packed", "npr_batch_cigar_text", "npr_sam_splice_text",
+    "npr_seed_index_create", "npr_seed_index_destroy", "npr_seed_matches", "npr_seed_sam_text",
 ]
 
 _lib = None
@@ -259,6 +261,14 @@ def load():
     L.npr_cigar_text_packed.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64]
     L.npr_batch_cigar_text.restype = i64
     L.npr_batch_cigar_text.argtypes = [vp, vp, vp, i64]
+    L.npr_seed_index_create.restype = i32
+    L.npr_seed_index_create.argtypes = [vp, i32, i64, vp, vp, C.POINTER(vp)]
+    L.npr_seed_index_destroy.restype = None
+    L.npr_seed_index_destroy.argtypes = [vp]
+    L.npr_seed_matches.restype = i64
+    L.npr_seed_matches.argtypes = [vp, i64, i32, i64, vp, vp, vp, vp, vp, i64]
+    L.npr_seed_sam_text.restype = i64
+    L.npr_seed_sam_text.argtypes = [i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64]
     L.npr_fasta_index.restype = i64
     L.npr_fasta_index.argtypes = [vp, i64, vp, vp, i64]
     L.npr_fasta_pack.restype = i32

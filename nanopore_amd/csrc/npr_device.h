@@ -308,6 +308,51 @@ int launch_pileup_add(const PileupArgs &a, void *stream);
 int64_t pileup_scan_tiles(int64_t n_slots);
 int launch_pileup_scan(const PileupScanArgs &a, void *stream);
 int launch_pileup_depth(const int32_t *tab, int64_t rows, int32_t *depth, uint8_t *covered, void *stream);
+// exact-match seeding (npr_seed.hip).  A set of sequences lies in a CODE BUFFER: one separator byte, then every sequence followed by one
+// separator, then NPR_SEED_PAD more separators; sequence s of ASCII offsets off[] starts at off[s] + s + 1.  Bases A C G T are 0..3; every
+// other byte of the two buffers that meet has a value of its own side (reference: other base 4, separator 6; read: 5 and 7), so that
+// "bytes equal" is "bases match" and a match ends at a separator at the latest.
+constexpr int NPR_SEED_MIN_K = 8, NPR_SEED_MAX_K = 32, NPR_SEED_MAX_KB = 12;
+constexpr int NPR_SEED_PAD = 48;  // a lane loads 32 bytes from its position, an extension step 8 bytes past a separator; rounded so that the buffer ends on 16 bytes
+constexpr uint8_t NPR_SEED_REF_OTHER = 4, NPR_SEED_READ_OTHER = 5, NPR_SEED_REF_SEP = 6, NPR_SEED_READ_SEP = 7;
+constexpr int NPR_SEED_SCAN_TILE = 4096;  // table entries a workgroup scans; the table is allocated in whole tiles
+NPR_HD constexpr int64_t seed_code_bytes(int64_t bases, int64_t n_seqs) { return (bases + n_seqs + 1 + NPR_SEED_PAD + 15) / 16 * 16; }
+NPR_HD constexpr int64_t seed_table_entries(int kb) { return ((int64_t(1) << (2 * kb)) + 1 + NPR_SEED_SCAN_TILE - 1) / NPR_SEED_SCAN_TILE * NPR_SEED_SCAN_TILE; }
+struct SeedEncodeArgs {  // k_seed_encode: ASCII sequences lying back to back -> a code buffer, and (rc != nullptr) the buffer of their reverse complements
+    const uint8_t *ascii;
+    const int64_t *off;      // [n_seqs + 1], off[0] = 0
+    int64_t n_seqs;
+    int64_t bytes;           // seed_code_bytes(off[n_seqs], n_seqs)
+    uint8_t other, sep;
+    uint8_t *codes, *rc;
+};
+int launch_seed_encode(const SeedEncodeArgs &a, void *stream);
+struct SeedIndexArgs {  // k_seed_bucket_count / the scan / k_seed_bucket_fill: the window starts of the reference by their first kb bases
+    const uint8_t *codes;
+    int64_t bytes;
+    int32_t k, kb;
+    int32_t *table;          // [seed_table_entries(kb)], zeroed; afterwards table[key] = END of bucket `key` in pos (it begins where bucket key - 1 ends)
+    int32_t *tile;           // [table entries / NPR_SEED_SCAN_TILE] scratch of the scan
+    int32_t *pos;            // [window starts]: positions in codes
+};
+int launch_seed_index(const SeedIndexArgs &a, void *stream);
+struct SeedMatchArgs {  // k_seed_match<false> counts every read's matches into count[], k_seed_match<true> writes them
+    const uint8_t *ref;      // the index's code buffer, table and positions
+    const int32_t *table, *pos;
+    const int64_t *ref_off;  // [n_refs + 1] ASCII offsets of the reference sequences
+    int64_t n_refs;
+    int32_t k, kb;
+    int32_t min_len;
+    const uint8_t *read;     // code buffer of the reads in one orientation
+    int64_t bytes;
+    const int64_t *read_off; // [n_reads + 1]
+    int64_t n_reads;
+    uint32_t strand;         // 0 forward, 1 reverse complement
+    uint32_t *count;         // [n_reads], zeroed: matches per read (emitting: the next free row of the read's range)
+    const int64_t *hit_off;  // [n_reads + 1] (emitting)
+    int32_t *hits;           // [hit_off[n_reads]][4] = reference index, a, b | strand << 31, L (emitting)
+};
+int launch_seed_match(const SeedMatchArgs &a, bool emit, void *stream);
 // SAM CIGAR text of packed cigars on the device (npr_cigtext.hip): list i = words[word_off[i] .. word_off[i] + n_ops[i])
 struct CigTextArgs {
     int64_t n;

@@ -1,0 +1,276 @@
+// npr_seed_api.cpp -- exact-match seeding: the index of a reference set and the maximal exact matches of reads against it on the device
+// (npr_seed.hip), and the matches as the SAM records of a base mapper (host code)
+// (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
+#include "npr_api_internal.h"
+
+#include <array>
+
+// the index of one reference set: lives on the device from npr_seed_index_create to npr_seed_index_destroy
+struct npr_seed_index {
+    npr_ctx *ctx = nullptr;
+    int32_t k = 0, kb = 0;
+    int64_t n_refs = 0, bytes = 0;  // bytes of the code buffer
+    DevBuf<uint8_t> codes;
+    DevBuf<int64_t> off;            // [n_refs + 1] ASCII offsets of the sequences
+    DevBuf<int32_t> table, pos;
+};
+
+namespace {
+
+// n ASCII sequences lying back to back on the host (`bases` bytes at `ascii`, offsets off[n + 1] from 0) -> their code buffer on the device, and
+// the buffer of their reverse complements when rc is given; d_off receives the offsets
+int32_t encode_on_device(npr_ctx *ctx, const uint8_t *ascii, const std::vector<int64_t> &off, uint8_t other, uint8_t sep, DevBuf<uint8_t> &codes,
+                         DevBuf<uint8_t> *rc, DevBuf<int64_t> &d_off, const char *what) {
+    const int64_t n = static_cast<int64_t>(off.size()) - 1, bases = off[n], bytes = seed_code_bytes(bases, n);
+    DevBuf<uint8_t> d_ascii;
+    hipError_t e;
+    if ((e = d_ascii.alloc(static_cast<size_t>(bases))) != hipSuccess || (e = codes.alloc(static_cast<size_t>(bytes))) != hipSuccess ||
+        (rc && (e = rc->alloc(static_cast<size_t>(bytes))) != hipSuccess) || (e = d_off.alloc(off.size())) != hipSuccess)
+        return fail(ctx, NPR_ERR_NOMEM, what, e);
+    if (bases) HIP_TRY(ctx, hipMemcpyAsync(d_ascii.p, ascii, static_cast<size_t>(bases), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_off.p, off.data(), d_off.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    const SeedEncodeArgs a{d_ascii.p, d_off.p, n, bytes, other, sep, codes.p, rc ? rc->p : nullptr};
+    const int r = launch_seed_encode(a, ctx->stream);
+    if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_seed_encode launch", static_cast<hipError_t>(r));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the ASCII copy on the device goes when this returns)
+    return NPR_OK;
+}
+
+struct HitLess {  // (strand, reference index, a, b)
+    bool operator()(const std::array<int32_t, 4> &x, const std::array<int32_t, 4> &y) const {
+        const uint32_t bx = static_cast<uint32_t>(x[2]), by = static_cast<uint32_t>(y[2]);
+        if ((bx >> 31) != (by >> 31)) return (bx >> 31) < (by >> 31);
+        if (x[0] != y[0]) return x[0] < y[0];
+        if (x[1] != y[1]) return x[1] < y[1];
+        return (bx & 0x7fffffffu) < (by & 0x7fffffffu);
+    }
+};
+
+inline int digits(int64_t v) {
+    int k = 1;
+    while (v >= 10) v /= 10, ++k;
+    return k;
+}
+inline void put(char *&w, int64_t v) {
+    const int k = digits(v);
+    for (int j = k - 1; j >= 0; --j) w[j] = static_cast<char>('0' + v % 10), v /= 10;
+    w += k;
+}
+inline char complement(char c) {
+    switch (c) {
+        case 'A': return 'T';
+        case 'C': return 'G';
+        case 'G': return 'C';
+        case 'T': return 'A';
+        case 'a': return 't';
+        case 'c': return 'g';
+        case 'g': return 'c';
+        case 't': return 'a';
+        default: return c;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t npr_seed_index_create(npr_ctx *ctx, int32_t k, int64_t n_refs, const uint8_t *ref, const int64_t *ref_off, npr_seed_index **out) {
+    if (!ctx || !out) return NPR_ERR_INVALID;
+    *out = nullptr;
+    if (k < NPR_SEED_MIN_K || k > NPR_SEED_MAX_K) return fail(ctx, NPR_ERR_INVALID, "npr_seed_index_create: k outside 8 .. 32");
+    if (n_refs < 0 || (n_refs && !ref_off)) return NPR_ERR_INVALID;
+    try {
+        std::vector<int64_t> off(n_refs + 1, 0);
+        for (int64_t i = 1; i <= n_refs; ++i) {
+            off[i] = ref_off[i] - ref_off[0];
+            if (off[i] < off[i - 1]) return fail(ctx, NPR_ERR_INVALID, "npr_seed_index_create: sequence offsets decrease");
+        }
+        if (off[n_refs] && !ref) return NPR_ERR_INVALID;
+        if (seed_code_bytes(off[n_refs], n_refs) >= (int64_t(1) << 31)) return fail(ctx, NPR_ERR_INVALID, "npr_seed_index_create: 2^31 reference positions and more");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        std::unique_ptr<npr_seed_index> ix(new npr_seed_index);
+        ix->ctx = ctx, ix->k = k, ix->kb = std::min<int32_t>(k, NPR_SEED_MAX_KB), ix->n_refs = n_refs;
+        ix->bytes = seed_code_bytes(off[n_refs], n_refs);
+        const int32_t rc = encode_on_device(ctx, n_refs ? ref + ref_off[0] : nullptr, off, NPR_SEED_REF_OTHER, NPR_SEED_REF_SEP, ix->codes, nullptr, ix->off,
+                                            "npr_seed_index_create: hipMalloc");
+        if (rc != NPR_OK) return rc;
+        const size_t entries = static_cast<size_t>(seed_table_entries(ix->kb));
+        DevBuf<int32_t> tile;
+        hipError_t e;
+        if ((e = ix->table.alloc(entries)) != hipSuccess || (e = ix->pos.alloc(static_cast<size_t>(ix->bytes))) != hipSuccess ||
+            (e = tile.alloc(entries / NPR_SEED_SCAN_TILE)) != hipSuccess)
+            return fail(ctx, NPR_ERR_NOMEM, "npr_seed_index_create: hipMalloc", e);
+        HIP_TRY(ctx, hipMemsetAsync(ix->table.p, 0, ix->table.bytes(), ctx->stream));
+        const SeedIndexArgs a{ix->codes.p, ix->bytes, ix->k, ix->kb, ix->table.p, tile.p, ix->pos.p};
+        const int r = launch_seed_index(a, ctx->stream);
+        if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_seed_bucket launch", static_cast<hipError_t>(r));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        *out = ix.release();
+        return NPR_OK;
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_seed_index_create: out of host memory");
+    }
+}
+
+void npr_seed_index_destroy(npr_seed_index *ix) {
+    if (!ix) return;
+    (void)hipSetDevice(ix->ctx->device);
+    delete ix;
+}
+
+int64_t npr_seed_matches(npr_seed_index *ix, int64_t min_len, int32_t strands, int64_t n_reads, const uint8_t *text, const int64_t *begin, const int64_t *end,
+                         int64_t *hit_off, int32_t *hits, int64_t cap) {
+    if (!ix) return NPR_ERR_INVALID;
+    npr_ctx *ctx = ix->ctx;
+    if (min_len < ix->k || min_len >= (int64_t(1) << 31)) return fail(ctx, NPR_ERR_INVALID, "npr_seed_matches: min_len outside k .. 2^31 - 1");
+    if (strands < 1 || strands > 3) return fail(ctx, NPR_ERR_INVALID, "npr_seed_matches: strands outside 1 .. 3");
+    if (n_reads < 0 || cap < 0 || !hit_off || (n_reads && (!begin || !end))) return NPR_ERR_INVALID;
+    try {
+        std::vector<int64_t> off(n_reads + 1, 0);
+        for (int64_t i = 0; i < n_reads; ++i) {
+            if (end[i] < begin[i] || begin[i] < 0) return fail(ctx, NPR_ERR_INVALID, "npr_seed_matches: a span that ends before it begins");
+            off[i + 1] = off[i] + (end[i] - begin[i]);
+        }
+        const int64_t bases = off[n_reads];
+        if (bases && !text) return NPR_ERR_INVALID;
+        if (seed_code_bytes(bases, n_reads) >= (int64_t(1) << 31))
+            return fail(ctx, NPR_ERR_INVALID, "npr_seed_matches: 2^31 read positions and more in one call (give the reads in several)");
+        std::fill(hit_off, hit_off + n_reads + 1, int64_t(0));
+        if (bases == 0) return 0;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        // the reads back to back in the pinned staging, then as code buffers on the device (both orientations when the reverse strand is asked for)
+        const int32_t grown = grow_pin_stage(ctx, static_cast<size_t>(bases), "npr_seed_matches: hipHostMalloc");
+        if (grown != NPR_OK) return grown;
+        uint8_t *const h_ascii = static_cast<uint8_t *>(ctx->pin_stage);
+        parallel_for((n_reads + 255) / 256, ctx->host_threads, [&](int64_t c) {
+            for (int64_t i = c * 256, hi = std::min(n_reads, (c + 1) * 256); i < hi; ++i)
+                std::memcpy(h_ascii + off[i], text + begin[i], static_cast<size_t>(end[i] - begin[i]));
+        });
+        DevBuf<uint8_t> fwd, rev;
+        DevBuf<int64_t> d_off, d_hit_off;
+        DevBuf<uint32_t> d_count;
+        DevBuf<int32_t> d_hits;
+        const int32_t rc = encode_on_device(ctx, h_ascii, off, NPR_SEED_READ_OTHER, NPR_SEED_READ_SEP, fwd, (strands & 2) ? &rev : nullptr, d_off, "npr_seed_matches: hipMalloc");
+        if (rc != NPR_OK) return rc;
+        hipError_t e;
+        if ((e = d_count.alloc(static_cast<size_t>(n_reads))) != hipSuccess || (e = d_hit_off.alloc(static_cast<size_t>(n_reads) + 1)) != hipSuccess)
+            return fail(ctx, NPR_ERR_NOMEM, "npr_seed_matches: hipMalloc", e);
+        SeedMatchArgs a{ix->codes.p, ix->table.p, ix->pos.p, ix->off.p, ix->n_refs, ix->k, ix->kb, static_cast<int32_t>(min_len), nullptr, seed_code_bytes(bases, n_reads),
+                        d_off.p, n_reads, 0u, d_count.p, d_hit_off.p, nullptr};
+        auto both_strands = [&](bool emit) -> int32_t {  // the pass over the orientations asked for
+            HIP_TRY(ctx, hipMemsetAsync(d_count.p, 0, d_count.bytes(), ctx->stream));
+            for (uint32_t strand = 0; strand < 2; ++strand) {
+                if (!(strands & (1 << strand))) continue;
+                a.read = strand ? rev.p : fwd.p, a.strand = strand;
+                const int r = launch_seed_match(a, emit, ctx->stream);
+                if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_seed_match launch", static_cast<hipError_t>(r));
+            }
+            return NPR_OK;
+        };
+        int32_t rs = both_strands(false);
+        if (rs != NPR_OK) return rs;
+        std::vector<uint32_t> count(n_reads);
+        HIP_TRY(ctx, hipMemcpyAsync(count.data(), d_count.p, d_count.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (int64_t i = 0; i < n_reads; ++i) hit_off[i + 1] = hit_off[i] + count[i];
+        const int64_t total = hit_off[n_reads];
+        if (total == 0) return 0;
+        if (!hits || total > cap) return fail(ctx, NPR_ERR_CAPACITY, "npr_seed_matches: more matches than the buffer holds (hit_off says how many)");
+        if ((e = d_hits.alloc(static_cast<size_t>(total) * 4)) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_seed_matches: hipMalloc", e);
+        HIP_TRY(ctx, hipMemcpyAsync(d_hit_off.p, hit_off, d_hit_off.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        a.hits = d_hits.p;
+        rs = both_strands(true);
+        if (rs != NPR_OK) return rs;
+        HIP_TRY(ctx, hipMemcpyAsync(hits, d_hits.p, d_hits.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        // a read's matches arrive in the order the lanes found them: sorted here, the result is the same from run to run
+        static_assert(sizeof(std::array<int32_t, 4>) == 4 * sizeof(int32_t), "a match is four int32");
+        parallel_for((n_reads + 63) / 64, ctx->host_threads, [&](int64_t c) {
+            std::vector<std::array<int32_t, 4>> rows;
+            for (int64_t i = c * 64, hi = std::min(n_reads, (c + 1) * 64); i < hi; ++i) {
+                const int64_t m = hit_off[i + 1] - hit_off[i];
+                if (m < 2) continue;
+                rows.resize(static_cast<size_t>(m));
+                std::memcpy(rows.data(), hits + 4 * hit_off[i], static_cast<size_t>(m) * 16);
+                std::sort(rows.begin(), rows.end(), HitLess());
+                std::memcpy(hits + 4 * hit_off[i], rows.data(), static_cast<size_t>(m) * 16);
+            }
+        });
+        return total;
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_seed_matches: out of host memory");
+    }
+}
+
+int64_t npr_seed_sam_text(int64_t n_reads, const uint8_t *text, const int64_t *name_span, const int64_t *begin, const int64_t *end, const char *rnames,
+                          const int64_t *rname_off, int64_t n_refs, const int64_t *hit_off, const int32_t *hits, int64_t *rec_off, char *out, int64_t cap) {
+    if (n_reads < 0 || n_refs < 0 || !hit_off || !rec_off || (n_reads && (!text || !name_span || !begin || !end))) return NPR_ERR_INVALID;
+    const int64_t total = hit_off[n_reads];
+    if (hit_off[0] != 0 || total < 0 || (total && (!hits || !rnames || !rname_off))) return NPR_ERR_INVALID;
+    try {
+        const int threads = usable_cpus();
+        std::atomic<int> bad{0};
+        // lengths first (into rec_off[q + 1]), then their running sum
+        parallel_for((n_reads + 63) / 64, threads, [&](int64_t c) {
+            for (int64_t i = c * 64, hi = std::min(n_reads, (c + 1) * 64); i < hi; ++i) {
+                const int64_t len = end[i] - begin[i], nl = name_span[2 * i + 1] - name_span[2 * i];
+                if (hit_off[i + 1] < hit_off[i] || len < 0 || nl < 0) {
+                    bad = 1;
+                    continue;
+                }
+                for (int64_t q = hit_off[i]; q < hit_off[i + 1]; ++q) {
+                    const int32_t *h = hits + 4 * q;
+                    const int64_t r = h[0], a = h[1], b = static_cast<uint32_t>(h[2]) & 0x7fffffffu, L = h[3];
+                    if (r < 0 || r >= n_refs || a < 0 || L < 1 || b + L > len) {
+                        bad = 1, rec_off[q + 1] = 0;
+                        continue;
+                    }
+                    const int64_t rest = len - b - L, flag = static_cast<uint32_t>(h[2]) >> 31 ? 16 : 0;
+                    // qname, flag, rname, pos, "255", cigar, "*", "0", "0", seq, "*": ten tabs, a newline
+                    rec_off[q + 1] = nl + digits(flag) + (rname_off[r + 1] - rname_off[r]) + digits(a + 1) + 3 + (b ? digits(b) + 1 : 0) + digits(L) + 1 +
+                                  (rest ? digits(rest) + 1 : 0) + 3 + L + 1 + 11;
+                }
+            }
+        });
+        if (bad) return NPR_ERR_INVALID;
+        rec_off[0] = 0;
+        for (int64_t q = 0; q < total; ++q) rec_off[q + 1] += rec_off[q];
+        if (!out) return rec_off[total];
+        if (cap < rec_off[total]) return NPR_ERR_CAPACITY;
+        parallel_for((n_reads + 63) / 64, threads, [&](int64_t c) {
+            for (int64_t i = c * 64, hi = std::min(n_reads, (c + 1) * 64); i < hi; ++i) {
+                const int64_t len = end[i] - begin[i], nl = name_span[2 * i + 1] - name_span[2 * i];
+                const uint8_t *seq = text + begin[i];
+                for (int64_t q = hit_off[i]; q < hit_off[i + 1]; ++q) {
+                    const int32_t *h = hits + 4 * q;
+                    const int64_t r = h[0], a = h[1], b = static_cast<uint32_t>(h[2]) & 0x7fffffffu, L = h[3], rest = len - b - L;
+                    const bool reverse = static_cast<uint32_t>(h[2]) >> 31;
+                    char *w = out + rec_off[q];
+                    std::memcpy(w, text + name_span[2 * i], static_cast<size_t>(nl)), w += nl;
+                    *w++ = '\t';
+                    put(w, reverse ? 16 : 0);
+                    *w++ = '\t';
+                    std::memcpy(w, rnames + rname_off[r], static_cast<size_t>(rname_off[r + 1] - rname_off[r])), w += rname_off[r + 1] - rname_off[r];
+                    *w++ = '\t';
+                    put(w, a + 1);
+                    std::memcpy(w, "\t255\t", 5), w += 5;
+                    if (b) put(w, b), *w++ = 'H';
+                    put(w, L), *w++ = 'M';
+                    if (rest) put(w, rest), *w++ = 'H';
+                    std::memcpy(w, "\t*\t0\t0\t", 7), w += 7;
+                    if (!reverse) {
+                        std::memcpy(w, seq + b, static_cast<size_t>(L)), w += L;
+                    } else {  // base u of the match is base b + u of the reverse complement: the complement of read base len - 1 - (b + u)
+                        for (int64_t u = 0; u < L; ++u) *w++ = complement(static_cast<char>(seq[len - 1 - b - u]));
+                    }
+                    std::memcpy(w, "\t*\n", 3), w += 3;
+                }
+            }
+        });
+        return rec_off[total];
+    } catch (const std::exception &) {
+        return NPR_ERR_NOMEM;
+    }
+}
+
+}  // extern "C"

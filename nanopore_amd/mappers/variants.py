@@ -6,6 +6,7 @@ class of nanopore/mappers/{last,last_params,lastz,lastzParams,bwa,bwa_params,bla
 combinedMapper}.py exists here with the same name and the same realignSamFile arguments.
 """
 from .abstractMapper import AbstractMapper
+from .seedMapper import SeedMapper  # the build's own base mapper (seedMapper.py); the ones below are the reference's
 
 
 class Last(AbstractMapper):            # last.py:5
@@ -57,7 +58,7 @@ def _variant(base, suffix, **kwargs):
 
 
 _g = globals()
-for _base in (Last, LastParams, Lastz, LastzParams, Bwa, BwaParams, Blasr, BlasrParams, CombinedMapper):
+for _base in (Last, LastParams, Lastz, LastzParams, Bwa, BwaParams, Blasr, BlasrParams, CombinedMapper, SeedMapper):
     for _suffix, _kw in (("Chain", {}), ("Realign", {}), ("RealignEm", {"doEm": True}),
                          ("RealignTrainedModel", {"useTrainedModel": True})):
         _cls = _variant(_base, _suffix, **_kw)

@@ -354,6 +354,68 @@ class Pileup(object):
             pass
 
 
+class SeedIndex(object):
+    """The exact-match seed index of a set of reference sequences on the device (include/nprealign.h: npr_seed_*; csrc/npr_seed.hip):
+    built once, asked for the maximal exact matches of any number of reads."""
+
+    def __init__(self, ctx, ref, ref_off, k=16):
+        self._L = _lib.load()
+        self.ctx = ctx
+        self.k = int(k)
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        ref_off = np.ascontiguousarray(ref_off, dtype=np.int64)
+        self.n_refs = len(ref_off) - 1
+        h = C.c_void_p()
+        rc = self._L.npr_seed_index_create(ctx._h, self.k, self.n_refs, ptr(ref), ptr(ref_off), C.byref(h))
+        if rc != _lib.OK:
+            raise NprError(rc, "npr_seed_index_create", ctx.last_error())
+        self._h = h
+        ctx._open.add(self)
+
+    def matches(self, text, begin, end, min_len=20, strands=3, chunk_bases=1 << 26):
+        """All maximal exact matches of at least min_len bases of the reads text[begin[i]:end[i]] (spans inside a larger uint8 text, e.g.
+        FastqTable.text / .seq_span) on the strands asked for (1 forward, 2 reverse, 3 both): (hit_off int64 [n + 1], hits int32 [m, 4]) --
+        the rows of read i are hits[hit_off[i]:hit_off[i + 1]], each (reference index, a, b | strand << 31, L), sorted by (strand,
+        reference index, a, b).  The reads go to the device in chunks of about chunk_bases bases, each counted first and then fetched
+        into a buffer of exactly its size."""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        begin, end = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
+        n = len(begin)
+        if len(end) != n or (n and (int(begin.min()) < 0 or int(end.max()) > len(text))):
+            raise NprError(_lib.ERR_INVALID, "npr_seed_matches", "begin and end differ in number, or a span lies outside the text")
+        hit_off = np.zeros(n + 1, dtype=np.int64)
+        first = np.zeros(n + 1, dtype=np.int64)  # bases before read i
+        np.cumsum(end - begin, out=first[1:])
+        chunks = []  # reads lo .. hi whose bases stay within chunk_bases (one read at least); one empty call when there are no reads
+        while not chunks or chunks[-1][1] < n:
+            lo = chunks[-1][1] if chunks else 0
+            chunks.append((lo, min(n, max(int(np.searchsorted(first, first[lo] + chunk_bases, side="right")) - 1, lo + 1))))
+        parts = []
+        for lo, hi in chunks:
+            off = np.zeros(hi - lo + 1, dtype=np.int64)
+            args = [self._h, int(min_len), int(strands), hi - lo, ptr(text), ptr(begin[lo:hi]), ptr(end[lo:hi]), ptr(off)]
+            total = self._L.npr_seed_matches(*args, None, 0)
+            if total == ERR_CAPACITY:  # (there are matches: the offsets say how many)
+                rows = np.empty((int(off[-1]), 4), dtype=np.int32)
+                total = self._L.npr_seed_matches(*args, ptr(rows), len(rows))
+                parts.append(rows)
+            if total < 0:
+                raise NprError(int(total), "npr_seed_matches", self.ctx.last_error())
+            hit_off[lo + 1:hi + 1] = hit_off[lo] + off[1:]
+        return hit_off, (np.concatenate(parts) if parts else np.zeros((0, 4), dtype=np.int32))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.npr_seed_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context(object):
     """One realigner context = one GPU + one HIP stream.  Raises if no gfx950 device is usable."""
 
@@ -516,6 +578,15 @@ class Context(object):
     def pileup(self, ref_lengths):
         """A zeroed per-position table for reference sequences of these lengths (Pileup; include/nprealign.h: npr_pileup_create)."""
         return Pileup(self, ref_lengths)
+
+    def seed_index(self, refs, k=16):
+        """The exact-match seed index of the ASCII sequences `refs` (SeedIndex; include/nprealign.h: npr_seed_index_create)."""
+        ref, ref_off = _csr(refs)
+        return SeedIndex(self, ref, ref_off, k)
+
+    def seed_index_csr(self, ref, ref_off, k=16):
+        """seed_index on arrays: sequence i = ref[ref_off[i]:ref_off[i + 1]] (FastaTable.seq / .off fit directly)."""
+        return SeedIndex(self, ref, ref_off, k)
 
     def _realign_once(self, params, refs, reads, guides, model_slot, want_pairs, ref_index, guide_start=None):
         b = self.stage(params, refs, reads, guides, model_slot, ref_index, guide_start)
@@ -754,6 +825,32 @@ def format_sam_records(qnames, ref_names, ref_index, pos, word_off, n_ops, words
     rc = L.npr_format_sam_records(*args, ptr(buf), int(total))
     if rc < 0:
         raise NprError(int(rc), "npr_format_sam_records")
+    return buf[:int(total)], rec_off
+
+
+def seed_sam_text(text, name_span, begin, end, ref_names, hit_off, hits):
+    """The matches SeedIndex.matches returned as the SAM records of a base mapper, one per match (include/nprealign.h:
+    npr_seed_sam_text; host code, no device needed): (uint8 array, offsets[m + 1]).  Read i is text[begin[i]:end[i]] and is named
+    text[name_span[i, 0]:name_span[i, 1]] (FastqTable.text / .seq_span / .name_span); ref_names: list of bytes."""
+    L = _lib.load()
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    name_span = np.ascontiguousarray(name_span, dtype=np.int64).reshape(-1, 2)
+    begin, end = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
+    hit_off = np.ascontiguousarray(hit_off, dtype=np.int64)
+    hits = np.ascontiguousarray(hits, dtype=np.int32).reshape(-1, 4)
+    n = len(begin)
+    if not (len(end) == len(name_span) == n and len(hit_off) == n + 1 and int(hit_off[-1]) == len(hits)):
+        raise NprError(_lib.ERR_INVALID, "npr_seed_sam_text", "one name, begin and end per read, hit_off[n + 1], one row per match")
+    rn, roff = _ragged(ref_names)
+    rec_off = np.zeros(len(hits) + 1, dtype=np.int64)
+    args = [n, ptr(text), ptr(name_span), ptr(begin), ptr(end), ptr(rn), ptr(roff), len(ref_names), ptr(hit_off), ptr(hits), ptr(rec_off)]
+    total = L.npr_seed_sam_text(*args, None, 0)
+    if total < 0:
+        raise NprError(int(total), "npr_seed_sam_text")
+    buf = np.empty(max(int(total), 1), dtype=np.uint8)
+    rc = L.npr_seed_sam_text(*args, ptr(buf), int(total))
+    if rc < 0:
+        raise NprError(int(rc), "npr_seed_sam_text")
     return buf[:int(total)], rec_off
 
 
