@@ -19,6 +19,7 @@ files gathered in input order and spliced into a copy of the input SAM (utils.py
 `realign_sam_file` is what `analyses.utils.realignSamFile` (the plugin surface: AbstractMapper.realignSamFile,
 realignSamFileTargetFn) runs; `run_job` is the same pipeline over resident synthetic arrays (`bench.py --workload c3`).
 """
+import contextlib
 import gc
 import os
 import queue
@@ -35,7 +36,7 @@ _DEFAULT_CHUNK_BASES = 50_000_000
 CHUNK_BASES = int(os.environ.get("NPR_JOB_CHUNK_BASES", _DEFAULT_CHUNK_BASES))  # ~6 k reads of 8 kb (round 5; rounds 3-4: 10^8, see chunk_bounds)
 MIN_CHUNK_READS = int(os.environ.get("NPR_JOB_MIN_CHUNK_READS", 4096))  # reads of a chunk at the default chunk size (a caller who asks for smaller chunks gets them)
 WORKERS = int(os.environ.get("NPR_JOB_WORKERS", 3))  # chunks in flight (contexts per GPU): one in its DP, one being finished / fetched, one staged ahead
-TRACE = os.environ.get("NPR_JOB_TRACE") is not None  # timings["trace"]: (phase, start, end) per chunk, seconds (tools/job_trace.py)
+TRACE = os.environ.get("NPR_JOB_TRACE") is not None  # timings["trace"]: (phase, start, end) per chunk, seconds (bench.py prints them: [job trace])
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -65,15 +66,17 @@ class ArraySource(object):
     def lengths(self):
         return self.read_end - self.read_begin
 
+    def _stage_rows(self, ctx, params, rows, gops, goff, refs=None):
+        """The reads `rows` (a slice or an index array) with the guides (gops, goff) as one batch.  refs: (ref, ref_off, ref_index) made for
+        exactly these reads, as a source of per-read reference slices has to; else they find theirs in the source's table."""
+        pick = lambda x: None if x is None else x[rows]  # noqa: E731
+        ref, ref_off, ref_index = refs or (self.ref, self.ref_off, self.ref_index[rows])
+        return ctx.stage_spans(params, ref, ref_off, self.text, self.read_begin[rows], self.read_end[rows], gops, goff,
+                               model_slot=pick(self.model_slot), ref_index=ref_index, guide_start=pick(self.guide_start))
+
     def stage(self, ctx, params, lo, hi):
-        sl = slice(lo, hi)
-        if self.ref_index is None:  # per-read slices: the range's own part of the reference table
-            ref, ref_off, ri = self.ref, self.ref_off[lo:hi + 1], None
-        else:
-            ref, ref_off, ri = self.ref, self.ref_off, self.ref_index[sl]
-        return ctx.stage_spans(params, ref, ref_off, self.text, self.read_begin[sl], self.read_end[sl], self.guide_ops,
-                               self.guide_off[lo:hi + 1], model_slot=None if self.model_slot is None else self.model_slot[sl],
-                               ref_index=ri, guide_start=None if self.guide_start is None else self.guide_start[sl])
+        refs = (self.ref, self.ref_off[lo:hi + 1], None) if self.ref_index is None else None  # (per-read slices: the range's own part of the table)
+        return self._stage_rows(ctx, params, slice(lo, hi), self.guide_ops, self.guide_off[lo:hi + 1], refs)
 
     def stage_records(self, ctx, params, idx):
         """The records `idx` (any subset, in that order) as one batch: the few reads of a chunk that have to run again."""
@@ -82,17 +85,14 @@ class ArraySource(object):
         goff = np.zeros(len(idx) + 1, dtype=np.int64)
         np.cumsum(k, out=goff[1:])
         gops = self.guide_ops[np.repeat(self.guide_off[idx] - goff[:-1], k) + np.arange(int(goff[-1]))]
+        refs = None
         if self.ref_index is None:  # per-read slices: a private table of the subset's slices, read where they lie
-            ri = np.arange(len(idx), dtype=np.int32)
             lens = self.ref_off[idx + 1] - self.ref_off[idx]
             ref_off = np.zeros(len(idx) + 1, dtype=np.int64)
             np.cumsum(lens, out=ref_off[1:])
             ref = self.ref[np.repeat(self.ref_off[idx] - ref_off[:-1], lens) + np.arange(int(ref_off[-1]))]
-        else:
-            ref, ref_off, ri = self.ref, self.ref_off, self.ref_index[idx]
-        return ctx.stage_spans(params, ref, ref_off, self.text, self.read_begin[idx], self.read_end[idx], gops, goff,
-                               model_slot=None if self.model_slot is None else self.model_slot[idx], ref_index=ri,
-                               guide_start=None if self.guide_start is None else self.guide_start[idx])
+            refs = (ref, ref_off, np.arange(len(idx), dtype=np.int32))
+        return self._stage_rows(ctx, params, idx, gops, goff, refs)
 
     def format_block(self, lo, hi, ops_off, words):
         raise NotImplementedError
@@ -175,9 +175,7 @@ class SamSource(ArraySource):
         goff = gops = None
         try:
             goff, gops = self.sam.guides(self.fields[sl], buffer=buf.view(np.int32))
-            return ctx.stage_spans(params, self.ref, self.ref_off, self.text, self.read_begin[sl], self.read_end[sl], gops, goff,
-                                   model_slot=None if self.model_slot is None else self.model_slot[sl], ref_index=self.ref_index[sl],
-                                   guide_start=self.guide_start[sl])
+            return self._stage_rows(ctx, params, sl, gops, goff)
         finally:
             del goff, gops
             _give(buf)
@@ -185,9 +183,7 @@ class SamSource(ArraySource):
     def stage_records(self, ctx, params, idx):
         idx = np.asarray(idx, dtype=np.int64)
         goff, gops = self.sam.guides(self.fields[idx])
-        return ctx.stage_spans(params, self.ref, self.ref_off, self.text, self.read_begin[idx], self.read_end[idx], gops, goff,
-                               model_slot=None if self.model_slot is None else self.model_slot[idx], ref_index=self.ref_index[idx],
-                               guide_start=self.guide_start[idx])
+        return self._stage_rows(ctx, params, idx, gops, goff)
 
     def format_block(self, lo, hi, ops_off, words):
         nops = np.asarray(ops_off[1:]) - np.asarray(ops_off[:-1])
@@ -280,7 +276,6 @@ def _gc_hold():
             if _gc_jobs[1]:
                 gc.disable()
         _gc_jobs[0] += 1
-    return True
 
 
 def _gc_release():
@@ -288,6 +283,22 @@ def _gc_release():
         _gc_jobs[0] -= 1
         if _gc_jobs[0] == 0 and _gc_jobs[1]:
             gc.enable()
+
+
+@contextlib.contextmanager
+def _gc_held():
+    """The cyclic collector stays out of a pipeline: a full collection walks every object of the process (millions once torch is imported)
+    with the interpreter lock held, tens of ms during which no phase can take its next chunk over.  (The 10-25 ms gaps in round 4's traces
+    turned out to be something else -- munmaps of the chunks' buffers under the same lock, see _take -- and the job times the same with the
+    collector on, NPR_JOB_GC=1; it is kept out because the pipeline makes no cycles worth collecting.)"""
+    hold = os.environ.get("NPR_JOB_GC") is None
+    if hold:
+        _gc_hold()
+    try:
+        yield
+    finally:
+        if hold:
+            _gc_release()
 
 
 def chunk_bounds(lengths, lo, hi, chunk_bases=None, workers=None):
@@ -339,12 +350,11 @@ def _fetch_text(b, want_stats, buffer=None):
     return (text.base if text.base is not None else text), res, off, text, None
 
 
-def _rerun_overflowed(ctx, src, params, lo, res, off, words, stats, want_stats, tm, fetch=None):
+def _rerun_overflowed(ctx, src, params, lo, res, off, words, stats, want_stats, tm, fetch):
     """Reads whose sparse posterior list overflowed its capacity (NPR_ERR_CAPACITY: a diffuse model can put up to
     1 / threshold pairs on a base) run again with a four times larger `max_pairs_per_base` until they fit, as
-    Context.realign does; their results and cigars replace the failed ones.  `fetch`: _fetch (the default) or _fetch_text -- `off` and
-    `words` are then the strings' offsets and bytes."""
-    fetch = fetch or _fetch
+    Context.realign does; their results and cigars replace the failed ones.  `fetch`: _fetch, or _fetch_text -- `off` and `words` are
+    then the strings' offsets and bytes."""
     from . import realign
     per_base = params.max_pairs_per_base if params.max_pairs_per_base > 0 else 6
     limit = int(1.0 / max(params.posterior_threshold, 1e-6)) + 1
@@ -377,8 +387,218 @@ def _rerun_overflowed(ctx, src, params, lo, res, off, words, stats, want_stats, 
     return res, off, words, stats
 
 
+def _overlap_option(n_ctxs, n_chunks):
+    """NPR_OPT_OVERLAP of a job's contexts.  2: the MEA tables of a chunk off the device's shared scratch, so that the next chunk's DP pass
+    starts when it is staged and not when this chunk's MEA stage has given the scratch back (a kernel trace showed 10-15 ms per chunk of
+    exactly that wait: 414 -> 403 ms per 50 000 reads, 393 with GPU_MAX_HW_QUEUES=8).  1 (the default since the end of round 5) also has the
+    DP launches leave half of every SIMD to the other chunks' staging and MEA kernels: with ONE slot per SIMD left free (rounds 4-5) it
+    bought nothing -- 80 registers and one wavefront hold none of the kernels that matter --, with four the job of 50 000 reads takes
+    352-361 ms instead of 367-372.  NPR_JOB_OVERLAP=0 / 1 / 2 picks one for an A/B run.  A rank held to a few host
+    threads (NPR_HOST_THREADS, as bench.py sets it per rank) is bound by its host phases: the DP passes keep the whole chip there (2
+    threads, 50 000 reads: 645 ms against 672).  0 for a job with nothing to run beside: one context or one chunk."""
+    if n_ctxs < 2 or n_chunks < 2:
+        return 0
+    try:
+        few_threads = 0 < int(os.environ.get("NPR_HOST_THREADS") or "0") < 4
+    except ValueError:  # (the library reads the variable with atoi: anything else is "one thread" there)
+        few_threads = True
+    return int(os.environ.get("NPR_JOB_OVERLAP") or ("2" if few_threads else "1"))  # (set but empty: the default)
+
+
+def _halves(e, lo, hi):
+    """The two halves of a chunk the device could not hold (NPR_ERR_NOMEM at staging or at launch: the reference's per-read jobs have no such
+    limit); any other error, and a chunk of one read, is raised again."""
+    if e.code != _lib.ERR_NOMEM or hi - lo < 2:
+        raise e
+    mid = (lo + hi) // 2
+    return (lo, mid), (mid, hi)
+
+
+_END = object()  # closes a queue of the pipeline
+
+
+class _Chunk(object):
+    """Records lo .. hi staged as `batch` on context `j`, on their way through the phases.  Whoever holds a chunk ends it with release(),
+    exactly once: that is what keeps one batch per context (calls on one npr_ctx must be serialised, include/nprealign.h).  last: the chunk
+    gives the context's permit back (not the first half of a chunk split at launch); gate: set when the batch is closed (that half's)."""
+
+    def __init__(self, j, permit, lo, hi, batch, last=True, gate=None):
+        self.j, self.permit, self.lo, self.hi, self.batch, self.last, self.gate = j, permit, lo, hi, batch, last, gate
+
+    def close_batch(self):
+        batch, self.batch = self.batch, None
+        if batch is not None:
+            batch.close()
+
+    def release(self):
+        """The batch, then whoever waits for the batch to be gone, then the context."""
+        try:
+            self.close_batch()
+        finally:
+            if self.gate is not None:
+                self.gate.set()
+            if self.last:
+                self.permit.release()
+
+
+class _Pipeline(object):
+    """The phases of run_pipeline and what they share: stage_all -> run -> finish -> fetch_and_format + close, each on its own thread,
+    chunks handed on through queues, blocks and errors to the caller through `done`."""
+
+    def __init__(self, src, params, ctxs, pending, want_stats, fetch, format_block, n_ops_from_results):
+        self.src, self.params, self.ctxs, self.pending, self.want_stats = src, params, ctxs, pending, want_stats
+        self.fetch_cigars, self.format_block, self.n_ops_from_results = fetch, format_block, n_ops_from_results
+        self.tm = dict(stage_s=0.0, run_s=0.0, finish_s=0.0, fetch_s=0.0, format_s=0.0, kernel_ms=0.0, cells=0, trace=[])
+        self.free = [threading.Semaphore(1) for _ in ctxs]  # the permit of a context: held from a chunk's staging to its release
+        self.flushed = set()
+        self.words_buf = None  # the fetch phase's, from chunk to chunk
+        self.q_run, self.q_fin, self.q_out, self.done = queue.Queue(), queue.Queue(), queue.Queue(), queue.Queue()
+        self.stop = threading.Event()
+
+    def trace(self, label, t0, t1):
+        if TRACE:
+            self.tm["trace"].append((label, t0, t1))
+
+    @contextlib.contextmanager
+    def timed(self, label):
+        """Adds what it spans to the phase's seconds (a step that fails adds nothing)."""
+        t0 = time.perf_counter()
+        yield
+        t1 = time.perf_counter()
+        self.tm[label + "_s"] += t1 - t0
+        self.trace(label, t0, t1)
+
+    def start(self):
+        phases = ((self.stage_all, None, self.q_run),
+                  (lambda: self.phase(self.q_run, self.run, self.q_fin.put), self.q_run, self.q_fin),
+                  (lambda: self.phase(self.q_fin, self.finish, self.q_out.put), self.q_fin, self.q_out),
+                  (lambda: self.phase(self.q_out, self.fetch_and_format, self.close), self.q_out, self.done))
+        threads = [threading.Thread(target=self.guarded, args=p, daemon=True) for p in phases]
+        for t in threads:
+            t.start()
+        return threads
+
+    def guarded(self, body, upstream, downstream):
+        try:
+            body()
+        except BaseException as e:  # handed to the caller's thread
+            self.stop.set()
+            self.done.put(e)
+            # what the phases before this one still hand over ends here: nobody else will look at this queue again
+            while upstream is not None:
+                chunk = upstream.get()
+                if chunk is _END:
+                    break
+                chunk.release()
+        finally:
+            downstream.put(_END)
+
+    def phase(self, upstream, step, hand_over):
+        while True:
+            chunk = upstream.get()
+            if chunk is _END:
+                return
+            if self.stop.is_set():
+                chunk.release()
+                continue
+            try:
+                step(chunk)
+            except BaseException:
+                chunk.release()
+                raise
+            hand_over(chunk)
+
+    def stage_all(self):
+        """Chunk k on context k mod len(ctxs), as soon as that context's permit is free."""
+        k = 0
+        while self.pending and not self.stop.is_set():
+            lo, hi = self.pending.pop()
+            j = k % len(self.ctxs)
+            while not self.free[j].acquire(timeout=0.2):
+                if self.stop.is_set():
+                    return
+            try:
+                with self.timed("stage"):
+                    batch = self.src.stage(self.ctxs[j], self.params, lo, hi)
+            except _lib.NprError as e:
+                self.free[j].release()  # (no chunk yet that could)
+                first, second = _halves(e, lo, hi)
+                if j not in self.flushed:  # once per context: the buffers it cached from earlier, differently sized batches may be what is in
+                    self.flushed.add(j)    # the way (only this context's: nobody else touches it while the stager holds it)
+                    self.ctxs[j].set_option(_lib.OPT_RELEASE_SCRATCH, 2)
+                    self.pending.append((lo, hi))
+                else:
+                    self.pending.extend([second, first])
+                continue
+            self.q_run.put(_Chunk(j, self.free[j], lo, hi, batch))
+            k += 1
+
+    def run(self, chunk):
+        with self.timed("run"):
+            try:
+                self.tm["kernel_ms"] += chunk.batch.run()
+            except _lib.NprError as e:
+                self.run_in_halves(chunk, *_halves(e, chunk.lo, chunk.hi))
+
+    def run_in_halves(self, chunk, first, second):
+        """The device was full at launch (a kernel's private segment, the scratch regrown): the chunk's halves one after the other in the
+        same context, as the stager does for a chunk that does not fit at staging.  ONE AFTER THE OTHER all the way: the finisher and the
+        fetcher work on the first half's batch from their own threads -- the second half is staged when the fetcher has closed the first
+        (its gate), and goes on as `chunk`."""
+        chunk.close_batch()
+        ctx = self.ctxs[chunk.j]
+        half = _Chunk(chunk.j, chunk.permit, first[0], first[1], self.src.stage(ctx, self.params, *first), last=False, gate=threading.Event())
+        try:
+            self.tm["kernel_ms"] += half.batch.run()
+        except BaseException:
+            half.release()
+            raise
+        self.q_fin.put(half)
+        while not half.gate.wait(0.2) and not self.stop.is_set():
+            pass
+        # a later phase failed (it ends what it was handed; a failing finisher SETS the gate on its way out): nothing more is staged here
+        if self.stop.is_set():
+            raise RuntimeError("pipeline stopped while a chunk's first half was in flight")
+        chunk.lo, chunk.batch = second[0], self.src.stage(ctx, self.params, *second)
+        self.tm["kernel_ms"] += chunk.batch.run()
+
+    def finish(self, chunk):
+        with self.timed("finish"):
+            chunk.batch.finish()
+
+    def fetch_and_format(self, chunk):
+        self.format_and_hand_over(chunk, *self.fetch(chunk))  # (no name here keeps the chunk's arrays: they are gone before the close)
+
+    def fetch(self, chunk):
+        """-> (results, offsets, words, stats) of the chunk, the reads that overflowed run again."""
+        with self.timed("fetch"):
+            self.words_buf, res, off, words, stats = self.fetch_cigars(chunk.batch, self.want_stats, self.words_buf)
+            self.tm["cells"] += int(chunk.batch.stats()["cells"])
+            if (res["status"] == _lib.ERR_CAPACITY).any():
+                chunk.close_batch()  # (they run on this context)
+                res, off, words, stats = _rerun_overflowed(self.ctxs[chunk.j], self.src, self.params, chunk.lo, res, off, words, stats,
+                                                           self.want_stats, self.tm, self.fetch_cigars)
+        return res, off, words, stats
+
+    def format_and_hand_over(self, chunk, res, off, words, stats):
+        """The records in two halves: the first is being written while the second is formatted (a job of one chunk -- a rank's share of a
+        sharded set -- has nothing else to overlap its 8 ms of pwrite with)."""
+        with self.timed("format"):
+            lo, hi = chunk.lo, chunk.hi
+            m = (hi - lo) // 2
+            self.done.put((self.format_block(lo, lo + m, off[:m + 1], words[:int(off[m])]), None, None, None))
+            block = self.format_block(lo + m, hi, off[m:] - off[m], words[int(off[m]):])
+        self.done.put((block, res, res["n_ops"].astype(np.int64) if self.n_ops_from_results else off[1:] - off[:-1], stats))
+
+    def close(self, chunk):
+        """The batch goes after its last block is on its way (releasing its host buffers takes 13 ms), the context after the batch."""
+        t0 = time.perf_counter()
+        chunk.release()  # (the runner may stage the chunk's second half on this context now)
+        self.trace("close", t0, time.perf_counter())
+
+
 def run_pipeline(src, params, lo, hi, ctxs, sink, want_stats=False, chunk_bases=None, device_text=False):
-    """Records lo .. hi of `src` as a pipeline of chunks over the contexts `ctxs`, one thread per phase:
+    """Records lo .. hi of `src` as a pipeline of chunks over the contexts `ctxs`, one thread per phase (_Pipeline):
 
         stager (band planning + pack + H2D + device planner)  ->  DP pass  ->  finish (MEA chain + cigar on the device)
         ->  fetch + splice / format of the chunk's records  ->  `sink(block)` on the caller's thread, in record order
@@ -387,264 +607,64 @@ def run_pipeline(src, params, lo, hi, ctxs, sink, want_stats=False, chunk_bases=
 
     Chunk k uses context k mod len(ctxs) from its staging to its close, so len(ctxs) chunks are in flight and the stager
     runs that far ahead of the DP; the DP passes and MEA stages of different chunks take turns on the device's shared
-    scratch (its mutex), everything else overlaps them.  A chunk the device cannot hold (NPR_ERR_NOMEM: the reference's
-    per-read jobs have no such limit) is halved and staged again.  Returns (results[hi - lo], n_ops[hi - lo], stats or None,
-    timings).  device_text: the contexts run with NPR_OPT_FINISH_TEXT (the caller has set it) -- the fetch phase takes the cigars as SAM
-    text made on the device and the source splices them in as they are (format_block_text); n_ops is then what the results say."""
-    from . import realign
+    scratch (its mutex), everything else overlaps them.  A chunk the device cannot hold is halved and staged again (_halves).  Returns
+    (results[hi - lo], n_ops[hi - lo], stats or None, timings).  device_text: the contexts run with NPR_OPT_FINISH_TEXT (the caller has set
+    it) -- the fetch phase takes the cigars as SAM text made on the device and the source splices them in as they are
+    (format_block_text); n_ops is then what the results say."""
     if device_text and want_stats:
         raise ValueError("device_text: the statistics are reduced from the packed cigars, which such a job does not fetch")
     fetch, format_block = (_fetch_text, src.format_block_text) if device_text else (_fetch, src.format_block)
     pending = list(reversed(chunk_bounds(src.lengths(), lo, hi, chunk_bases, len(ctxs))))  # a stack: splits go back on top
-    # NPR_OPT_OVERLAP = 2: the MEA tables of a chunk off the device's shared scratch, so that the next chunk's DP pass starts when it
-    # is staged and not when this chunk's MEA stage has given the scratch back (a kernel trace showed 10-15 ms per chunk of exactly
-    # that wait: 414 -> 403 ms per 50 000 reads, 393 with GPU_MAX_HW_QUEUES=8).  Value 1 (the default since the end of round 5) also has
-    # the DP launches leave half of every SIMD to the other chunks' staging and MEA kernels: with ONE slot per SIMD left free (rounds
-    # 4-5) it bought nothing -- 80 registers and one wavefront hold none of the kernels that matter --, with four the job of 50 000
-    # reads takes 352-361 ms instead of 367-372 (DESIGN.md section 9).  NPR_JOB_OVERLAP=0 / 1 / 2 picks one for an A/B run.
-    # A rank held to a few host threads (NPR_HOST_THREADS, as bench.py sets it per rank) is bound by its host phases: the DP passes
-    # keep the whole chip there (2 threads, 50 000 reads: 645 ms against 672).
-    try:
-        few_threads = 0 < int(os.environ.get("NPR_HOST_THREADS") or "0") < 4
-    except ValueError:  # (the library reads the variable with atoi: anything else is "one thread" there)
-        few_threads = True
-    overlap = int(os.environ.get("NPR_JOB_OVERLAP") or ("2" if few_threads else "1")) if (len(ctxs) > 1 and len(pending) > 1) else 0  # (set but empty: the default)
+    overlap = _overlap_option(len(ctxs), len(pending))
     for c in ctxs:
         c.set_option(_lib.OPT_OVERLAP, overlap)
-    n_planned = len(pending)
-    tm = dict(stage_s=0.0, run_s=0.0, finish_s=0.0, fetch_s=0.0, format_s=0.0, kernel_ms=0.0, cells=0, trace=[])
-    free = [threading.Semaphore(1) for _ in ctxs]
-    q_run, q_fin, q_out, done = queue.Queue(), queue.Queue(), queue.Queue(), queue.Queue()
-    stop = threading.Event()
-    END = object()
-
-    def note(label, t0, t1):
-        tm[label + "_s"] += t1 - t0
-        if TRACE:
-            tm["trace"].append((label, t0, t1))
-
-    def guarded(fn, upstream, downstream):
-        def run():
-            try:
-                fn()
-            except BaseException as e:  # handed to the caller's thread
-                stop.set()
-                done.put(e)
-                # what the phases before this one still hand over is closed here: nobody else will look at this queue again
-                while upstream is not None:
-                    item = upstream.get()
-                    if item is END:
-                        break
-                    item[3].close()
-                    if item[5] is not None:
-                        item[5].set()
-                    if item[4]:
-                        free[item[0]].release()
-            finally:
-                downstream.put(END)
-        return run
-
-    flushed = set()
-
-    def stager():
-        k = 0
-        while pending and not stop.is_set():
-            a, b_ = pending.pop()
-            j = k % len(ctxs)
-            while not free[j].acquire(timeout=0.2):
-                if stop.is_set():
-                    return
-            t0 = time.perf_counter()
-            try:
-                batch = src.stage(ctxs[j], params, a, b_)
-            except realign.NprError as e:
-                free[j].release()
-                if e.code != realign.ERR_NOMEM or b_ - a < 2:
-                    raise
-                if j not in flushed:  # once per context: the buffers it cached from earlier, differently sized batches may be what is in the
-                    flushed.add(j)    # way (only this context's: nobody else touches it while the stager holds it)
-                    ctxs[j].set_option(_lib.OPT_RELEASE_SCRATCH, 2)
-                    pending.append((a, b_))
-                    continue
-                mid = (a + b_) // 2
-                pending.extend([(mid, b_), (a, mid)])
-                continue
-            note("stage", t0, time.perf_counter())
-            q_run.put((j, a, b_, batch, True, None))  # (last: the chunk's end gives the context back; gate: set when the batch is closed)
-            k += 1
-
-    def runner():
-        while True:
-            item = q_run.get()
-            if item is END:
-                return
-            j, a, b_, batch, last, gate = item
-            if stop.is_set():
-                batch.close(), free[j].release()
-                continue
-            t0 = time.perf_counter()
-            try:
-                tm["kernel_ms"] += batch.run()
-            except realign.NprError as e:
-                batch.close()
-                if e.code != realign.ERR_NOMEM or b_ - a < 2:
-                    free[j].release()
-                    raise
-                # the device was full at launch (a kernel's private segment, the scratch regrown): the chunk's halves one after
-                # the other in the same context, as the stager does for a chunk that does not fit at staging.  ONE AFTER THE OTHER all the
-                # way: calls on one context must be serialised (include/nprealign.h), and the finisher and the fetcher work on the first
-                # half's batch from their own threads -- the second half is staged when the fetcher has closed the first (its gate).
-                try:
-                    mid = (a + b_) // 2
-                    for x, y, fin in ((a, mid, False), (mid, b_, True)):
-                        half = src.stage(ctxs[j], params, x, y)
-                        try:
-                            tm["kernel_ms"] += half.run()
-                        except BaseException:
-                            half.close()
-                            raise
-                        gate = None if fin else threading.Event()
-                        q_fin.put((j, x, y, half, fin, gate))
-                        while gate is not None and not gate.wait(0.2):
-                            if stop.is_set():  # a later phase failed (it closes what it was handed): nothing more is staged here
-                                raise RuntimeError("pipeline stopped while a chunk's first half was in flight")
-                        if gate is not None and stop.is_set():  # (a failing finisher SETS the gate on its way out: the wait above ends without having looked)
-                            raise RuntimeError("pipeline stopped while a chunk's first half was in flight")
-                except BaseException:
-                    free[j].release()
-                    raise
-                note("run", t0, time.perf_counter())
-                continue
-            except BaseException:
-                batch.close(), free[j].release()
-                raise
-            note("run", t0, time.perf_counter())
-            q_fin.put(item)
-
-    def finisher():
-        while True:
-            item = q_fin.get()
-            if item is END:
-                return
-            j, a, b_, batch, last, gate = item
-            if stop.is_set():
-                batch.close()
-                if gate is not None:
-                    gate.set()
-                if last:
-                    free[j].release()
-                continue
-            t0 = time.perf_counter()
-            try:
-                batch.finish()
-            except BaseException:
-                batch.close()
-                if gate is not None:
-                    gate.set()
-                if last:
-                    free[j].release()
-                raise
-            note("finish", t0, time.perf_counter())
-            q_out.put(item)
-
-    def fetcher():
-        words_buf = [None]
-        while True:
-            item = q_out.get()
-            if item is END:
-                _give(words_buf[0])
-                return
-            j, a, b_, batch, last, gate = item
-            t0 = time.perf_counter()
-            open_batch = [batch]
-            try:  # the context goes back exactly once, whatever happens in between
-                try:
-                    if stop.is_set():
-                        continue
-                    words_buf[0], res, off, words, stats = fetch(batch, want_stats, words_buf[0])
-                    tm["cells"] += int(batch.stats()["cells"])
-                    if (res["status"] == realign.ERR_CAPACITY).any():
-                        batch.close(), open_batch.clear()  # (the reads that overflowed run again on this context)
-                        res, off, words, stats = _rerun_overflowed(ctxs[j], src, params, a, res, off, words, stats, want_stats, tm, fetch)
-                    t1 = time.perf_counter()
-                    note("fetch", t0, t1)
-                    # the records in two halves: the first is being written while the second is formatted (a job of one chunk -- a rank's
-                    # share of a sharded set -- has nothing else to overlap its 8 ms of pwrite with)
-                    m = (b_ - a) // 2
-                    block = format_block(a, a + m, off[:m + 1], words[:int(off[m])])
-                    done.put((block, None, None, None))
-                    block = format_block(a + m, b_, off[m:] - off[m], words[int(off[m]):])
-                    note("format", t1, time.perf_counter())
-                    done.put((block, res, res["n_ops"].astype(np.int64) if device_text else off[1:] - off[:-1], stats))
-                    del block, res, off, words, stats
-                finally:
-                    # the batch goes after its block is on its way (releasing its host buffers takes 13 ms); the context after the batch
-                    tc = time.perf_counter()
-                    if open_batch:
-                        batch.close()
-                    if TRACE:
-                        tm["trace"].append(("close", tc, time.perf_counter()))
-            finally:
-                if gate is not None:
-                    gate.set()  # (the runner may stage the chunk's second half on this context now)
-                if last:
-                    free[j].release()
-
-    threads = [threading.Thread(target=guarded(fn, up, down), daemon=True)
-               for fn, up, down in ((stager, None, q_run), (runner, q_run, q_fin), (finisher, q_fin, q_out), (fetcher, q_out, done))]
-    # The cyclic collector stays out of the job: a full collection walks every object of the process (millions once torch is
-    # imported) with the interpreter lock held, tens of ms during which no phase can take its next chunk over.  (The 10-25 ms gaps
-    # in round 4's traces turned out to be something else -- munmaps of the chunks' buffers under the same lock, see _take -- and
-    # the job times the same with the collector on, NPR_JOB_GC=1; it is kept out because the pipeline makes no cycles worth collecting.)
-    gc_held = os.environ.get("NPR_JOB_GC") is None and _gc_hold()
-    for t in threads:
-        t.start()
-    parts, sink_s, error = [], 0.0, None
-    finished = False
-    try:
-        while True:
-            item = done.get()
-            if item is END:
-                finished = True
-                break
-            if isinstance(item, BaseException):
-                error = error or item
-                continue
-            if error is None:
-                block, res, nops, stats = item
-                t0 = time.perf_counter()
-                consumed = sink(block) is CONSUMED
-                sink_s += time.perf_counter() - t0
-                if res is not None:
-                    parts.append((res, nops, stats))
-                if TRACE:
-                    tm["trace"].append(("sink", t0, time.perf_counter()))
-                if consumed:
-                    _give(block)  # (a pooled buffer goes back; anything else is released now, not when the next block is waiting to be written)
-                del block, item
-    finally:
-        if not finished:  # the sink failed on this thread (a full disk): the phases stop, what is in flight is closed, nothing keeps a context
-            stop.set()
-            while done.get() is not END:
-                pass
-        for t in threads:
-            t.join()
-        if gc_held:
-            _gc_release()
+    pipe = _Pipeline(src, params, ctxs, pending, want_stats, fetch, format_block, n_ops_from_results=device_text)
+    tm = pipe.tm
+    tm.update(sink_s=0.0, planned_chunks=len(pending), in_flight=len(ctxs))
+    parts, error, finished = [], None, False
+    with _gc_held():
+        threads = pipe.start()
+        try:
+            while not finished:
+                item = pipe.done.get()
+                if item is _END:
+                    finished = True
+                elif isinstance(item, BaseException):
+                    error = error or item
+                elif error is None:
+                    block, res, nops, stats = item
+                    t0 = time.perf_counter()
+                    consumed = sink(block) is CONSUMED
+                    tm["sink_s"] += time.perf_counter() - t0
+                    if res is not None:
+                        parts.append((res, nops, stats))
+                    pipe.trace("sink", t0, time.perf_counter())
+                    if consumed:
+                        _give(block)  # (a pooled buffer goes back; anything else is released now, not when the next block is waiting to be written)
+                    del block, item
+        finally:
+            if not finished:  # the sink failed on this thread (a full disk): the phases stop, what is in flight is closed, nothing keeps a context
+                pipe.stop.set()
+                while pipe.done.get() is not _END:
+                    pass
+            for t in threads:
+                t.join()
+            _give(pipe.words_buf)
     if error is not None:
         raise error
-    n = hi - lo
-    results = np.concatenate([p[0] for p in parts]) if parts else np.zeros(0, dtype=_lib.RESULT_DTYPE)
-    n_ops = np.concatenate([p[1] for p in parts]) if parts else np.zeros(0, dtype=np.int64)
-    stats = np.concatenate([p[2] for p in parts]) if (parts and want_stats) else (np.zeros((0, _lib.STATS_WORDS), dtype=np.int32) if want_stats else None)
-    assert len(results) == n
     if not TRACE:
         del tm["trace"]
-    tm["sink_s"] = sink_s
     tm["chunks"] = len(parts)
-    tm["planned_chunks"] = n_planned
-    tm["in_flight"] = len(ctxs)
-    return results, n_ops, stats, tm
+    return _concatenated(parts, hi - lo, want_stats) + (tm,)
+
+
+def _concatenated(parts, n, want_stats):
+    """(results, n_ops, stats or None) of the n records from the chunks' (results, n_ops, stats)."""
+    if not parts:
+        parts = [(np.zeros(0, dtype=_lib.RESULT_DTYPE), np.zeros(0, dtype=np.int64), np.zeros((0, _lib.STATS_WORDS), dtype=np.int32))]
+    results, n_ops = (np.concatenate([p[k] for p in parts]) for k in (0, 1))
+    assert len(results) == n
+    return results, n_ops, np.concatenate([p[2] for p in parts]) if want_stats else None
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -697,6 +717,53 @@ def write_summary_xml(path, status, score, nops, cells=None):
     ET.ElementTree(root).write(path)
 
 
+class _RankOutput(object):
+    """This rank's part of the one output file.  Rank 0 creates it, writes the header and then its blocks as they come; another rank keeps
+    its blocks (its share of the text: tens of MB) until the ranks before it know their sizes (write_kept)."""
+
+    def __init__(self, path, header, rank):
+        self.path, self.rank, self.kept, self.size, self.fd = path, rank, [], 0, None
+        self.header_len = len(header)
+        if path is not None and rank == 0:
+            self.fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+            os.pwrite(self.fd, header, 0)
+
+    def sink(self, block):
+        if self.path is None:
+            return CONSUMED
+        at, self.size = self.header_len + self.size, self.size + len(block)
+        if self.rank == 0:
+            os.pwrite(self.fd, memoryview(block), at)
+            return CONSUMED
+        self.kept.append(block)  # (the block stays this rank's)
+
+    def write_kept(self, sizes):
+        """sizes: every rank's.  Rank 0 created the file before its first chunk; this is after everyone's last."""
+        self.fd = os.open(self.path, os.O_WRONLY)
+        at = self.header_len + sum(sizes[:self.rank])
+        for b in self.kept:
+            os.pwrite(self.fd, memoryview(b), at)
+            at += len(b)
+
+    def close(self):
+        if self.fd is not None:
+            os.close(self.fd)
+
+
+def _pack_results(results, n_ops, stats):
+    """A rank's per-read results as the bytes of one gather: the count (int64), results[count], n_ops[count] (int64) and, if there are
+    any, stats[count][STATS_WORDS] (int32).  _unpack_results reads the same layout."""
+    parts = [np.array([len(results)], dtype=np.int64), results, n_ops.astype(np.int64)] + ([] if stats is None else [np.ascontiguousarray(stats)])
+    return np.concatenate([p.view(np.uint8).reshape(-1) for p in parts])
+
+
+def _unpack_results(buf, want_stats):
+    k = int(buf[:8].view(np.int64)[0])
+    ends = np.cumsum([8, k * _lib.RESULT_DTYPE.itemsize, 8 * k, 4 * _lib.STATS_WORDS * k])
+    results, n_ops = buf[ends[0]:ends[1]].view(_lib.RESULT_DTYPE), buf[ends[1]:ends[2]].view(np.int64)
+    return results, n_ops, buf[ends[2]:ends[3]].view(np.int32).reshape(k, _lib.STATS_WORDS) if want_stats else None
+
+
 def run_source(src, params, bounds, out_path, ctxs=None, gpu=None, group=None, want_stats=False, chunk_bases=None, workers=None,
                coll_device=None, device_text=False):
     """The job on this rank (collective: every rank of the process group calls it; without torch.distributed initialised it
@@ -704,9 +771,9 @@ def run_source(src, params, bounds, out_path, ctxs=None, gpu=None, group=None, w
     `src`'s numbering.  Output: `out_path` = src.header + every rank's block in rank order.
 
     One rank: blocks are written as they complete, under the DP of the chunks behind them.  Several ranks: a rank's offset
-    is known once the ranks before it know their sizes, so rank 0 writes as it goes and the others keep their blocks (a
-    rank's share of the text: tens of MB) and write them after the all_gather of the sizes.  Only the per-read results are
-    gathered to rank 0 (RCCL over xGMI under backend nccl).  Returns a dict: on rank 0 `results` (structured array in input order),
+    is known once the ranks before it know their sizes, so rank 0 writes as it goes and the others keep their blocks and write
+    them after the all_gather of the sizes (_RankOutput).  Only the per-read results are gathered to rank 0 (RCCL over xGMI under
+    backend nccl).  Returns a dict: on rank 0 `results` (structured array in input order),
     `n_ops`, `stats` (if asked for), `timings`; on the others `timings` only."""
     import torch
     _lib.want_hw_queues()  # (a deployment setting, INTEGRATION.md: asked for here, not when the binding is imported)
@@ -714,73 +781,34 @@ def run_source(src, params, bounds, out_path, ctxs=None, gpu=None, group=None, w
     gpu = default_gpu() if gpu is None else gpu
     dev = torch.device(coll_device) if coll_device is not None else _collective_device(dist, group, gpu)
     ctxs = ctxs or contexts(gpu, workers or WORKERS)
-    lo, hi = int(bounds[rank]), int(bounds[rank + 1])
-    header = src.header
     t_begin = time.perf_counter()
-    fd = None
-    kept = []
-    state = dict(off=len(header))
-    if out_path is not None and rank == 0:
-        fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
-        os.pwrite(fd, header, 0)
-
-    def sink(block):
-        if out_path is None:
-            return CONSUMED
-        if rank == 0:
-            os.pwrite(fd, memoryview(block), state["off"])
-            state["off"] += len(block)
-            return CONSUMED
-        kept.append(block)  # (written after the all_gather of the sizes: the block stays this rank's)
-
+    output = _RankOutput(out_path, src.header, rank)
     try:
-        results, n_ops, stats, tm = run_pipeline(src, params, lo, hi, ctxs, sink, want_stats=want_stats, chunk_bases=chunk_bases,
-                                                 device_text=device_text)
+        results, n_ops, stats, tm = run_pipeline(src, params, int(bounds[rank]), int(bounds[rank + 1]), ctxs, output.sink, want_stats=want_stats,
+                                                 chunk_bases=chunk_bases, device_text=device_text)
         t0 = time.perf_counter()
         if out_path is not None and dist is not None:
-            mine = state["off"] - len(header) if rank == 0 else sum(len(b) for b in kept)
-            t = torch.tensor([mine], dtype=torch.int64, device=dev)
             got = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
-            dist.all_gather(got, t, group=group)
-            sizes = [int(g.item()) for g in got]
+            dist.all_gather(got, torch.tensor([output.size], dtype=torch.int64, device=dev), group=group)
             if rank != 0:
-                fd = os.open(out_path, os.O_WRONLY)  # rank 0 created it before its first chunk; this is after everyone's last
-                at = len(header) + sum(sizes[:rank])
-                for b in kept:
-                    os.pwrite(fd, memoryview(b), at)
-                    at += len(b)
+                output.write_kept([int(g.item()) for g in got])
         tm["write_tail_s"] = time.perf_counter() - t0
     finally:
-        if fd is not None:
-            os.close(fd)
-    out = dict(timings=tm)
+        output.close()
     # the one gather: per-read results for the summary
     t0 = time.perf_counter()
     if dist is not None:
-        payload = [results.view(np.uint8).reshape(-1), n_ops.astype(np.int64).view(np.uint8)]
-        if want_stats:
-            payload.append(np.ascontiguousarray(stats).view(np.uint8).reshape(-1))
-        head = np.array([len(results)], dtype=np.int64).view(np.uint8)
-        got = npd.gather_to_root(np.concatenate([head] + payload), device=dev, group=group)
+        got = npd.gather_to_root(_pack_results(results, n_ops, stats), device=dev, group=group)
         if rank == 0:
-            rs, ns, ss = [], [], []
-            for g in got:
-                k = int(g[:8].view(np.int64)[0])
-                a = 8
-                rs.append(g[a:a + k * _lib.RESULT_DTYPE.itemsize].view(_lib.RESULT_DTYPE))
-                a += k * _lib.RESULT_DTYPE.itemsize
-                ns.append(g[a:a + 8 * k].view(np.int64))
-                a += 8 * k
-                if want_stats:
-                    ss.append(g[a:a + 4 * _lib.STATS_WORDS * k].view(np.int32).reshape(k, _lib.STATS_WORDS))
-            results, n_ops = np.concatenate(rs), np.concatenate(ns)
-            stats = np.concatenate(ss) if want_stats else None
+            rs, ns, ss = zip(*[_unpack_results(g, want_stats) for g in got])
+            results, n_ops, stats = np.concatenate(rs), np.concatenate(ns), np.concatenate(ss) if want_stats else None
         dist.barrier(group=group)  # every rank's block is on disk when rank 0 returns
     tm["gather_s"] = time.perf_counter() - t0
     tm["wall_s"] = time.perf_counter() - t_begin
     _trim_host_pool(_HOST_POOL_BYTES // 4)  # a long-lived host application does not keep a job's gigabyte of chunk buffers
     if TRACE:
         tm["trace"] += [("source", t_begin, t_begin), ("gather", t0, time.perf_counter())]
+    out = dict(timings=tm)
     if rank == 0:
         out.update(results=results, n_ops=n_ops, stats=stats, sam=out_path)
     return out

@@ -283,6 +283,43 @@ def test_config5_at_full_size_through_the_job_with_device_statistics(tmp_path, g
     assert total_cells > 1.5e11
 
 
+def test_reads_that_overflow_their_pair_capacity_run_again_inside_the_job(tmp_path, gpu_ctx, monkeypatch):
+    """NPR_ERR_CAPACITY inside the pipelined job (job._rerun_overflowed from the fetch phase): with one posterior pair per base allowed the
+    reads overflow, run again on their chunk's context with four times the room, and the file is the one a roomy job writes -- from packed
+    cigars and from cigars made text on the device."""
+    from nanopore_amd import job, realign as R
+    from nanopore_amd.hmm import Hmm
+    w, sam, fa, fq = _c3_files(str(tmp_path), 24, True, seed_genome=60000)
+    monkeypatch.setattr(job, "CHUNK_BASES", 50000)               # ~190 kb of reads: four chunks on three contexts
+    band = dict(band_mode=R.BAND_FIXED, fixed_width=100)
+    tight = R.make_params(max_pairs_per_base=1, **band)
+    files = []
+    try:
+        for per_base in (40, 1):
+            for text in (False, True):
+                files.append(str(tmp_path / ("out_%d_%d.sam" % (per_base, text))))
+                r = job.realign_sam_file(sam, files[-1], fa, hmm=HMM0, params=R.make_params(max_pairs_per_base=per_base, **band), device_text=text)
+                assert len(r["results"]) == 24 and (r["results"]["status"] == 0).all(), (per_base, text)
+                assert r["timings"]["chunks"] >= 3
+        want = open(files[0], "rb").read()
+        assert want.count(b"\n") == 24 + len(w["ref_off"]) and all(open(f, "rb").read() == want for f in files[1:])
+        # ... and the tight jobs did take the second run: the same reads as one plain batch report the overflow
+        gpu_ctx.set_hmm(Hmm.loadHmm(HMM0))
+        b = gpu_ctx.stage_csr(tight, w["ref"], w["ref_off"], w["read"], w["read_off"], w["guide_ops"], w["guide_off"],
+                              ref_index=w["ref_index"], guide_start=w["guide_start"])
+        try:
+            b.run(), b.finish()
+            status = b.results()["status"].copy()
+        finally:
+            b.close()
+        assert (status == R.ERR_CAPACITY).any() and set(status.tolist()) <= {0, R.ERR_CAPACITY}
+    finally:
+        for pool in job._ctx_pool.values():   # (the job keeps its contexts; the tests after this one want the memory)
+            for c in pool:
+                if getattr(c, "_h", None):
+                    c.release_scratch()
+
+
 def teardown_module(module):
     """The job keeps its contexts (and their device buffers) for the life of the process; the tests after this module want the memory.
     (Released, not closed: a caller's context -- the session's -- joins the pool when it is passed to realignSamFile.)"""

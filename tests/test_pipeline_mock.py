@@ -21,15 +21,25 @@ class FakeCtx(object):
         self.options[option] = value
 
 
+RERUN_WORD = 1 << 20  # a read that ran again has two words, i and RERUN_WORD + i, and the score -1 - i: not what any first run gives
+
+
 class FakeBatch(object):
-    def __init__(self, src, ctx, a, b):
+    """Records a .. b of a FakeSrc, or -- staged by stage_records -- the records `ids` with `per_base` pairs per base."""
+
+    def __init__(self, src, ctx, a, b, ids=None, per_base=0):
         self.src, self.ctx, self.a, self.b = src, ctx, a, b
+        self.rerun = ids is not None
+        self.ids = np.arange(a, b) if ids is None else np.asarray(ids)
+        self.fits = np.array([per_base >= src.needs.get(int(i), 0) for i in self.ids], dtype=bool)
         ctx.open += 1
         ctx.peak = max(ctx.peak, ctx.open)
         src.staged.append((a, b))
         self.closed = False
 
     def run(self):
+        if self.rerun and self.src.fail_rerun:
+            raise RuntimeError("the second run failed")
         if self.src.fail_run == "nomem" and self.b - self.a > self.src.max_run:
             raise realign.NprError(realign.ERR_NOMEM, "npr_batch_run", "device full")
         if self.src.fail_run == "boom":
@@ -41,13 +51,16 @@ class FakeBatch(object):
             raise RuntimeError("finish failed")
 
     def results(self):
-        r = np.zeros(self.b - self.a, dtype=_lib.RESULT_DTYPE)
-        r["score"] = np.arange(self.a, self.b)
+        r = np.zeros(len(self.ids), dtype=_lib.RESULT_DTYPE)
+        r["score"] = -1 - self.ids if self.rerun else self.ids
+        r["status"] = np.where(self.fits, 0, realign.ERR_CAPACITY)
+        r["n_ops"] = np.where(self.fits, 2 if self.rerun else 1, 0)
         return r
 
     def ops_packed(self):
-        n = self.b - self.a
-        return np.arange(n + 1, dtype=np.int64), np.arange(self.a, self.b).astype(np.uint32)
+        lists = [([i, RERUN_WORD + i] if self.rerun else [i]) if ok else [] for i, ok in zip(self.ids.tolist(), self.fits)]
+        off = np.concatenate([[0], np.cumsum([len(w) for w in lists])]).astype(np.int64)
+        return off, np.array([w for ws in lists for w in ws], dtype=np.uint32)
 
     def ops_packed_into(self, buffer):
         off, words = self.ops_packed()
@@ -67,9 +80,13 @@ class FakeBatch(object):
 
 
 class FakeSrc(object):
-    def __init__(self, n, max_stage=1 << 30, max_run=1 << 30, fail_run=None, fail_finish=False):
+    """needs: {record: the least max_pairs_per_base at which its pair list fits} -- below it the record's status is ERR_CAPACITY;
+    fail_rerun: run() of a batch of stage_records raises; fail_format: the format_block call (counted from 1) that raises."""
+
+    def __init__(self, n, max_stage=1 << 30, max_run=1 << 30, fail_run=None, fail_finish=False, needs=None, fail_rerun=False, fail_format=0):
         self.n, self.max_stage, self.max_run, self.fail_run, self.fail_finish = n, max_stage, max_run, fail_run, fail_finish
-        self.staged, self.closed = [], 0
+        self.needs, self.fail_rerun, self.fail_format = needs or {}, fail_rerun, fail_format
+        self.staged, self.closed, self.formatted = [], 0, []
 
     def lengths(self):
         return np.full(self.n, 1000, dtype=np.int64)
@@ -77,16 +94,24 @@ class FakeSrc(object):
     def stage(self, ctx, params, lo, hi):
         if hi - lo > self.max_stage:
             raise realign.NprError(realign.ERR_NOMEM, "npr_batch_create", "device full")
-        return FakeBatch(self, ctx, lo, hi)
+        return FakeBatch(self, ctx, lo, hi, per_base=params.max_pairs_per_base)
+
+    def stage_records(self, ctx, params, idx):
+        idx = np.asarray(idx)
+        return FakeBatch(self, ctx, int(idx.min()), int(idx.max()) + 1, ids=idx, per_base=params.max_pairs_per_base)
 
     def format_block(self, lo, hi, ops_off, words):
-        assert list(words) == list(range(lo, hi))
+        self.formatted.append((lo, hi, [int(k) for k in ops_off], [int(w) for w in words]))
+        if len(self.formatted) == self.fail_format:
+            raise RuntimeError("format failed")
+        if not self.needs:
+            assert list(words) == list(range(lo, hi))
         return np.arange(lo, hi, dtype=np.int64).tobytes()
 
 
-def _run(src, ctxs, sink=None, chunk_bases=100000):
+def _run(src, ctxs, sink=None, chunk_bases=100000, **params):
     blocks = []
-    params = realign.make_params()
+    params = realign.make_params(**params)
     out = job.run_pipeline(src, params, 0, src.n, ctxs, sink or blocks.append, chunk_bases=chunk_bases)
     return out, blocks
 
@@ -138,6 +163,75 @@ def test_a_failing_phase_reaches_the_caller_and_leaves_nothing_behind(kw, exc):
     src = FakeSrc(1000, **kw)
     with pytest.raises(exc):
         _run(src, ctxs)
+    _all_back(src, ctxs, before)
+
+
+# Records whose pair lists overflow at max_pairs_per_base = 1: 17 and 401 fit at 4 (one more run), 3 and 999 at 16 (two more), in the first
+# and the last chunk and one in the middle -- 400 / 401 lie on either side of a chunk's two blocks or not, whatever the cuts are
+NEEDS = {3: 16, 17: 4, 400: 4, 401: 4, 999: 16}
+
+
+def test_reads_that_overflow_run_again_inside_the_pipeline():
+    """ERR_CAPACITY from the first run: the fetch phase closes the chunk's batch, runs those reads again on the same context with four
+    times the capacity until they fit (_rerun_overflowed), and splices their results, operation counts and words in where the failed
+    ones were -- the formatter and the caller see one chunk in record order."""
+    before = threading.active_count()
+    ctxs = [FakeCtx() for _ in range(3)]
+    src = FakeSrc(1000, needs=NEEDS)
+    (res, nops, stats, tm), blocks = _run(src, ctxs, max_pairs_per_base=1)
+    again = np.zeros(1000, dtype=bool)
+    again[list(NEEDS)] = True
+    ids = np.arange(1000)
+    assert (res["status"] == 0).all()
+    assert np.array_equal(res["score"], np.where(again, -1 - ids, ids))
+    assert np.array_equal(nops, np.where(again, 2, 1)) and np.array_equal(res["n_ops"], nops)
+    assert list(np.frombuffer(b"".join(blocks), dtype=np.int64)) == list(range(1000))
+    # what the formatter was handed: the blocks in record order, each with its own offsets from 0 and the words of exactly its records
+    assert [lo for lo, _, _, _ in src.formatted] == [0] + [hi for _, hi, _, _ in src.formatted[:-1]] and src.formatted[-1][1] == 1000
+    for lo, hi, off, words in src.formatted:
+        want = [[i, RERUN_WORD + i] if again[i] else [i] for i in range(lo, hi)]
+        assert off == [0] + list(np.cumsum([len(w) for w in want])) and words == [w for ws in want for w in ws], (lo, hi)
+    # first runs + one batch per round (capacity 4, 16) of every chunk that had an overflow; all closed once, never two open on one context
+    cuts = job.chunk_bounds(src.lengths(), 0, 1000, 100000, len(ctxs))
+    rounds = [max([0] + [{4: 1, 16: 2}[k] for i, k in NEEDS.items() if a <= i < b]) for a, b in cuts]
+    assert len(cuts) >= 3 and sum(r > 0 for r in rounds) >= 3 and len(src.formatted) == 2 * len(cuts)
+    assert len(src.staged) == len(cuts) + sum(rounds)
+    assert all(c.peak == 1 for c in ctxs)
+    _all_back(src, ctxs, before)
+
+
+def test_a_failing_second_run_reaches_the_caller_and_leaves_nothing_behind():
+    before = threading.active_count()
+    ctxs = [FakeCtx() for _ in range(3)]
+    src = FakeSrc(1000, needs=NEEDS, fail_rerun=True)
+    with pytest.raises(RuntimeError, match="second run"):
+        _run(src, ctxs, max_pairs_per_base=1)
+    assert all(c.peak == 1 for c in ctxs)
+    _all_back(src, ctxs, before)
+
+
+def test_a_failing_format_reaches_the_caller_and_the_contexts_can_be_used_again():
+    """The fetch / format phase is the last one: nobody drains behind it, so it gives back what it holds itself."""
+    before = threading.active_count()
+    ctxs = [FakeCtx() for _ in range(3)]
+    src = FakeSrc(1000, fail_format=2)
+    with pytest.raises(RuntimeError, match="format failed"):
+        _run(src, ctxs)
+    _all_back(src, ctxs, before)
+    (res, _, _, _), blocks = _run(FakeSrc(300), ctxs)
+    assert len(res) == 300 and all(c.peak == 1 for c in ctxs)
+
+
+@pytest.mark.timeout(10)
+def test_a_failing_finish_while_a_first_half_is_in_flight_does_not_hang():
+    """The launch refuses every chunk (halved, the halves one after the other on the chunk's context) and the finish of the first half
+    fails while the runner waits for that half's gate: the runner must wake up, nothing more is staged for good, and everything goes back."""
+    before = threading.active_count()
+    ctxs = [FakeCtx() for _ in range(3)]
+    src = FakeSrc(1000, fail_run="nomem", max_run=60, fail_finish=True)
+    with pytest.raises(RuntimeError):
+        _run(src, ctxs)
+    assert all(c.peak == 1 for c in ctxs)
     _all_back(src, ctxs, before)
 
 
