@@ -406,6 +406,49 @@ int64_t npr_seed_sam_text(int64_t n_reads, const uint8_t *text, const int64_t *n
                           const char *rnames, const int64_t *rname_off, int64_t n_refs, const int64_t *hit_off, const int32_t *hits,
                           int64_t *rec_off, char *out, int64_t cap);
 
+/* ---- chaining of seed rows on the device: the guide alignments chainSamFile makes of a base mapper's local hits ----
+ * The co-linear chains of the rows npr_seed_matches returned (csrc/npr_seedchain.hip), one per (read, reference) that has rows, all reads
+ * of a call at once; npr_chain_hits + npr_chain_merge below state the same rule for one (read, reference) on the host.
+ * ROWS.  A row is (reference index r, a, b | strand << 31, L): the block of reference positions [a, a + L) against read positions
+ * [b, b + L) in that strand's orientation, of score L.  Rows need not be maximal matches; any rows are legal that satisfy, for read i:
+ * sorted by (strand, r, a, b) (equal neighbours allowed), 0 <= r < n_refs, L >= 1, a >= 0, a + L <= ref_len[r], b + L <= read_len[i];
+ * lengths below 2^31; hit_off starts at 0 and never decreases; max_gap >= 0.  Anything else: NPR_ERR_INVALID, decided on the host in one
+ * pass over the rows before any output is written and before any kernel indexes with them.
+ * RULE (the reference's chainFn, nanopore/analyses/utils.py:388-426).  Within one (read, reference) order the rows by (a, strand, b),
+ * row order among equals -- the stable sort by first reference position of the SAM order.  Row j may precede row i when j sorts before
+ * i, both lie on one strand, a_i > a_j + L_j - 1, b_i > b_j + L_j - 1 and (a_i - (a_j + L_j - 1)) + (b_i - (b_j + L_j - 1)) <= max_gap.
+ * best_i = L_i + the largest best_j of such j (none: L_i); among equally good j the one that sorts first.  The chain ends at the row of
+ * largest best, among equals -- across both strands -- the one that sorts last, and is followed back from there.  The reference compares
+ * SIGNED read coordinates (utils.py _blockCoordinates): on the reverse strand those are b minus the constant read length - 1, so b in
+ * the strand's orientation compares identically and is what is used here.
+ * GUIDE.  What npr_chain_merge gives for the chain's blocks over ref_len[r] x read_len[i]: before every block, between blocks and after
+ * the last one a D for the reference bases and then an I for the read bases not covered, lengths of 0 left out, neighbours of one kind
+ * merged (two blocks adjacent on one diagonal are one M).  It spans exactly ref_len[r] x read_len[i]; a chain of m rows has at most
+ * 3 m + 2 op pairs.
+ * OUTPUT.  The chains of read i are chains[4 * chain_off[i] .. 4 * chain_off[i + 1]) in ascending reference index, each (r, strand,
+ * score, rows in the chain); chain c's guide is the (op, length) pairs ops[2 * ops_off[c] .. 2 * ops_off[c + 1]) with NPR_OP_M / I / D:
+ * the layout npr_batch_create* takes as guide_off / guide_ops.  Returns the number of chains (>= 0).
+ * CAPACITY, as npr_seed_matches: chain_off[n_reads + 1] is filled whenever the rows are valid; chains (cap_chains rows of four), ops_off
+ * [cap_chains + 1] and ops (cap_ops pairs) are written only when everything fits.  More chains than cap_chains (or chains / ops_off
+ * NULL): NPR_ERR_CAPACITY, chain_off[n_reads] says how many, nothing else is written and nothing runs on the device.  The chains fit
+ * but not the op pairs: NPR_ERR_CAPACITY and ops_off[0] alone receives the number of pairs needed (it is 0 in every successful result,
+ * so the two cannot be confused).  n_reads == 0 and reads without rows are legal; without any chain the result is 0 and ops_off[0] = 0
+ * when ops_off is given. */
+int64_t npr_seed_chains(npr_ctx *ctx, int64_t max_gap, int64_t n_reads, const int64_t *read_len, int64_t n_refs, const int64_t *ref_len,
+                        const int64_t *hit_off, const int32_t *hits, int64_t *chain_off, int32_t *chains, int64_t cap_chains,
+                        int64_t *ops_off, int32_t *ops, int64_t cap_ops);
+/* The chains as the records chainSamFile writes, one per chain: QNAME \t FLAG \t RNAME \t 1 \t 255 \t CIGAR \t * \t 0 \t 0 \t SEQ \t * \n
+ * with QNAME, RNAME as npr_seed_sam_text takes them, FLAG 0 or 16 by the chain's strand, CIGAR the text of its op pairs (operations 0..8
+ * = MIDNSHP=X; "*" without any), SEQ the whole read text[begin[i] .. end[i]) as it stands, reversed and complemented (A <-> T, C <-> G
+ * in either case, everything else kept) for strand 1.  Records come in the file order of chainSamFile: by (reference index, QNAME as
+ * bytes), NOT in chain order: record k lands at out[rec_off[k] .. rec_off[k + 1]), rec_off[chain_off[n_reads] + 1]; out == NULL: only
+ * the offsets.  Returns the total length, NPR_ERR_CAPACITY when cap is smaller, NPR_ERR_INVALID for offsets that decrease, a chain
+ * outside the reference list, a strand other than 0 / 1, an operation outside 0..8, a negative length -- and for two reads of one name:
+ * their order would be undefined, and the pipeline makes names unique before it maps.  Threaded host code, no GPU needed. */
+int64_t npr_seed_chain_sam_text(int64_t n_reads, const uint8_t *text, const int64_t *name_span, const int64_t *begin, const int64_t *end,
+                                const char *rnames, const int64_t *rname_off, int64_t n_refs, const int64_t *chain_off, const int32_t *chains,
+                                const int64_t *ops_off, const int32_t *ops, int64_t *rec_off, char *out, int64_t cap);
+
 /* Expected base counts per reference position from the posterior pairs of a finished batch, on the device (SURVEY.md 8f
  * next #4): what marginAlignSnpCaller.py:150-155 collates from the --outputAllPosteriorProbs files, one text line at a time:
  * every pair (refPos, readPos, p) of a selected read adds p to expect[(first row of its reference + refPos) * 4 + base] for

@@ -124,7 +124,7 @@ EXPORTS = [
     "npr_sam_index", "npr_sam_parse", "npr_sam_guides", "npr_sam_splice", "npr_fasta_index", "npr_fasta_pack", "npr_fastq_index", "npr_names_mark",
     "npr_batch_create_spans", "npr_chain_merge", "npr_ctx_option", "npr_batch_segment_arith",
     "npr_cigar_text_packed", "npr_batch_cigar_text", "npr_sam_splice_text",
-    "npr_seed_index_create", "npr_seed_index_destroy", "npr_seed_matches", "npr_seed_sam_text",
+    "npr_seed_index_create", "npr_seed_index_destroy", "npr_seed_matches", "npr_seed_sam_text", "npr_seed_chains", "npr_seed_chain_sam_text",
 ]
 
 _lib = None
@@ -269,6 +269,10 @@ def load():
     L.npr_seed_matches.argtypes = [vp, i64, i32, i64, vp, vp, vp, vp, vp, i64]
     L.npr_seed_sam_text.restype = i64
     L.npr_seed_sam_text.argtypes = [i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64]
+    L.npr_seed_chains.restype = i64
+    L.npr_seed_chains.argtypes = [vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64]
+    L.npr_seed_chain_sam_text.restype = i64
+    L.npr_seed_chain_sam_text.argtypes = [i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64]
     L.npr_fasta_index.restype = i64
     L.npr_fasta_index.argtypes = [vp, i64, vp, vp, i64]
     L.npr_fasta_pack.restype = i32

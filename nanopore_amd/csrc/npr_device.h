@@ -353,6 +353,29 @@ struct SeedMatchArgs {  // k_seed_match<false> counts every read's matches into 
     int32_t *hits;           // [hit_off[n_reads]][4] = reference index, a, b | strand << 31, L (emitting)
 };
 int launch_seed_match(const SeedMatchArgs &a, bool emit, void *stream);
+// chaining of seed rows on the device (npr_seedchain.hip).  A CHAIN SPAN is one (read, reference) that has rows: its forward-strand run
+// and its reverse-strand run of rows (either may be empty), each contiguous in the rows and in (a, b) order.
+struct SeedChainSpan {
+    int64_t first[2];        // first row of the run on strand 0 / 1
+    int32_t n[2];            // rows of the run (0: the strand has none)
+    int32_t read, ref;
+};
+struct SeedChainArgs {
+    const int32_t *hits;     // [rows][4] = reference index, a, b | strand << 31, L: validated on the host
+    const SeedChainSpan *span;
+    int64_t n_chains;
+    uint32_t max_gap;        // (clamped: a gap sum is below 2^32)
+    const int32_t *ref_len, *read_len;
+    int32_t *node;           // [rows][4] scratch: a row's last reference position, last read position, best chain score ending in it, and the
+                             // largest last reference position of its run's rows up to it
+    int32_t *back;           // [rows] scratch: the predecessor as an index into the run, -1 none
+    int32_t *run_end;        // [2 * n_chains][2] scratch: the row (index into the run) the best chain of a run ends in, and its score
+    int32_t *chains;         // [n_chains][4] = reference index, strand, score, rows in the chain
+    int64_t *n_ops;          // [n_chains + 1]: op pairs per chain, then (k_chain_scan) their exclusive prefix
+    int32_t *ops;            // [n_ops[n_chains]][2]
+};
+int launch_seed_chain_dp(const SeedChainArgs &a, void *stream);     // k_chain_dp, k_chain_trace<false>, k_chain_scan
+int launch_seed_chain_write(const SeedChainArgs &a, void *stream);  // k_chain_trace<true>
 // SAM CIGAR text of packed cigars on the device (npr_cigtext.hip): list i = words[word_off[i] .. word_off[i] + n_ops[i])
 struct CigTextArgs {
     int64_t n;

@@ -588,6 +588,33 @@ class Context(object):
         """seed_index on arrays: sequence i = ref[ref_off[i]:ref_off[i + 1]] (FastaTable.seq / .off fit directly)."""
         return SeedIndex(self, ref, ref_off, k)
 
+    def seed_chains(self, read_len, ref_len, hit_off, hits, max_gap=200):
+        """The co-linear chains of the rows SeedIndex.matches returned, one per (read, reference) that has rows, as guide alignments made
+        on the device (include/nprealign.h: npr_seed_chains; csrc/npr_seedchain.hip): (chain_off int64 [n + 1], chains int32 [m, 4],
+        ops_off int64 [m + 1], ops int32 [p, 2]).  The chains of read i are chains[chain_off[i]:chain_off[i + 1]] in ascending reference
+        index, each (reference index, strand, score, rows in the chain); chain c's guide over ref_len x read_len is
+        ops[ops_off[c]:ops_off[c + 1]] -- what stage_csr and stage_spans take as guide_off and guide_ops."""
+        read_len, ref_len = np.ascontiguousarray(read_len, dtype=np.int64), np.ascontiguousarray(ref_len, dtype=np.int64)
+        hit_off = np.ascontiguousarray(hit_off, dtype=np.int64)
+        hits = np.ascontiguousarray(hits, dtype=np.int32).reshape(-1, 4)
+        n = len(read_len)
+        if len(hit_off) != n + 1 or int(hit_off[-1]) != len(hits):
+            raise NprError(_lib.ERR_INVALID, "npr_seed_chains", "one length per read, hit_off[n + 1], one row per match")
+        chain_off = np.zeros(n + 1, dtype=np.int64)
+        head = [self._h, int(max_gap), n, ptr(read_len), len(ref_len), ptr(ref_len), ptr(hit_off), ptr(hits), ptr(chain_off)]
+        m = self._L.npr_seed_chains(*head, None, 0, None, None, 0)  # (nothing runs on the device: the offsets say how many chains)
+        if m == ERR_CAPACITY:
+            m = int(chain_off[-1])
+            chains, ops_off = np.empty((m, 4), dtype=np.int32), np.zeros(m + 1, dtype=np.int64)
+            ops = np.empty((3 * len(hits) + 2 * m, 2), dtype=np.int32)  # a chain of k rows has at most 3 k + 2 pairs
+            rc = self._L.npr_seed_chains(*head, ptr(chains), m, ptr(ops_off), ptr(ops), len(ops))
+            if rc < 0:
+                raise NprError(int(rc), "npr_seed_chains", self.last_error())
+            return chain_off, chains, ops_off, ops[:int(ops_off[-1])].copy()
+        if m < 0:
+            raise NprError(int(m), "npr_seed_chains", self.last_error())
+        return chain_off, np.zeros((0, 4), dtype=np.int32), np.zeros(1, dtype=np.int64), np.zeros((0, 2), dtype=np.int32)
+
     def _realign_once(self, params, refs, reads, guides, model_slot, want_pairs, ref_index, guide_start=None):
         b = self.stage(params, refs, reads, guides, model_slot, ref_index, guide_start)
         try:
@@ -851,6 +878,34 @@ def seed_sam_text(text, name_span, begin, end, ref_names, hit_off, hits):
     rc = L.npr_seed_sam_text(*args, ptr(buf), int(total))
     if rc < 0:
         raise NprError(int(rc), "npr_seed_sam_text")
+    return buf[:int(total)], rec_off
+
+
+def seed_chain_sam_text(text, name_span, begin, end, ref_names, chain_off, chains, ops_off, ops):
+    """The chains Context.seed_chains returned as the records chainSamFile writes, one per chain, sorted by (reference index, read name)
+    (include/nprealign.h: npr_seed_chain_sam_text; host code, no device needed): (uint8 array, offsets[m + 1]).  Reads and names as
+    seed_sam_text takes them; read names must be unique."""
+    L = _lib.load()
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    name_span = np.ascontiguousarray(name_span, dtype=np.int64).reshape(-1, 2)
+    begin, end = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
+    chain_off, ops_off = np.ascontiguousarray(chain_off, dtype=np.int64), np.ascontiguousarray(ops_off, dtype=np.int64)
+    chains = np.ascontiguousarray(chains, dtype=np.int32).reshape(-1, 4)
+    ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 2)
+    n = len(begin)
+    if not (len(end) == len(name_span) == n and len(chain_off) == n + 1 and int(chain_off[-1]) == len(chains) and len(ops_off) == len(chains) + 1
+            and int(ops_off[-1]) == len(ops)):
+        raise NprError(_lib.ERR_INVALID, "npr_seed_chain_sam_text", "one name, begin and end per read, chain_off[n + 1], one row per chain, ops_off[m + 1], one pair per op")
+    rn, roff = _ragged(ref_names)
+    rec_off = np.zeros(len(chains) + 1, dtype=np.int64)
+    args = [n, ptr(text), ptr(name_span), ptr(begin), ptr(end), ptr(rn), ptr(roff), len(ref_names), ptr(chain_off), ptr(chains), ptr(ops_off), ptr(ops), ptr(rec_off)]
+    total = L.npr_seed_chain_sam_text(*args, None, 0)
+    if total < 0:
+        raise NprError(int(total), "npr_seed_chain_sam_text")
+    buf = np.empty(max(int(total), 1), dtype=np.uint8)
+    rc = L.npr_seed_chain_sam_text(*args, ptr(buf), int(total))
+    if rc < 0:
+        raise NprError(int(rc), "npr_seed_chain_sam_text")
     return buf[:int(total)], rec_off
 
 
