@@ -86,8 +86,9 @@ typedef struct {
     int64_t split_threshold;     /* --splitMatrixBiggerThanThis: 3000 realign (utils.py:587), 100 analyses
                                     (alignmentUncertainty.py:41, marginAlignSnpCaller.py:136) */
     int32_t fixed_width;         /* W for NPR_BAND_FIXED, >= 2 (narrower: NPR_ERR_INVALID for the read) */
-    double gap_gamma;            /* --gapGamma  (abstractMapper.py:25 default 0.5) */
-    double match_gamma;          /* --matchGamma (abstractMapper.py:25 default 0.0) */
+    double gap_gamma;            /* --gapGamma  (abstractMapper.py:25 default 0.5); in [0, 1], else npr_batch_create returns NPR_ERR_INVALID */
+    double match_gamma;          /* --matchGamma (abstractMapper.py:25 default 0.0); in [-1, 1], else NPR_ERR_INVALID (the device MEA stage keeps
+                                    its weights, quantum - gapGamma * gap mass in units of 1e-7, in 32 bits; npr_mea_cigar takes any value) */
     double posterior_threshold;  /* 0.01 */
     int32_t mode;                /* NPR_MODE_* */
     int32_t max_pairs_per_base;  /* capacity of the sparse posterior list per read base (0 -> 6) */
@@ -262,6 +263,11 @@ int32_t npr_batch_pairs(const npr_batch *b, int64_t *pair_off, int32_t *x, int32
  * written them with status `task_status` (NPR_OK, or e.g. NPR_ERR_CAPACITY for a list that overflowed).  Between npr_batch_run and npr_batch_finish.
  * Nothing in the product calls it. */
 int32_t npr_batch_debug_set_pairs(npr_batch *b, int64_t read, const int32_t *x, const int32_t *y, const float *p, int64_t n, int32_t task_status);
+/* TEST HOOK (tests/test_gpu_mea_cases.py).  Which stage the last npr_batch_finish of the batch took: 0 the device stage (the MEA chain of
+ * csrc/npr_mea.hip; in NPR_MODE_RESCORE_ORIGINAL the device's fixed-point sum), 1 the host stage (NPR_OPT_HOST_MEA, tables that found no room,
+ * or a read the device chain gave up on -- more than 64 pairs on a reference position, a pair 8192 read positions below the chain's top: the
+ * WHOLE batch is finished on the host then, with the same results).  NPR_ERR_STATE before npr_batch_finish.  Read-only. */
+int32_t npr_batch_debug_finish_stage(const npr_batch *b);
 
 /* ---- post-alignment statistics on the device ----
  * The per-read integer reductions the reference's analyses make by walking every aligned pair in Python:

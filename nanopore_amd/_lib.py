@@ -39,6 +39,7 @@ OP_M, OP_I, OP_D = 0, 1, 2
 BAND_ANCHOR, BAND_FIXED = 0, 1
 MODE_REALIGN, MODE_RESCORE_ORIGINAL, MODE_ALL_POSTERIORS, MODE_EXPECTATIONS = 0, 1, 2, 3
 OPT_OVERLAP = 1
+FINISH_DEVICE, FINISH_HOST = 0, 1  # npr_batch_debug_finish_stage
 OPT_RELEASE_SCRATCH = 2
 # test / bring-up switches (include/nprealign.h: NPR_OPT_*; none changes a result)
 OPTIONS = dict(kernel=3, arith=4, pair=5, no_tile=6, no_wide=7, tile_rs=8, tile_waves=9, host_mea=13, mea_ring_only=14,
@@ -114,7 +115,7 @@ class NprError(RuntimeError):
 EXPORTS = [
     "npr_abi_version", "npr_strerror", "npr_create", "npr_destroy", "npr_last_error", "npr_set_hmm",
     "npr_batch_create", "npr_batch_create_at", "npr_batch_run", "npr_batch_finish", "npr_batch_destroy", "npr_batch_get_stats", "npr_batch_class_stats",
-    "npr_batch_results", "npr_batch_ops", "npr_batch_ops_packed", "npr_batch_pairs", "npr_batch_debug_set_pairs", "npr_batch_dense", "npr_batch_rs_forward", "npr_batch_expectations",
+    "npr_batch_results", "npr_batch_ops", "npr_batch_ops_packed", "npr_batch_pairs", "npr_batch_debug_set_pairs", "npr_batch_debug_finish_stage", "npr_batch_dense", "npr_batch_rs_forward", "npr_batch_expectations",
     "npr_batch_align_stats", "npr_align_stats", "npr_batch_plan_check", "npr_batch_base_expectations",
     "npr_kmer_counts", "npr_kmer_counts_groups", "npr_align_indel_kmers", "npr_batch_indel_kmers",
     "npr_pileup_create", "npr_pileup_destroy", "npr_pileup_add_batch", "npr_pileup_add", "npr_pileup_counts", "npr_pileup_depth",
@@ -183,6 +184,8 @@ def load():
     L.npr_batch_pairs.argtypes = [vp, vp, vp, vp, vp, i64]
     L.npr_batch_debug_set_pairs.restype = i32
     L.npr_batch_debug_set_pairs.argtypes = [vp, i64, vp, vp, vp, i64, i32]
+    L.npr_batch_debug_finish_stage.restype = i32
+    L.npr_batch_debug_finish_stage.argtypes = [vp]
     L.npr_batch_expectations.restype = i32
     L.npr_batch_expectations.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_float)]
     L.npr_batch_base_expectations.restype = i32

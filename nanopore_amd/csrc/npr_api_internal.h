@@ -356,6 +356,7 @@ struct npr_batch {
     std::vector<Launch> launches;
     DevBuf<float> d_ring;
     bool ran = false, finished = false;
+    int32_t finish_stage = 0;  // which stage the last npr_batch_finish took: 0 the device stage, 1 the host stage (npr_batch_debug_finish_stage)
     // results
     std::vector<npr_read_result> results;
     std::vector<int64_t> ops_off;

@@ -651,6 +651,7 @@ int32_t batch_finish_impl(npr_batch *b) {
         if ((rc = gated_device_mea(b)) < 0) return rc;
         if (rc == NPR_OK) {
             tm.lap("device MEA");
+            b->finish_stage = 0;
             b->finished = true;
             return NPR_OK;
         }
@@ -664,6 +665,7 @@ int32_t batch_finish_impl(npr_batch *b) {
     } else {
         host_mea(b, tm);
     }
+    b->finish_stage = have_dev_score ? 0 : 1;
     b->finished = true;
     return NPR_OK;
 }
@@ -831,6 +833,12 @@ int32_t npr_batch_debug_set_pairs(npr_batch *b, int64_t read, const int32_t *x, 
     HIP_TRY(ctx, hipMemcpy(b->d_outs.p + k, &o, sizeof(TaskOut), hipMemcpyHostToDevice));
     b->finished = false;
     return NPR_OK;
+}
+
+int32_t npr_batch_debug_finish_stage(const npr_batch *b) {
+    if (!b) return NPR_ERR_INVALID;
+    if (!b->finished) return NPR_ERR_STATE;
+    return b->finish_stage;
 }
 
 }  // extern "C"

@@ -16,7 +16,7 @@
 //   k_mea_chain_lanes  ONE LANE per read, 64 reads per wavefront (round 4; before: one wavefront per read, every
 //                  instruction doing one lane's worth of work -- 21 ms for 4.5e8 pairs, half of the finish): each lane walks
 //                  its read's kept pairs; the heaviest chain ending at or below every read position is a monotone prefix
-//                  maximum held for a window of 128 read positions in the lane's column of an LDS table; ties go to the
+//                  maximum held for a window of 64 read positions (LWIN) in the lane's column of an LDS table; ties go to the
 //                  pair that sorts last
 //   k_mea_chain    one wavefront per read with the prefix maximum in an LDS ring of any length, over the sorted pairs
 //                  themselves (prep_chunk weighs them): the reads whose pairs reach back further than the window (none

@@ -790,6 +790,10 @@ int32_t batch_create_at_impl(npr_ctx *ctx, const npr_params *params, const Reads
     if (!ctx || !params || !out || n_reads < 0 || in.n_refs < 0) return NPR_ERR_INVALID;
     if (!in.ref_index && in.n_refs != n_reads) return fail(ctx, NPR_ERR_INVALID, "npr_batch_create: without ref_index, n_refs must equal n_reads");
     if (n_reads > 0 && (!in.ref_off || !in.read_begin || !in.read_end || !in.guide_off)) return fail(ctx, NPR_ERR_INVALID, "npr_batch_create: null offsets");
+    // the MEA stage's weights are 32-bit on the device (posterior quantum - gapGamma * gap mass, npr_mea.hip k_mea_weigh): gammas are weights between 0 and 1
+    // (matchGamma down to -1: "keep every pair"); gapGamma = 250 would wrap them.  !(..): NaN is refused as well
+    if (!(params->gap_gamma >= 0.0 && params->gap_gamma <= 1.0) || !(params->match_gamma >= -1.0 && params->match_gamma <= 1.0))
+        return fail(ctx, NPR_ERR_INVALID, "npr_batch_create: gap_gamma must lie in [0, 1] and match_gamma in [-1, 1]");
     *out = nullptr;
     std::unique_ptr<npr_batch> b(new (std::nothrow) npr_batch);
     if (!b) return NPR_ERR_NOMEM;

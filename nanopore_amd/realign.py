@@ -174,6 +174,13 @@ class Batch(object):
         if rc != 0:
             raise NprError(rc, "npr_batch_debug_set_pairs")
 
+    def finish_stage(self):
+        """TEST HOOK (include/nprealign.h npr_batch_debug_finish_stage): the stage the last finish() took, FINISH_DEVICE (0) or FINISH_HOST (1)."""
+        rc = self._L.npr_batch_debug_finish_stage(self._h)
+        if rc < 0:
+            raise NprError(rc, "npr_batch_debug_finish_stage")
+        return int(rc)
+
     def pairs(self):
         """-> (pair_off[n+1], x, y, p) sparse posterior match probabilities sorted by (x, y)."""
         off = np.zeros(self.n_reads + 1, dtype=np.int64)
@@ -624,6 +631,7 @@ class Context(object):
             off, ops = b.ops()
             out = []
             aoff, arith = b.segment_arith()
+            stage = b.finish_stage()
             if want_pairs:
                 poff, x, y, p = b.pairs()
             for i in range(b.n_reads):
@@ -631,7 +639,7 @@ class Context(object):
                          loglik_bwd=float(res["loglik_bwd"][i]), cells=int(res["cells"][i]),
                          n_segments=int(res["n_segments"][i]), n_pairs=int(res["n_pairs"][i]),
                          ops=[(int(a), int(c)) for a, c in ops[off[i]:off[i + 1]]],
-                         seg_arith=[int(v) for v in arith[aoff[i]:aoff[i + 1]]])
+                         seg_arith=[int(v) for v in arith[aoff[i]:aoff[i + 1]]], finish_stage=stage)
                 if want_pairs:
                     d["x"] = x[poff[i]:poff[i + 1]].copy()
                     d["y"] = y[poff[i]:poff[i + 1]].copy()

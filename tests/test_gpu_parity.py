@@ -340,6 +340,8 @@ def test_device_mea_matches_host_stage(gpu_ctx, monkeypatch):
             gpu_ctx.set_option(_lib.OPTIONS[k], 0)
         for u, t, v in zip(got["device"], got["device_ring"], got["host"]):
             assert u["status"] == t["status"] == v["status"] == 0
+            # (which stage finished the batch: a device stage that handed every batch to the host stage would compare the host stage with itself)
+            assert u["finish_stage"] == t["finish_stage"] == _lib.FINISH_DEVICE and v["finish_stage"] == _lib.FINISH_HOST, kw
             assert u["ops"] == v["ops"] and u["score"] == v["score"] and u["n_pairs"] == v["n_pairs"], kw
             assert t["ops"] == v["ops"] and t["score"] == v["score"], kw
             assert len(u["p"]) == u["n_pairs"]
@@ -419,6 +421,7 @@ def test_device_mea_long_spans(gpu_ctx, monkeypatch):
     gpu_ctx.set_option(_lib.OPTIONS["host_mea"], 0)
     for u, v, (X, Y, _) in zip(dev, host, cases):
         assert u["status"] == v["status"] == 0 and u["ops"] == v["ops"] and u["score"] == v["score"]
+        assert u["finish_stage"] == _lib.FINISH_DEVICE and v["finish_stage"] == _lib.FINISH_HOST
         assert cigar_spans(u["ops"]) == (len(X), len(Y))
     # The packed cigars cross PCIe as 16-bit words when no run of the batch needs more than 14 bits (round 5) and as whole words
     # otherwise: both forms of the same batch, and a batch with runs of 17 000 and 21 000 (matchGamma 1 keeps no pair: a read's cigar
@@ -427,6 +430,7 @@ def test_device_mea_long_spans(gpu_ctx, monkeypatch):
     wide = gpu_ctx.realign(P, refs, reads, guides)
     gpu_ctx.set_option(_lib.OPTIONS["mea_wide_ops"], 0)
     assert [u["ops"] for u in wide] == [u["ops"] for u in dev]
+    assert all(u["finish_stage"] == _lib.FINISH_DEVICE for u in wide)
     P1 = R.make_params(band_mode=1, fixed_width=80, match_gamma=1.0)
     dev = gpu_ctx.realign(P1, refs, reads, guides)
     gpu_ctx.set_option(_lib.OPTIONS["host_mea"], 1)
@@ -434,6 +438,7 @@ def test_device_mea_long_spans(gpu_ctx, monkeypatch):
     gpu_ctx.set_option(_lib.OPTIONS["host_mea"], 0)
     for u, v, (X, Y, _) in zip(dev, host, cases):
         assert u["status"] == v["status"] == 0 and u["ops"] == v["ops"] and u["score"] == v["score"] == 0.0
+        assert u["finish_stage"] == _lib.FINISH_DEVICE and v["finish_stage"] == _lib.FINISH_HOST
         assert sorted(u["ops"]) == sorted([(_lib.OP_I, len(Y)), (_lib.OP_D, len(X))])
 
 
