@@ -106,6 +106,8 @@ int launch_wide(const KernelArgs &a, int R, int NW, int grid, void *stream);
 int launch_em_stair(const KernelArgs &a, int R, int grid, void *stream);
 size_t em_stair_lds_bytes();
 // device MEA stage (npr_mea.hip); offsets are per read, prefix sums with n_reads + 1 entries
+// k_mea_sort_lds takes a read whose spans (lX + 1 and lY) both stay within this: its two tables, lX + 1 + lY ints, then fit the LDS of a CU
+constexpr int kMeaSortLdsSpan = 16 * 1024;
 struct MeaArgs {
     const Task *tasks;
     const TaskOut *outs;
@@ -117,6 +119,7 @@ struct MeaArgs {
     const int64_t *rp_off;   // pairs: the read's slice of sx / sy / sq / back
     int32_t *cnt, *start, *colsum;
     int32_t *sx, *sy, *sq, *back;
+    int32_t *sw;             // weight of every sorted pair (the sort writes it, k_mea_weigh reads it)
     // the kept pairs (weight above matchGamma) of every read, at the read's slice too: by id = in (x, y) order (kx, ky, kq and
     // the chain's back pointers kback), and in the order the chain visits them (vrec: read position, weight, id, 0)
     int32_t *kx, *ky, *kq, *kback;
@@ -134,9 +137,9 @@ struct MeaArgs {
     int32_t ring;            // entries of the prefix-maximum ring (power of two)
     const int32_t *order;    // reads by decreasing pair count: the per-read kernels take them in this order (no long read last)
     const int32_t *read_first, *read_ntasks, *task_of;  // the tasks of a read: task_of[read_first[r] + s]
-    int32_t sort_lds_bytes;  // > 0: k_mea_sort_lds with this much LDS for the reads whose spans fit it
+    int32_t sort_lds_bytes;  // > 0: k_mea_sort_lds with this much LDS for the reads whose tables fit it
     int32_t sort_threads;    // threads of its workgroups (0: 1024)
-    int32_t any_global_sort; // some read's span does not: the three global-memory kernels for those
+    int32_t any_global_sort; // some read's tables do not: the global-memory kernels for those
     const int64_t *cnt_off;  // per read: its slice of cnt / start (lX + 1 entries), -1 for a read sorted in LDS
     int32_t ring_only;       // tests: every read through the LDS-ring kernel
     int32_t *ops_tmp;        // (op, length) pairs, each read's written backwards from the end of its slice

@@ -240,7 +240,7 @@ constexpr int32_t kHostStage = 1;  // what the stage's steps answer besides NPR_
 struct MeaPlan {
     int64_t n = 0, total = 0, n_pieces = 0;  // reads, posterior pairs, chain pieces
     size_t ntask_map = 0, n_cnt = 1;         // entries of task_of; cells of the global-memory sort's tables
-    int64_t span = 0;                        // the widest table among the reads that sort in LDS
+    int64_t span = 0;                        // the most table entries among the reads that sort in LDS
     bool sort_in_lds = true;
     // rx | ry | rp | ot | cnt_off as m.off takes them, n + 1 each: reference rows, read columns, pairs, the bound of the ops; first count cell or -1
     std::vector<int64_t> offs;
@@ -268,14 +268,15 @@ MeaPlan plan_mea(const npr_batch *b) {
         ot[i + 1] = ot[i] + 3 * std::min({np, lX, lY}) + 2;  // (D, I, M) per chain pair, one trailing (D, I)
     }
     p.total = rp[n];
-    // per-position tables of one read in LDS (count + scan + scatter in one kernel) when the longest span fits
+    // per-position tables of one read in LDS (count, masses, scan, scatter and weights in one kernel) when the longer span fits: one table
+    // over the reference positions and one over the read positions
     // ... read by read (round 4: one read of more than 16 k bases used to send its whole batch through the global-memory kernels)
-    const int64_t lds_span = b->ctx->opt[NPR_OPT_MEA_GLOBAL_SORT] != 0 ? 0 : 16 * 1024;
+    const int64_t lds_span = b->ctx->opt[NPR_OPT_MEA_GLOBAL_SORT] != 0 ? 0 : kMeaSortLdsSpan;
     int64_t cnt_total = 0;
     for (int64_t i = 0; i < n; ++i) {
         const int64_t sp = std::max(rx[i + 1] - rx[i], ry[i + 1] - ry[i]);
         cnt_off[i] = -1;
-        if (sp <= lds_span) p.span = std::max(p.span, sp);
+        if (sp <= lds_span) p.span = std::max(p.span, (rx[i + 1] - rx[i]) + (ry[i + 1] - ry[i]));
         else cnt_off[i] = cnt_total, cnt_total += rx[i + 1] - rx[i];
     }
     cnt_off[n] = -1;
@@ -306,7 +307,7 @@ MeaPlan plan_mea(const npr_batch *b) {
 
 // The stage's tables.  Five of the buffers hold several arrays one behind the other; what follows is the only place that says how many and how long:
 //   off     rx | ry | rp | ot | cnt_off, n + 1 each
-//   sorted  sx | sy | sq | back | kx | ky | kq | kback, total + 1 each, then total + 2 records of 16 bytes (vrec)
+//   sorted  sx | sy | sq | back | kx | ky | kq | kback, total + 1 each, then total + 2 records of 16 bytes (vrec), then sw, total + 1
 //   small   best_who | read_flag | n_ops | chain_len | kept | max_run, n each
 //   map     read_first[n] | read_ntasks[n] | task_of[ntask_map] | order[n]
 //   pieces  np[n] | poff[n] | pboff[n] | lane_read[P] | lane_piece[P] | pbest[P] | pb[P + n], P = n_pieces; lanes in the reads' order
@@ -326,7 +327,7 @@ hipError_t for_each_table(MeaScratch &m, const MeaPlan &p, F &&f) {
     one(m.cnt, p.n_cnt);
     one(m.start, p.n_cnt);
     one(m.col, p.cols() + 1);
-    one(m.sorted, kSortedArrays * sorted_stride(p) + kVrecWords * (p.total + 2));
+    one(m.sorted, kSortedArrays * sorted_stride(p) + kVrecWords * (p.total + 2) + sorted_stride(p));
     one(m.small, kSmallArrays * p.n);
     one(m.tmp, 2 * p.ops_bound());
     one(m.map, 3 * p.n + p.ntask_map);
@@ -365,7 +366,7 @@ int32_t obtain_tables(npr_ctx *ctx, MeaScratch &m, const MeaPlan &p, std::unique
     if (for_each_table(m, p, [](auto &buf, size_t count) { return buf.reserve(count); }) == hipSuccess) return NPR_OK;
     (void)hipGetLastError();
     if (!(ctx->overlap && fits)) return kHostStage;  // no room on the device
-    // When the own buffers do not fit beside the batches in flight (long reads: 48 bytes per pair, three chunks of a pipelined job on the
+    // When the own buffers do not fit beside the batches in flight (long reads: 52 bytes per pair, three chunks of a pipelined job on the
     // device) the context waits for the shared scratch after all, and gives back what it had reserved.
     (void)for_each_table(m, p, [](auto &buf, size_t) { return buf.release(), hipSuccess; });
     ctx->cache_flush();
@@ -387,6 +388,7 @@ int32_t upload_tables(npr_batch *b, const MeaPlan &p, MeaScratch &m, MeaArgs &a)
     a.sx = m.sorted.p, a.sy = m.sorted.p + ss, a.sq = m.sorted.p + 2 * ss, a.back = m.sorted.p + 3 * ss;
     a.kx = m.sorted.p + 4 * ss, a.ky = m.sorted.p + 5 * ss, a.kq = m.sorted.p + 6 * ss, a.kback = m.sorted.p + 7 * ss;
     a.vrec = reinterpret_cast<int4 *>(m.sorted.p + kSortedArrays * ss);
+    a.sw = m.sorted.p + kSortedArrays * ss + kVrecWords * (p.total + 2);
     a.best_who = m.small.p, a.read_flag = m.small.p + n, a.n_ops = m.small.p + 2 * n, a.chain_len = m.small.p + 3 * n, a.kept = m.small.p + 4 * n, a.max_run = m.small.p + 5 * n;
     a.chain_mass = m.mass.p;
     int32_t *const read_first = m.map.p, *const read_ntasks = read_first + n, *const task_of = read_ntasks + n, *const order = task_of + p.ntask_map;

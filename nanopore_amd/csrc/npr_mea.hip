@@ -3,16 +3,19 @@
 // one npr_host.cpp's mea_cigar() produces from the same posterior pairs, bit for bit; what changes is where it runs:
 // the pairs (about 12 bytes per reference base and read) stay in HBM and only the run-length encoded ops cross PCIe.
 //
-//   k_mea_sort_lds count + scan + scatter below in one kernel, one workgroup per read with its tables in LDS; used
-//                  when every read's span fits (the three kernels below otherwise: records chained over long spans)
-//   k_mea_count    per pair: quantise the posterior (floor(p * 1e7)), count the pair on its reference position,
-//                  add the quantum to its read position's column sum
+//   k_mea_sort_lds one workgroup per read with its tables in LDS, the posterior pairs read once: quantise (floor(p * 1e7)),
+//                  count per reference position, posterior mass per reference position (row) and read position (column),
+//                  scan, and every pair to its reference position's group (order inside a group arbitrary) WITH its weight
+//                  (posterior - gapGamma * gap mass of its row and column); the reads whose tables fit the LDS
+//   k_mea_count    the other reads (records chained over long spans), tables in global memory.  Per pair: quantise, count
+//                  the pair on its reference position, add the quantum to its read position's column sum
 //   k_mea_scan     per read: exclusive scan of the counts -> first sorted slot of every reference position
-//   k_mea_scatter  per pair: move to its reference position's group (order inside a group arbitrary)
-//   k_mea_weigh    one workgroup per read, a thread per sorted pair: the pair's weight (posterior - gapGamma * gap mass of
-//                  its row and column), the pairs not above matchGamma dropped, the kept ones written out twice -- in
-//                  (x, y) order (their ids: what back pointers and the trace use) and in the order the chain visits them
-//                  (reference positions in order, the pairs of one position from the highest read position down)
+//   k_mea_scatter  per pair: move to its reference position's group
+//   k_mea_weight_sorted  per sorted pair: its weight, the row mass summed over its group
+//   k_mea_weigh    one workgroup per read, a thread per sorted pair: the pairs whose weight is not above matchGamma dropped,
+//                  the kept ones written out twice -- in (x, y) order (their ids: what back pointers and the trace use) and
+//                  in the order the chain visits them (reference positions in order, the pairs of one position from the
+//                  highest read position down)
 //   k_mea_chain_lanes  ONE LANE per read, 64 reads per wavefront (round 4; before: one wavefront per read, every
 //                  instruction doing one lane's worth of work -- 21 ms for 4.5e8 pairs, half of the finish): each lane walks
 //                  its read's kept pairs; the heaviest chain ending at or below every read position is a monotone prefix
@@ -133,9 +136,53 @@ __global__ void __launch_bounds__(256) k_mea_scatter(MeaArgs a) {
     }
 }
 
-// count + scan + scatter of one read in LDS (one workgroup per read, its tasks' pairs read three times, from L2 after
-// the first): column sums first, then -- in the same LDS -- the per-position counts, their exclusive scan in place and
-// the scatter with the scanned counts as fill pointers.  For reads whose longer span fits the LDS (4 bytes per base).
+// Weight of a pair from its posterior quantum and the posterior mass of its reference position (row) and read position (column).
+__device__ __forceinline__ int64_t pair_weight(int q, int rowsum, int colsum, double gap_gamma) {
+    const int64_t gap = max(P1 - rowsum, int64_t(0)) + max(P1 - colsum, int64_t(0));
+    return q - static_cast<int64_t>(floor(gap_gamma * static_cast<double>(gap)));
+}
+// ... as the sorted pairs carry it (sw).  The gammas staging admits keep every weight inside 32 bits as long as no mass has wrapped; one that
+// has is far below every threshold (>= -PROB_ONE) and stays there.
+__device__ __forceinline__ int stored_weight(int q, int rowsum, int colsum, double gap_gamma) {
+    return static_cast<int>(max(pair_weight(q, rowsum, colsum, gap_gamma), static_cast<int64_t>(INT32_MIN)));
+}
+__device__ __forceinline__ int mea_quantum(float p) { return static_cast<int>(floor(static_cast<double>(p) * static_cast<double>(P1))); }
+
+// The weights of the reads k_mea_scatter sorted (k_mea_sort_lds writes its own): a thread per sorted pair, the row mass summed over the pair's
+// group, whose bounds `start` still holds, the column mass from colsum.
+__global__ void __launch_bounds__(256) k_mea_weight_sorted(MeaArgs a) {
+    const int r = blockIdx.x;
+    const int64_t rx = a.cnt_off[r], ry = a.ry_off[r], rp = a.rp_off[r];
+    if (rx < 0 || a.read_flag[r]) return;  // (sorted in LDS; or flagged: the scatter was incomplete)
+    const int n = static_cast<int>(a.rp_off[r + 1] - rp);
+    const int lX = static_cast<int>(a.rx_off[r + 1] - a.rx_off[r]) - 1, lY = static_cast<int>(a.ry_off[r + 1] - ry);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int x = a.sx[rp + i], y = a.sy[rp + i];
+        if (x < 0 || x >= lX || y < 0 || y >= lY) continue;  // (a slot the scatter did not fill)
+        int rowsum = 0;
+        for (int j = max(a.start[rx + x], 0); j < min(a.start[rx + x + 1], n); ++j) rowsum += a.sq[rp + j];
+        a.sw[rp + i] = stored_weight(a.sq[rp + i], rowsum, a.colsum[ry + y], a.gap_gamma);
+    }
+}
+
+// Sort and weights of one read, one workgroup per read, for the reads whose tables fit the LDS (spans up to kMeaSortLdsSpan): pairs per
+// reference position (cnt, lX + 1 ints) and posterior mass per read position (col, lY).  The read's pairs are numbered through its tasks;
+// thread t takes the pairs t, t + threads, ... and keeps the first SORT_BUDGET of them in registers:
+//   1. one read of px / py / pp: range checks, mea_is_posterior and the quantisation once per pair; the quantum added to col[y], one added
+//      to cnt[x] -- what that atomic returns is the pair's rank inside its reference position and stays in a register with (x, y) (one
+//      word: both are below 2^16) and the quantum
+//   2. col to colsum (prep_chunk reads it), exclusive scan of cnt in place: first sorted slot of every reference position; a pair's slot,
+//      cnt[x] + rank, replaces its rank
+//   3. cnt is free then and takes the posterior mass per reference position, from the registers (a third table would put the headline's
+//      reads, 14.7 k reference positions and up to 14 k read positions, at the 160 KB of a CU)
+//   4. every pair to its slot with its weight, pair_weight(q, cnt[x], col[y]), all from registers and LDS
+// A read with more than threads * SORT_BUDGET pairs: the pairs beyond are counted BEFORE step 1 (so the ranks step 1 hands out lie above
+// them), scattered between steps 2 and 3, reloaded, with the scanned counts as fill pointers, reloaded once more for step 3's masses, and
+// the weights of such a read are written by a last pass over its sorted pairs.  The order inside a group is arbitrary.
+// 1024 threads, 128 VGPRs; the batch's widest read sizes the launch's LDS: two workgroups (32 wavefronts) per CU up to 80 KB (lX + lY of
+// 20 k), one beyond -- the headline batch's widest read takes 116 KB.
+constexpr int SORT_BUDGET = 22;  // (the most that leaves the 128 VGPRs of a 1024-thread workgroup without spills)
+static_assert(kMeaSortLdsSpan <= (1 << 16), "k_mea_sort_lds packs (x, y) into one word");
 __global__ void __launch_bounds__(SORT_THREADS) k_mea_sort_lds(MeaArgs a) {
     extern __shared__ int h[];
     __shared__ int wsum[SORT_THREADS / WAVE];
@@ -143,39 +190,88 @@ __global__ void __launch_bounds__(SORT_THREADS) k_mea_sort_lds(MeaArgs a) {
     const int nthreads = static_cast<int>(blockDim.x);  // (SORT_THREADS, or fewer when the launch shares the chip with a DP pass: MeaArgs::sort_threads)
     const int64_t rx = a.rx_off[r], ry = a.ry_off[r], rp = a.rp_off[r];
     const int lX = static_cast<int>(a.rx_off[r + 1] - rx) - 1, lY = static_cast<int>(a.ry_off[r + 1] - ry);
-    if (a.rp_off[r + 1] == rp || a.cnt_off[r] >= 0) return;  // (no pairs; or a span beyond the LDS: the three kernels above)
+    if (a.rp_off[r + 1] == rp || a.cnt_off[r] >= 0) return;  // (no pairs; or tables beyond the LDS: the global-memory kernels above)
+    int *const cnt = h, *const col = cnt + lX + 1;
+    const int slots = static_cast<int>(a.rp_off[r + 1] - rp);
     const int ft = a.read_first[r], nt = a.read_ntasks[r];
-    int bad = 0;
-    // the pairs of every task of the read, f(x, y, p-quantum)
-    auto for_pairs = [&](auto f) {
+    const int budget = nthreads * SORT_BUDGET;
+    int bad = 0, total = 0;
+    for (int s = 0; s < nt; ++s) {
+        const int t = a.task_of[ft + s];
+        total += mea_task_pairs(a.outs[t], a.tasks[t]);
+    }
+    // the pairs beyond the register budget, f(x, y, p-quantum)
+    auto for_overflow = [&](auto f) {
+        int first = 0;  // number of the task's first pair
         for (int s = 0; s < nt; ++s) {
             const int t = a.task_of[ft + s];
             const Task &tk = a.tasks[t];
             const int n = mea_task_pairs(a.outs[t], tk);
-            for (int i = tid; i < n; i += nthreads) {
+            for (int i = max(budget - first, 0) + tid; i < n; i += nthreads) {
                 const int x = a.px[tk.pair_off + i], y = a.py[tk.pair_off + i];
-                if (x < 0 || x >= lX || y < 0 || y >= lY || !mea_is_posterior(a.pp[tk.pair_off + i])) {
+                const float p = a.pp[tk.pair_off + i];
+                if (x < 0 || x >= lX || y < 0 || y >= lY || !mea_is_posterior(p)) {
                     bad = 1;
                     continue;
                 }
-                f(x, y, static_cast<int>(floor(static_cast<double>(a.pp[tk.pair_off + i]) * static_cast<double>(P1))));
+                f(x, y, mea_quantum(p));
             }
+            first += n;
         }
     };
-    for (int i = tid; i < lY; i += nthreads) h[i] = 0;
+    // the budget's loads first: nothing below needs them before the tables are clear
+    // (where they lie first, the loads after that with nothing else to wait for between them: all of a thread's pairs are in flight at once)
+    int vx[SORT_BUDGET], vy[SORT_BUDGET];
+    float vp[SORT_BUDGET];
+    {
+        int64_t where[SORT_BUDGET];
+        int s = -1, first = 0, n = 0;  // the task pair g lies in: pairs first .. first + n - 1 at `at`
+        int64_t at = 0;
+#pragma unroll
+        for (int k = 0; k < SORT_BUDGET; ++k) {
+            const int g = k * nthreads + tid;
+            where[k] = -1;
+            if (g < total) {
+                while (g >= first + n) {
+                    const int t = a.task_of[ft + ++s];
+                    first += n, n = mea_task_pairs(a.outs[t], a.tasks[t]), at = a.tasks[t].pair_off;
+                }
+                where[k] = at + (g - first);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < SORT_BUDGET; ++k) {
+            const bool have = where[k] >= 0;
+            vx[k] = have ? a.px[where[k]] : 0, vy[k] = have ? a.py[where[k]] : 0, vp[k] = have ? a.pp[where[k]] : 0.f;
+        }
+    }
+    for (int i = tid; i < lX + 1 + lY; i += nthreads) h[i] = 0;
     __syncthreads();
-    for_pairs([&](int, int y, int q) { atomicAdd(&h[y], q); });
+    if (total > budget) {
+        for_overflow([&](int x, int y, int q) { atomicAdd(&cnt[x], 1), atomicAdd(&col[y], q); });
+        __syncthreads();
+    }
+    int vxy[SORT_BUDGET], vq[SORT_BUDGET], vrank[SORT_BUDGET];  // (vxy -1: no pair)
+#pragma unroll
+    for (int k = 0; k < SORT_BUDGET; ++k) {
+        const int x = vx[k], y = vy[k];
+        const bool have = k * nthreads + tid < total;
+        const bool ok = have && x >= 0 && x < lX && y >= 0 && y < lY && mea_is_posterior(vp[k]);
+        if (have && !ok) bad = 1;
+        vxy[k] = -1, vq[k] = 0, vrank[k] = 0;
+        if (ok) {
+            const int q = mea_quantum(vp[k]);
+            vxy[k] = x << 16 | y, vq[k] = q;
+            vrank[k] = atomicAdd(&cnt[x], 1);
+            atomicAdd(&col[y], q);
+        }
+    }
     __syncthreads();
-    for (int i = tid; i < lY; i += nthreads) a.colsum[ry + i] = h[i];
-    __syncthreads();
-    for (int i = tid; i <= lX; i += nthreads) h[i] = 0;
-    __syncthreads();
-    for_pairs([&](int x, int, int) { atomicAdd(&h[x], 1); });
-    __syncthreads();
+    for (int i = tid; i < lY; i += nthreads) a.colsum[ry + i] = col[i];
     int carry = 0;
     for (int base = 0; base <= lX; base += nthreads) {
         const int i = base + tid;
-        const int v = i <= lX ? h[i] : 0;
+        const int v = i <= lX ? cnt[i] : 0;
         int sc = v;
         for (int o = 1; o < WAVE; o <<= 1) {
             const int t = __shfl_up(sc, o);
@@ -183,16 +279,44 @@ __global__ void __launch_bounds__(SORT_THREADS) k_mea_sort_lds(MeaArgs a) {
         }
         if (lane == WAVE - 1) wsum[wv] = sc;
         __syncthreads();
-        int before = 0, total = 0;
-        for (int k = 0; k < nthreads / WAVE; ++k) before += k < wv ? wsum[k] : 0, total += wsum[k];
-        if (i <= lX) h[i] = carry + before + sc - v;
-        carry += total;
+        int before = 0, sum = 0;
+        for (int k = 0; k < nthreads / WAVE; ++k) before += k < wv ? wsum[k] : 0, sum += wsum[k];
+        if (i <= lX) cnt[i] = carry + before + sc - v;
+        carry += sum;
         __syncthreads();
     }
-    for_pairs([&](int x, int y, int q) {
-        const int64_t pos = rp + atomicAdd(&h[x], 1);
-        a.sx[pos] = x, a.sy[pos] = y, a.sq[pos] = q;
-    });
+#pragma unroll
+    for (int k = 0; k < SORT_BUDGET; ++k)
+        if (vxy[k] != -1) vrank[k] += cnt[vxy[k] >> 16];  // the pair's slot
+    if (total > budget) {
+        __syncthreads();  // (every start has been read: they count up from here)
+        for_overflow([&](int x, int y, int q) {
+            const int64_t pos = rp + atomicAdd(&cnt[x], 1);
+            a.sx[pos] = x, a.sy[pos] = y, a.sq[pos] = q;
+        });
+    }
+    __syncthreads();
+    for (int i = tid; i <= lX; i += nthreads) cnt[i] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SORT_BUDGET; ++k)
+        if (vxy[k] != -1) atomicAdd(&cnt[vxy[k] >> 16], vq[k]);
+    if (total > budget) for_overflow([&](int x, int, int q) { atomicAdd(&cnt[x], q); });
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SORT_BUDGET; ++k)
+        if (vxy[k] != -1) {
+            const int x = vxy[k] >> 16, y = vxy[k] & 0xffff;
+            const int64_t pos = rp + vrank[k];
+            a.sx[pos] = x, a.sy[pos] = y, a.sq[pos] = vq[k], a.sw[pos] = stored_weight(vq[k], cnt[x], col[y], a.gap_gamma);
+        }
+    if (total > budget) {
+        __syncthreads();  // (the workgroup's own stores: visible to it behind the barrier)
+        for (int i = tid; i < slots; i += nthreads) {
+            const int x = a.sx[rp + i], y = a.sy[rp + i];
+            if (x >= 0 && x < lX && y >= 0 && y < lY) a.sw[rp + i] = stored_weight(a.sq[rp + i], cnt[x], col[y], a.gap_gamma);  // (else: a slot a refused pair left empty)
+        }
+    }
     if (bad) a.read_flag[r] = NPR_ERR_INVALID;
 }
 
@@ -248,55 +372,46 @@ __device__ __forceinline__ Chunk prep_chunk(const MeaArgs &a, int *sx, int *sy, 
     return c;
 }
 
-// Weights of a read's sorted pairs and the two compacted forms of the kept ones.  The pairs of a reference position (a
-// "group") are contiguous after the sort, in arbitrary order; a thread looks at its own group only: the group's posterior
-// mass (row sum), which of its pairs are kept, where its own pair ranks among them.  ids: the kept pairs in (x, y) order
+// The two compacted forms of a read's kept pairs.  The pairs of a reference position (a "group") are contiguous after the
+// sort, in arbitrary order, each with its weight; a thread looks at its own group only: which of its pairs are kept, where
+// its own pair ranks among them.  ids: the kept pairs in (x, y) order
 // (the order ties are decided by: the later pair wins, as in npr_host.cpp's mea_cigar); visit order: groups in order, a
 // group from its highest read position down (a pair must not see the chains of its own reference position, and an insert
 // at y leaves every position below y alone).
 constexpr int WEIGH_CHUNK = 128;  // positions a wavefront weighs per round (two per lane)
 constexpr int WEIGH_RING = 512;   // LDS ring of staged positions: the round's chunk, the one before and the one after, and the one being loaded
 constexpr int WEIGH_HALO = 64;    // a group (the pairs of one reference position) is looked for this far on both sides
-__device__ __forceinline__ int64_t pair_weight(int q, int rowsum, int colsum, double gap_gamma) {
-    const int64_t gap = max(P1 - rowsum, int64_t(0)) + max(P1 - colsum, int64_t(0));
-    return q - static_cast<int64_t>(floor(gap_gamma * static_cast<double>(gap)));
-}
-// One wavefront per read, rounds of 128 sorted positions.  The positions are staged in an LDS ring with the column sums of their
-// read positions -- the chunk after the round's is fetched while the round is worked on (its x / y / q a round ahead, its column
-// sums when they have arrived) --, and everything a lane then does for its two pairs -- the bounds and the posterior mass of
-// their groups, which of a group's pairs are kept, the pair's rank among them -- reads LDS.  Many reads are in flight per CU (a
-// wavefront and 8 KB of LDS each), which is what hides the latency of a round's one dependent load.  A group that reaches past the
-// halo (more than 64 pairs on one reference position: cannot happen above a 0.01 threshold) hands the read to the ring kernel,
-// which reports it.
+// One wavefront per read, rounds of 128 sorted positions.  The positions are staged in an LDS ring with the weights the sort left
+// beside them -- the chunk after the round's is fetched while the round is worked on, a round ahead --, and everything a lane then
+// does for its two pairs -- the bounds of their groups, which of a group's pairs are kept (a staged weight above the threshold),
+// the pair's rank among them -- reads LDS.  Many reads are in flight per CU (a wavefront and 8 KB of LDS each).  A group that
+// reaches past the halo (more than 64 pairs on one reference position: cannot happen above a 0.01 threshold) hands the read to
+// the ring kernel, which reports it.
 __global__ void __launch_bounds__(WAVE) k_mea_weigh(MeaArgs a) {
-    __shared__ int X[WEIGH_RING], Y[WEIGH_RING], Q[WEIGH_RING], C[WEIGH_RING];
+    __shared__ int X[WEIGH_RING], Y[WEIGH_RING], Q[WEIGH_RING], W[WEIGH_RING];
     const int r = a.order[blockIdx.x], lane = threadIdx.x;
-    const int64_t rp = a.rp_off[r], ry = a.ry_off[r];
+    const int64_t rp = a.rp_off[r];
     const int n = a.read_flag[r] ? 0 : static_cast<int>(a.rp_off[r + 1] - rp);  // (flagged: the scatter was incomplete)
-    const int *const sx = a.sx + rp, *const sy = a.sy + rp, *const sq = a.sq + rp;
-    const int *const col = a.colsum + ry;
+    const int *const sx = a.sx + rp, *const sy = a.sy + rp, *const sq = a.sq + rp, *const sw = a.sw + rp;
     const int64_t floor_w = static_cast<int64_t>(floor(a.match_gamma * static_cast<double>(P1)));
     constexpr int RM = WEIGH_RING - 1;
     const int nc = (n + WEIGH_CHUNK - 1) / WEIGH_CHUNK;
     int giveup = 0;
     // registers of the chunk in flight: positions base + lane, base + 64 + lane
-    int fx[2], fy[2], fq[2];
+    int fx[2], fy[2], fq[2], fw[2];
     auto fetch = [&](int chunk) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int j = chunk * WEIGH_CHUNK + h * WAVE + lane;
             const bool ok = j < n;
-            fx[h] = ok ? sx[j] : -1, fy[h] = ok ? sy[j] : 0, fq[h] = ok ? sq[j] : 0;  // (-1: no position's group)
+            fx[h] = ok ? sx[j] : -1, fy[h] = ok ? sy[j] : 0, fq[h] = ok ? sq[j] : 0, fw[h] = ok ? sw[j] : 0;  // (-1: no position's group)
         }
     };
-    auto stage = [&](int chunk) {  // the fetched chunk and its column sums into the ring
-        int fc[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) fc[h] = fx[h] >= 0 ? col[fy[h]] : 0;
+    auto stage = [&](int chunk) {  // the fetched chunk into the ring
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int k = (chunk * WEIGH_CHUNK + h * WAVE + lane) & RM;
-            X[k] = fx[h], Y[k] = fy[h], Q[k] = fq[h], C[k] = fc[h];
+            X[k] = fx[h], Y[k] = fy[h], Q[k] = fq[h], W[k] = fw[h];
         }
     };
     for (int k = lane; k < WEIGH_CHUNK; k += WAVE) X[(-WEIGH_CHUNK + k) & RM] = -2;  // "chunk -1": before the first position
@@ -310,29 +425,27 @@ __global__ void __launch_bounds__(WAVE) k_mea_weigh(MeaArgs a) {
         stage(c + 1);  // (past the end: sentinels)
         fetch(c + 2);
         wave_sync();
-        int keep[2], below[2], above[2], before[2], xs[2], ys[2], qs[2];
-        int64_t ws[2];
+        int keep[2], below[2], above[2], before[2], xs[2], ys[2], qs[2], ws[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int i = c * WEIGH_CHUNK + h * WAVE + lane, me = i & RM;
             const bool in = i < n;
-            const int x = X[me], y = Y[me], q = Q[me];
-            int gs = i, ge = i, rowsum = q;
+            const int x = X[me], y = Y[me], w = W[me];
+            int gs = i, ge = i;
             if (in) {
-                while (gs > i - WEIGH_HALO && X[(gs - 1) & RM] == x) rowsum += Q[(--gs) & RM];
-                while (ge < i + WEIGH_HALO && X[(ge + 1) & RM] == x) rowsum += Q[(++ge) & RM];
+                while (gs > i - WEIGH_HALO && X[(gs - 1) & RM] == x) --gs;
+                while (ge < i + WEIGH_HALO && X[(ge + 1) & RM] == x) ++ge;
                 if (gs == i - WEIGH_HALO || ge == i + WEIGH_HALO) giveup = 1;  // (the group may go on beyond the halo)
             }
-            const int64_t w = in ? pair_weight(q, rowsum, C[me], a.gap_gamma) : 0;
             keep[h] = in && w > floor_w;
             // kept pairs of the group: at positions before mine, with a smaller / a larger read position
             before[h] = below[h] = above[h] = 0;
             if (keep[h])
                 for (int j = gs; j <= ge; ++j) {
                     const int k = j & RM;
-                    if (j != i && pair_weight(Q[k], rowsum, C[k], a.gap_gamma) > floor_w) before[h] += j < i, below[h] += Y[k] < y, above[h] += Y[k] > y;
+                    if (j != i && W[k] > floor_w) before[h] += j < i, below[h] += Y[k] < y, above[h] += Y[k] > y;
                 }
-            xs[h] = x, ys[h] = y, qs[h] = q, ws[h] = w;
+            xs[h] = x, ys[h] = y, qs[h] = Q[me], ws[h] = w;
         }
         // exclusive prefix count of the kept pairs by position: the first halves of all lanes, then the second halves
         int sc0 = keep[0], sc1 = keep[1];
@@ -726,7 +839,7 @@ size_t mea_chain_lds_bytes(int ring) { return static_cast<size_t>(ring) * 12 + W
 
 int launch_mea_sort(const MeaArgs &a, void *stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (a.sort_lds_bytes > 0) {  // the reads whose per-position tables fit the LDS
+    if (a.sort_lds_bytes > 0) {  // the reads whose three per-position tables fit the LDS: the widest of them sizes the launch
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mea_sort_lds), hipFuncAttributeMaxDynamicSharedMemorySize, a.sort_lds_bytes);
         if (e != hipSuccess) return static_cast<int>(e);
         hipLaunchKernelGGL(k_mea_sort_lds, dim3(a.n_reads), dim3(a.sort_threads >= WAVE && a.sort_threads < SORT_THREADS ? a.sort_threads & ~(WAVE - 1) : SORT_THREADS), a.sort_lds_bytes, s, a);
@@ -737,6 +850,7 @@ int launch_mea_sort(const MeaArgs &a, void *stream) {
         hipLaunchKernelGGL(k_mea_count, dim3(tg), dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_mea_scan, dim3(a.n_reads), dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_mea_scatter, dim3(tg), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_mea_weight_sorted, dim3(a.n_reads), dim3(256), 0, s, a);
     }
     return static_cast<int>(hipGetLastError());
 }
