@@ -296,3 +296,18 @@ def strerror(code):
 
 def ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _sized(fn, where, args, ctx=None, buffer=None):
+    """The two calls of an entry point whose last arguments are (out, cap) and which returns the length of its text: the sizing call
+    fn(*args, None, 0), then the filling call into `buffer` (a uint8 array) when that is large enough, else into a new array.  -> the
+    text, a view of the array it was written into.  `ctx`: the Context whose last_error() goes with a failure."""
+    total = int(fn(*args, None, 0))
+    if total < 0:
+        raise NprError(total, where, ctx.last_error() if ctx is not None else "")
+    if buffer is None or buffer.size < max(total, 1):
+        buffer = np.empty(max(total, 1), dtype=np.uint8)  # (filled by the call: no memset first)
+    rc = int(fn(*args, ptr(buffer), total))
+    if rc < 0:
+        raise NprError(rc, where, ctx.last_error() if ctx is not None else "")
+    return buffer[:total]

@@ -275,31 +275,6 @@ struct StageTimer {
     }
 };
 
-// text pieces of the SAM records the seed stages write (npr_seed_api.cpp, npr_seedchain_api.cpp)
-inline int digits(int64_t v) {
-    int k = 1;
-    while (v >= 10) v /= 10, ++k;
-    return k;
-}
-inline void put(char *&w, int64_t v) {
-    const int k = digits(v);
-    for (int j = k - 1; j >= 0; --j) w[j] = static_cast<char>('0' + v % 10), v /= 10;
-    w += k;
-}
-inline char complement(char c) {
-    switch (c) {
-        case 'A': return 'T';
-        case 'C': return 'G';
-        case 'G': return 'C';
-        case 'T': return 'A';
-        case 'a': return 't';
-        case 'c': return 'g';
-        case 'g': return 'c';
-        case 't': return 'a';
-        default: return c;
-    }
-}
-
 }  // namespace npr_impl
 using namespace npr_impl;
 

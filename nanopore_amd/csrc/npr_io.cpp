@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "nprealign.h"
+#include "npr_textout.h"
 #include "npr_threads.h"
 
 using npr::parallel_for;
@@ -64,16 +65,6 @@ inline int op_code(char c) {
         case 'X': return 8;
         default: return -1;
     }
-}
-
-inline int digits(int64_t v) {
-    int k = 1;
-    while (v >= 10) v /= 10, ++k;
-    return k;
-}
-// ... of a cigar length (30 bits), without a division: a job formats 10^8 of them
-inline int digits30(uint32_t v) {
-    return v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 : v < 1000000u ? 6 : v < 10000000u ? 7 : v < 100000000u ? 8 : v < 1000000000u ? 9 : 10;
 }
 
 }  // namespace
@@ -249,55 +240,15 @@ int64_t npr_sam_splice(const char *text, const int64_t *span, const int64_t *fie
                        const int64_t *n_ops, const uint32_t *words, int64_t *rec_off, char *out, int64_t cap) {
     if (n < 0 || (n && (!text || !span || !fields || !word_off || !n_ops || !rec_off))) return NPR_ERR_INVALID;
     try {
-        static const char code[3] = {'M', 'I', 'D'};
-        const int threads = usable_cpus();
-        std::atomic<int> bad{0};
-        std::vector<int64_t> lens(n);
-        parallel_for((n + 255) / 256, threads, [&](int64_t c) {
-            for (int64_t i = c * 256, hi = std::min(n, (c + 1) * 256); i < hi; ++i) {
-                const int64_t *f = fields + i * NPR_SAM_COLS;
-                int64_t k = 0;
-                if (n_ops[i] < 0 || (n_ops[i] && !words)) {
-                    bad = 1;
-                    continue;
-                }
-                for (int64_t q = 0; q < n_ops[i]; ++q) {
-                    const uint32_t w = words[word_off[i] + q];
-                    if ((w & 3u) > 2u) bad = 1;
-                    k += digits30(w >> 2) + 1;
-                }
-                lens[i] = (f[3] - span[2 * i]) + (k ? k : 1) + (span[2 * i + 1] - f[4]) + 1;
-            }
+        return npr::format_records(n, usable_cpus(), rec_off, out, cap, [&](int64_t i, auto &s) {
+            const int64_t *f = fields + i * NPR_SAM_COLS;
+            if (n_ops[i] < 0 || (n_ops[i] && !words)) return false;
+            s.bytes(text + span[2 * i], f[3] - span[2 * i]);
+            const bool ok = s.cigar_words(n_ops[i] ? words + word_off[i] : nullptr, n_ops[i]);
+            s.bytes(text + f[4], span[2 * i + 1] - f[4]);
+            s.ch('\n');
+            return ok;
         });
-        if (bad) return NPR_ERR_INVALID;
-        rec_off[0] = 0;
-        for (int64_t i = 0; i < n; ++i) rec_off[i + 1] = rec_off[i] + lens[i];
-        if (!out) return rec_off[n];
-        if (cap < rec_off[n]) return NPR_ERR_CAPACITY;
-        parallel_for((n + 63) / 64, threads, [&](int64_t c) {
-            for (int64_t i = c * 64, hi = std::min(n, (c + 1) * 64); i < hi; ++i) {
-                const int64_t *f = fields + i * NPR_SAM_COLS;
-                char *w = out + rec_off[i];
-                const size_t head = static_cast<size_t>(f[3] - span[2 * i]), tail = static_cast<size_t>(span[2 * i + 1] - f[4]);
-                std::memcpy(w, text + span[2 * i], head), w += head;
-                if (n_ops[i] == 0) *w++ = '*';
-                for (int64_t q = 0; q < n_ops[i]; ++q) {
-                    const uint32_t cw = words[word_off[i] + q];
-                    uint32_t v = cw >> 2;
-                    if (v < 10u) {  // (most operations of a realigned nanopore read)
-                        w[0] = static_cast<char>('0' + v), w[1] = code[cw & 3u], w += 2;
-                        continue;
-                    }
-                    const int k = digits30(v);
-                    for (int j = k - 1; j >= 0; --j) w[j] = static_cast<char>('0' + v % 10u), v /= 10u;
-                    w[k] = code[cw & 3u];
-                    w += k + 1;
-                }
-                std::memcpy(w, text + f[4], tail), w += tail;
-                *w = '\n';
-            }
-        });
-        return rec_off[n];
     } catch (const std::exception &) {
         return NPR_ERR_NOMEM;
     }
@@ -307,29 +258,16 @@ int64_t npr_sam_splice_text(const char *text, const int64_t *span, const int64_t
                             const char *cigar_text, int64_t *rec_off, char *out, int64_t cap) {
     if (n < 0 || (n && (!text || !span || !fields || !str_off || !rec_off))) return NPR_ERR_INVALID;
     try {
-        const int threads = usable_cpus();
-        rec_off[0] = 0;
-        for (int64_t i = 0; i < n; ++i) {
+        return npr::format_records(n, usable_cpus(), rec_off, out, cap, [&](int64_t i, auto &s) {
             const int64_t *f = fields + i * NPR_SAM_COLS;
             const int64_t k = str_off[i + 1] - str_off[i];
-            if (k < 0 || (k && !cigar_text)) return NPR_ERR_INVALID;
-            rec_off[i + 1] = rec_off[i] + (f[3] - span[2 * i]) + k + (span[2 * i + 1] - f[4]) + 1;
-        }
-        if (!out) return rec_off[n];
-        if (cap < rec_off[n]) return NPR_ERR_CAPACITY;
-        parallel_for((n + 63) / 64, threads, [&](int64_t c) {
-            for (int64_t i = c * 64, hi = std::min(n, (c + 1) * 64); i < hi; ++i) {
-                const int64_t *f = fields + i * NPR_SAM_COLS;
-                char *w = out + rec_off[i];
-                const size_t head = static_cast<size_t>(f[3] - span[2 * i]), tail = static_cast<size_t>(span[2 * i + 1] - f[4]),
-                             k = static_cast<size_t>(str_off[i + 1] - str_off[i]);
-                std::memcpy(w, text + span[2 * i], head), w += head;
-                if (k) std::memcpy(w, cigar_text + str_off[i], k), w += k;
-                std::memcpy(w, text + f[4], tail), w += tail;
-                *w = '\n';
-            }
+            if (k < 0 || (k && !cigar_text)) return false;
+            s.bytes(text + span[2 * i], f[3] - span[2 * i]);
+            s.bytes(k ? cigar_text + str_off[i] : nullptr, k);
+            s.bytes(text + f[4], span[2 * i + 1] - f[4]);
+            s.ch('\n');
+            return true;
         });
-        return rec_off[n];
     } catch (const std::exception &) {
         return NPR_ERR_NOMEM;
     }

@@ -2,6 +2,7 @@
 // (npr_seed.hip), and the matches as the SAM records of a base mapper (host code)
 // (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
 #include "npr_api_internal.h"
+#include "npr_textout.h"
 
 #include <array>
 
@@ -184,66 +185,36 @@ int64_t npr_seed_sam_text(int64_t n_reads, const uint8_t *text, const int64_t *n
     const int64_t total = hit_off[n_reads];
     if (hit_off[0] != 0 || total < 0 || (total && (!hits || !rnames || !rname_off))) return NPR_ERR_INVALID;
     try {
-        const int threads = usable_cpus();
-        std::atomic<int> bad{0};
-        // lengths first (into rec_off[q + 1]), then their running sum
-        parallel_for((n_reads + 63) / 64, threads, [&](int64_t c) {
-            for (int64_t i = c * 64, hi = std::min(n_reads, (c + 1) * 64); i < hi; ++i) {
-                const int64_t len = end[i] - begin[i], nl = name_span[2 * i + 1] - name_span[2 * i];
-                if (hit_off[i + 1] < hit_off[i] || len < 0 || nl < 0) {
-                    bad = 1;
-                    continue;
-                }
-                for (int64_t q = hit_off[i]; q < hit_off[i + 1]; ++q) {
-                    const int32_t *h = hits + 4 * q;
-                    const int64_t r = h[0], a = h[1], b = static_cast<uint32_t>(h[2]) & 0x7fffffffu, L = h[3];
-                    if (r < 0 || r >= n_refs || a < 0 || L < 1 || b + L > len) {
-                        bad = 1, rec_off[q + 1] = 0;
-                        continue;
-                    }
-                    const int64_t rest = len - b - L, flag = static_cast<uint32_t>(h[2]) >> 31 ? 16 : 0;
-                    // qname, flag, rname, pos, "255", cigar, "*", "0", "0", seq, "*": ten tabs, a newline
-                    rec_off[q + 1] = nl + digits(flag) + (rname_off[r + 1] - rname_off[r]) + digits(a + 1) + 3 + (b ? digits(b) + 1 : 0) + digits(L) + 1 +
-                                  (rest ? digits(rest) + 1 : 0) + 3 + L + 1 + 11;
-                }
+        for (int64_t i = 0; i < n_reads; ++i)
+            if (hit_off[i + 1] < hit_off[i] || end[i] < begin[i] || name_span[2 * i + 1] < name_span[2 * i]) return NPR_ERR_INVALID;
+        // qname, flag, rname, pos, "255", cigar, "*", "0", "0", seq, "*"
+        return format_records(total, usable_cpus(), rec_off, out, cap, [&](int64_t q, auto &s) {
+            const int64_t i = std::upper_bound(hit_off, hit_off + n_reads + 1, q) - hit_off - 1;  // the row's read: hit_off[i] <= q < hit_off[i + 1]
+            const int64_t len = end[i] - begin[i];
+            const int32_t *h = hits + 4 * q;
+            const int64_t r = h[0], a = h[1], b = static_cast<uint32_t>(h[2]) & 0x7fffffffu, L = h[3], rest = len - b - L;
+            const bool reverse = static_cast<uint32_t>(h[2]) >> 31;
+            if (r < 0 || r >= n_refs || a < 0 || L < 1 || rest < 0) return false;
+            s.bytes(text + name_span[2 * i], name_span[2 * i + 1] - name_span[2 * i]);
+            s.ch('\t');
+            s.num(reverse ? 16 : 0);
+            s.ch('\t');
+            s.bytes(rnames + rname_off[r], rname_off[r + 1] - rname_off[r]);
+            s.ch('\t');
+            s.num(a + 1);
+            s.lit("\t255\t");
+            if (b) s.num(b), s.ch('H');
+            s.num(L), s.ch('M');
+            if (rest) s.num(rest), s.ch('H');
+            s.lit("\t*\t0\t0\t");
+            if (!reverse) {
+                s.bytes(text + begin[i] + b, L);
+            } else {  // base u of the match is base b + u of the reverse complement: the complement of read base len - 1 - (b + u)
+                s.revcomp(text + begin[i] + rest, L);
             }
+            s.lit("\t*\n");
+            return true;
         });
-        if (bad) return NPR_ERR_INVALID;
-        rec_off[0] = 0;
-        for (int64_t q = 0; q < total; ++q) rec_off[q + 1] += rec_off[q];
-        if (!out) return rec_off[total];
-        if (cap < rec_off[total]) return NPR_ERR_CAPACITY;
-        parallel_for((n_reads + 63) / 64, threads, [&](int64_t c) {
-            for (int64_t i = c * 64, hi = std::min(n_reads, (c + 1) * 64); i < hi; ++i) {
-                const int64_t len = end[i] - begin[i], nl = name_span[2 * i + 1] - name_span[2 * i];
-                const uint8_t *seq = text + begin[i];
-                for (int64_t q = hit_off[i]; q < hit_off[i + 1]; ++q) {
-                    const int32_t *h = hits + 4 * q;
-                    const int64_t r = h[0], a = h[1], b = static_cast<uint32_t>(h[2]) & 0x7fffffffu, L = h[3], rest = len - b - L;
-                    const bool reverse = static_cast<uint32_t>(h[2]) >> 31;
-                    char *w = out + rec_off[q];
-                    std::memcpy(w, text + name_span[2 * i], static_cast<size_t>(nl)), w += nl;
-                    *w++ = '\t';
-                    put(w, reverse ? 16 : 0);
-                    *w++ = '\t';
-                    std::memcpy(w, rnames + rname_off[r], static_cast<size_t>(rname_off[r + 1] - rname_off[r])), w += rname_off[r + 1] - rname_off[r];
-                    *w++ = '\t';
-                    put(w, a + 1);
-                    std::memcpy(w, "\t255\t", 5), w += 5;
-                    if (b) put(w, b), *w++ = 'H';
-                    put(w, L), *w++ = 'M';
-                    if (rest) put(w, rest), *w++ = 'H';
-                    std::memcpy(w, "\t*\t0\t0\t", 7), w += 7;
-                    if (!reverse) {
-                        std::memcpy(w, seq + b, static_cast<size_t>(L)), w += L;
-                    } else {  // base u of the match is base b + u of the reverse complement: the complement of read base len - 1 - (b + u)
-                        for (int64_t u = 0; u < L; ++u) *w++ = complement(static_cast<char>(seq[len - 1 - b - u]));
-                    }
-                    std::memcpy(w, "\t*\n", 3), w += 3;
-                }
-            }
-        });
-        return rec_off[total];
     } catch (const std::exception &) {
         return NPR_ERR_NOMEM;
     }

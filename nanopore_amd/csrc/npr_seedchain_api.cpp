@@ -2,6 +2,7 @@
 // chainSamFile writes (host code)
 // (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
 #include "npr_api_internal.h"
+#include "npr_textout.h"
 
 namespace {
 
@@ -139,7 +140,6 @@ int64_t npr_seed_chain_sam_text(int64_t n_reads, const uint8_t *text, const int6
     const int64_t total = chain_off[n_reads];
     if (chain_off[0] != 0 || total < 0 || (total && (!chains || !ops_off || !rnames || !rname_off))) return NPR_ERR_INVALID;
     if (total && (ops_off[0] != 0 || (ops_off[total] && !ops))) return NPR_ERR_INVALID;
-    static const char kOps[] = "MIDNSHP=X";
     try {
         const int threads = usable_cpus();
         for (int64_t i = 0; i < n_reads; ++i)
@@ -175,45 +175,27 @@ int64_t npr_seed_chain_sam_text(int64_t n_reads, const uint8_t *text, const int6
         });
         if (bad) return NPR_ERR_INVALID;
         std::sort(order.begin(), order.end(), [](const Key &x, const Key &y) { return x.ref != y.ref ? x.ref < y.ref : x.rank < y.rank; });
-        // qname, flag, rname, "1", "255", cigar, "*", "0", "0", seq, "*": ten tabs, a newline
-        parallel_for((total + 63) / 64, threads, [&](int64_t c) {
-            for (int64_t k = c * 64, hi = std::min(total, (c + 1) * 64); k < hi; ++k) {
-                const Key &o = order[k];
-                int64_t cig = 0;
-                for (int64_t u = ops_off[o.chain]; u < ops_off[o.chain + 1]; ++u) cig += digits(ops[2 * u + 1]) + 1;
-                rec_off[k + 1] = (name_span[2 * o.read + 1] - name_span[2 * o.read]) + (chains[4 * o.chain + 1] ? 2 : 1) + (rname_off[o.ref + 1] - rname_off[o.ref]) + 1 + 3 +
-                                 (cig ? cig : 1) + 3 + (end[o.read] - begin[o.read]) + 1 + 11;
+        // qname, flag, rname, "1", "255", cigar, "*", "0", "0", seq, "*"
+        return format_records(total, threads, rec_off, out, cap, [&](int64_t k, auto &s) {
+            const Key &o = order[k];
+            const int64_t len = end[o.read] - begin[o.read];
+            const bool reverse = chains[4 * o.chain + 1] != 0;
+            s.bytes(text + name_span[2 * o.read], name_span[2 * o.read + 1] - name_span[2 * o.read]);
+            s.ch('\t');
+            s.num(reverse ? 16 : 0);
+            s.ch('\t');
+            s.bytes(rnames + rname_off[o.ref], rname_off[o.ref + 1] - rname_off[o.ref]);
+            s.lit("\t1\t255\t");
+            s.cigar_pairs(ops + 2 * ops_off[o.chain], ops_off[o.chain + 1] - ops_off[o.chain], kOpsSam);  // (looked at above, before the sort)
+            s.lit("\t*\t0\t0\t");
+            if (!reverse) {
+                s.bytes(text + begin[o.read], len);
+            } else {
+                s.revcomp(text + begin[o.read], len);
             }
+            s.lit("\t*\n");
+            return true;
         });
-        rec_off[0] = 0;
-        for (int64_t k = 0; k < total; ++k) rec_off[k + 1] += rec_off[k];
-        if (!out) return rec_off[total];
-        if (cap < rec_off[total]) return NPR_ERR_CAPACITY;
-        parallel_for((total + 63) / 64, threads, [&](int64_t c) {
-            for (int64_t k = c * 64, hi = std::min(total, (c + 1) * 64); k < hi; ++k) {
-                const Key &o = order[k];
-                const int64_t nl = name_span[2 * o.read + 1] - name_span[2 * o.read], rl = rname_off[o.ref + 1] - rname_off[o.ref], len = end[o.read] - begin[o.read];
-                const bool reverse = chains[4 * o.chain + 1] != 0;
-                const uint8_t *seq = text + begin[o.read];
-                char *w = out + rec_off[k];
-                std::memcpy(w, text + name_span[2 * o.read], static_cast<size_t>(nl)), w += nl;
-                *w++ = '\t';
-                put(w, reverse ? 16 : 0);
-                *w++ = '\t';
-                std::memcpy(w, rnames + rname_off[o.ref], static_cast<size_t>(rl)), w += rl;
-                std::memcpy(w, "\t1\t255\t", 7), w += 7;
-                if (ops_off[o.chain] == ops_off[o.chain + 1]) *w++ = '*';
-                for (int64_t u = ops_off[o.chain]; u < ops_off[o.chain + 1]; ++u) put(w, ops[2 * u + 1]), *w++ = kOps[ops[2 * u]];
-                std::memcpy(w, "\t*\t0\t0\t", 7), w += 7;
-                if (!reverse) {
-                    std::memcpy(w, seq, static_cast<size_t>(len)), w += len;
-                } else {
-                    for (int64_t u = 0; u < len; ++u) *w++ = complement(static_cast<char>(seq[len - 1 - u]));
-                }
-                std::memcpy(w, "\t*\n", 3), w += 3;
-            }
-        });
-        return rec_off[total];
     } catch (const std::exception &) {
         return NPR_ERR_NOMEM;
     }

@@ -14,7 +14,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import ptr
+from ._lib import _sized, ptr
 
 SAM_COLS = 16
 (F_QNAME_END, F_RNAME_LO, F_RNAME_HI, F_CIGAR_LO, F_CIGAR_HI, F_SEQ_LO, F_SEQ_HI, F_FLAG, F_POS, F_MAPQ, F_TID, F_QUERY_LO,
@@ -138,10 +138,7 @@ class SamText(object):
             out = take(bound)
             total = _check(L.npr_sam_splice(*args, ptr(out), out.nbytes), "npr_sam_splice")
             return out[:int(total)]
-        total = _check(L.npr_sam_splice(*args, None, 0), "npr_sam_splice")
-        out = np.empty(max(int(total), 1), dtype=np.uint8)
-        _check(L.npr_sam_splice(*args, ptr(out), int(total)), "npr_sam_splice")
-        return out[:int(total)]
+        return _sized(L.npr_sam_splice, "npr_sam_splice", args)
 
     def splice_text(self, span, fields, str_off, cigar_text, take=None):
         """splice() for cigars that are text already -- Batch.cigar_text() (include/nprealign.h: npr_sam_splice_text): line i with its
@@ -158,10 +155,7 @@ class SamText(object):
             out = take(int((span[:, 1] - span[:, 0]).sum() + (str_off[-1] - str_off[0] if n else 0) + 2 * n + 1))
             total = _check(L.npr_sam_splice_text(*args, ptr(out), out.nbytes), "npr_sam_splice_text")
             return out[:int(total)]
-        total = _check(L.npr_sam_splice_text(*args, None, 0), "npr_sam_splice_text")
-        out = np.empty(max(int(total), 1), dtype=np.uint8)
-        _check(L.npr_sam_splice_text(*args, ptr(out), int(total)), "npr_sam_splice_text")
-        return out[:int(total)]
+        return _sized(L.npr_sam_splice_text, "npr_sam_splice_text", args)
 
     def field_bytes(self, lo, hi):
         return bytes(self.text[lo:hi])

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (BAND_ANCHOR, BAND_FIXED, ERR_CAPACITY, ERR_NOMEM, MODE_ALL_POSTERIORS, MODE_EXPECTATIONS, MODE_REALIGN, MODE_RESCORE_ORIGINAL, NprError,
-                   Params, ptr)
+                   Params, _sized, ptr)
 
 
 def make_params(band_mode=BAND_ANCHOR, diagonal_expansion=10, constraint_trim=14, split_threshold=3000,
@@ -155,15 +155,7 @@ class Batch(object):
         string i = buffer[offsets[i]:offsets[i + 1]], "*" for a read that failed.  `buffer`: a uint8 array the text may be written into (a view
         of it is returned when it is large enough)."""
         off = np.zeros(self.n_reads + 1, dtype=np.int64)
-        total = self._L.npr_batch_cigar_text(self._h, ptr(off), None, 0)
-        if total < 0:
-            raise NprError(int(total), "npr_batch_cigar_text", self.ctx.last_error())
-        if buffer is None or buffer.size < max(int(total), 1):
-            buffer = np.empty(max(int(total), 1), dtype=np.uint8)
-        rc = self._L.npr_batch_cigar_text(self._h, ptr(off), ptr(buffer), int(total))
-        if rc < 0:
-            raise NprError(int(rc), "npr_batch_cigar_text", self.ctx.last_error())
-        return buffer[:int(total)], off
+        return _sized(self._L.npr_batch_cigar_text, "npr_batch_cigar_text", [self._h, ptr(off)], self.ctx, buffer), off
 
     def debug_set_pairs(self, read, x, y, p, task_status=0):
         """TEST HOOK (include/nprealign.h npr_batch_debug_set_pairs): replaces on the device the posterior pairs the DP pass left for `read`."""
@@ -777,14 +769,7 @@ def format_cigars(ops_off, ops):
     ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 2)
     n = len(ops_off) - 1
     str_off = np.zeros(n + 1, dtype=np.int64)
-    total = L.npr_format_cigars(n, ptr(ops_off), ptr(ops), ptr(str_off), None, 0)
-    if total < 0:
-        raise NprError(int(total), "npr_format_cigars")
-    buf = np.empty(max(int(total), 1), dtype=np.uint8)
-    rc = L.npr_format_cigars(n, ptr(ops_off), ptr(ops), ptr(str_off), ptr(buf), int(total))
-    if rc < 0:
-        raise NprError(int(rc), "npr_format_cigars")
-    return buf[:int(total)], str_off
+    return _sized(L.npr_format_cigars, "npr_format_cigars", [n, ptr(ops_off), ptr(ops), ptr(str_off)]), str_off
 
 
 def format_cigars_packed(word_off, n_ops, words):
@@ -796,14 +781,7 @@ def format_cigars_packed(word_off, n_ops, words):
     words = np.ascontiguousarray(words, dtype=np.uint32)
     n = len(n_ops)
     str_off = np.zeros(n + 1, dtype=np.int64)
-    total = L.npr_format_cigars_packed(n, ptr(word_off), ptr(n_ops), ptr(words), ptr(str_off), None, 0)
-    if total < 0:
-        raise NprError(int(total), "npr_format_cigars_packed")
-    buf = np.empty(max(int(total), 1), dtype=np.uint8)
-    rc = L.npr_format_cigars_packed(n, ptr(word_off), ptr(n_ops), ptr(words), ptr(str_off), ptr(buf), int(total))
-    if rc < 0:
-        raise NprError(int(rc), "npr_format_cigars_packed")
-    return buf[:int(total)], str_off
+    return _sized(L.npr_format_cigars_packed, "npr_format_cigars_packed", [n, ptr(word_off), ptr(n_ops), ptr(words), ptr(str_off)]), str_off
 
 
 def cigar_text_packed(ctx, word_off, n_ops, words):
@@ -815,14 +793,7 @@ def cigar_text_packed(ctx, word_off, n_ops, words):
     words = np.ascontiguousarray(words, dtype=np.uint32)
     n = len(n_ops)
     str_off = np.zeros(n + 1, dtype=np.int64)
-    total = L.npr_cigar_text_packed(ctx._h, n, ptr(word_off), ptr(n_ops), ptr(words), ptr(str_off), None, 0)
-    if total < 0:
-        raise NprError(int(total), "npr_cigar_text_packed", ctx.last_error())
-    buf = np.empty(max(int(total), 1), dtype=np.uint8)
-    rc = L.npr_cigar_text_packed(ctx._h, n, ptr(word_off), ptr(n_ops), ptr(words), ptr(str_off), ptr(buf), int(total))
-    if rc < 0:
-        raise NprError(int(rc), "npr_cigar_text_packed", ctx.last_error())
-    return buf[:int(total)], str_off
+    return _sized(L.npr_cigar_text_packed, "npr_cigar_text_packed", [ctx._h, n, ptr(word_off), ptr(n_ops), ptr(words), ptr(str_off)], ctx), str_off
 
 
 def _ragged(items):
@@ -853,14 +824,7 @@ def format_sam_records(qnames, ref_names, ref_index, pos, word_off, n_ops, words
     rec_off = np.zeros(n + 1, dtype=np.int64)
     args = [n, ptr(qn), ptr(qoff), None if flag is None else ptr(flag), ptr(rn), ptr(roff), ptr(ref_index), ptr(pos),
             None if mapq is None else ptr(mapq), ptr(word_off), ptr(n_ops), ptr(words), ptr(seq), ptr(seq_off), ptr(rec_off)]
-    total = L.npr_format_sam_records(*args, None, 0)
-    if total < 0:
-        raise NprError(int(total), "npr_format_sam_records")
-    buf = np.empty(max(int(total), 1), dtype=np.uint8)
-    rc = L.npr_format_sam_records(*args, ptr(buf), int(total))
-    if rc < 0:
-        raise NprError(int(rc), "npr_format_sam_records")
-    return buf[:int(total)], rec_off
+    return _sized(L.npr_format_sam_records, "npr_format_sam_records", args), rec_off
 
 
 def seed_sam_text(text, name_span, begin, end, ref_names, hit_off, hits):
@@ -879,14 +843,7 @@ def seed_sam_text(text, name_span, begin, end, ref_names, hit_off, hits):
     rn, roff = _ragged(ref_names)
     rec_off = np.zeros(len(hits) + 1, dtype=np.int64)
     args = [n, ptr(text), ptr(name_span), ptr(begin), ptr(end), ptr(rn), ptr(roff), len(ref_names), ptr(hit_off), ptr(hits), ptr(rec_off)]
-    total = L.npr_seed_sam_text(*args, None, 0)
-    if total < 0:
-        raise NprError(int(total), "npr_seed_sam_text")
-    buf = np.empty(max(int(total), 1), dtype=np.uint8)
-    rc = L.npr_seed_sam_text(*args, ptr(buf), int(total))
-    if rc < 0:
-        raise NprError(int(rc), "npr_seed_sam_text")
-    return buf[:int(total)], rec_off
+    return _sized(L.npr_seed_sam_text, "npr_seed_sam_text", args), rec_off
 
 
 def seed_chain_sam_text(text, name_span, begin, end, ref_names, chain_off, chains, ops_off, ops):
@@ -907,14 +864,7 @@ def seed_chain_sam_text(text, name_span, begin, end, ref_names, chain_off, chain
     rn, roff = _ragged(ref_names)
     rec_off = np.zeros(len(chains) + 1, dtype=np.int64)
     args = [n, ptr(text), ptr(name_span), ptr(begin), ptr(end), ptr(rn), ptr(roff), len(ref_names), ptr(chain_off), ptr(chains), ptr(ops_off), ptr(ops), ptr(rec_off)]
-    total = L.npr_seed_chain_sam_text(*args, None, 0)
-    if total < 0:
-        raise NprError(int(total), "npr_seed_chain_sam_text")
-    buf = np.empty(max(int(total), 1), dtype=np.uint8)
-    rc = L.npr_seed_chain_sam_text(*args, ptr(buf), int(total))
-    if rc < 0:
-        raise NprError(int(rc), "npr_seed_chain_sam_text")
-    return buf[:int(total)], rec_off
+    return _sized(L.npr_seed_chain_sam_text, "npr_seed_chain_sam_text", args), rec_off
 
 
 def mea_cigar(lX, lY, x, y, p, gap_gamma=0.5, match_gamma=0.0):
