@@ -111,181 +111,101 @@ class NprError(RuntimeError):
         RuntimeError.__init__(self, msg)
 
 
-# every symbol include/nprealign.h declares
-EXPORTS = [
-    "npr_abi_version", "npr_strerror", "npr_create", "npr_destroy", "npr_last_error", "npr_set_hmm",
-    "npr_batch_create", "npr_batch_create_at", "npr_batch_run", "npr_batch_finish", "npr_batch_destroy", "npr_batch_get_stats", "npr_batch_class_stats",
-    "npr_batch_results", "npr_batch_ops", "npr_batch_ops_packed", "npr_batch_pairs", "npr_batch_debug_set_pairs", "npr_batch_debug_finish_stage", "npr_batch_dense", "npr_batch_rs_forward", "npr_batch_expectations",
-    "npr_batch_align_stats", "npr_align_stats", "npr_batch_plan_check", "npr_batch_base_expectations",
-    "npr_kmer_counts", "npr_kmer_counts_groups", "npr_align_indel_kmers", "npr_batch_indel_kmers",
-    "npr_pileup_create", "npr_pileup_destroy", "npr_pileup_add_batch", "npr_pileup_add", "npr_pileup_counts", "npr_pileup_depth",
-    "npr_realign_batch",
-    "npr_plan_create", "npr_plan_destroy", "npr_plan_segments", "npr_plan_segment_info",
-    "npr_plan_segment_band", "npr_plan_frame_schedule", "npr_plan_stripes", "npr_format_cigars", "npr_format_cigars_packed", "npr_format_sam_records", "npr_chain_hits", "npr_mea_cigar", "npr_rescore", "npr_encode_bases",
-    "npr_sam_index", "npr_sam_parse", "npr_sam_guides", "npr_sam_splice", "npr_fasta_index", "npr_fasta_pack", "npr_fastq_index", "npr_names_mark",
-    "npr_batch_create_spans", "npr_chain_merge", "npr_ctx_option", "npr_batch_segment_arith",
-    "npr_cigar_text_packed", "npr_batch_cigar_text", "npr_sam_splice_text",
-    "npr_seed_index_create", "npr_seed_index_destroy", "npr_seed_matches", "npr_seed_sam_text", "npr_seed_chains", "npr_seed_chain_sam_text",
-]
+vp, i32, i64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+_params, _out = C.POINTER(Params), C.POINTER(vp)
+# every symbol include/nprealign.h declares: name -> (restype, argtypes), in the header's order
+SIGNATURES = {
+    "npr_abi_version": (i32, []),
+    "npr_strerror": (C.c_char_p, [i32]),
+    "npr_create": (i32, [i32, _out, C.c_char_p, C.c_size_t]),
+    "npr_destroy": (None, [vp]),
+    "npr_last_error": (C.c_char_p, [vp]),
+    "npr_ctx_option": (i32, [vp, i32, i64]),
+    "npr_set_hmm": (i32, [vp, i32, vp, vp]),
+    "npr_batch_create": (i32, [vp, _params, i64, i64] + [vp] * 8 + [_out]),
+    "npr_batch_create_at": (i32, [vp, _params, i64, i64] + [vp] * 9 + [_out]),
+    "npr_batch_run": (i32, [vp, C.POINTER(C.c_float)]),
+    "npr_batch_finish": (i32, [vp]),
+    "npr_batch_destroy": (None, [vp]),
+    "npr_batch_get_stats": (i32, [vp, C.POINTER(BatchStats)]),
+    "npr_batch_class_stats": (i32, [vp, vp, vp, i32]),
+    "npr_batch_segment_arith": (i32, [vp, vp, vp, i64]),
+    "npr_batch_results": (i32, [vp, vp]),
+    "npr_batch_ops": (i32, [vp, vp, vp, i64]),
+    "npr_batch_ops_packed": (i32, [vp, vp, vp, i64]),
+    "npr_batch_pairs": (i32, [vp, vp, vp, vp, vp, i64]),
+    "npr_batch_debug_set_pairs": (i32, [vp, i64, vp, vp, vp, i64, i32]),
+    "npr_batch_debug_finish_stage": (i32, [vp]),
+    "npr_batch_align_stats": (i32, [vp, vp]),
+    "npr_align_stats": (i32, [vp, i64, i64] + [vp] * 9),
+    "npr_kmer_counts": (i32, [vp, i32, i64, vp, vp, vp]),
+    "npr_kmer_counts_groups": (i32, [vp, i32, i64, vp, vp, vp, vp, i32, vp]),
+    "npr_align_indel_kmers": (i32, [vp, i32, i64, i64] + [vp] * 10),
+    "npr_batch_indel_kmers": (i32, [vp, i32, vp, vp]),
+    "npr_pileup_create": (i32, [vp, i64, vp, _out]),
+    "npr_pileup_destroy": (None, [vp]),
+    "npr_pileup_add_batch": (i32, [vp, vp, vp]),
+    "npr_pileup_add": (i32, [vp, i64] + [vp] * 8),
+    "npr_pileup_counts": (i32, [vp, vp]),
+    "npr_pileup_depth": (i32, [vp, vp, vp]),
+    "npr_seed_index_create": (i32, [vp, i32, i64, vp, vp, _out]),
+    "npr_seed_index_destroy": (None, [vp]),
+    "npr_seed_matches": (i64, [vp, i64, i32, i64, vp, vp, vp, vp, vp, i64]),
+    "npr_seed_sam_text": (i64, [i64] + [vp] * 6 + [i64] + [vp] * 4 + [i64]),
+    "npr_seed_chains": (i64, [vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64]),
+    "npr_seed_chain_sam_text": (i64, [i64] + [vp] * 6 + [i64] + [vp] * 6 + [i64]),
+    "npr_batch_base_expectations": (i32, [vp, vp, i64, vp, vp, vp]),
+    "npr_batch_expectations": (i32, [vp, vp, vp, vp, C.POINTER(C.c_float)]),
+    "npr_batch_dense": (i32, [vp, i64, vp, vp, vp, vp, i64]),
+    "npr_batch_rs_forward": (i32, [vp, i64, vp, vp, i64]),
+    "npr_batch_plan_check": (i64, [vp, vp]),
+    "npr_realign_batch": (i32, [vp, _params, i64, i64] + [vp] * 11 + [i64]),
+    "npr_plan_create": (i32, [_params, i64, i64, vp, i64, _out]),
+    "npr_plan_destroy": (None, [vp]),
+    "npr_plan_segments": (i32, [vp]),
+    "npr_plan_segment_info": (i32, [vp, i32, vp]),
+    "npr_plan_segment_band": (i32, [vp, i32, vp, vp]),
+    "npr_plan_frame_schedule": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
+    "npr_plan_stripes": (i32, [vp, i32, i32, vp, i32, vp]),
+    "npr_mea_cigar": (i64, [i64, i64, vp, vp, vp, i64, dbl, dbl, vp, i64, C.POINTER(dbl)]),
+    "npr_rescore": (i32, [vp, i64, vp, vp, vp, i64, C.POINTER(dbl)]),
+    "npr_chain_hits": (i64, [i64, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "npr_chain_merge": (i64, [i64, vp, vp, vp, vp, i64, i64, vp, i64]),
+    "npr_format_cigars": (i64, [i64, vp, vp, vp, vp, i64]),
+    "npr_format_cigars_packed": (i64, [i64, vp, vp, vp, vp, vp, i64]),
+    "npr_cigar_text_packed": (i64, [vp, i64, vp, vp, vp, vp, vp, i64]),
+    "npr_batch_cigar_text": (i64, [vp, vp, vp, i64]),
+    "npr_format_sam_records": (i64, [i64] + [vp] * 15 + [i64]),
+    "npr_encode_bases": (None, [vp, i64, vp]),
+    "npr_sam_index": (i64, [vp, i64, C.POINTER(i64), vp, i64]),
+    "npr_sam_parse": (i32, [vp, vp, i64, vp, vp, i64, vp]),
+    "npr_sam_guides": (i32, [vp, vp, i64, vp, vp]),
+    "npr_sam_splice": (i64, [vp, vp, vp, i64, vp, vp, vp, vp, vp, i64]),
+    "npr_sam_splice_text": (i64, [vp, vp, vp, i64, vp, vp, vp, vp, i64]),
+    "npr_fasta_index": (i64, [vp, i64, vp, vp, i64]),
+    "npr_fasta_pack": (i32, [vp, vp, i64, vp, vp]),
+    "npr_fastq_index": (i64, [vp, i64, vp, i64]),
+    "npr_names_mark": (i64, [vp, vp, i64, vp, vp, vp, i64, vp]),
+    "npr_batch_create_spans": (i32, [vp, _params, i64, i64] + [vp] * 10 + [_out]),
+}
+EXPORTS = list(SIGNATURES)
 
 _lib = None
 
 
 def load():
-    """Loads libnprealign.so; raises RuntimeError (never falls back) when it is absent."""
-    global _lib
+    """Loads libnprealign.so and gives every symbol its signature; raises RuntimeError (never falls back) when it is absent."""
+    global _lib, LIB_LOADED
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
         raise RuntimeError("libnprealign.so not found at %s: build it with `python -c 'import __graft_entry__ as g; "
                            "g.build()'` or `make -C nanopore_amd/csrc`; there is no CPU fallback" % LIB_PATH)
-    global LIB_LOADED
     L = C.CDLL(LIB_PATH)
     LIB_LOADED = True
-    vp, i32, i64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_double
-    L.npr_abi_version.restype = i32
-    L.npr_strerror.restype = C.c_char_p
-    L.npr_strerror.argtypes = [i32]
-    L.npr_create.restype = i32
-    L.npr_create.argtypes = [i32, C.POINTER(vp), C.c_char_p, C.c_size_t]
-    L.npr_destroy.restype = None
-    L.npr_destroy.argtypes = [vp]
-    L.npr_last_error.restype = C.c_char_p
-    L.npr_last_error.argtypes = [vp]
-    L.npr_ctx_option.restype = i32
-    L.npr_ctx_option.argtypes = [vp, i32, i64]
-    L.npr_set_hmm.restype = i32
-    L.npr_set_hmm.argtypes = [vp, i32, vp, vp]
-    L.npr_batch_create.restype = i32
-    L.npr_batch_create.argtypes = [vp, C.POINTER(Params), i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
-    L.npr_plan_frame_schedule.restype = i32
-    L.npr_plan_frame_schedule.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
-    L.npr_batch_class_stats.restype = i32
-    L.npr_batch_class_stats.argtypes = [vp, vp, vp, i32]
-    L.npr_batch_segment_arith.restype = i32
-    L.npr_batch_segment_arith.argtypes = [vp, vp, vp, i64]
-    L.npr_batch_create_at.restype = i32
-    L.npr_batch_create_at.argtypes = [vp, C.POINTER(Params), i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
-    L.npr_batch_run.restype = i32
-    L.npr_batch_run.argtypes = [vp, C.POINTER(C.c_float)]
-    L.npr_batch_finish.restype = i32
-    L.npr_batch_finish.argtypes = [vp]
-    L.npr_batch_destroy.restype = None
-    L.npr_batch_destroy.argtypes = [vp]
-    L.npr_batch_get_stats.restype = i32
-    L.npr_batch_get_stats.argtypes = [vp, C.POINTER(BatchStats)]
-    L.npr_batch_results.restype = i32
-    L.npr_batch_results.argtypes = [vp, vp]
-    L.npr_batch_ops.restype = i32
-    L.npr_batch_ops.argtypes = [vp, vp, vp, i64]
-    L.npr_batch_ops_packed.restype = i32
-    L.npr_batch_ops_packed.argtypes = [vp, vp, vp, i64]
-    L.npr_batch_pairs.restype = i32
-    L.npr_batch_pairs.argtypes = [vp, vp, vp, vp, vp, i64]
-    L.npr_batch_debug_set_pairs.restype = i32
-    L.npr_batch_debug_set_pairs.argtypes = [vp, i64, vp, vp, vp, i64, i32]
-    L.npr_batch_debug_finish_stage.restype = i32
-    L.npr_batch_debug_finish_stage.argtypes = [vp]
-    L.npr_batch_expectations.restype = i32
-    L.npr_batch_expectations.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_float)]
-    L.npr_batch_base_expectations.restype = i32
-    L.npr_batch_base_expectations.argtypes = [vp, vp, i64, vp, vp, vp]
-    L.npr_batch_plan_check.restype = i64
-    L.npr_batch_plan_check.argtypes = [vp, vp]
-    L.npr_batch_align_stats.restype = i32
-    L.npr_batch_align_stats.argtypes = [vp, vp]
-    L.npr_align_stats.restype = i32
-    L.npr_align_stats.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.npr_kmer_counts.restype = i32
-    L.npr_kmer_counts.argtypes = [vp, i32, i64, vp, vp, vp]
-    L.npr_kmer_counts_groups.restype = i32
-    L.npr_kmer_counts_groups.argtypes = [vp, i32, i64, vp, vp, vp, vp, i32, vp]
-    L.npr_align_indel_kmers.restype = i32
-    L.npr_align_indel_kmers.argtypes = [vp, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.npr_batch_indel_kmers.restype = i32
-    L.npr_batch_indel_kmers.argtypes = [vp, i32, vp, vp]
-    L.npr_pileup_create.restype = i32
-    L.npr_pileup_create.argtypes = [vp, i64, vp, C.POINTER(vp)]
-    L.npr_pileup_destroy.restype = None
-    L.npr_pileup_destroy.argtypes = [vp]
-    L.npr_pileup_add_batch.restype = i32
-    L.npr_pileup_add_batch.argtypes = [vp, vp, vp]
-    L.npr_pileup_add.restype = i32
-    L.npr_pileup_add.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.npr_pileup_counts.restype = i32
-    L.npr_pileup_counts.argtypes = [vp, vp]
-    L.npr_pileup_depth.restype = i32
-    L.npr_pileup_depth.argtypes = [vp, vp, vp]
-    L.npr_batch_dense.restype = i32
-    L.npr_batch_dense.argtypes = [vp, i64, vp, vp, vp, vp, i64]
-    L.npr_batch_rs_forward.restype = i32
-    L.npr_batch_rs_forward.argtypes = [vp, i64, vp, vp, i64]
-    L.npr_realign_batch.restype = i32
-    L.npr_realign_batch.argtypes = [vp, C.POINTER(Params), i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]
-    L.npr_plan_create.restype = i32
-    L.npr_plan_create.argtypes = [C.POINTER(Params), i64, i64, vp, i64, C.POINTER(vp)]
-    L.npr_plan_destroy.restype = None
-    L.npr_plan_destroy.argtypes = [vp]
-    L.npr_plan_segments.restype = i32
-    L.npr_plan_segments.argtypes = [vp]
-    L.npr_plan_segment_info.restype = i32
-    L.npr_plan_segment_info.argtypes = [vp, i32, vp]
-    L.npr_plan_segment_band.restype = i32
-    L.npr_plan_segment_band.argtypes = [vp, i32, vp, vp]
-    L.npr_plan_stripes.restype = i32
-    L.npr_plan_stripes.argtypes = [vp, i32, i32, vp, i32, vp]
-    L.npr_format_cigars_packed.restype = i64
-    L.npr_format_cigars_packed.argtypes = [i64, vp, vp, vp, vp, vp, i64]
-    L.npr_format_sam_records.restype = i64
-    L.npr_format_sam_records.argtypes = [i64] + [vp] * 15 + [i64]
-    L.npr_chain_hits.restype = i64
-    L.npr_chain_hits.argtypes = [i64, vp, vp, vp, vp, vp, vp, i64, vp]
-    L.npr_chain_merge.restype = i64
-    L.npr_chain_merge.argtypes = [i64, vp, vp, vp, vp, i64, i64, vp, i64]
-    L.npr_format_cigars.restype = i64
-    L.npr_format_cigars.argtypes = [i64, vp, vp, vp, vp, i64]
-    L.npr_mea_cigar.restype = i64
-    L.npr_mea_cigar.argtypes = [i64, i64, vp, vp, vp, i64, dbl, dbl, vp, i64, C.POINTER(dbl)]
-    L.npr_rescore.restype = i32
-    L.npr_rescore.argtypes = [vp, i64, vp, vp, vp, i64, C.POINTER(dbl)]
-    L.npr_encode_bases.restype = None
-    L.npr_encode_bases.argtypes = [vp, i64, vp]
-    L.npr_sam_index.restype = i64
-    L.npr_sam_index.argtypes = [vp, i64, C.POINTER(i64), vp, i64]
-    L.npr_sam_parse.restype = i32
-    L.npr_sam_parse.argtypes = [vp, vp, i64, vp, vp, i64, vp]
-    L.npr_sam_guides.restype = i32
-    L.npr_sam_guides.argtypes = [vp, vp, i64, vp, vp]
-    L.npr_sam_splice.restype = i64
-    L.npr_sam_splice.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, i64]
-    L.npr_sam_splice_text.restype = i64
-    L.npr_sam_splice_text.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, i64]
-    L.npr_cigar_text_packed.restype = i64
-    L.npr_cigar_text_packed.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64]
-    L.npr_batch_cigar_text.restype = i64
-    L.npr_batch_cigar_text.argtypes = [vp, vp, vp, i64]
-    L.npr_seed_index_create.restype = i32
-    L.npr_seed_index_create.argtypes = [vp, i32, i64, vp, vp, C.POINTER(vp)]
-    L.npr_seed_index_destroy.restype = None
-    L.npr_seed_index_destroy.argtypes = [vp]
-    L.npr_seed_matches.restype = i64
-    L.npr_seed_matches.argtypes = [vp, i64, i32, i64, vp, vp, vp, vp, vp, i64]
-    L.npr_seed_sam_text.restype = i64
-    L.npr_seed_sam_text.argtypes = [i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64]
-    L.npr_seed_chains.restype = i64
-    L.npr_seed_chains.argtypes = [vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64]
-    L.npr_seed_chain_sam_text.restype = i64
-    L.npr_seed_chain_sam_text.argtypes = [i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64]
-    L.npr_fasta_index.restype = i64
-    L.npr_fasta_index.argtypes = [vp, i64, vp, vp, i64]
-    L.npr_fasta_pack.restype = i32
-    L.npr_fasta_pack.argtypes = [vp, vp, i64, vp, vp]
-    L.npr_fastq_index.restype = i64
-    L.npr_fastq_index.argtypes = [vp, i64, vp, i64]
-    L.npr_names_mark.restype = i64
-    L.npr_names_mark.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp]
-    L.npr_batch_create_spans.restype = i32
-    L.npr_batch_create_spans.argtypes = [vp, C.POINTER(Params), i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -298,16 +218,20 @@ def ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def check(rc, where, ctx=None):
+    """The return value of an entry point: a negative one raises NprError (with ctx.last_error() when the Context is given), any other --
+    NPR_OK, or the count, length or stage of the entry points that return one -- is handed back."""
+    if rc < 0:
+        raise NprError(int(rc), where, ctx.last_error() if ctx is not None else "")
+    return rc
+
+
 def _sized(fn, where, args, ctx=None, buffer=None):
     """The two calls of an entry point whose last arguments are (out, cap) and which returns the length of its text: the sizing call
     fn(*args, None, 0), then the filling call into `buffer` (a uint8 array) when that is large enough, else into a new array.  -> the
     text, a view of the array it was written into.  `ctx`: the Context whose last_error() goes with a failure."""
-    total = int(fn(*args, None, 0))
-    if total < 0:
-        raise NprError(total, where, ctx.last_error() if ctx is not None else "")
+    total = int(check(fn(*args, None, 0), where, ctx))
     if buffer is None or buffer.size < max(total, 1):
         buffer = np.empty(max(total, 1), dtype=np.uint8)  # (filled by the call: no memset first)
-    rc = int(fn(*args, ptr(buffer), total))
-    if rc < 0:
-        raise NprError(rc, where, ctx.last_error() if ctx is not None else "")
+    check(fn(*args, ptr(buffer), total), where, ctx)
     return buffer[:total]

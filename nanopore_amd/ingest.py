@@ -14,9 +14,10 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import _sized, ptr
+from ._lib import _sized, check, ptr
+from .realign import _arr, _packed_cigars, _ragged
 
-SAM_COLS = 16
+SAM_COLS = _lib.SAM_COLS
 (F_QNAME_END, F_RNAME_LO, F_RNAME_HI, F_CIGAR_LO, F_CIGAR_HI, F_SEQ_LO, F_SEQ_HI, F_FLAG, F_POS, F_MAPQ, F_TID, F_QUERY_LO,
  F_QUERY_HI, F_GUIDE_OPS, F_REF_SPAN, F_STATUS) = range(SAM_COLS)
 SAM_NO_REFERENCE, SAM_UNKNOWN_REFERENCE = 1, 2  # F_STATUS besides NPR_OK / NPR_ERR_INVALID (include/nprealign.h)
@@ -27,12 +28,6 @@ def _map(path):
     if os.path.getsize(path) == 0:
         return np.zeros(0, dtype=np.uint8)
     return np.memmap(path, dtype=np.uint8, mode="r")
-
-
-def _check(rc, where):
-    if rc < 0:
-        raise _lib.NprError(int(rc), where)
-    return rc
 
 
 class SamText(object):
@@ -51,12 +46,12 @@ class SamText(object):
         self.span = np.zeros((guess, 2), dtype=np.int64)
         n = L.npr_sam_index(ptr(self.text), n_bytes, C.byref(hend), ptr(self.span), guess)
         if n == _lib.ERR_CAPACITY:
-            n = _check(L.npr_sam_index(ptr(self.text), n_bytes, C.byref(hend), None, 0), "npr_sam_index")
+            n = check(L.npr_sam_index(ptr(self.text), n_bytes, C.byref(hend), None, 0), "npr_sam_index")
             self.span = np.zeros((n, 2), dtype=np.int64)
             if n:
-                _check(L.npr_sam_index(ptr(self.text), n_bytes, C.byref(hend), ptr(self.span), n), "npr_sam_index")
+                check(L.npr_sam_index(ptr(self.text), n_bytes, C.byref(hend), ptr(self.span), n), "npr_sam_index")
         else:
-            self.span = self.span[:_check(n, "npr_sam_index")]
+            self.span = self.span[:check(n, "npr_sam_index")]
         self.header = bytes(self.text[:hend.value])
         self.references, self.lengths = [], []
         for line in self.header.decode("ascii", errors="replace").splitlines():
@@ -64,11 +59,7 @@ class SamText(object):
                 fields = dict(f.split(":", 1) for f in line.split("\t")[1:] if ":" in f)
                 self.references.append(fields.get("SN", "*"))
                 self.lengths.append(int(fields.get("LN", 0)))
-        names = [r.encode() for r in self.references]
-        self._rn = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)
-        self._rn_off = np.zeros(len(names) + 1, dtype=np.int64)
-        if names:
-            np.cumsum([len(x) for x in names], out=self._rn_off[1:])
+        self._rn, self._rn_off = _ragged([r.encode() for r in self.references])
 
     def __len__(self):
         return len(self.span)
@@ -83,8 +74,8 @@ class SamText(object):
         fields = np.zeros((n, SAM_COLS), dtype=np.int64)
         if n:
             span = np.ascontiguousarray(self.span[lo:hi])
-            _check(_lib.load().npr_sam_parse(ptr(self.text), ptr(span), n, ptr(self._rn), ptr(self._rn_off), len(self.references),
-                                             ptr(fields)), "npr_sam_parse")
+            check(_lib.load().npr_sam_parse(ptr(self.text), ptr(span), n, ptr(self._rn), ptr(self._rn_off), len(self.references),
+                                            ptr(fields)), "npr_sam_parse")
         return fields
 
     def records_with_a_reference(self, fields, span):
@@ -116,7 +107,7 @@ class SamText(object):
             ops = np.zeros((int(off[-1]), 2), dtype=np.int32)
         if n:
             fields = np.ascontiguousarray(fields)
-            _check(_lib.load().npr_sam_guides(ptr(self.text), ptr(fields), n, ptr(off), ptr(ops)), "npr_sam_guides")
+            check(_lib.load().npr_sam_guides(ptr(self.text), ptr(fields), n, ptr(off), ptr(ops)), "npr_sam_guides")
         return off, ops
 
     def splice(self, span, fields, word_off, n_ops, words, take=None):
@@ -124,11 +115,8 @@ class SamText(object):
         of the buffer `take(nbytes)` returns (a uint8 array of at least that size), when the caller has a pool of them."""
         L = _lib.load()
         n = len(fields)
-        span = np.ascontiguousarray(span, dtype=np.int64)
-        fields = np.ascontiguousarray(fields, dtype=np.int64)
-        word_off = np.ascontiguousarray(word_off, dtype=np.int64)
-        n_ops = np.ascontiguousarray(n_ops, dtype=np.int64)
-        words = np.ascontiguousarray(words, dtype=np.uint32)
+        span, fields = _arr(span, np.int64), _arr(fields, np.int64)
+        word_off, n_ops, words = _packed_cigars(word_off, n_ops, words)
         rec_off = np.zeros(n + 1, dtype=np.int64)
         args = [ptr(self.text), ptr(span), ptr(fields), n, ptr(word_off), ptr(n_ops), ptr(words), ptr(rec_off)]
         if take is not None:
@@ -136,7 +124,7 @@ class SamText(object):
             # call first: the sizing pass over 10^7-10^8 operations is a third of the work, and pages nobody touches cost nothing
             bound = int((span[:, 1] - span[:, 0]).sum() + 11 * n_ops.sum() + 2 * n + 1)
             out = take(bound)
-            total = _check(L.npr_sam_splice(*args, ptr(out), out.nbytes), "npr_sam_splice")
+            total = check(L.npr_sam_splice(*args, ptr(out), out.nbytes), "npr_sam_splice")
             return out[:int(total)]
         return _sized(L.npr_sam_splice, "npr_sam_splice", args)
 
@@ -145,15 +133,13 @@ class SamText(object):
         CIGAR replaced by cigar_text[str_off[i]:str_off[i + 1]]."""
         L = _lib.load()
         n = len(fields)
-        span = np.ascontiguousarray(span, dtype=np.int64)
-        fields = np.ascontiguousarray(fields, dtype=np.int64)
-        str_off = np.ascontiguousarray(str_off, dtype=np.int64)
-        cigar_text = np.ascontiguousarray(cigar_text, dtype=np.uint8)
+        span, fields = _arr(span, np.int64), _arr(fields, np.int64)
+        str_off, cigar_text = _arr(str_off, np.int64), _arr(cigar_text, np.uint8)
         rec_off = np.zeros(n + 1, dtype=np.int64)
         args = [ptr(self.text), ptr(span), ptr(fields), n, ptr(str_off), ptr(cigar_text), ptr(rec_off)]
         if take is not None:  # (the sizes are known without a pass over anything: the bound is exact up to the fields cut out)
             out = take(int((span[:, 1] - span[:, 0]).sum() + (str_off[-1] - str_off[0] if n else 0) + 2 * n + 1))
-            total = _check(L.npr_sam_splice_text(*args, ptr(out), out.nbytes), "npr_sam_splice_text")
+            total = check(L.npr_sam_splice_text(*args, ptr(out), out.nbytes), "npr_sam_splice_text")
             return out[:int(total)]
         return _sized(L.npr_sam_splice_text, "npr_sam_splice_text", args)
 
@@ -168,16 +154,16 @@ class FastaTable(object):
     def __init__(self, path):
         L = _lib.load()
         text = _map(path)
-        n = _check(L.npr_fasta_index(ptr(text), len(text), None, None, 0), "npr_fasta_index")
+        n = check(L.npr_fasta_index(ptr(text), len(text), None, None, 0), "npr_fasta_index")
         rec = np.zeros((n, 4), dtype=np.int64)
         lens = np.zeros(n, dtype=np.int64)
         if n:
-            _check(L.npr_fasta_index(ptr(text), len(text), ptr(rec), ptr(lens), n), "npr_fasta_index")
+            check(L.npr_fasta_index(ptr(text), len(text), ptr(rec), ptr(lens), n), "npr_fasta_index")
         self.off = np.zeros(n + 1, dtype=np.int64)
         np.cumsum(lens, out=self.off[1:])
         self.seq = np.zeros(max(int(self.off[-1]), 1), dtype=np.uint8)
         if n:
-            _check(L.npr_fasta_pack(ptr(text), ptr(rec), n, ptr(self.off), ptr(self.seq)), "npr_fasta_pack")
+            check(L.npr_fasta_pack(ptr(text), ptr(rec), n, ptr(self.off), ptr(self.seq)), "npr_fasta_pack")
         self.names = [bytes(text[a:b]).decode("ascii", errors="replace") for a, b in rec[:, :2]]
         self.index = {}
         for k, name in enumerate(self.names):
@@ -202,10 +188,10 @@ class FastqTable(object):
         L = _lib.load()
         self.path = path
         self.text = _map(path)
-        n = _check(L.npr_fastq_index(ptr(self.text), len(self.text), None, 0), "npr_fastq_index")
+        n = check(L.npr_fastq_index(ptr(self.text), len(self.text), None, 0), "npr_fastq_index")
         rec = np.zeros((n, 4), dtype=np.int64)
         if n:
-            _check(L.npr_fastq_index(ptr(self.text), len(self.text), ptr(rec), n), "npr_fastq_index")
+            check(L.npr_fastq_index(ptr(self.text), len(self.text), ptr(rec), n), "npr_fastq_index")
         self.name_span = np.ascontiguousarray(rec[:, 0:2])
         self.seq_span = np.ascontiguousarray(rec[:, 2:4])
         self.lengths = self.seq_span[:, 1] - self.seq_span[:, 0]
@@ -222,11 +208,5 @@ class FastqTable(object):
 
 def fastq_table(path):
     """getFastqDictionary (utils.py:240-245) without a Python loop over the lines: (names, text, seq spans [n, 2])."""
-    L = _lib.load()
-    text = _map(path)
-    n = _check(L.npr_fastq_index(ptr(text), len(text), None, 0), "npr_fastq_index")
-    rec = np.zeros((n, 4), dtype=np.int64)
-    if n:
-        _check(L.npr_fastq_index(ptr(text), len(text), ptr(rec), n), "npr_fastq_index")
-    names = [bytes(text[a:b]).decode("ascii", errors="replace") for a, b in rec[:, :2]]
-    return names, text, rec[:, 2:4].copy()
+    table = FastqTable(path)
+    return [table.name(i) for i in range(len(table))], table.text, table.seq_span

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (BAND_ANCHOR, BAND_FIXED, ERR_CAPACITY, ERR_NOMEM, MODE_ALL_POSTERIORS, MODE_EXPECTATIONS, MODE_REALIGN, MODE_RESCORE_ORIGINAL, NprError,
-                   Params, _sized, ptr)
+                   Params, _sized, check, ptr)
 
 
 def make_params(band_mode=BAND_ANCHOR, diagonal_expansion=10, constraint_trim=14, split_threshold=3000,
@@ -24,17 +24,25 @@ def make_params(band_mode=BAND_ANCHOR, diagonal_expansion=10, constraint_trim=14
                   match_gamma, posterior_threshold, mode, max_pairs_per_base)
 
 
-def _csr(seqs):
-    """list of bytes/str -> (uint8 buffer, int64 offsets)."""
-    lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=len(seqs))
-    off = np.zeros(len(seqs) + 1, dtype=np.int64)
-    np.cumsum(lens, out=off[1:])
-    buf = np.empty(int(off[-1]), dtype=np.uint8)
-    for i, s in enumerate(seqs):
-        if isinstance(s, str):
-            s = s.encode("ascii")
-        buf[off[i]:off[i + 1]] = np.frombuffer(s, dtype=np.uint8) if not isinstance(s, np.ndarray) else s
-    return buf, off
+def _arr(x, dtype, cols=None):
+    """None for None, else x as a contiguous array of `dtype`, as rows of `cols` when that is given."""
+    if x is None:
+        return None
+    a = np.ascontiguousarray(x, dtype=dtype)
+    return a if cols is None else a.reshape(-1, cols)
+
+
+def _csr(items, pad=False):
+    """list of bytes / str / uint8 arrays -> (uint8 buffer, int64 offsets[n + 1]).  pad: a buffer without bytes becomes one zero byte,
+    for the entry points that refuse a null pointer."""
+    items = [s.encode("ascii") if isinstance(s, str) else s.astype(np.uint8).tobytes() if isinstance(s, np.ndarray) else s for s in items]
+    off = np.zeros(len(items) + 1, dtype=np.int64)
+    np.cumsum(np.fromiter(map(len, items), dtype=np.int64, count=len(items)), out=off[1:])
+    return np.frombuffer(b"".join(items) or (b"\0" if pad else b""), dtype=np.uint8), off
+
+
+def _ragged(items):
+    return _csr(items, pad=True)
 
 
 def _csr_ops(guides):
@@ -48,86 +56,112 @@ def _csr_ops(guides):
     return ops, off
 
 
-class Batch(object):
+def _host_alignments(refs, reads, cigars, ref_index, start):
+    """Alignments given on the host, as npr_align_stats and npr_align_indel_kmers take them: (n_reads, n_refs, the eight arrays from
+    `ref` to `start` in the order of both signatures)."""
+    ref, ref_off = _csr(refs)
+    read, read_off = _csr(reads)
+    ops, ops_off = _csr_ops(cigars)
+    return len(read_off) - 1, len(ref_off) - 1, (ref, ref_off, _arr(ref_index, np.int32), read, read_off, ops, ops_off, _arr(start, np.int64, 2))
+
+
+def _packed_cigars(word_off, n_ops, words):
+    """Packed cigars (one uint32 per op, length << 2 | op; list i at words[word_off[i] .. + n_ops[i])) as the library takes them."""
+    return _arr(word_off, np.int64), _arr(n_ops, np.int64), _arr(words, np.uint32)
+
+
+def _read_spans(text, name_span, begin, end):
+    """Reads and their names as spans of one text (FastqTable.text / .name_span / .seq_span) as the library takes them."""
+    return _arr(text, np.uint8), _arr(name_span, np.int64, 2), _arr(begin, np.int64), _arr(end, np.int64)
+
+
+class _Handle(object):
+    """An object of the library that belongs to a Context (Batch, Pileup, SeedIndex): destroyed once, by close(), by the context's
+    close() or when it is collected, whichever comes first."""
+    _destroy = None  # the entry point that destroys the handle
+
+    def _create(self, ctx, create, where, *args):
+        """self._h = the handle `create`(ctx, *args, &handle) makes."""
+        self._L, self.ctx, self._h = _lib.load(), ctx, None
+        h = C.c_void_p()
+        check(getattr(self._L, create)(ctx._h, *args, C.byref(h)), where, ctx)
+        self._h = h
+        ctx._open.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Batch(_Handle):
     """A staged batch: inputs resident in HBM after construction."""
+    _destroy = "npr_batch_destroy"
 
     def __init__(self, ctx, params, ref, ref_off, read, read_off, guide_ops, guide_off, model_slot=None,
                  ref_index=None, guide_start=None, read_end=None):
-        self._L = _lib.load()
-        self.ctx = ctx
+        model_slot, ref_index, guide_start = _arr(model_slot, np.int32), _arr(ref_index, np.int32), _arr(guide_start, np.int64, 2)
         n_refs = len(ref_off) - 1
         self._keep = (ref, ref_off, read, read_off, guide_ops, guide_off, model_slot, ref_index, guide_start, read_end)
-        h = C.c_void_p()
         if read_end is not None:  # reads scattered in `read` (the SEQ fields of a mapped SAM text): read_off = their starts
             self.n_reads = len(read_off)
-            rc = self._L.npr_batch_create_spans(ctx._h, C.byref(params), self.n_reads, n_refs, ptr(ref), ptr(ref_off),
-                                                ptr(ref_index), ptr(read), ptr(read_off), ptr(read_end), ptr(guide_ops), ptr(guide_off),
-                                                ptr(guide_start), ptr(model_slot), C.byref(h))
+            self._create(ctx, "npr_batch_create_spans", "npr_batch_create", C.byref(params), self.n_reads, n_refs, ptr(ref), ptr(ref_off),
+                         ptr(ref_index), ptr(read), ptr(read_off), ptr(read_end), ptr(guide_ops), ptr(guide_off), ptr(guide_start),
+                         ptr(model_slot))
         else:
             self.n_reads = len(read_off) - 1
-            rc = self._L.npr_batch_create_at(ctx._h, C.byref(params), self.n_reads, n_refs, ptr(ref), ptr(ref_off),
-                                             ptr(ref_index), ptr(read), ptr(read_off), ptr(guide_ops), ptr(guide_off),
-                                             ptr(guide_start), ptr(model_slot), C.byref(h))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_create", ctx.last_error())
-        self._h = h
-        ctx._open.add(self)
+            self._create(ctx, "npr_batch_create_at", "npr_batch_create", C.byref(params), self.n_reads, n_refs, ptr(ref), ptr(ref_off),
+                         ptr(ref_index), ptr(read), ptr(read_off), ptr(guide_ops), ptr(guide_off), ptr(guide_start), ptr(model_slot))
 
     def class_stats(self):
         """(tasks, cells) per kernel class (include/nprealign.h: npr_batch_class_stats)."""
         t = np.zeros(32, dtype=np.int64)
         c = np.zeros(32, dtype=np.int64)
-        k = self._L.npr_batch_class_stats(self._h, ptr(t), ptr(c), 32)
+        k = check(self._L.npr_batch_class_stats(self._h, ptr(t), ptr(c), 32), "npr_batch_class_stats", self.ctx)
         return t[:k], c[:k]
 
     def segment_arith(self):
         """-> (seg_off[n+1], arith): per segment of every read, in read order, the device arithmetic it ran in (0: one
         exponent per cell, 1: one per anti-diagonal row; include/nprealign.h: npr_batch_segment_arith)."""
         off = np.zeros(self.n_reads + 1, dtype=np.int64)
-        rc = self._L.npr_batch_segment_arith(self._h, ptr(off), None, 0)
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_segment_arith")
+        check(self._L.npr_batch_segment_arith(self._h, ptr(off), None, 0), "npr_batch_segment_arith", self.ctx)
         ar = np.zeros(max(int(off[-1]), 1), dtype=np.int32)
-        self._L.npr_batch_segment_arith(self._h, ptr(off), ptr(ar), len(ar))
+        check(self._L.npr_batch_segment_arith(self._h, ptr(off), ptr(ar), len(ar)), "npr_batch_segment_arith", self.ctx)
         return off, ar[:int(off[-1])]
 
     def stats(self):
         st = _lib.BatchStats()
-        self._L.npr_batch_get_stats(self._h, C.byref(st))
+        check(self._L.npr_batch_get_stats(self._h, C.byref(st)), "npr_batch_get_stats", self.ctx)
         return {k: getattr(st, k) for k, _ in st._fields_}
 
     def run(self):
         """Device DP pass (forward + backward + posterior extraction).  Returns kernel milliseconds
         measured with HIP events on the library's stream."""
         ms = C.c_float(0)
-        rc = self._L.npr_batch_run(self._h, C.byref(ms))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_run", self.ctx.last_error())
+        check(self._L.npr_batch_run(self._h, C.byref(ms)), "npr_batch_run", self.ctx)
         return ms.value
 
     def finish(self):
-        rc = self._L.npr_batch_finish(self._h)
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_finish", self.ctx.last_error())
+        check(self._L.npr_batch_finish(self._h), "npr_batch_finish", self.ctx)
 
     def results(self):
         out = np.zeros(self.n_reads, dtype=_lib.RESULT_DTYPE)
         assert out.dtype.itemsize == C.sizeof(_lib.ReadResult)
-        rc = self._L.npr_batch_results(self._h, ptr(out))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_results")
+        check(self._L.npr_batch_results(self._h, ptr(out)), "npr_batch_results", self.ctx)
         return out
 
     def ops(self):
         """-> (ops_off[n+1], ops[k,2]) CSR of output cigars."""
         off = np.zeros(self.n_reads + 1, dtype=np.int64)
-        rc = self._L.npr_batch_ops(self._h, ptr(off), None, 0)
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_ops")
+        check(self._L.npr_batch_ops(self._h, ptr(off), None, 0), "npr_batch_ops", self.ctx)
         ops = np.zeros((int(off[-1]), 2), dtype=np.int32)
-        rc = self._L.npr_batch_ops(self._h, ptr(off), ptr(ops), len(ops))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_ops")
+        check(self._L.npr_batch_ops(self._h, ptr(off), ptr(ops), len(ops)), "npr_batch_ops", self.ctx)
         return off, ops
 
     def ops_packed(self):
@@ -139,15 +173,11 @@ class Batch(object):
         """ops_packed for a caller that fetches batch after batch: -> (offsets, words, buffer) -- the words are a view of `buffer`
         (a uint32 array or None) when it is large enough, else of a new, larger one, which is returned for the next call."""
         off = np.zeros(self.n_reads + 1, dtype=np.int64)
-        rc = self._L.npr_batch_ops_packed(self._h, ptr(off), None, 0)
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_ops_packed", self.ctx.last_error())
+        check(self._L.npr_batch_ops_packed(self._h, ptr(off), None, 0), "npr_batch_ops_packed", self.ctx)
         total = int(off[-1])
         if buffer is None or buffer.size < max(total, 1):
             buffer = np.empty(max(total + (total // 4 if slack else 0), 1), dtype=np.uint32)  # (filled by the call: no memset first)
-        rc = self._L.npr_batch_ops_packed(self._h, ptr(off), ptr(buffer), total)
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_ops_packed", self.ctx.last_error())
+        check(self._L.npr_batch_ops_packed(self._h, ptr(off), ptr(buffer), total), "npr_batch_ops_packed", self.ctx)
         return off, buffer[:total], buffer
 
     def cigar_text(self, buffer=None):
@@ -159,63 +189,46 @@ class Batch(object):
 
     def debug_set_pairs(self, read, x, y, p, task_status=0):
         """TEST HOOK (include/nprealign.h npr_batch_debug_set_pairs): replaces on the device the posterior pairs the DP pass left for `read`."""
-        x = np.ascontiguousarray(x, np.int32)
-        y = np.ascontiguousarray(y, np.int32)
-        p = np.ascontiguousarray(p, np.float32)
-        rc = self._L.npr_batch_debug_set_pairs(self._h, int(read), ptr(x), ptr(y), ptr(p), len(x), int(task_status))
-        if rc != 0:
-            raise NprError(rc, "npr_batch_debug_set_pairs")
+        x, y, p = _arr(x, np.int32), _arr(y, np.int32), _arr(p, np.float32)
+        check(self._L.npr_batch_debug_set_pairs(self._h, int(read), ptr(x), ptr(y), ptr(p), len(x), int(task_status)), "npr_batch_debug_set_pairs", self.ctx)
 
     def finish_stage(self):
         """TEST HOOK (include/nprealign.h npr_batch_debug_finish_stage): the stage the last finish() took, FINISH_DEVICE (0) or FINISH_HOST (1)."""
-        rc = self._L.npr_batch_debug_finish_stage(self._h)
-        if rc < 0:
-            raise NprError(rc, "npr_batch_debug_finish_stage")
-        return int(rc)
+        return int(check(self._L.npr_batch_debug_finish_stage(self._h), "npr_batch_debug_finish_stage", self.ctx))
 
     def pairs(self):
         """-> (pair_off[n+1], x, y, p) sparse posterior match probabilities sorted by (x, y)."""
         off = np.zeros(self.n_reads + 1, dtype=np.int64)
-        rc = self._L.npr_batch_pairs(self._h, ptr(off), None, None, None, 0)
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_pairs")
+        check(self._L.npr_batch_pairs(self._h, ptr(off), None, None, None, 0), "npr_batch_pairs", self.ctx)
         k = int(off[-1])
         x = np.zeros(k, dtype=np.int32)
         y = np.zeros(k, dtype=np.int32)
         p = np.zeros(k, dtype=np.float32)
-        rc = self._L.npr_batch_pairs(self._h, ptr(off), ptr(x), ptr(y), ptr(p), k)
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_pairs")
+        check(self._L.npr_batch_pairs(self._h, ptr(off), ptr(x), ptr(y), ptr(p), k), "npr_batch_pairs", self.ctx)
         return off, x, y, p
 
     def base_expectations(self, ref_lengths, use=None):
         """Posterior-weighted base counts per reference position of the (selected) reads, scattered on the device
         (include/nprealign.h: npr_batch_base_expectations): (expect[sum(ref_lengths), 4], seen[sum(ref_lengths)])."""
-        ref_lengths = np.ascontiguousarray(ref_lengths, dtype=np.int64)
+        ref_lengths = _arr(ref_lengths, np.int64)
         rows = int(ref_lengths.sum())
         expect = np.zeros((rows, 4), dtype=np.float64)
         seen = np.zeros(rows, dtype=np.uint8)
-        u = None if use is None else np.ascontiguousarray(use, dtype=np.uint8)
-        rc = self._L.npr_batch_base_expectations(self._h, ptr(u), len(ref_lengths), ptr(ref_lengths), ptr(expect), ptr(seen))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_base_expectations", self.ctx.last_error())
+        u = _arr(use, np.uint8)
+        check(self._L.npr_batch_base_expectations(self._h, ptr(u), len(ref_lengths), ptr(ref_lengths), ptr(expect), ptr(seen)),
+              "npr_batch_base_expectations", self.ctx)
         return expect, seen.astype(bool)
 
     def plan_check(self):
         """Tasks whose device-made band rows / schedules / stripe tables differ from the host planner's (test aid;
         include/nprealign.h: npr_batch_plan_check)."""
-        rc = self._L.npr_batch_plan_check(self._h, ptr(self._keep[4]))
-        if rc < 0:
-            raise NprError(int(rc), "npr_batch_plan_check", self.ctx.last_error())
-        return int(rc)
+        return int(check(self._L.npr_batch_plan_check(self._h, ptr(self._keep[4])), "npr_batch_plan_check", self.ctx))
 
     def align_stats(self):
         """Per-read reductions over the aligned pairs of the cigars finish() produced, computed where they lie
         (include/nprealign.h: npr_batch_align_stats): int32 array [n_reads, STATS_WORDS]."""
         out = np.zeros((self.n_reads, _lib.STATS_WORDS), dtype=np.int32)
-        rc = self._L.npr_batch_align_stats(self._h, ptr(out))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_align_stats", self.ctx.last_error())
+        check(self._L.npr_batch_align_stats(self._h, ptr(out)), "npr_batch_align_stats", self.ctx)
         return out
 
     def indel_kmers(self, k=5):
@@ -223,9 +236,7 @@ class Batch(object):
         npr_batch_indel_kmers): (read-side table, reference-side table), int64 [4^k + 1] each."""
         nb = 4 ** k + 1 if 1 <= k <= _lib.KMER_MAX_K else 1
         rd, rf = np.zeros(nb, dtype=np.int64), np.zeros(nb, dtype=np.int64)
-        rc = self._L.npr_batch_indel_kmers(self._h, int(k), ptr(rd), ptr(rf))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_indel_kmers", self.ctx.last_error())
+        check(self._L.npr_batch_indel_kmers(self._h, int(k), ptr(rd), ptr(rf)), "npr_batch_indel_kmers", self.ctx)
         return rd, rf
 
     def expectations(self):
@@ -234,9 +245,7 @@ class Batch(object):
         E = np.zeros((_lib.MAX_MODELS, 80))
         ll = np.zeros(_lib.MAX_MODELS)
         ms = C.c_float(0)
-        rc = self._L.npr_batch_expectations(self._h, ptr(T), ptr(E), ptr(ll), C.byref(ms))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_expectations", self.ctx.last_error())
+        check(self._L.npr_batch_expectations(self._h, ptr(T), ptr(E), ptr(ll), C.byref(ms)), "npr_batch_expectations", self.ctx)
         return T, E, ll, ms.value
 
     def dense(self, read_index, cells):
@@ -244,58 +253,35 @@ class Batch(object):
         fe = np.zeros(cells, dtype=np.int32)
         bv = np.zeros(cells, dtype=np.float32)
         be = np.zeros(cells, dtype=np.int32)
-        rc = self._L.npr_batch_dense(self._h, read_index, ptr(fv), ptr(fe), ptr(bv), ptr(be), cells)
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_dense", self.ctx.last_error())
+        check(self._L.npr_batch_dense(self._h, read_index, ptr(fv), ptr(fe), ptr(bv), ptr(be), cells), "npr_batch_dense", self.ctx)
         return fv, fe, bv, be
 
     def rs_forward(self, read_index, cells):
         """include/nprealign.h: npr_batch_rs_forward -- the forward match rows k_dp_rs stores, (value, row exponent) in band order."""
         fv = np.zeros(cells, dtype=np.float32)
         fe = np.zeros(cells, dtype=np.int32)
-        rc = self._L.npr_batch_rs_forward(self._h, read_index, ptr(fv), ptr(fe), cells)
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_batch_rs_forward", self.ctx.last_error())
+        check(self._L.npr_batch_rs_forward(self._h, read_index, ptr(fv), ptr(fe), cells), "npr_batch_rs_forward", self.ctx)
         return fv, fe
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.npr_batch_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Pileup(object):
+class Pileup(_Handle):
     """A per-position table on the device (include/nprealign.h: npr_pileup_*; csrc/npr_pileup.hip): PILEUP_WORDS int32 counters per
     position of the reference sequences whose lengths it was made with, rows in their order.  It accumulates over add_batch() / add()
     calls -- a file realigned in several chunks is one table -- and may be read in between."""
+    _destroy = "npr_pileup_destroy"
 
     def __init__(self, ctx, ref_lengths):
-        self._L = _lib.load()
-        self.ctx = ctx
-        self.ref_lengths = np.ascontiguousarray(ref_lengths, dtype=np.int64).reshape(-1)
+        self.ref_lengths = _arr(ref_lengths, np.int64).reshape(-1)
         self.rows = int(self.ref_lengths.sum())
-        h = C.c_void_p()
-        rc = self._L.npr_pileup_create(ctx._h, len(self.ref_lengths), ptr(self.ref_lengths), C.byref(h))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_pileup_create", ctx.last_error())
-        self._h = h
-        ctx._open.add(self)
+        self._create(ctx, "npr_pileup_create", "npr_pileup_create", len(self.ref_lengths), ptr(self.ref_lengths))
 
     def add_batch(self, batch, use=None):
         """The alignments batch.finish() just produced, where they lie; use[i] != 0 selects read i (None: all); reads that failed add
         nothing."""
-        u = None if use is None else np.ascontiguousarray(use, dtype=np.uint8)
+        u = _arr(use, np.uint8)
         if u is not None and len(u) != batch.n_reads:
             raise ValueError("use must have one entry per read of the batch")
-        rc = self._L.npr_pileup_add_batch(self._h, batch._h, ptr(u))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_pileup_add_batch", self.ctx.last_error())
+        check(self._L.npr_pileup_add_batch(self._h, batch._h, ptr(u)), "npr_pileup_add_batch", self.ctx)
 
     def add(self, reads, cigars, ref_index, start=None, use=None):
         """Any alignments: reads = ASCII sequences, cigars = [(op, len)] lists with ops M/I/D (0/1/2), ref_index[i] = the reference
@@ -307,28 +293,20 @@ class Pileup(object):
     def add_csr(self, read, read_begin, read_end, ops, ops_off, ref_index, start=None, use=None):
         """add() on arrays: read i = read[read_begin[i] : read_end[i]] (read_end None: read_begin has n + 1 entries, the reads lie back
         to back), cigar i = ops[ops_off[i] : ops_off[i + 1]] (rows of (op, len))."""
-        read = np.ascontiguousarray(read, dtype=np.uint8)
-        read_begin = np.ascontiguousarray(read_begin, dtype=np.int64)
-        read_end = None if read_end is None else np.ascontiguousarray(read_end, dtype=np.int64)
-        ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 2)
-        ops_off = np.ascontiguousarray(ops_off, dtype=np.int64)
+        read, read_begin, read_end = _arr(read, np.uint8), _arr(read_begin, np.int64), _arr(read_end, np.int64)
+        ops, ops_off = _arr(ops, np.int32, 2), _arr(ops_off, np.int64)
         n = len(ops_off) - 1
-        ri = np.ascontiguousarray(ref_index, dtype=np.int32)
-        st = None if start is None else np.ascontiguousarray(start, dtype=np.int64).reshape(-1, 2)
-        u = None if use is None else np.ascontiguousarray(use, dtype=np.uint8)
+        ri, st, u = _arr(ref_index, np.int32), _arr(start, np.int64, 2), _arr(use, np.uint8)
         if len(ri) != n or len(read_begin) != (n + 1 if read_end is None else n) or (read_end is not None and len(read_end) != n) or \
                 (st is not None and len(st) != n) or (u is not None and len(u) != n):
             raise ValueError("one reference index, read, start and use entry per cigar")
-        rc = self._L.npr_pileup_add(self._h, n, ptr(ri), ptr(read), ptr(read_begin), ptr(read_end), ptr(ops), ptr(ops_off), ptr(st), ptr(u))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_pileup_add", self.ctx.last_error())
+        check(self._L.npr_pileup_add(self._h, n, ptr(ri), ptr(read), ptr(read_begin), ptr(read_end), ptr(ops), ptr(ops_off), ptr(st), ptr(u)),
+              "npr_pileup_add", self.ctx)
 
     def counts(self):
         """The table so far: int32 [rows, PILEUP_WORDS]."""
         out = np.zeros((self.rows, _lib.PILEUP_WORDS), dtype=np.int32)
-        rc = self._L.npr_pileup_counts(self._h, ptr(out))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_pileup_counts", self.ctx.last_error())
+        check(self._L.npr_pileup_counts(self._h, ptr(out)), "npr_pileup_counts", self.ctx)
         return out
 
     def depth(self):
@@ -336,40 +314,20 @@ class Pileup(object):
         (M or deletion columns), summed on the device."""
         depth = np.zeros(self.rows, dtype=np.int32)
         covered = np.zeros(self.rows, dtype=np.uint8)
-        rc = self._L.npr_pileup_depth(self._h, ptr(depth), ptr(covered))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_pileup_depth", self.ctx.last_error())
+        check(self._L.npr_pileup_depth(self._h, ptr(depth), ptr(covered)), "npr_pileup_depth", self.ctx)
         return depth, covered.astype(bool)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.npr_pileup_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SeedIndex(object):
+class SeedIndex(_Handle):
     """The exact-match seed index of a set of reference sequences on the device (include/nprealign.h: npr_seed_*; csrc/npr_seed.hip):
     built once, asked for the maximal exact matches of any number of reads."""
+    _destroy = "npr_seed_index_destroy"
 
     def __init__(self, ctx, ref, ref_off, k=16):
-        self._L = _lib.load()
-        self.ctx = ctx
         self.k = int(k)
-        ref = np.ascontiguousarray(ref, dtype=np.uint8)
-        ref_off = np.ascontiguousarray(ref_off, dtype=np.int64)
+        ref, ref_off = _arr(ref, np.uint8), _arr(ref_off, np.int64)
         self.n_refs = len(ref_off) - 1
-        h = C.c_void_p()
-        rc = self._L.npr_seed_index_create(ctx._h, self.k, self.n_refs, ptr(ref), ptr(ref_off), C.byref(h))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_seed_index_create", ctx.last_error())
-        self._h = h
-        ctx._open.add(self)
+        self._create(ctx, "npr_seed_index_create", "npr_seed_index_create", self.k, self.n_refs, ptr(ref), ptr(ref_off))
 
     def matches(self, text, begin, end, min_len=20, strands=3, chunk_bases=1 << 26):
         """All maximal exact matches of at least min_len bases of the reads text[begin[i]:end[i]] (spans inside a larger uint8 text, e.g.
@@ -377,8 +335,7 @@ class SeedIndex(object):
         the rows of read i are hits[hit_off[i]:hit_off[i + 1]], each (reference index, a, b | strand << 31, L), sorted by (strand,
         reference index, a, b).  The reads go to the device in chunks of about chunk_bases bases, each counted first and then fetched
         into a buffer of exactly its size."""
-        text = np.ascontiguousarray(text, dtype=np.uint8)
-        begin, end = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
+        text, begin, end = _arr(text, np.uint8), _arr(begin, np.int64), _arr(end, np.int64)
         n = len(begin)
         if len(end) != n or (n and (int(begin.min()) < 0 or int(end.max()) > len(text))):
             raise NprError(_lib.ERR_INVALID, "npr_seed_matches", "begin and end differ in number, or a span lies outside the text")
@@ -396,23 +353,11 @@ class SeedIndex(object):
             total = self._L.npr_seed_matches(*args, None, 0)
             if total == ERR_CAPACITY:  # (there are matches: the offsets say how many)
                 rows = np.empty((int(off[-1]), 4), dtype=np.int32)
-                total = self._L.npr_seed_matches(*args, ptr(rows), len(rows))
+                total = check(self._L.npr_seed_matches(*args, ptr(rows), len(rows)), "npr_seed_matches", self.ctx)
                 parts.append(rows)
-            if total < 0:
-                raise NprError(int(total), "npr_seed_matches", self.ctx.last_error())
+            check(total, "npr_seed_matches", self.ctx)
             hit_off[lo + 1:hi + 1] = hit_off[lo] + off[1:]
         return hit_off, (np.concatenate(parts) if parts else np.zeros((0, 4), dtype=np.int32))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.npr_seed_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Context(object):
@@ -432,9 +377,7 @@ class Context(object):
 
     def set_option(self, option, value):
         """include/nprealign.h: npr_ctx_option (e.g. _lib.OPT_OVERLAP for a context of a pipelined job)."""
-        rc = self._L.npr_ctx_option(self._h, option, int(value))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_ctx_option", self.last_error())
+        check(self._L.npr_ctx_option(self._h, option, int(value)), "npr_ctx_option", self)
 
     def release_scratch(self):
         """NPR_OPT_RELEASE_SCRATCH: the device's forward scratch and this context's cached buffers go back to the driver."""
@@ -458,9 +401,8 @@ class Context(object):
             self._set(slot, m)
 
     def _set(self, slot, m):
-        rc = self._L.npr_set_hmm(self._h, slot, None, None) if m is None else self._L.npr_set_hmm(self._h, slot, ptr(m[0]), ptr(m[1]))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_set_hmm", self.last_error())
+        T, E = (None, None) if m is None else m
+        check(self._L.npr_set_hmm(self._h, slot, ptr(T), ptr(E)), "npr_set_hmm", self)
         self._models[slot] = m
 
     def last_error(self):
@@ -471,8 +413,7 @@ class Context(object):
         the stock model used when the reference passes no --loadHmm."""
         if hmm is None:
             return self._set(slot, None)
-        T = np.ascontiguousarray(hmm.transitions, dtype=np.float64)
-        E = np.ascontiguousarray(hmm.emissions, dtype=np.float64)
+        T, E = _arr(hmm.transitions, np.float64), _arr(hmm.emissions, np.float64)
         if T.size != 25 or E.size != 80:
             raise ValueError("HMM must have 25 transitions and 80 emissions")
         self._set(slot, (T, E))
@@ -482,53 +423,27 @@ class Context(object):
         ref_index[i] = which entry of `refs` read i aligns to (None: read i <-> refs[i]).
         guide_start[i] = (first reference position, first read position) of guide i -- the coordinates of the
         exonerate cigar line cactus_realign reads; None: every guide is global over both sequences."""
-        ref, ref_off = _csr(refs)
-        read, read_off = _csr(reads)
-        gops, goff = _csr_ops(guides)
-        ms = None if model_slot is None else np.ascontiguousarray(model_slot, dtype=np.int32)
-        ri = None if ref_index is None else np.ascontiguousarray(ref_index, dtype=np.int32)
-        gs = None if guide_start is None else np.ascontiguousarray(guide_start, dtype=np.int64).reshape(-1, 2)
-        return Batch(self, params, ref, ref_off, read, read_off, gops, goff, ms, ri, gs)
+        return Batch(self, params, *_csr(refs), *_csr(reads), *_csr_ops(guides), model_slot, ref_index, guide_start)
 
     def stage_csr(self, params, ref, ref_off, read, read_off, guide_ops, guide_off, model_slot=None,
                   ref_index=None, guide_start=None):
-        ref = np.ascontiguousarray(ref, dtype=np.uint8)
-        read = np.ascontiguousarray(read, dtype=np.uint8)
-        ref_off = np.ascontiguousarray(ref_off, dtype=np.int64)
-        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
-        guide_ops = np.ascontiguousarray(guide_ops, dtype=np.int32).reshape(-1, 2)
-        guide_off = np.ascontiguousarray(guide_off, dtype=np.int64)
-        ms = None if model_slot is None else np.ascontiguousarray(model_slot, dtype=np.int32)
-        ri = None if ref_index is None else np.ascontiguousarray(ref_index, dtype=np.int32)
-        gs = None if guide_start is None else np.ascontiguousarray(guide_start, dtype=np.int64).reshape(-1, 2)
-        return Batch(self, params, ref, ref_off, read, read_off, guide_ops, guide_off, ms, ri, gs)
+        return Batch(self, params, _arr(ref, np.uint8), _arr(ref_off, np.int64), _arr(read, np.uint8), _arr(read_off, np.int64),
+                     _arr(guide_ops, np.int32, 2), _arr(guide_off, np.int64), model_slot, ref_index, guide_start)
 
     def stage_spans(self, params, ref, ref_off, text, read_begin, read_end, guide_ops, guide_off, model_slot=None,
                     ref_index=None, guide_start=None):
         """Stages reads that lie scattered in `text` (uint8): read i = text[read_begin[i] : read_end[i]]
         (include/nprealign.h: npr_batch_create_spans).  guide_off may be a slice of a longer CSR: its values index guide_ops."""
-        ms = None if model_slot is None else np.ascontiguousarray(model_slot, dtype=np.int32)
-        ri = None if ref_index is None else np.ascontiguousarray(ref_index, dtype=np.int32)
-        gs = None if guide_start is None else np.ascontiguousarray(guide_start, dtype=np.int64).reshape(-1, 2)
-        return Batch(self, params, ref, np.ascontiguousarray(ref_off, dtype=np.int64), text,
-                     np.ascontiguousarray(read_begin, dtype=np.int64), np.ascontiguousarray(guide_ops, dtype=np.int32).reshape(-1, 2),
-                     np.ascontiguousarray(guide_off, dtype=np.int64), ms, ri, gs, read_end=np.ascontiguousarray(read_end, dtype=np.int64))
+        return Batch(self, params, ref, _arr(ref_off, np.int64), text, _arr(read_begin, np.int64), _arr(guide_ops, np.int32, 2),
+                     _arr(guide_off, np.int64), model_slot, ref_index, guide_start, read_end=_arr(read_end, np.int64))
 
     def align_stats(self, refs, reads, cigars, ref_index=None, start=None):
         """Per-read reductions over the aligned pairs of arbitrary alignments (a mapper's SAM records) on the device
         (include/nprealign.h: npr_align_stats).  refs / reads: ASCII sequences; cigars: [(op, len)] lists with ops M/I/D
         (0/1/2); start[i] = (first reference position, first read position) of cigar i.  int32 [n, STATS_WORDS]."""
-        ref, ref_off = _csr(refs)
-        read, read_off = _csr(reads)
-        ops, ops_off = _csr_ops(cigars)
-        n = len(read_off) - 1
-        ri = None if ref_index is None else np.ascontiguousarray(ref_index, dtype=np.int32)
-        st = None if start is None else np.ascontiguousarray(start, dtype=np.int64).reshape(-1, 2)
+        n, n_refs, arrays = _host_alignments(refs, reads, cigars, ref_index, start)
         out = np.zeros((n, _lib.STATS_WORDS), dtype=np.int32)
-        rc = self._L.npr_align_stats(self._h, n, len(ref_off) - 1, ptr(ref), ptr(ref_off), ptr(ri), ptr(read), ptr(read_off),
-                                     ptr(ops), ptr(ops_off), ptr(st), ptr(out))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_align_stats", self.last_error())
+        check(self._L.npr_align_stats(self._h, n, n_refs, *map(ptr, arrays), ptr(out)), "npr_align_stats", self)
         return out
 
     def kmer_counts(self, seqs, k=5):
@@ -537,41 +452,29 @@ class Context(object):
         most significant), the last bin for k-mers with a base outside ACGT."""
         seq, off = _csr(seqs)
         out = np.zeros(4 ** k + 1 if 1 <= k <= _lib.KMER_MAX_K else 1, dtype=np.int64)
-        rc = self._L.npr_kmer_counts(self._h, int(k), len(off) - 1, ptr(seq), ptr(off), ptr(out))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_kmer_counts", self.last_error())
+        check(self._L.npr_kmer_counts(self._h, int(k), len(off) - 1, ptr(seq), ptr(off), ptr(out)), "npr_kmer_counts", self)
         return out
 
     def kmer_counts_groups(self, text, begin, end, group, n_groups, k=5):
         """kmer_counts into one table per group in one pass (include/nprealign.h: npr_kmer_counts_groups): sequence i is
         text[begin[i]:end[i]] -- spans inside a larger uint8 text, e.g. FastqTable.text / .seq_span --, group[i] in 0 .. n_groups - 1 picks
         its table and -1 leaves it out: int64 [n_groups, 4^k + 1]."""
-        text = np.ascontiguousarray(text, dtype=np.uint8)
-        begin, end = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
-        group = np.ascontiguousarray(group, dtype=np.int32)
+        text, begin, end, group = _arr(text, np.uint8), _arr(begin, np.int64), _arr(end, np.int64), _arr(group, np.int32)
         if not (len(begin) == len(end) == len(group)) or (len(begin) and (int(begin.min()) < 0 or int(end.max()) > len(text))):
             raise NprError(_lib.ERR_INVALID, "npr_kmer_counts_groups", "spans and groups differ in number, or a span lies outside the text")
         ok = 1 <= k <= _lib.KMER_MAX_K and 1 <= n_groups <= _lib.KMER_MAX_GROUPS
         out = np.zeros((n_groups, 4 ** k + 1) if ok else (1, 1), dtype=np.int64)
-        rc = self._L.npr_kmer_counts_groups(self._h, int(k), len(begin), ptr(text), ptr(begin), ptr(end), ptr(group), int(n_groups), ptr(out))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_kmer_counts_groups", self.last_error())
+        check(self._L.npr_kmer_counts_groups(self._h, int(k), len(begin), ptr(text), ptr(begin), ptr(end), ptr(group), int(n_groups), ptr(out)),
+              "npr_kmer_counts_groups", self)
         return out
 
     def align_indel_kmers(self, refs, reads, cigars, k=5, ref_index=None, start=None):
         """The k-mers that straddle a gap of arbitrary alignments (arguments as for align_stats), counted on the device
         (include/nprealign.h: npr_align_indel_kmers): (read-side table, reference-side table), int64 [4^k + 1] each."""
-        ref, ref_off = _csr(refs)
-        read, read_off = _csr(reads)
-        ops, ops_off = _csr_ops(cigars)
-        ri = None if ref_index is None else np.ascontiguousarray(ref_index, dtype=np.int32)
-        st = None if start is None else np.ascontiguousarray(start, dtype=np.int64).reshape(-1, 2)
+        n, n_refs, arrays = _host_alignments(refs, reads, cigars, ref_index, start)
         nb = 4 ** k + 1 if 1 <= k <= _lib.KMER_MAX_K else 1
         rd, rf = np.zeros(nb, dtype=np.int64), np.zeros(nb, dtype=np.int64)
-        rc = self._L.npr_align_indel_kmers(self._h, int(k), len(read_off) - 1, len(ref_off) - 1, ptr(ref), ptr(ref_off), ptr(ri), ptr(read),
-                                           ptr(read_off), ptr(ops), ptr(ops_off), ptr(st), ptr(rd), ptr(rf))
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_align_indel_kmers", self.last_error())
+        check(self._L.npr_align_indel_kmers(self._h, int(k), n, n_refs, *map(ptr, arrays), ptr(rd), ptr(rf)), "npr_align_indel_kmers", self)
         return rd, rf
 
     def pileup(self, ref_lengths):
@@ -580,8 +483,7 @@ class Context(object):
 
     def seed_index(self, refs, k=16):
         """The exact-match seed index of the ASCII sequences `refs` (SeedIndex; include/nprealign.h: npr_seed_index_create)."""
-        ref, ref_off = _csr(refs)
-        return SeedIndex(self, ref, ref_off, k)
+        return SeedIndex(self, *_csr(refs), k)
 
     def seed_index_csr(self, ref, ref_off, k=16):
         """seed_index on arrays: sequence i = ref[ref_off[i]:ref_off[i + 1]] (FastaTable.seq / .off fit directly)."""
@@ -593,9 +495,7 @@ class Context(object):
         ops_off int64 [m + 1], ops int32 [p, 2]).  The chains of read i are chains[chain_off[i]:chain_off[i + 1]] in ascending reference
         index, each (reference index, strand, score, rows in the chain); chain c's guide over ref_len x read_len is
         ops[ops_off[c]:ops_off[c + 1]] -- what stage_csr and stage_spans take as guide_off and guide_ops."""
-        read_len, ref_len = np.ascontiguousarray(read_len, dtype=np.int64), np.ascontiguousarray(ref_len, dtype=np.int64)
-        hit_off = np.ascontiguousarray(hit_off, dtype=np.int64)
-        hits = np.ascontiguousarray(hits, dtype=np.int32).reshape(-1, 4)
+        read_len, ref_len, hit_off, hits = _arr(read_len, np.int64), _arr(ref_len, np.int64), _arr(hit_off, np.int64), _arr(hits, np.int32, 4)
         n = len(read_len)
         if len(hit_off) != n + 1 or int(hit_off[-1]) != len(hits):
             raise NprError(_lib.ERR_INVALID, "npr_seed_chains", "one length per read, hit_off[n + 1], one row per match")
@@ -606,12 +506,9 @@ class Context(object):
             m = int(chain_off[-1])
             chains, ops_off = np.empty((m, 4), dtype=np.int32), np.zeros(m + 1, dtype=np.int64)
             ops = np.empty((3 * len(hits) + 2 * m, 2), dtype=np.int32)  # a chain of k rows has at most 3 k + 2 pairs
-            rc = self._L.npr_seed_chains(*head, ptr(chains), m, ptr(ops_off), ptr(ops), len(ops))
-            if rc < 0:
-                raise NprError(int(rc), "npr_seed_chains", self.last_error())
+            check(self._L.npr_seed_chains(*head, ptr(chains), m, ptr(ops_off), ptr(ops), len(ops)), "npr_seed_chains", self)
             return chain_off, chains, ops_off, ops[:int(ops_off[-1])].copy()
-        if m < 0:
-            raise NprError(int(m), "npr_seed_chains", self.last_error())
+        check(m, "npr_seed_chains", self)
         return chain_off, np.zeros((0, 4), dtype=np.int32), np.zeros(1, dtype=np.int64), np.zeros((0, 2), dtype=np.int32)
 
     def _realign_once(self, params, refs, reads, guides, model_slot, want_pairs, ref_index, guide_start=None):
@@ -685,27 +582,32 @@ class Context(object):
 
 # ---- host logic (no GPU needed) ----
 
-def plan(params, lX, lY, guide):
+@contextlib.contextmanager
+def _plan(params, lX, lY, guide):
+    """`with _plan(...) as (L, h)`: the library and the npr_plan handle of one read's band plan, destroyed when the body ends."""
     L = _lib.load()
-    g = np.ascontiguousarray(np.asarray(guide, dtype=np.int32).reshape(-1, 2))
+    g = _arr(guide, np.int32, 2)
     h = C.c_void_p()
-    rc = L.npr_plan_create(C.byref(params), lX, lY, ptr(g), len(g), C.byref(h))
-    if rc != _lib.OK:
-        raise NprError(rc, "npr_plan_create")
-    out = []
+    check(L.npr_plan_create(C.byref(params), lX, lY, ptr(g), len(g), C.byref(h)), "npr_plan_create")
     try:
-        for s in range(L.npr_plan_segments(h)):
+        yield L, h
+    finally:
+        L.npr_plan_destroy(h)
+
+
+def plan(params, lX, lY, guide):
+    out = []
+    with _plan(params, lX, lY, guide) as (L, h):
+        for s in range(check(L.npr_plan_segments(h), "npr_plan_segments")):
             info = np.zeros(8, dtype=np.int64)
-            L.npr_plan_segment_info(h, s, ptr(info))
+            check(L.npr_plan_segment_info(h, s, ptr(info)), "npr_plan_segment_info")
             D = int(info[6])
             lo = np.zeros(D + 1, dtype=np.int32)
             n = np.zeros(D + 1, dtype=np.int32)
-            L.npr_plan_segment_band(h, s, ptr(lo), ptr(n))
+            check(L.npr_plan_segment_band(h, s, ptr(lo), ptr(n)), "npr_plan_segment_band")
             out.append(dict(xs=int(info[0]), ys=int(info[1]), xe=int(info[2]), ye=int(info[3]),
                             ragged_start=int(info[4]), ragged_end=int(info[5]), D=D, cells=int(info[7]), lo=lo,
                             n=n))
-    finally:
-        L.npr_plan_destroy(h)
     return out
 
 
@@ -713,15 +615,9 @@ def frame_schedule(params, lX, lY, guide, slots, slots_per_lane, segment=0):
     """Frame schedule of the register kernels for one segment of the plan (host logic, no GPU needed):
     dict(jlo, rebase, row_off, cells) or None when a frame of `slots` slots cannot follow the band
     (include/nprealign.h: npr_plan_frame_schedule)."""
-    L = _lib.load()
-    g = np.ascontiguousarray(np.asarray(guide, dtype=np.int32).reshape(-1, 2))
-    h = C.c_void_p()
-    rc = L.npr_plan_create(C.byref(params), lX, lY, ptr(g), len(g), C.byref(h))
-    if rc != _lib.OK:
-        raise NprError(rc, "npr_plan_create")
-    try:
+    with _plan(params, lX, lY, guide) as (L, h):
         info = np.zeros(8, dtype=np.int64)
-        L.npr_plan_segment_info(h, segment, ptr(info))
+        check(L.npr_plan_segment_info(h, segment, ptr(info)), "npr_plan_segment_info")
         D = int(info[6])
         jlo = np.zeros(D + 1, dtype=np.int32)
         reb = np.zeros(D + 1, dtype=np.int32)
@@ -730,43 +626,27 @@ def frame_schedule(params, lX, lY, guide, slots, slots_per_lane, segment=0):
         rc = L.npr_plan_frame_schedule(h, segment, slots, slots_per_lane, ptr(jlo), ptr(reb), ptr(off), ptr(cells))
         if rc == _lib.ERR_BAND_TOO_WIDE:
             return None
-        if rc != _lib.OK:
-            raise NprError(rc, "npr_plan_frame_schedule")
+        check(rc, "npr_plan_frame_schedule")
         return dict(jlo=jlo, rebase=reb, row_off=off, cells=int(cells[0]))
-    finally:
-        L.npr_plan_destroy(h)
 
 
 def stripes(params, lX, lY, guide, slots_per_lane=2, segment=0):
     """Stripe table of the wide-band kernel for one segment of the plan (host logic, no GPU needed):
     dict(X, K, df, dl, row0 -- arrays per stripe --, rows) (include/nprealign.h: npr_plan_stripes)."""
-    L = _lib.load()
-    g = np.ascontiguousarray(np.asarray(guide, dtype=np.int32).reshape(-1, 2))
-    h = C.c_void_p()
-    rc = L.npr_plan_create(C.byref(params), lX, lY, ptr(g), len(g), C.byref(h))
-    if rc != _lib.OK:
-        raise NprError(rc, "npr_plan_create")
-    try:
-        S = L.npr_plan_stripes(h, segment, slots_per_lane, None, 0, None)
-        if S < 0:
-            raise NprError(S, "npr_plan_stripes")
+    with _plan(params, lX, lY, guide) as (L, h):
+        S = check(L.npr_plan_stripes(h, segment, slots_per_lane, None, 0, None), "npr_plan_stripes")
         tab = np.zeros((S, 5), dtype=np.int32)
         rows = np.zeros(1, dtype=np.int64)
-        rc = L.npr_plan_stripes(h, segment, slots_per_lane, ptr(tab), S, ptr(rows))
-        if rc < 0:
-            raise NprError(rc, "npr_plan_stripes")
+        check(L.npr_plan_stripes(h, segment, slots_per_lane, ptr(tab), S, ptr(rows)), "npr_plan_stripes")
         return dict(X=tab[:, 0].copy(), K=tab[:, 1].copy(), df=tab[:, 2].copy(), dl=tab[:, 3].copy(),
                     row0=tab[:, 4].copy(), rows=int(rows[0]))
-    finally:
-        L.npr_plan_destroy(h)
 
 
 def format_cigars(ops_off, ops):
     """SAM CIGAR text of every op list of a CSR pair as Batch.ops() returns it: (bytes buffer, offsets[n+1])
     (include/nprealign.h: npr_format_cigars)."""
     L = _lib.load()
-    ops_off = np.ascontiguousarray(ops_off, dtype=np.int64)
-    ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 2)
+    ops_off, ops = _arr(ops_off, np.int64), _arr(ops, np.int32, 2)
     n = len(ops_off) - 1
     str_off = np.zeros(n + 1, dtype=np.int64)
     return _sized(L.npr_format_cigars, "npr_format_cigars", [n, ptr(ops_off), ptr(ops), ptr(str_off)]), str_off
@@ -776,32 +656,20 @@ def format_cigars_packed(word_off, n_ops, words):
     """SAM CIGAR text from packed cigars (one uint32 per op, length << 2 | op), list i at words[word_off[i] .. + n_ops[i]):
     (bytes buffer, offsets[n+1]) (include/nprealign.h: npr_format_cigars_packed)."""
     L = _lib.load()
-    word_off = np.ascontiguousarray(word_off, dtype=np.int64)
-    n_ops = np.ascontiguousarray(n_ops, dtype=np.int64)
-    words = np.ascontiguousarray(words, dtype=np.uint32)
-    n = len(n_ops)
+    packed = _packed_cigars(word_off, n_ops, words)
+    n = len(packed[1])
     str_off = np.zeros(n + 1, dtype=np.int64)
-    return _sized(L.npr_format_cigars_packed, "npr_format_cigars_packed", [n, ptr(word_off), ptr(n_ops), ptr(words), ptr(str_off)]), str_off
+    return _sized(L.npr_format_cigars_packed, "npr_format_cigars_packed", [n, *map(ptr, packed), ptr(str_off)]), str_off
 
 
 def cigar_text_packed(ctx, word_off, n_ops, words):
     """format_cigars_packed with the text made on the device of `ctx` (include/nprealign.h: npr_cigar_text_packed; the kernels of
     csrc/npr_cigtext.hip on lists given on the host): (bytes buffer, offsets[n+1])."""
     L = _lib.load()
-    word_off = np.ascontiguousarray(word_off, dtype=np.int64)
-    n_ops = np.ascontiguousarray(n_ops, dtype=np.int64)
-    words = np.ascontiguousarray(words, dtype=np.uint32)
-    n = len(n_ops)
+    packed = _packed_cigars(word_off, n_ops, words)
+    n = len(packed[1])
     str_off = np.zeros(n + 1, dtype=np.int64)
-    return _sized(L.npr_cigar_text_packed, "npr_cigar_text_packed", [ctx._h, n, ptr(word_off), ptr(n_ops), ptr(words), ptr(str_off)], ctx), str_off
-
-
-def _ragged(items):
-    """list of bytes -> (uint8 array, int64 offsets[n+1])"""
-    off = np.zeros(len(items) + 1, dtype=np.int64)
-    if len(items):
-        np.cumsum(np.fromiter(map(len, items), dtype=np.int64, count=len(items)), out=off[1:])
-    return np.frombuffer(b"".join(items) or b"\0", dtype=np.uint8), off
+    return _sized(L.npr_cigar_text_packed, "npr_cigar_text_packed", [ctx._h, n, *map(ptr, packed), ptr(str_off)], ctx), str_off
 
 
 def format_sam_records(qnames, ref_names, ref_index, pos, word_off, n_ops, words, seq, seq_off, flag=None, mapq=None):
@@ -812,18 +680,13 @@ def format_sam_records(qnames, ref_names, ref_index, pos, word_off, n_ops, words
     n = len(qnames)
     qn, qoff = _ragged(qnames)
     rn, roff = _ragged(ref_names)
-    ref_index = np.ascontiguousarray(ref_index, dtype=np.int32)
-    pos = np.ascontiguousarray(pos, dtype=np.int64)
-    word_off = np.ascontiguousarray(word_off, dtype=np.int64)
-    n_ops = np.ascontiguousarray(n_ops, dtype=np.int64)
-    words = np.ascontiguousarray(words, dtype=np.uint32)
-    seq = np.ascontiguousarray(seq, dtype=np.uint8)
-    seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
-    flag = None if flag is None else np.ascontiguousarray(flag, dtype=np.int32)
-    mapq = None if mapq is None else np.ascontiguousarray(mapq, dtype=np.int32)
+    ref_index, pos = _arr(ref_index, np.int32), _arr(pos, np.int64)
+    packed = _packed_cigars(word_off, n_ops, words)
+    seq, seq_off = _arr(seq, np.uint8), _arr(seq_off, np.int64)
+    flag, mapq = _arr(flag, np.int32), _arr(mapq, np.int32)
     rec_off = np.zeros(n + 1, dtype=np.int64)
-    args = [n, ptr(qn), ptr(qoff), None if flag is None else ptr(flag), ptr(rn), ptr(roff), ptr(ref_index), ptr(pos),
-            None if mapq is None else ptr(mapq), ptr(word_off), ptr(n_ops), ptr(words), ptr(seq), ptr(seq_off), ptr(rec_off)]
+    args = [n, ptr(qn), ptr(qoff), ptr(flag), ptr(rn), ptr(roff), ptr(ref_index), ptr(pos), ptr(mapq), *map(ptr, packed), ptr(seq),
+            ptr(seq_off), ptr(rec_off)]
     return _sized(L.npr_format_sam_records, "npr_format_sam_records", args), rec_off
 
 
@@ -832,17 +695,14 @@ def seed_sam_text(text, name_span, begin, end, ref_names, hit_off, hits):
     npr_seed_sam_text; host code, no device needed): (uint8 array, offsets[m + 1]).  Read i is text[begin[i]:end[i]] and is named
     text[name_span[i, 0]:name_span[i, 1]] (FastqTable.text / .seq_span / .name_span); ref_names: list of bytes."""
     L = _lib.load()
-    text = np.ascontiguousarray(text, dtype=np.uint8)
-    name_span = np.ascontiguousarray(name_span, dtype=np.int64).reshape(-1, 2)
-    begin, end = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
-    hit_off = np.ascontiguousarray(hit_off, dtype=np.int64)
-    hits = np.ascontiguousarray(hits, dtype=np.int32).reshape(-1, 4)
+    text, name_span, begin, end = spans = _read_spans(text, name_span, begin, end)
+    hit_off, hits = _arr(hit_off, np.int64), _arr(hits, np.int32, 4)
     n = len(begin)
     if not (len(end) == len(name_span) == n and len(hit_off) == n + 1 and int(hit_off[-1]) == len(hits)):
         raise NprError(_lib.ERR_INVALID, "npr_seed_sam_text", "one name, begin and end per read, hit_off[n + 1], one row per match")
     rn, roff = _ragged(ref_names)
     rec_off = np.zeros(len(hits) + 1, dtype=np.int64)
-    args = [n, ptr(text), ptr(name_span), ptr(begin), ptr(end), ptr(rn), ptr(roff), len(ref_names), ptr(hit_off), ptr(hits), ptr(rec_off)]
+    args = [n, *map(ptr, spans), ptr(rn), ptr(roff), len(ref_names), ptr(hit_off), ptr(hits), ptr(rec_off)]
     return _sized(L.npr_seed_sam_text, "npr_seed_sam_text", args), rec_off
 
 
@@ -851,47 +711,33 @@ def seed_chain_sam_text(text, name_span, begin, end, ref_names, chain_off, chain
     (include/nprealign.h: npr_seed_chain_sam_text; host code, no device needed): (uint8 array, offsets[m + 1]).  Reads and names as
     seed_sam_text takes them; read names must be unique."""
     L = _lib.load()
-    text = np.ascontiguousarray(text, dtype=np.uint8)
-    name_span = np.ascontiguousarray(name_span, dtype=np.int64).reshape(-1, 2)
-    begin, end = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
-    chain_off, ops_off = np.ascontiguousarray(chain_off, dtype=np.int64), np.ascontiguousarray(ops_off, dtype=np.int64)
-    chains = np.ascontiguousarray(chains, dtype=np.int32).reshape(-1, 4)
-    ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 2)
+    text, name_span, begin, end = spans = _read_spans(text, name_span, begin, end)
+    chain_off, chains, ops_off, ops = _arr(chain_off, np.int64), _arr(chains, np.int32, 4), _arr(ops_off, np.int64), _arr(ops, np.int32, 2)
     n = len(begin)
     if not (len(end) == len(name_span) == n and len(chain_off) == n + 1 and int(chain_off[-1]) == len(chains) and len(ops_off) == len(chains) + 1
             and int(ops_off[-1]) == len(ops)):
         raise NprError(_lib.ERR_INVALID, "npr_seed_chain_sam_text", "one name, begin and end per read, chain_off[n + 1], one row per chain, ops_off[m + 1], one pair per op")
     rn, roff = _ragged(ref_names)
     rec_off = np.zeros(len(chains) + 1, dtype=np.int64)
-    args = [n, ptr(text), ptr(name_span), ptr(begin), ptr(end), ptr(rn), ptr(roff), len(ref_names), ptr(chain_off), ptr(chains), ptr(ops_off), ptr(ops), ptr(rec_off)]
+    args = [n, *map(ptr, spans), ptr(rn), ptr(roff), len(ref_names), ptr(chain_off), ptr(chains), ptr(ops_off), ptr(ops), ptr(rec_off)]
     return _sized(L.npr_seed_chain_sam_text, "npr_seed_chain_sam_text", args), rec_off
 
 
 def mea_cigar(lX, lY, x, y, p, gap_gamma=0.5, match_gamma=0.0):
     L = _lib.load()
-    x = np.ascontiguousarray(x, dtype=np.int32)
-    y = np.ascontiguousarray(y, dtype=np.int32)
-    p = np.ascontiguousarray(p, dtype=np.float32)
+    x, y, p = _arr(x, np.int32), _arr(y, np.int32), _arr(p, np.float32)
     cap = 2 * len(x) + 8
     ops = np.zeros((cap, 2), dtype=np.int32)
     score = C.c_double(0)
-    k = L.npr_mea_cigar(lX, lY, ptr(x), ptr(y), ptr(p), len(x), gap_gamma, match_gamma, ptr(ops), cap,
-                        C.byref(score))
-    if k < 0:
-        raise NprError(int(k), "npr_mea_cigar")
+    k = check(L.npr_mea_cigar(lX, lY, ptr(x), ptr(y), ptr(p), len(x), gap_gamma, match_gamma, ptr(ops), cap, C.byref(score)), "npr_mea_cigar")
     return [(int(a), int(c)) for a, c in ops[:k]], score.value
 
 
 def rescore(guide, x, y, p):
     L = _lib.load()
-    g = np.ascontiguousarray(np.asarray(guide, dtype=np.int32).reshape(-1, 2))
-    x = np.ascontiguousarray(x, dtype=np.int32)
-    y = np.ascontiguousarray(y, dtype=np.int32)
-    p = np.ascontiguousarray(p, dtype=np.float32)
+    g, x, y, p = _arr(guide, np.int32, 2), _arr(x, np.int32), _arr(y, np.int32), _arr(p, np.float32)
     score = C.c_double(0)
-    rc = L.npr_rescore(ptr(g), len(g), ptr(x), ptr(y), ptr(p), len(x), C.byref(score))
-    if rc != _lib.OK:
-        raise NprError(rc, "npr_rescore")
+    check(L.npr_rescore(ptr(g), len(g), ptr(x), ptr(y), ptr(p), len(x), C.byref(score)), "npr_rescore")
     return score.value
 
 
@@ -900,16 +746,12 @@ def names_mark(names_text, name_span, sam_text, span, fields, mark):
     name i = names_text[name_span[i, 0]:name_span[i, 1]] that is the QNAME of an alignment line with a reference and without
     FLAG 4 -- span / fields as SamText.span / SamText.parse() give them; marks already set stay set.  `mark`: uint8 [n],
     written in place.  Returns the number of such lines whose QNAME is none of the names."""
-    names_text, sam_text = np.ascontiguousarray(names_text, dtype=np.uint8), np.ascontiguousarray(sam_text, dtype=np.uint8)
-    name_span = np.ascontiguousarray(name_span, dtype=np.int64).reshape(-1, 2)
-    span = np.ascontiguousarray(span, dtype=np.int64).reshape(-1, 2)
-    fields = np.ascontiguousarray(fields, dtype=np.int64).reshape(-1, _lib.SAM_COLS)
+    names_text, sam_text = _arr(names_text, np.uint8), _arr(sam_text, np.uint8)
+    name_span, span, fields = _arr(name_span, np.int64, 2), _arr(span, np.int64, 2), _arr(fields, np.int64, _lib.SAM_COLS)
     if not (isinstance(mark, np.ndarray) and mark.dtype == np.uint8 and mark.flags.c_contiguous and mark.shape == (len(name_span),)) or len(span) != len(fields):
         raise NprError(_lib.ERR_INVALID, "npr_names_mark", "mark must be a contiguous uint8 array with one entry per name, span and fields one row per line")
-    rc = _lib.load().npr_names_mark(ptr(names_text), ptr(name_span), len(name_span), ptr(sam_text), ptr(span), ptr(fields), len(span), ptr(mark))
-    if rc < 0:
-        raise NprError(int(rc), "npr_names_mark")
-    return int(rc)
+    return int(check(_lib.load().npr_names_mark(ptr(names_text), ptr(name_span), len(name_span), ptr(sam_text), ptr(span), ptr(fields), len(span), ptr(mark)),
+                     "npr_names_mark"))
 
 
 def encode(seq):

@@ -647,3 +647,22 @@ def test_a_context_closes_the_batches_still_staged_on_it():
     assert b._h is None
     b.close()   # (nothing left to do)
     del b
+
+
+def test_a_context_closes_every_kind_of_handle_made_on_it():
+    """Batch, Pileup and SeedIndex share one lifecycle: Context.close() destroys whichever are still open (each through its own destroy entry
+    point), leaves them with _h None, and a close() of their own afterwards has nothing left to do."""
+    from nanopore_amd import realign as R
+    ctx = R.Context(0)
+    ctx.set_hmm(_hmm_obj("blasr_hmm_0.txt"))
+    rng = np.random.default_rng(5)
+    reads = [bytes(b"ACGT"[c] for c in rng.integers(0, 4, 40)) for _ in range(2)]
+    made = [ctx.stage(R.make_params(band_mode=R.BAND_FIXED, fixed_width=10), reads, reads, [[(_lib.OP_M, 40)]] * 2),
+            ctx.pileup([40]),
+            ctx.seed_index([bytes(b"ACGT"[c] for c in rng.integers(0, 4, 64))], k=8)]
+    assert [type(o) for o in made] == [R.Batch, R.Pileup, R.SeedIndex] and all(o._h for o in made)
+    ctx.close()
+    assert [o._h for o in made] == [None, None, None]
+    for o in made:
+        o.close()
+        assert o._h is None
