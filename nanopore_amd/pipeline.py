@@ -1,0 +1,274 @@
+"""The experiment pipeline: every (read file x reference x mapper) mapped, analysed, then the meta-analyses over all of them.
+
+Interface of nanopore/pipeline.py (setupExperiments, mapThenAnalyse, runAnalyses, runMetaAnalyses, main; the module lists
+`mappers`, `analyses`, `metaAnalyses`), on this package's bioio.Target: a child runs when it is added, a follow-on after its
+target's function returned -- the order the reference relies on, without jobTree's engine.  One process, one device context
+(analyses.utils._context, shared by every mapper and analysis); the driver makes no second one and starts no child process.
+
+    workingDir/readFastqFiles/<readType>/*.fq | *.fastq      the reads, one directory per read type
+    workingDir/referenceFastaFiles/*.fa | *.fasta            the references
+    workingDir/output/
+        processedReadFastqFiles/<readType>/<file>            the inputs with unique names cut at the first blank
+        processedReferenceFastaFiles/<file>                    (analyses/names.py); what everything below reads
+        analysis_<readType>/
+            experiment_<read file>_<reference file>_<MapperClass>/
+                mapping.sam                                  the mapper's output
+                hmm.txt, hmm.txt.xml, ...                    the model a *RealignEm mapper trains
+                analysis_<AnalysisClass>/                    one directory per analysis, `DONE` inside when finished
+        metaAnalysis_<MetaAnalysisClass>/                    one directory per meta-analysis
+
+A second run resumes: an experiment whose mapping.sam exists is not mapped again, and an analysis of such an experiment that
+is finished (AbstractAnalysis.isFinished) is not repeated; an experiment that had to be mapped has all its analyses reset and
+run.  The meta-analyses always run.
+
+Failures: an experiment whose mapper or analyses raised is recorded (a mapper that raised leaves no mapping.sam behind, so the
+next run maps again; the other analyses of the experiment still run), the other experiments and the meta-analyses are finished,
+and main then raises RuntimeError("Got failed jobs") naming the failed directories, as the reference does for a job tree with
+failed jobs.
+
+Differences from the reference: `setupExperiments` hands its `analysers` argument to the experiments (the reference hands the
+module's list whatever it was given); input files are taken in sorted order; the job tree options are gone, `--mappers`,
+`--analyses`, `--metaAnalyses` (class names) and `--device` are new.
+
+    python -m nanopore_amd.pipeline workingDir [--mappers A,B] [--analyses C,D] [--metaAnalyses E,F] [--device N]
+"""
+import argparse
+import importlib
+import logging
+import os
+import pkgutil
+import sys
+
+from .analyses.abstractAnalysis import AbstractAnalysis
+from .analyses.names import makeFastaSequenceNamesUnique, makeFastqSequenceNamesUnique
+from .bioio import Target
+from .mappers.abstractMapper import AbstractMapper
+from .metaAnalyses.abstractMetaAnalysis import AbstractMetaAnalysis
+
+# what a run without --mappers / --analyses / --metaAnalyses uses
+from .mappers.variants import SeedMapperChain, SeedMapperRealign, SeedMapperRealignEm
+
+from .analyses.alignmentUncertainty import AlignmentUncertainty
+from .analyses.channelMappability import ChannelMappability
+from .analyses.coverage import GlobalCoverage, LocalCoverage
+from .analyses.hmmAnalysis import Hmm
+from .analyses.indelKmerAnalysis import IndelKmerAnalysis
+from .analyses.indels import Indels
+from .analyses.kmerAnalysis import KmerAnalysis
+from .analyses.substitutions import Substitutions
+
+from .metaAnalyses.comparePerReadMappabilityByMapper import ComparePerReadMappabilityByMapper
+from .metaAnalyses.coverageDepth import CoverageDepth
+from .metaAnalyses.coverageSummary import CoverageSummary
+from .metaAnalyses.hmmMetaAnalysis import HmmMetaAnalysis
+from .metaAnalyses.unmappedKmerAnalysis import UnmappedKmerAnalysis
+from .metaAnalyses.unmappedLengthDistributionAnalysis import UnmappedLengthDistributionAnalysis
+
+mappers = [SeedMapperChain, SeedMapperRealign, SeedMapperRealignEm]
+
+analyses = [Hmm, GlobalCoverage, LocalCoverage, Substitutions, Indels, AlignmentUncertainty, ChannelMappability, KmerAnalysis,
+            IndelKmerAnalysis]
+
+metaAnalyses = [UnmappedKmerAnalysis, CoverageSummary, UnmappedLengthDistributionAnalysis, ComparePerReadMappabilityByMapper,
+                HmmMetaAnalysis, CoverageDepth]
+
+logger = logging.getLogger(__name__)
+
+
+class PipelineTarget(Target):
+    """The Target the driver's functions run on: what is logged to the master goes to this module's logger as well, and
+    `failedJobs` collects (directory, exception) of what raised."""
+
+    def __init__(self, failedJobs=None):
+        Target.__init__(self)
+        self.failedJobs = [] if failedJobs is None else failedJobs
+
+    def logToMaster(self, message):
+        Target.logToMaster(self, message)
+        logger.info(message)
+
+
+def _runChild(target, child):
+    """A child Target (mapper, analysis, meta-analysis): run, its follow-ons, its temporary directory removed."""
+    try:
+        target.addChildTarget(child)
+        child.runFollowOns()
+    finally:
+        child.cleanup()
+
+
+def _runChildFn(target, fn, args):
+    """A child function: on a Target of its own (it sets its own follow-on), which reports to `target`."""
+    child = PipelineTarget(getattr(target, "failedJobs", None))
+    try:
+        fn(child, *args)
+        child.runFollowOns()
+    finally:
+        target.messages.extend(child.messages)
+        child.cleanup()
+
+
+def _failed(target, directory, error):
+    target.logToMaster("Failed: %s: %s: %s" % (directory, type(error).__name__, error))
+    if not hasattr(target, "failedJobs"):
+        target.failedJobs = []
+    target.failedJobs.append((directory, error))
+
+
+# one experiment per (read file, reference, mapper), in that nesting; the meta-analyses follow
+def setupExperiments(target, readFastqFiles, referenceFastaFiles, mappers, analysers, metaAnalyses, outputDir):
+    experiments = []
+    for readType, readTypeFastqFiles in readFastqFiles:
+        outputBase = os.path.join(outputDir, "analysis_" + readType)
+        os.makedirs(outputBase, exist_ok=True)
+        for readFastqFile in readTypeFastqFiles:
+            for referenceFastaFile in referenceFastaFiles:
+                for mapper in mappers:
+                    experimentDir = os.path.join(outputBase, "experiment_%s_%s_%s" % (
+                        os.path.basename(readFastqFile), os.path.basename(referenceFastaFile), mapper.__name__))
+                    experiment = (readFastqFile, readType, referenceFastaFile, mapper, analysers, experimentDir)
+                    experiments.append(experiment)
+                    try:
+                        _runChildFn(target, mapThenAnalyse, experiment)
+                    except Exception as e:  # the other experiments and the meta-analyses still run
+                        _failed(target, experimentDir, e)
+    target.setFollowOnTargetFn(runMetaAnalyses, args=(metaAnalyses, outputDir, experiments))
+
+
+def mapThenAnalyse(target, readFastqFile, readType, referenceFastaFile, mapper, analyses, experimentDir):
+    if not os.path.exists(experimentDir):
+        os.mkdir(experimentDir)
+        target.logToMaster("New experiment directory %s" % experimentDir)
+    else:
+        target.logToMaster("Resuming experiment directory %s" % experimentDir)
+    samFile = os.path.join(experimentDir, "mapping.sam")
+    hmmFileToTrain = os.path.join(experimentDir, "hmm.txt")
+    remapped = False
+    if not os.path.exists(samFile):
+        target.logToMaster("Mapping %s to %s with %s" % (readFastqFile, referenceFastaFile, mapper.__name__))
+        try:
+            _runChild(target, mapper(readFastqFile, readType, referenceFastaFile, samFile, hmmFileToTrain))
+        except BaseException:
+            if os.path.exists(samFile):  # half a mapper's work must not pass for a finished mapping in the next run
+                os.remove(samFile)
+            raise
+        remapped = True
+    else:
+        target.logToMaster("Keeping the mapping of %s to %s by %s" % (readFastqFile, referenceFastaFile, mapper.__name__))
+    target.setFollowOnTargetFn(runAnalyses, args=(readFastqFile, readType, referenceFastaFile, samFile, analyses, experimentDir, remapped, mapper))
+
+
+def runAnalyses(target, readFastqFile, readType, referenceFastaFile, samFile, analyses, experimentDir, remapped, mapper):
+    failed = []
+    for analysis in analyses:
+        analysisDir = os.path.join(experimentDir, "analysis_" + analysis.__name__)
+        if not os.path.exists(analysisDir):
+            os.mkdir(analysisDir)
+        if remapped or not AbstractAnalysis.isFinished(analysisDir):
+            target.logToMaster("Running %s on the mapping of %s to %s by %s" % (analysis.__name__, readFastqFile, referenceFastaFile, mapper.__name__))
+            AbstractAnalysis.reset(analysisDir)
+            try:
+                _runChild(target, analysis(readFastqFile, readType, referenceFastaFile, samFile, analysisDir))
+            except Exception as e:  # the analyses are siblings: one that fails does not keep the others from running
+                target.logToMaster("Analysis %s failed in %s: %s: %s" % (analysis.__name__, experimentDir, type(e).__name__, e))
+                failed.append((analysis.__name__, e))
+        else:
+            target.logToMaster("Keeping %s of the mapping of %s to %s by %s" % (analysis.__name__, readFastqFile, referenceFastaFile, mapper.__name__))
+    if failed:
+        raise RuntimeError("Analyses failed in %s: %s" % (experimentDir, ", ".join("%s (%s: %s)" % (n, type(e).__name__, e) for n, e in failed))) from failed[0][1]
+
+
+def runMetaAnalyses(target, metaAnalyses, outputDir, experiments):
+    for metaAnalysis in metaAnalyses:
+        metaAnalysisDir = os.path.join(outputDir, "metaAnalysis_" + metaAnalysis.__name__)
+        if not os.path.exists(metaAnalysisDir):
+            os.mkdir(metaAnalysisDir)
+        try:
+            _runChild(target, metaAnalysis(metaAnalysisDir, experiments))
+        except Exception as e:
+            _failed(target, metaAnalysisDir, e)
+
+
+def resolveClasses(names, package, base):
+    """The classes of a comma-separated list of class names: subclasses of `base` defined in (or imported into) a module of
+    `package`, modules tried in sorted order.  An unknown name raises."""
+    package = importlib.import_module(package)
+    modules = [importlib.import_module(package.__name__ + "." + m.name) for m in sorted(pkgutil.iter_modules(package.__path__), key=lambda m: m.name)]
+    out = []
+    for name in [n.strip() for n in names.split(",") if n.strip()]:
+        found = [getattr(m, name) for m in modules if isinstance(getattr(m, name, None), type) and issubclass(getattr(m, name), base)]
+        if not found:
+            raise RuntimeError("No class %s in %s" % (name, package.__name__))
+        out.append(found[0])
+    return out
+
+
+def useDevice(device):
+    """Device 0 is where everything runs by default.  Another one: it becomes torch's current device, which is where the
+    realignment jobs go (job.default_gpu), and its context becomes the one analyses.utils._context() hands out."""
+    if device == 0:
+        return
+    import torch
+    from .analyses import utils
+    torch.cuda.set_device(device)
+    utils._shared_ctx[0] = utils._context(device)
+
+
+def _inputFiles(directory, suffixes):
+    return [f for f in sorted(os.listdir(directory)) if f.endswith(suffixes) and os.path.isfile(os.path.join(directory, f))]
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(prog="python -m nanopore_amd.pipeline", description="Maps every read file of workingDir/readFastqFiles/<readType>/ to "
+                                     "every reference of workingDir/referenceFastaFiles/ with every mapper, analyses each mapping, then runs the meta-analyses; "
+                                     "results go to workingDir/output/.")
+    parser.add_argument("workingDir")
+    parser.add_argument("--mappers", help="comma-separated mapper class names (default: %s)" % ",".join(m.__name__ for m in mappers))
+    parser.add_argument("--analyses", help="comma-separated analysis class names (default: %s)" % ",".join(a.__name__ for a in analyses))
+    parser.add_argument("--metaAnalyses", help="comma-separated meta-analysis class names (default: %s)" % ",".join(m.__name__ for m in metaAnalyses))
+    parser.add_argument("--device", type=int, default=0, help="the GPU everything runs on (default 0)")
+    options = parser.parse_args(argv)
+    workingDir = options.workingDir
+    chosenMappers = mappers if options.mappers is None else resolveClasses(options.mappers, "nanopore_amd.mappers", AbstractMapper)
+    chosenAnalyses = analyses if options.analyses is None else resolveClasses(options.analyses, "nanopore_amd.analyses", AbstractAnalysis)
+    chosenMetaAnalyses = metaAnalyses if options.metaAnalyses is None else resolveClasses(options.metaAnalyses, "nanopore_amd.metaAnalyses", AbstractMetaAnalysis)
+    useDevice(options.device)
+
+    outputDir = os.path.join(workingDir, "output")
+    os.makedirs(outputDir, exist_ok=True)
+
+    # the processed copies of the reads, per read type
+    fastqParentDir = os.path.join(workingDir, "readFastqFiles")
+    readFastqFiles = []
+    for readType in sorted(d for d in os.listdir(fastqParentDir) if os.path.isdir(os.path.join(fastqParentDir, d))):
+        processedDir = os.path.join(outputDir, "processedReadFastqFiles", readType)
+        os.makedirs(processedDir, exist_ok=True)
+        readFastqFiles.append([readType, [makeFastqSequenceNamesUnique(os.path.join(fastqParentDir, readType, f), os.path.join(processedDir, f))
+                                          for f in _inputFiles(os.path.join(fastqParentDir, readType), (".fq", ".fastq"))]])
+
+    # the processed copies of the references
+    fastaParentDir = os.path.join(workingDir, "referenceFastaFiles")
+    processedDir = os.path.join(outputDir, "processedReferenceFastaFiles")
+    os.makedirs(processedDir, exist_ok=True)
+    referenceFastaFiles = [makeFastaSequenceNamesUnique(os.path.join(fastaParentDir, f), os.path.join(processedDir, f))
+                           for f in _inputFiles(fastaParentDir, (".fa", ".fasta"))]
+
+    logger.info("Working directory %s, output directory %s" % (workingDir, outputDir))
+    for readType, readTypeFastqFiles in readFastqFiles:
+        logger.info("Read type %s: %s" % (readType, ", ".join(readTypeFastqFiles) or "no read files"))
+    logger.info("References: %s" % (", ".join(referenceFastaFiles) or "none"))
+
+    root = PipelineTarget()
+    try:
+        setupExperiments(root, readFastqFiles, referenceFastaFiles, chosenMappers, chosenAnalyses, chosenMetaAnalyses, outputDir)
+        root.runFollowOns()
+    finally:
+        root.cleanup()
+    if root.failedJobs:
+        raise RuntimeError("Got failed jobs: %s" % "; ".join("%s (%s: %s)" % (d, type(e).__name__, e) for d, e in root.failedJobs))
+    return 0
+
+
+if __name__ == "__main__":
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    sys.exit(main())
