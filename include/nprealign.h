@@ -268,6 +268,13 @@ int32_t npr_batch_debug_set_pairs(npr_batch *b, int64_t read, const int32_t *x, 
  * or a read the device chain gave up on -- more than 64 pairs on a reference position, a pair 8192 read positions below the chain's top: the
  * WHOLE batch is finished on the host then, with the same results).  NPR_ERR_STATE before npr_batch_finish.  Read-only. */
 int32_t npr_batch_debug_finish_stage(const npr_batch *b);
+/* TEST HOOK (tests/test_gpu_second_pass.py: the second pass of npr_batch_run on every scaled class).  mark[n_segments]: one byte per segment, in
+ * the order npr_batch_segment_arith reports them (n_segments must be its seg_off[n_reads], else NPR_ERR_INVALID).  In the next npr_batch_run
+ * every task of a row- / column-scaled launch (classes 12-18) whose segment is marked counts as refused by its range certificate: its first-pass
+ * result gets the status such a task leaves (on the host and on the device; its pairs and totals are written, as a refused task's are) before
+ * the run looks for the tasks to run again, and everything from there on is the path of a task refused by itself.  Marks on tasks of other
+ * classes are ignored.  That run clears the marks.  Nothing in the product calls it. */
+int32_t npr_batch_debug_refuse(npr_batch *b, const uint8_t *mark, int64_t n_segments);
 
 /* ---- post-alignment statistics on the device ----
  * The per-read integer reductions the reference's analyses make by walking every aligned pair in Python:

@@ -136,6 +136,7 @@ SIGNATURES = {
     "npr_batch_pairs": (i32, [vp, vp, vp, vp, vp, i64]),
     "npr_batch_debug_set_pairs": (i32, [vp, i64, vp, vp, vp, i64, i32]),
     "npr_batch_debug_finish_stage": (i32, [vp]),
+    "npr_batch_debug_refuse": (i32, [vp, vp, i64]),
     "npr_batch_align_stats": (i32, [vp, vp]),
     "npr_align_stats": (i32, [vp, i64, i64] + [vp] * 9),
     "npr_kmer_counts": (i32, [vp, i32, i64, vp, vp, vp]),

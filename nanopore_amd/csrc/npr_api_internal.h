@@ -295,6 +295,7 @@ struct npr_batch {
     std::vector<int64_t> task_cells;     // in-band lattice cells per task (device order)
     std::vector<TaskOut> outs;
     std::vector<uint8_t> task_rerun;     // row-scaled tasks npr_batch_run ran again with a per-cell exponent
+    std::vector<uint8_t> debug_refuse;   // per task (empty: none): the next npr_batch_run takes it as refused by its range certificate (npr_batch_debug_refuse)
     npr_batch_stats stats{};
     // device
     DevBuf<Task> d_tasks;

@@ -244,6 +244,8 @@ int32_t npr_batch_run(npr_batch *b, float *kernel_ms) {
     npr_ctx *ctx = b->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (kernel_ms) *kernel_ms = 0.f;
+    std::vector<uint8_t> refuse;  // (npr_batch_debug_refuse: this run's, and gone after it however it ends)
+    refuse.swap(b->debug_refuse);
     if (b->tasks.empty()) {
         b->ran = true;
         return NPR_OK;
@@ -290,9 +292,17 @@ int32_t npr_batch_run(npr_batch *b, float *kernel_ms) {
         const KClass &kc = kClassTab[L.cls];
         if (kc.kind != K_RS && kc.kind != K_TILE_RS && kc.kind != K_MID) continue;
         HIP_TRY(ctx, hipMemcpy(b->outs.data() + L.first, b->d_outs.p + L.first, sizeof(TaskOut) * L.count, hipMemcpyDeviceToHost));
+        for (int k = L.first; !refuse.empty() && k < L.first + L.count; ++k)  // (test hook: as if the kernel had refused them, on both sides)
+            if (refuse[k] && b->outs[k].status != TASK_RERUN) {
+                b->outs[k].status = TASK_RERUN;
+                HIP_TRY(ctx, hipMemcpy(b->d_outs.p + k, &b->outs[k], sizeof(TaskOut), hipMemcpyHostToDevice));
+            }
         Rerun r;
         if ((rc = stage_rerun(b, L.first, L.count, L.cls, false, "npr_batch_run: hipMalloc", &r)) != NPR_OK) return rc;
         if (r.again.empty()) continue;
+        // (what the second launch's addressing rests on, checked where a test chose the tasks: workgroup j starts in the region of the class's j-th task)
+        for (size_t j = 0; !refuse.empty() && j < r.again.size(); ++j)
+            if (r.again[j] < L.first + static_cast<int32_t>(j)) return fail(ctx, NPR_ERR_STATE, "npr_batch_run: a task of the second pass is larger than the task its scratch region was sized for");
         if (std::getenv("NPR_TIMING"))
             for (const int32_t k : r.again)
                 std::fprintf(stderr, "[npr] task %d (D %d) runs again; the first pass left in its result: npairs (k_dp_mid_rs: why, 1 nothing at the cut / 2 no total / 3 exponents apart / 4 totals apart / 5 range certificate; k_dp_tile_cs: its certificate value) %d, btot_m (k_dp_mid_rs: total' / total) %.9g, btot_e (k_dp_mid_rs: exponent difference) %d, total %g x 2^%d\n", k, b->tasks[k].D, b->outs[k].npairs, b->outs[k].btot_m, b->outs[k].btot_e, b->outs[k].tot_m, b->outs[k].tot_e);
@@ -311,6 +321,18 @@ int32_t npr_batch_run(npr_batch *b, float *kernel_ms) {
     }
     b->ran = true;
     b->finished = false;
+    return NPR_OK;
+}
+
+int32_t npr_batch_debug_refuse(npr_batch *b, const uint8_t *mark, int64_t n_segments) {
+    if (!b || !mark) return NPR_ERR_INVALID;
+    int64_t n = 0;
+    for (int64_t r = 0; r < b->n_reads; ++r) n += b->read_ntasks[r];
+    if (n_segments != n) return fail(b->ctx, NPR_ERR_INVALID, "npr_batch_debug_refuse: one mark per segment, in npr_batch_segment_arith's order");
+    b->debug_refuse.assign(b->tasks.size(), 0);
+    n = 0;
+    for (int64_t r = 0; r < b->n_reads; ++r)
+        for (int32_t s = 0; s < b->read_ntasks[r]; ++s, ++n) b->debug_refuse[b->task_of[b->read_first_task[r] + s]] = mark[n] != 0;
     return NPR_OK;
 }
 

@@ -196,6 +196,12 @@ class Batch(_Handle):
         """TEST HOOK (include/nprealign.h npr_batch_debug_finish_stage): the stage the last finish() took, FINISH_DEVICE (0) or FINISH_HOST (1)."""
         return int(check(self._L.npr_batch_debug_finish_stage(self._h), "npr_batch_debug_finish_stage", self.ctx))
 
+    def debug_refuse(self, mark):
+        """TEST HOOK (include/nprealign.h npr_batch_debug_refuse): the next run() takes the scaled tasks of the marked segments (one entry per
+        segment, in segment_arith()'s order) as refused by their range certificate and runs them again per cell."""
+        mark = _arr(np.asarray(mark) != 0, np.uint8)
+        check(self._L.npr_batch_debug_refuse(self._h, ptr(mark), len(mark)), "npr_batch_debug_refuse", self.ctx)
+
     def pairs(self):
         """-> (pair_off[n+1], x, y, p) sparse posterior match probabilities sorted by (x, y)."""
         off = np.zeros(self.n_reads + 1, dtype=np.int64)
