@@ -472,6 +472,45 @@ int64_t npr_seed_chain_sam_text(int64_t n_reads, const uint8_t *text, const int6
 int32_t npr_batch_base_expectations(npr_batch *b, const uint8_t *use, int64_t n_refs, const int64_t *ref_len, double *expect,
                                     uint8_t *seen);
 
+/* ---- SNP calls on the device: the calling step of MarginAlignSnpCaller (marginAlignSnpCaller.py:18-23, :163-197) ----
+ * A table has one row per reference position (rows laid out as for npr_batch_base_expectations and npr_pileup_create) with four
+ * non-negative base weights w[A C G T], a `seen` flag, the reference base code and the true base code (npr_encode_bases' codes,
+ * 4 = not A/C/G/T).  Per row and error model m:
+ *   not seen                     -> not_called += 1, nothing else
+ *   total = ((w0+w1)+w2)+w3 == 0, or the reference base is not A/C/G/T -> nothing
+ *   otherwise  log p[c] = log evolution[ref][c] + sum_o (w[o] / total) log error_m[c][o], normalised over the four candidates c
+ *              (fp64), and every candidate c != ref is one call with bin = rint(100 p[c]) (round half to even, 0..100):
+ *              true_pos[bin] += 1 when true != ref and true == c, else false_pos[bin] += 1;  rows_called += 1.
+ * What leaves the device is this structure per model: the cumulative sums of the two histograms from the top are the
+ * curves the reference computes from its lists of calls.  Counts are integers: the same from run to run.
+ * evolution16 ([reference][candidate]) and error16 ([model][candidate][observed]) are PROBABILITIES; the library takes the
+ * logs.  A zero in evolution16 makes that candidate impossible (p = 0).  NPR_ERR_INVALID, with `out` untouched: n_models
+ * outside 1..NPR_SNP_MAX_MODELS, an error16 entry that is not a finite number above zero (the host path's 0 * log 0 is a
+ * NaN), an evolution16 entry that is negative or not finite, or a row of evolution16 that is all zero.
+ * true_code == NULL: the truth is the reference, every call is a false positive. */
+#define NPR_SNP_BINS 101
+#define NPR_SNP_MAX_MODELS 4
+typedef struct npr_snp_calls {
+    int64_t true_pos[NPR_SNP_BINS];   /* calls with rint(100 p) == bin that name the held-out base */
+    int64_t false_pos[NPR_SNP_BINS];  /* every other call */
+    int64_t not_called;               /* rows never seen */
+    int64_t rows_called;              /* rows that produced their three calls */
+} npr_snp_calls;
+/* any table given on the host: rows x 4 weights (finite, >= 0: NPR_ERR_INVALID otherwise), seen, ref / true codes */
+int32_t npr_snp_calls_table(npr_ctx *ctx, int64_t rows, const double *weights, const uint8_t *seen, const uint8_t *ref_code,
+                            const uint8_t *true_code, int32_t n_models, const double *evolution16,
+                            const double *error16 /* [n_models][16] */, npr_snp_calls *out /* [n_models] */);
+/* the posterior expectations of a finished all-posteriors batch, selected by use[] (arguments, state and validity rules as for
+ * npr_batch_base_expectations), read where k_base_expectations left them: the table never leaves the device.
+ * ref_code / true_code: [sum ref_len]. */
+int32_t npr_batch_snp_calls(npr_batch *b, const uint8_t *use, int64_t n_refs, const int64_t *ref_len, const uint8_t *ref_code,
+                            const uint8_t *true_code, int32_t n_models, const double *evolution16, const double *error16,
+                            npr_snp_calls *out);
+/* the aligned-base frequencies of a pileup: w = words 0-3, seen = (words 0-4 summed != 0).  ref_code / true_code: one per row
+ * of the pileup's table. */
+int32_t npr_pileup_snp_calls(npr_pileup *pl, const uint8_t *ref_code, const uint8_t *true_code, int32_t n_models,
+                             const double *evolution16, const double *error16, npr_snp_calls *out);
+
 /* Baum-Welch E-step over the staged batch with the models currently installed: what
  * `cactus_realign --outputExpectations` produces per alignment and cactus_expectationMaximisation sums over all of
  * them in every EM iteration (nanopore/analyses/utils.py:509-528).  T_exp[slot*25 + from*5 + to] and

@@ -52,6 +52,7 @@ KMER_MAX_GROUPS = 64  # npr_kmer_counts_groups: tables of one call
 SAM_COLS = 16     # NPR_SAM_COLS
 SEED_MIN_K, SEED_MAX_K = 8, 32  # npr_seed_index_create: the k of a seed index
 PILEUP_WORDS = 8  # NPR_PILEUP_WORDS: M columns by read base A C G T other, deletion columns, insertion runs, record starts
+SNP_BINS, SNP_MAX_MODELS = 101, 4  # NPR_SNP_BINS, NPR_SNP_MAX_MODELS
 MAX_MODELS = 8
 E_DEAD = -(1 << 28)
 
@@ -99,6 +100,15 @@ class BatchStats(C.Structure):
         ("device_bytes", C.c_int64),
         ("slots", C.c_int64),
         ("kernel_variant", C.c_int32),
+    ]
+
+
+class SnpCalls(C.Structure):  # npr_snp_calls: what the SNP-call entry points return per error model
+    _fields_ = [
+        ("true_pos", C.c_int64 * SNP_BINS),
+        ("false_pos", C.c_int64 * SNP_BINS),
+        ("not_called", C.c_int64),
+        ("rows_called", C.c_int64),
     ]
 
 
@@ -156,6 +166,9 @@ SIGNATURES = {
     "npr_seed_chains": (i64, [vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64]),
     "npr_seed_chain_sam_text": (i64, [i64] + [vp] * 6 + [i64] + [vp] * 6 + [i64]),
     "npr_batch_base_expectations": (i32, [vp, vp, i64, vp, vp, vp]),
+    "npr_snp_calls_table": (i32, [vp, i64, vp, vp, vp, vp, i32, vp, vp, vp]),
+    "npr_batch_snp_calls": (i32, [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp]),
+    "npr_pileup_snp_calls": (i32, [vp, vp, vp, i32, vp, vp, vp]),
     "npr_batch_expectations": (i32, [vp, vp, vp, vp, C.POINTER(C.c_float)]),
     "npr_batch_dense": (i32, [vp, i64, vp, vp, vp, vp, i64]),
     "npr_batch_rs_forward": (i32, [vp, i64, vp, vp, i64]),

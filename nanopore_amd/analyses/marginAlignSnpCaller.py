@@ -7,6 +7,10 @@ posteriors do not depend on which other reads are sampled, so here each hmm type
 (NPR_MODE_ALL_POSTERIORS, --splitMatrixBiggerThanThis=100) over all reads; the coverage / replicate loops only
 re-sample which reads' posteriors are accumulated.  Output: marginaliseConsensus.xml with the reference's element
 and attribute names (:268-303).
+
+The calling itself -- candidate posteriors per position, one call per non-reference base, the curves over 101
+thresholds -- runs on the host by default; `MarginAlignSnpCaller.callsOnDevice = True` makes and counts the calls on the
+device (csrc/npr_snpcall.hip) and writes the same file.  The held-out SNPs come from analyses/mutate_reference.py.
 """
 import math
 import os
@@ -91,6 +95,21 @@ class SnpCalls(object):
         self.falsePositives = []
         self.falseNegatives = []
         self.notCalled = 0
+        self.histograms = None    # fromHistograms: (true positives, false positives) per round(100 p), instead of the two lists
+
+    @classmethod
+    def fromHistograms(cls, totalHeldOut, true_pos, false_pos, notCalled):
+        """The same curves from calls that were counted where they were made (Batch.snp_calls, Pileup.snp_calls): true_pos[b] / false_pos[b] =
+        number of true / false calls with round(100 p) == b, b = 0..100.  No list of calls exists."""
+        calls = cls(totalHeldOut)
+        calls.histograms = (np.asarray(true_pos, dtype=np.float64).reshape(101), np.asarray(false_pos, dtype=np.float64).reshape(101))
+        calls.notCalled = int(notCalled)
+        return calls
+
+    @staticmethod
+    def cumulate(hist):
+        """[sum of hist[t:] for t in 0..100], as floats: what bucket() makes of the calls the histogram counts."""
+        return np.asarray(hist, dtype=np.float64)[::-1].cumsum()[::-1].tolist()
 
     @staticmethod
     def bucket(calls):
@@ -99,18 +118,23 @@ class SnpCalls(object):
         hist = np.bincount(np.rint(p * 100).astype(np.int64), minlength=101).astype(np.float64) if len(p) else np.zeros(101)
         return hist[::-1].cumsum()[::-1].tolist()
 
+    def _bucketed(self, true):
+        if self.histograms is not None:
+            return self.cumulate(self.histograms[0 if true else 1])
+        return self.bucket(p for p, _ in (self.truePositives if true else self.falsePositives))
+
     def addCalls(self, probabilities, positions, isTrue):
         for p, x, t in zip(probabilities.tolist(), positions.tolist(), isTrue.tolist()):
             (self.truePositives if t else self.falsePositives).append((p, x))
 
     def getPrecisionByProbability(self):
-        tp = np.array(self.bucket(p for p, _ in self.truePositives))
-        fp = np.array(self.bucket(p for p, _ in self.falsePositives))
+        tp = np.array(self._bucketed(True))
+        fp = np.array(self._bucketed(False))
         made = tp + fp
         return [float(t / m) if m else 0 for t, m in zip(tp, made)]
 
     def getRecallByProbability(self):
-        return [t / self.totalHeldOut if self.totalHeldOut else 0 for t in self.bucket(p for p, _ in self.truePositives)]
+        return [t / self.totalHeldOut if self.totalHeldOut else 0 for t in self._bucketed(True)]
 
 
 def loadHeldOutSnps(referenceFastaFile, refSequences):
@@ -139,6 +163,10 @@ def loadHeldOutSnps(referenceFastaFile, refSequences):
 class MarginAlignSnpCaller(AbstractAnalysis):
     hmmTypes = ("cactus", "trained_0", "trained_20", "trained_40")
     coverages = (1000000, 120, 60, 30, 10)
+    # True: the calls of every sample are made and counted on the device (Batch.snp_calls on the posterior expectations where they lie,
+    # Pileup.snp_calls on a pileup of the sampled records); no [positions][4] table crosses PCIe and no list of calls exists on the host.
+    # Same XML.  Off until the two paths have been timed on hardware (tools/snp_calls_time.py).
+    callsOnDevice = False
 
     def run(self, ctx=None, seed=None):
         from .. import realign
@@ -160,7 +188,7 @@ class MarginAlignSnpCaller(AbstractAnalysis):
             assert aR.pos == 0 and aR.qstart == 0 and aR.qend == len(aR.query) and aR.aend == len(refSeq)
         # frequencies of aligned bases per read, from the SAM alignment itself (:111-118)
         alignedBases = []
-        for aR in records:
+        for aR in ([] if self.callsOnDevice else records):  # (callsOnDevice: a pileup of the records on the device instead)
             refName = sam.getrname(aR.rname)
             pos, code = [], []
             query = aR.query.upper()
@@ -168,6 +196,7 @@ class MarginAlignSnpCaller(AbstractAnalysis):
                 pos.append(r)
                 code.append(bases.find(query[q]))
             alignedBases.append((refIndex[refName], np.array(pos, dtype=np.int64), np.array(code, dtype=np.int64)))
+        staged = self._stageForDevice(sam, records, refSequences, refNames, refIndex, snpSet) if self.callsOnDevice else None
         node = ET.Element("marginAlignComparison")
         for hmmType in self.hmmTypes:
             # one batched GPU call per hmm type: all posterior match probabilities of every read (:135-146).  The pairs
@@ -181,7 +210,7 @@ class MarginAlignSnpCaller(AbstractAnalysis):
             stagedSam.close()
             try:
                 self._callsOfOneModel(node, hmmType, batch, records, refSequences, readSequences, refNames, alignedBases, snpSet,
-                                      hmmErrorMatrix, totalReferenceLength, rng)
+                                      hmmErrorMatrix, totalReferenceLength, rng, staged)
             finally:
                 batch.close()
         sam.close()
@@ -190,9 +219,78 @@ class MarginAlignSnpCaller(AbstractAnalysis):
         self.finish()
         return node
 
+    @staticmethod
+    def _stageForDevice(sam, records, refSequences, refNames, refIndex, snpSet):
+        """What callsOnDevice needs of the SAM records and the references, made once per run: the records as Pileup.add_csr takes them
+        (the alignments the host path counts its frequencies of aligned bases from), the aligned pairs of every record, and the reference /
+        true base codes of every table row (npr_encode_bases' codes; rows in the order of refNames)."""
+        from ..realign import _csr, _csr_ops
+        from .utils import _guideOf
+        for aR in records:
+            assert all(op in (0, 1, 2) for op, _ in aR.cigar), "callsOnDevice: %s has cigar operations other than M / I / D" % aR.qname
+        guides = [_guideOf(aR) for aR in records]
+        refLengths = [len(refSequences[n]) for n in refNames]
+        refRows = np.concatenate([[0], np.cumsum(refLengths)])
+        code = np.where(_BASE_CODE < 0, 4, _BASE_CODE).astype(np.uint8)
+        refCodes = code[np.frombuffer("".join(refSequences[n] for n in refNames).encode(), dtype=np.uint8)]
+        trueCodes = refCodes.copy()
+        for (name, i), base in snpSet.items():
+            trueCodes[refRows[refIndex[name]] + i] = code[ord(base)]
+        read, readOff = _csr([aR.query for aR in records])
+        ops, opsOff = _csr_ops(guides)
+        return {"read": read, "readOff": readOff, "ops": ops, "opsOff": opsOff,
+                "refIndex": np.array([refIndex[sam.getrname(aR.rname)] for aR in records], dtype=np.int32),
+                "start": np.array([(aR.pos, 0) for aR in records], dtype=np.int64).reshape(-1, 2),
+                # (a record is global, asserted in run(): every M column lies on the reference)
+                "alignedPairs": [sum(length for op, length in g if op == 0) for g in guides],
+                "refCodes": refCodes, "trueCodes": trueCodes}
+
+    def _callSetsOnDevice(self, batch, staged, sampled, refLengths, hmmErrorMatrix, totalHeldOut):
+        """The four call sets of one sample, in the order of the element tags, counted on the device: the two error models over the posterior
+        expectations of the sampled reads, then over a pileup of the sampled records."""
+        models = (FLAT_ERROR_MATRIX, hmmErrorMatrix)
+        counted = batch.snp_calls(refLengths, staged["refCodes"], staged["trueCodes"], NULL_MATRIX, models, use=sampled)
+        pileup = batch.ctx.pileup(refLengths)
+        try:
+            pileup.add_csr(staged["read"], staged["readOff"], None, staged["ops"], staged["opsOff"], staged["refIndex"], staged["start"], use=sampled)
+            counted += pileup.snp_calls(staged["refCodes"], staged["trueCodes"], NULL_MATRIX, models)
+        finally:
+            pileup.close()
+        return [SnpCalls.fromHistograms(totalHeldOut, truePos, falsePos, notCalled) for truePos, falsePos, notCalled, _ in counted]
+
+    @staticmethod
+    def _callSetsOnHost(batch, sampled, refLengths, refRows, refNames, refSequences, snpSet, hmmErrorMatrix, frequencies, seenF, totalHeldOut):
+        """The four call sets of one sample from tables on the host: the posterior expectations fetched from the device, and the frequencies of
+        aligned bases."""
+        allE, allSeen = batch.base_expectations(refLengths, use=sampled)
+        expectations = [allE[refRows[k]:refRows[k + 1]] for k in range(len(refNames))]
+        seenE = [allSeen[refRows[k]:refRows[k + 1]] for k in range(len(refNames))]
+        callSets = [SnpCalls(totalHeldOut) for _ in range(4)]
+        configs = ((FLAT_ERROR_MATRIX, expectations, seenE), (hmmErrorMatrix, expectations, seenE),
+                   (FLAT_ERROR_MATRIX, frequencies, seenF), (hmmErrorMatrix, frequencies, seenF))
+        for k, refSeqName in enumerate(refNames):
+            # every position of the sequence at once: candidate posteriors, then one call per non-reference base
+            refCodes = _BASE_CODE[np.frombuffer(refSequences[refSeqName].encode(), dtype=np.uint8)]
+            trueCodes = refCodes.copy()
+            for (name, i), base in snpSet.items():
+                if name == refSeqName:
+                    trueCodes[i] = _BASE_CODE[ord(base)]
+            for (errorM, table, seen), snpCalls in zip(configs, callSets):
+                snpCalls.notCalled += int((~seen[k]).sum())
+                total = table[k].sum(axis=1)
+                where = np.flatnonzero(seen[k] & (total > 0.0) & (refCodes >= 0))
+                if not len(where):
+                    continue
+                post = basePosteriors(table[k][where] / total[where, None], refCodes[where], NULL_MATRIX, errorM)
+                for c in range(4):
+                    called = refCodes[where] != c
+                    isTrue = (trueCodes[where] != refCodes[where]) & (trueCodes[where] == c)
+                    snpCalls.addCalls(post[called, c], where[called], isTrue[called])
+        return callSets
+
     def _callsOfOneModel(self, node, hmmType, batch, records, refSequences, readSequences, refNames, alignedBases, snpSet, hmmErrorMatrix,
-                         totalReferenceLength, rng):
-        """All coverages and replicates for one hmm type, on the posteriors of one batched GPU pass."""
+                         totalReferenceLength, rng, staged=None):
+        """All coverages and replicates for one hmm type, on the posteriors of one batched GPU pass.  staged: callsOnDevice (_stageForDevice)."""
         batch.run()
         batch.finish()
         status = batch.results()["status"]
@@ -205,8 +303,9 @@ class MarginAlignSnpCaller(AbstractAnalysis):
             for replicate in range(3 if coverage < 1000000 else 1):
                 order = list(range(len(records)))
                 rng.shuffle(order)  # :91
-                frequencies = [np.zeros((len(refSequences[n]), 4)) for n in refNames]
-                seenF = [np.zeros(len(refSequences[n]), dtype=bool) for n in refNames]
+                if staged is None:
+                    frequencies = [np.zeros((len(refSequences[n]), 4)) for n in refNames]
+                    seenF = [np.zeros(len(refSequences[n]), dtype=bool) for n in refNames]
                 totalSampledReads = totalAlignedPairs = totalReadLength = 0
                 sampled = np.zeros(len(records), dtype=np.uint8)
                 for i in order:
@@ -215,38 +314,22 @@ class MarginAlignSnpCaller(AbstractAnalysis):
                     aR = records[i]
                     totalReadLength += len(readSequences[aR.qname])
                     totalSampledReads += 1
+                    sampled[i] = 1
+                    if staged is not None:
+                        totalAlignedPairs += staged["alignedPairs"][i]
+                        continue
                     k, pos, code = alignedBases[i]
                     totalAlignedPairs += len(pos)
                     seenF[k][pos] = True
                     ok = code >= 0
                     np.add.at(frequencies[k], (pos[ok], code[ok]), 1.0)
-                    sampled[i] = 1
-                allE, allSeen = batch.base_expectations(refLengths, use=sampled)
-                expectations = [allE[refRows[k]:refRows[k + 1]] for k in range(len(refNames))]
-                seenE = [allSeen[refRows[k]:refRows[k + 1]] for k in range(len(refNames))]
                 totalHeldOut = len(snpSet)
                 totalNotHeldOut = totalReferenceLength - totalHeldOut
-                callSets = [SnpCalls(totalHeldOut) for _ in range(4)]
-                configs = ((FLAT_ERROR_MATRIX, expectations, seenE), (hmmErrorMatrix, expectations, seenE),
-                           (FLAT_ERROR_MATRIX, frequencies, seenF), (hmmErrorMatrix, frequencies, seenF))
-                for k, refSeqName in enumerate(refNames):
-                    # every position of the sequence at once: candidate posteriors, then one call per non-reference base
-                    refCodes = _BASE_CODE[np.frombuffer(refSequences[refSeqName].encode(), dtype=np.uint8)]
-                    trueCodes = refCodes.copy()
-                    for (name, i), base in snpSet.items():
-                        if name == refSeqName:
-                            trueCodes[i] = _BASE_CODE[ord(base)]
-                    for (errorM, table, seen), snpCalls in zip(configs, callSets):
-                        snpCalls.notCalled += int((~seen[k]).sum())
-                        total = table[k].sum(axis=1)
-                        where = np.flatnonzero(seen[k] & (total > 0.0) & (refCodes >= 0))
-                        if not len(where):
-                            continue
-                        post = basePosteriors(table[k][where] / total[where, None], refCodes[where], NULL_MATRIX, errorM)
-                        for c in range(4):
-                            called = refCodes[where] != c
-                            isTrue = (trueCodes[where] != refCodes[where]) & (trueCodes[where] == c)
-                            snpCalls.addCalls(post[called, c], where[called], isTrue[called])
+                if staged is not None:
+                    callSets = self._callSetsOnDevice(batch, staged, sampled, refLengths, hmmErrorMatrix, totalHeldOut)
+                else:
+                    callSets = self._callSetsOnHost(batch, sampled, refLengths, refRows, refNames, refSequences, snpSet, hmmErrorMatrix,
+                                                    frequencies, seenF, totalHeldOut)
                 tags = ("marginAlignMaxExpectedSnpCalls", "marginAlignMaxLikelihoodSnpCalls", "maxFrequencySnpCalls",
                         "maximumLikelihoodSnpCalls")
                 for snpCalls, tagName in zip(callSets, tags):

@@ -4,7 +4,7 @@
 //   npr_stage.cpp   npr_batch_create*: plan points, packing, H2D, the device planner, kernel classes and launch geometry
 //   npr_run.cpp     npr_batch_run (launch policy, second pass of tasks without a range certificate), the E-step, the dense dumps
 //   npr_finish.cpp  npr_batch_finish and what reads its results: the device MEA stage and its pieced D2H, the rescore sums, the host stage, ops / pairs
-//   npr_aux.cpp     post-alignment statistics, k-mer tables, base expectations, the device pileup, the planner cross-check
+//   npr_aux.cpp     post-alignment statistics, k-mer tables, base expectations and SNP calls, the device pileup, the planner cross-check
 //   npr_text.cpp    cigar and SAM record text (the transport forms a job ships)
 //   npr_seed_api.cpp  exact-match seeding (npr_seed.hip): the index, the matches, their SAM records
 //   npr_cigtext_api.cpp  cigar text made on the device (npr_cigtext.hip): npr_cigar_text_packed, npr_batch_cigar_text, NPR_OPT_FINISH_TEXT

@@ -1,6 +1,7 @@
-// npr_aux.cpp -- post-alignment statistics and k-mer tables on the device, base expectations of the marginAlign SNP caller, the device pileup, the planner cross-check (coverage.py / substitutions.py / indels.py; kmerAnalysis.py / indelKmerAnalysis.py; marginAlignSnpCaller.py:150-155)
+// npr_aux.cpp -- post-alignment statistics and k-mer tables on the device, base expectations and calls of the marginAlign SNP caller, the device pileup, the planner cross-check (coverage.py / substitutions.py / indels.py; kmerAnalysis.py / indelKmerAnalysis.py; marginAlignSnpCaller.py:150-155)
 // (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
 #include "npr_api_internal.h"
+#include "npr_snpmodel.h"
 
 #include <functional>
 
@@ -465,48 +466,109 @@ int64_t npr_batch_plan_check(npr_batch *b, const int32_t *guide_ops) {
     }
 }
 
+namespace {
+
+// The accumulate-on-device half of npr_batch_base_expectations: the fixed-point sums (npr_stats.hip: exact, hence the same from run to run) and
+// the seen bytes of the selected reads of a finished batch, queued on the context's stream and left in HBM for whoever reads them next -- the copy
+// to the caller's table, or k_snp_calls.  `base`: first row of every reference sequence, base[n_refs] = rows > 0.
+struct DeviceExpectations {
+    DevBuf<unsigned long long> e;  // [rows][4]
+    DevBuf<uint8_t> seen;          // [rows]
+};
+int32_t accumulate_base_expectations(npr_batch *b, const uint8_t *use, int64_t n_refs, const int64_t *ref_len, const std::vector<int64_t> &base, const char *unfit,
+                                     DeviceExpectations &d) {
+    npr_ctx *ctx = b->ctx;
+    const int64_t rows = base[n_refs], n = b->n_reads, ntasks = static_cast<int64_t>(b->tasks.size());
+    std::vector<int64_t> target(n, 0);
+    std::vector<uint8_t> mask(n, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t k = b->ref_id[i];
+        const bool ok = b->results[i].status == NPR_OK && (!use || use[i]) && k >= 0 && k < n_refs &&
+                        b->gstart[2 * i] + b->ref_len[i] <= ref_len[k];
+        if (use && use[i] && !ok && b->results[i].status == NPR_OK) return fail(ctx, NPR_ERR_INVALID, unfit);
+        mask[i] = ok ? 1 : 0;
+        target[i] = ok ? base[k] + b->gstart[2 * i] : 0;
+    }
+    DevBuf<uint8_t> d_use;
+    DevBuf<int64_t> d_target;
+    hipError_t e;
+    if ((e = d.e.alloc(4 * rows)) != hipSuccess || (e = d.seen.alloc(rows)) != hipSuccess || (e = d_use.alloc(n)) != hipSuccess ||
+        (e = d_target.alloc(n)) != hipSuccess)
+        return fail(ctx, NPR_ERR_NOMEM, "base expectations: hipMalloc", e);
+    HIP_TRY(ctx, hipMemsetAsync(d.e.p, 0, d.e.bytes(), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d.seen.p, 0, d.seen.bytes(), ctx->stream));
+    if (!ntasks) return NPR_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(d_use.p, mask.data(), d_use.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_target.p, target.data(), d_target.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    ExpectArgs a{b->d_tasks.p, b->d_outs.p, static_cast<int32_t>(ntasks), b->d_px.p, b->d_py.p, b->d_pp.p, b->d_seq.p, d_use.p, d_target.p, d.e.p, d.seen.p};
+    const int rc = launch_base_expectations(a, ctx->stream);
+    if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_base_expectations launch", static_cast<hipError_t>(rc));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (mask, target, d_use and d_target end with this call)
+    return NPR_OK;
+}
+
+// first row of every reference sequence; false: a negative length
+bool row_bases(int64_t n_refs, const int64_t *ref_len, std::vector<int64_t> &base) {
+    base.assign(n_refs + 1, 0);
+    for (int64_t k = 0; k < n_refs; ++k) {
+        if (ref_len[k] < 0) return false;
+        base[k + 1] = base[k] + ref_len[k];
+    }
+    return true;
+}
+
+static_assert(sizeof(npr_snp_calls) == SNP_OUT_WORDS * sizeof(int64_t) && NPR_SNP_BINS == SNP_BINS && NPR_SNP_MAX_MODELS == kSnpMaxModels,
+              "k_snp_calls writes an npr_snp_calls per model");
+
+// The device half of the three SNP-call entry points: k_snp_calls over a table that lies on the device in the form `source` says, with the
+// matrices' logs taken already; the base codes are uploaded, n_models structures come back.
+int32_t run_snp_calls(npr_ctx *ctx, int64_t rows, int32_t source, const void *d_table, const uint8_t *d_seen, const uint8_t *ref_code,
+                      const uint8_t *true_code, int32_t n_models, const double *log_evolution, const double *log_error, npr_snp_calls *out) {
+    std::vector<npr_snp_calls> result(n_models);  // (out is written only when everything has worked)
+    std::memset(static_cast<void *>(result.data()), 0, result.size() * sizeof(npr_snp_calls));
+    if (rows > 0) {
+        DevBuf<uint8_t> d_ref, d_true;
+        DevBuf<unsigned long long> d_out;
+        hipError_t e;
+        if ((e = d_ref.alloc(rows)) != hipSuccess || (e = d_true.alloc(true_code ? rows : 0)) != hipSuccess ||
+            (e = d_out.alloc(static_cast<size_t>(n_models) * SNP_OUT_WORDS)) != hipSuccess)
+            return fail(ctx, NPR_ERR_NOMEM, "SNP calls: hipMalloc", e);
+        HIP_TRY(ctx, hipMemcpyAsync(d_ref.p, ref_code, d_ref.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        if (true_code) HIP_TRY(ctx, hipMemcpyAsync(d_true.p, true_code, d_true.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(d_out.p, 0, d_out.bytes(), ctx->stream));
+        SnpCallArgs a{};
+        a.rows = rows, a.source = source, a.n_models = n_models, a.table = d_table, a.seen = d_seen, a.ref_code = d_ref.p, a.true_code = d_true.p, a.out = d_out.p;
+        std::memcpy(a.log_evolution, log_evolution, sizeof(a.log_evolution));
+        std::memcpy(a.log_error, log_error, static_cast<size_t>(n_models) * 16 * sizeof(double));
+        const int rc = launch_snp_calls(a, ctx->stream);
+        if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_snp_calls launch", static_cast<hipError_t>(rc));
+        HIP_TRY(ctx, hipMemcpyAsync(result.data(), d_out.p, d_out.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    std::memcpy(static_cast<void *>(out), result.data(), result.size() * sizeof(npr_snp_calls));
+    return NPR_OK;
+}
+
+}  // namespace
+
 int32_t npr_batch_base_expectations(npr_batch *b, const uint8_t *use, int64_t n_refs, const int64_t *ref_len, double *expect, uint8_t *seen) {
     if (!b || n_refs < 0 || (n_refs && !ref_len) || !expect || !seen) return NPR_ERR_INVALID;
     if (!b->finished) return NPR_ERR_STATE;
     npr_ctx *ctx = b->ctx;
     try {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        std::vector<int64_t> base(n_refs + 1, 0);
-        for (int64_t k = 0; k < n_refs; ++k) {
-            if (ref_len[k] < 0) return NPR_ERR_INVALID;
-            base[k + 1] = base[k] + ref_len[k];
-        }
-        const int64_t rows = base[n_refs], n = b->n_reads, ntasks = static_cast<int64_t>(b->tasks.size());
+        std::vector<int64_t> base;
+        if (!row_bases(n_refs, ref_len, base)) return NPR_ERR_INVALID;
+        const int64_t rows = base[n_refs];
         std::fill(expect, expect + 4 * rows, 0.0);
         std::fill(seen, seen + rows, uint8_t(0));
-        if (!ntasks || !rows) return NPR_OK;
-        std::vector<int64_t> target(n, 0);
-        std::vector<uint8_t> mask(n, 0);
-        for (int64_t i = 0; i < n; ++i) {
-            const int64_t k = b->ref_id[i];
-            const bool ok = b->results[i].status == NPR_OK && (!use || use[i]) && k >= 0 && k < n_refs &&
-                            b->gstart[2 * i] + b->ref_len[i] <= ref_len[k];
-            if (use && use[i] && !ok && b->results[i].status == NPR_OK) return fail(ctx, NPR_ERR_INVALID, "npr_batch_base_expectations: a read's window does not fit its reference");
-            mask[i] = ok ? 1 : 0;
-            target[i] = ok ? base[k] + b->gstart[2 * i] : 0;
-        }
-        DevBuf<unsigned long long> d_e;  // fixed-point sums (npr_stats.hip): exact, hence the same from run to run
-        DevBuf<uint8_t> d_seen, d_use;
-        DevBuf<int64_t> d_target;
-        hipError_t e;
-        if ((e = d_e.alloc(4 * rows)) != hipSuccess || (e = d_seen.alloc(rows)) != hipSuccess || (e = d_use.alloc(n)) != hipSuccess ||
-            (e = d_target.alloc(n)) != hipSuccess)
-            return fail(ctx, NPR_ERR_NOMEM, "npr_batch_base_expectations: hipMalloc", e);
-        HIP_TRY(ctx, hipMemsetAsync(d_e.p, 0, d_e.bytes(), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(d_seen.p, 0, d_seen.bytes(), ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_use.p, mask.data(), d_use.bytes(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_target.p, target.data(), d_target.bytes(), hipMemcpyHostToDevice, ctx->stream));
-        ExpectArgs a{b->d_tasks.p, b->d_outs.p, static_cast<int32_t>(ntasks), b->d_px.p, b->d_py.p, b->d_pp.p, b->d_seq.p, d_use.p, d_target.p, d_e.p, d_seen.p};
-        const int rc = launch_base_expectations(a, ctx->stream);
-        if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_base_expectations launch", static_cast<hipError_t>(rc));
+        if (b->tasks.empty() || !rows) return NPR_OK;
+        DeviceExpectations d;
+        const int32_t rc = accumulate_base_expectations(b, use, n_refs, ref_len, base, "npr_batch_base_expectations: a read's window does not fit its reference", d);
+        if (rc != NPR_OK) return rc;
         static_assert(sizeof(unsigned long long) == sizeof(double), "the caller's table doubles as the staging of the fixed-point sums");
-        HIP_TRY(ctx, hipMemcpyAsync(expect, d_e.p, d_e.bytes(), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(seen, d_seen.p, d_seen.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(expect, d.e.p, d.e.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(seen, d.seen.p, d.seen.bytes(), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         for (int64_t i = 0; i < 4 * rows; ++i) {
             unsigned long long fixed;
@@ -516,6 +578,73 @@ int32_t npr_batch_base_expectations(npr_batch *b, const uint8_t *use, int64_t n_
         return NPR_OK;
     } catch (const std::exception &) {
         return fail(ctx, NPR_ERR_NOMEM, "npr_batch_base_expectations: out of host memory");
+    }
+}
+
+int32_t npr_snp_calls_table(npr_ctx *ctx, int64_t rows, const double *weights, const uint8_t *seen, const uint8_t *ref_code, const uint8_t *true_code,
+                            int32_t n_models, const double *evolution16, const double *error16, npr_snp_calls *out) {
+    if (!ctx) return NPR_ERR_INVALID;
+    if (rows < 0 || (rows && (!weights || !seen || !ref_code)) || !out) return fail(ctx, NPR_ERR_INVALID, "npr_snp_calls_table: bad argument");
+    double log_evolution[16], log_error[kSnpMaxModels * 16];
+    if (!snp_log_matrices(n_models, evolution16, error16, log_evolution, log_error))
+        return fail(ctx, NPR_ERR_INVALID, "npr_snp_calls_table: n_models outside 1..4, an error probability that is not a finite number above zero, or an evolution matrix with a negative entry or an all-zero row");
+    try {
+        for (int64_t i = 0; i < 4 * rows; ++i)
+            if (!(weights[i] >= 0.0) || !std::isfinite(weights[i])) return fail(ctx, NPR_ERR_INVALID, "npr_snp_calls_table: a weight is negative or not finite");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        DevBuf<double> d_w;
+        DevBuf<uint8_t> d_seen;
+        hipError_t e;
+        if ((e = d_w.alloc(4 * rows)) != hipSuccess || (e = d_seen.alloc(rows)) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_snp_calls_table: hipMalloc", e);
+        if (rows) {
+            HIP_TRY(ctx, hipMemcpyAsync(d_w.p, weights, d_w.bytes(), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(d_seen.p, seen, d_seen.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        }
+        return run_snp_calls(ctx, rows, SNP_SRC_DOUBLE, d_w.p, d_seen.p, ref_code, true_code, n_models, log_evolution, log_error, out);
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_snp_calls_table: out of host memory");
+    }
+}
+
+int32_t npr_batch_snp_calls(npr_batch *b, const uint8_t *use, int64_t n_refs, const int64_t *ref_len, const uint8_t *ref_code, const uint8_t *true_code,
+                            int32_t n_models, const double *evolution16, const double *error16, npr_snp_calls *out) {
+    if (!b || n_refs < 0 || (n_refs && !ref_len) || !out) return NPR_ERR_INVALID;
+    if (!b->finished) return NPR_ERR_STATE;
+    npr_ctx *ctx = b->ctx;
+    double log_evolution[16], log_error[kSnpMaxModels * 16];
+    if (!snp_log_matrices(n_models, evolution16, error16, log_evolution, log_error))
+        return fail(ctx, NPR_ERR_INVALID, "npr_batch_snp_calls: n_models outside 1..4, an error probability that is not a finite number above zero, or an evolution matrix with a negative entry or an all-zero row");
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        std::vector<int64_t> base;
+        if (!row_bases(n_refs, ref_len, base)) return NPR_ERR_INVALID;
+        const int64_t rows = base[n_refs];
+        if (rows && !ref_code) return fail(ctx, NPR_ERR_INVALID, "npr_batch_snp_calls: no reference base codes");
+        DeviceExpectations d;
+        if (rows) {
+            const int32_t rc = accumulate_base_expectations(b, use, n_refs, ref_len, base, "npr_batch_snp_calls: a read's window does not fit its reference", d);
+            if (rc != NPR_OK) return rc;
+        }
+        return run_snp_calls(ctx, rows, SNP_SRC_FIXED, d.e.p, d.seen.p, ref_code, true_code, n_models, log_evolution, log_error, out);
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_batch_snp_calls: out of host memory");
+    }
+}
+
+int32_t npr_pileup_snp_calls(npr_pileup *pl, const uint8_t *ref_code, const uint8_t *true_code, int32_t n_models, const double *evolution16,
+                             const double *error16, npr_snp_calls *out) {
+    if (!pl || !out) return NPR_ERR_INVALID;
+    npr_ctx *ctx = pl->ctx;
+    if (pl->rows && !ref_code) return fail(ctx, NPR_ERR_INVALID, "npr_pileup_snp_calls: no reference base codes");
+    double log_evolution[16], log_error[kSnpMaxModels * 16];
+    if (!snp_log_matrices(n_models, evolution16, error16, log_evolution, log_error))
+        return fail(ctx, NPR_ERR_INVALID, "npr_pileup_snp_calls: n_models outside 1..4, an error probability that is not a finite number above zero, or an evolution matrix with a negative entry or an all-zero row");
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        // (words 0-4 are what k_pileup_add wrote on this stream: the running sum of word 5 is not needed)
+        return run_snp_calls(ctx, pl->rows, SNP_SRC_PILEUP, pl->tab.p, nullptr, ref_code, true_code, n_models, log_evolution, log_error, out);
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_pileup_snp_calls: out of host memory");
     }
 }
 

@@ -407,6 +407,25 @@ struct ExpectArgs {
     uint8_t *seen;          // [positions]
 };
 int launch_base_expectations(const ExpectArgs &a, void *stream);
+// SNP calls from a table of four base weights per reference position (npr_snpcall.hip; include/nprealign.h: npr_*_snp_calls).  The table is
+// read where it lies, in the form it has: `source` says which.
+enum { SNP_SRC_FIXED = 0, SNP_SRC_PILEUP = 1, SNP_SRC_DOUBLE = 2 };
+constexpr int SNP_BINS = 101;                 // NPR_SNP_BINS
+constexpr int SNP_OUT_WORDS = 2 * SNP_BINS + 2;  // one model's output: true_pos[101], false_pos[101], not_called, rows_called (an npr_snp_calls)
+struct SnpCallArgs {
+    int64_t rows;
+    int32_t source;
+    int32_t n_models;           // 1 .. 4
+    const void *table;          // SNP_SRC_FIXED: unsigned long long [rows][4] in units of 1 / EXPECT_FIXED_ONE; SNP_SRC_PILEUP: int32 [rows][NPR_PILEUP_WORDS];
+                                // SNP_SRC_DOUBLE: double [rows][4]
+    const uint8_t *seen;        // [rows]; SNP_SRC_PILEUP: unused (seen = words 0-4 summed != 0)
+    const uint8_t *ref_code;    // [rows] base codes 0..4
+    const uint8_t *true_code;   // [rows], or NULL: the truth is the reference
+    double log_evolution[16];   // [reference][candidate]
+    double log_error[4][16];    // [model][candidate][observed]
+    unsigned long long *out;    // [n_models][SNP_OUT_WORDS], added to
+};
+int launch_snp_calls(const SnpCallArgs &a, void *stream);
 // NPR_MODE_RESCORE_ORIGINAL on the device (npr_stats.hip; cactus_realign --rescoreOriginalAlignment, nanopore/analyses/alignmentUncertainty.py:41):
 // the mean posterior over the M columns of the guide.  k_rescore_table spreads the guide's M runs into a table of one entry per reference
 // position of the read's window (the read position the guide aligns it to, -1: none); k_rescore_sum looks every posterior pair up in it where the

@@ -28,9 +28,11 @@ failed jobs.
 
 Differences from the reference: `setupExperiments` hands its `analysers` argument to the experiments (the reference hands the
 module's list whatever it was given); input files are taken in sorted order; the job tree options are gone, `--mappers`,
-`--analyses`, `--metaAnalyses` (class names) and `--device` are new.
+`--analyses`, `--metaAnalyses` (class names), `--device` and `--mutateReferences` are new.  `--mutateReferences` adds, for every
+processed reference, the mutated copies and truth files of analyses/mutate_reference.py (the held-out SNPs MarginAlignSnpCaller
+calls): the step the reference has commented out at pipeline.py:194.
 
-    python -m nanopore_amd.pipeline workingDir [--mappers A,B] [--analyses C,D] [--metaAnalyses E,F] [--device N]
+    python -m nanopore_amd.pipeline workingDir [--mappers A,B] [--analyses C,D] [--metaAnalyses E,F] [--device N] [--mutateReferences]
 """
 import argparse
 import importlib
@@ -40,6 +42,7 @@ import pkgutil
 import sys
 
 from .analyses.abstractAnalysis import AbstractAnalysis
+from .analyses.mutate_reference import mutateReferenceSequences
 from .analyses.names import makeFastaSequenceNamesUnique, makeFastqSequenceNamesUnique
 from .bioio import Target
 from .mappers.abstractMapper import AbstractMapper
@@ -227,6 +230,8 @@ def main(argv=None):
     parser.add_argument("--analyses", help="comma-separated analysis class names (default: %s)" % ",".join(a.__name__ for a in analyses))
     parser.add_argument("--metaAnalyses", help="comma-separated meta-analysis class names (default: %s)" % ",".join(m.__name__ for m in metaAnalyses))
     parser.add_argument("--device", type=int, default=0, help="the GPU everything runs on (default 0)")
+    parser.add_argument("--mutateReferences", action="store_true", help="also map to copies of every reference with 1, 5, 10 and 20 percent of the "
+                        "bases substituted, written with their truth files next to the processed references (default: off)")
     options = parser.parse_args(argv)
     workingDir = options.workingDir
     chosenMappers = mappers if options.mappers is None else resolveClasses(options.mappers, "nanopore_amd.mappers", AbstractMapper)
@@ -252,6 +257,8 @@ def main(argv=None):
     os.makedirs(processedDir, exist_ok=True)
     referenceFastaFiles = [makeFastaSequenceNamesUnique(os.path.join(fastaParentDir, f), os.path.join(processedDir, f))
                            for f in _inputFiles(fastaParentDir, (".fa", ".fasta"))]
+    if options.mutateReferences:
+        referenceFastaFiles = mutateReferenceSequences(referenceFastaFiles)
 
     logger.info("Working directory %s, output directory %s" % (workingDir, outputDir))
     for readType, readTypeFastqFiles in readFastqFiles:

@@ -75,6 +75,22 @@ def _read_spans(text, name_span, begin, end):
     return _arr(text, np.uint8), _arr(name_span, np.int64, 2), _arr(begin, np.int64), _arr(end, np.int64)
 
 
+def _snp_calls(fn, where, ctx, head, rows, ref_code, true_code, evolution, errors):
+    """The call the three SNP-call entry points share (include/nprealign.h: npr_snp_calls_table): fn(*head, ref_code, true_code, n_models,
+    evolution16, error16, out) with one 4 x 4 error matrix [candidate, observed] per model in `errors` and the 4 x 4 `evolution`
+    [reference, candidate], both as probabilities.  -> per model (true_pos int64[101], false_pos int64[101], not_called, rows_called)."""
+    ref_code, true_code = _arr(ref_code, np.uint8), _arr(true_code, np.uint8)
+    if ref_code is None or ref_code.shape != (rows,) or (true_code is not None and true_code.shape != (rows,)):
+        raise ValueError("one reference base code (and one true base code) per table row")
+    evolution, errors = _arr(evolution, np.float64), _arr(errors, np.float64)
+    if evolution.size != 16 or errors.size % 16:
+        raise ValueError("evolution is one 4 x 4 matrix, errors a list of 4 x 4 matrices")
+    n_models = errors.size // 16
+    out = (_lib.SnpCalls * max(n_models, 1))()
+    check(fn(*head, ptr(ref_code), ptr(true_code), n_models, ptr(evolution), ptr(errors), C.byref(out)), where, ctx)
+    return [(np.array(o.true_pos, dtype=np.int64), np.array(o.false_pos, dtype=np.int64), int(o.not_called), int(o.rows_called)) for o in out[:n_models]]
+
+
 class _Handle(object):
     """An object of the library that belongs to a Context (Batch, Pileup, SeedIndex): destroyed once, by close(), by the context's
     close() or when it is collected, whichever comes first."""
@@ -225,6 +241,15 @@ class Batch(_Handle):
               "npr_batch_base_expectations", self.ctx)
         return expect, seen.astype(bool)
 
+    def snp_calls(self, ref_lengths, ref_code, true_code, evolution, errors, use=None):
+        """SNP calls from the posterior-weighted base counts of the (selected) reads, made where k_base_expectations leaves the table: only
+        the histograms leave the device (include/nprealign.h: npr_batch_snp_calls; _snp_calls for the matrices and what comes back)."""
+        ref_lengths, u = _arr(ref_lengths, np.int64), _arr(use, np.uint8)
+        if u is not None and len(u) != self.n_reads:
+            raise ValueError("use must have one entry per read of the batch")
+        return _snp_calls(self._L.npr_batch_snp_calls, "npr_batch_snp_calls", self.ctx, (self._h, ptr(u), len(ref_lengths), ptr(ref_lengths)),
+                          int(ref_lengths.sum()), ref_code, true_code, evolution, errors)
+
     def plan_check(self):
         """Tasks whose device-made band rows / schedules / stripe tables differ from the host planner's (test aid;
         include/nprealign.h: npr_batch_plan_check)."""
@@ -314,6 +339,11 @@ class Pileup(_Handle):
         out = np.zeros((self.rows, _lib.PILEUP_WORDS), dtype=np.int32)
         check(self._L.npr_pileup_counts(self._h, ptr(out)), "npr_pileup_counts", self.ctx)
         return out
+
+    def snp_calls(self, ref_code, true_code, evolution, errors):
+        """SNP calls from the aligned-base frequencies of the table so far (words 0-3; a row is seen when words 0-4 are not all zero), made
+        on the device (include/nprealign.h: npr_pileup_snp_calls; _snp_calls for the matrices and what comes back)."""
+        return _snp_calls(self._L.npr_pileup_snp_calls, "npr_pileup_snp_calls", self.ctx, (self._h,), self.rows, ref_code, true_code, evolution, errors)
 
     def depth(self):
         """(depth int32 [rows], covered bool [rows]): what `samtools depth` prints (M columns) and which positions it prints a line for
@@ -486,6 +516,15 @@ class Context(object):
     def pileup(self, ref_lengths):
         """A zeroed per-position table for reference sequences of these lengths (Pileup; include/nprealign.h: npr_pileup_create)."""
         return Pileup(self, ref_lengths)
+
+    def snp_calls_table(self, weights, seen, ref_code, true_code, evolution, errors):
+        """SNP calls from any table of four non-negative base weights per row, uploaded and called on the device (include/nprealign.h:
+        npr_snp_calls_table; _snp_calls for the matrices and what comes back)."""
+        weights, seen = _arr(weights, np.float64, 4), _arr(seen, np.uint8)
+        if seen.shape != (len(weights),):
+            raise ValueError("one seen flag per table row")
+        return _snp_calls(self._L.npr_snp_calls_table, "npr_snp_calls_table", self, (self._h, len(weights), ptr(weights), ptr(seen)), len(weights),
+                          ref_code, true_code, evolution, errors)
 
     def seed_index(self, refs, k=16):
         """The exact-match seed index of the ASCII sequences `refs` (SeedIndex; include/nprealign.h: npr_seed_index_create)."""
