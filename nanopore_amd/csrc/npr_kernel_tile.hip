@@ -29,6 +29,12 @@
 // Any band shape and width goes: what is outside the band is masked per anti-diagonal from the band arrays.
 // Bit-identical to the other kernels and to the fp32 mirror (same cell arithmetic, order of evaluation is irrelevant to
 // a cell's value).
+//
+// Layout: what the three stripe kernels share with k_dp_tile_cs (stripe table entries, row masks, progress words, stripe
+// descriptors, the DPP shift of a cell) is npr_stripe.h.  Here: rows and neighbour cells in memory, the two steps, then the
+// pieces k_dp_tile and k_em_tile are both built from, each written once -- the task and its LDS preamble (TileTask), the
+// hand-over between neighbour stripes (TileEdge: the one polling loop and the one edge_stage call), the forward sweep
+// (tile_forward_sweep), corner cells, totals, the task epilogue --, then the two kernels, which differ in their backward sweeps.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +43,7 @@
 #include "npr_cell.h"
 #include "npr_device.h"
 #include "npr_frame.h"
+#include "npr_stripe.h"
 
 namespace npr {
 
@@ -47,40 +54,8 @@ constexpr int TILE_BLOCK = 16;  // neighbour cells staged / published at a time
 constexpr int EDGE_FLOATS = 8;  // one neighbour cell in memory: m, sx, sy, lx, ly, e, -, -
 constexpr int EDGE_ST_AUX = 0, EDGE_LD_AUX = 16;  // cache policy of the neighbour cells' stores and loads (16: sc1, edge_stage)
 
-typedef const __attribute__((address_space(4))) int32_t *cptr_i32;
-
-struct UStripe {
-    int X, K, df, dl;
-    uint32_t row0;
-};
-__device__ __forceinline__ UStripe load_stripe(const Stripe *tab, int s) {
-    cptr_i32 p = (cptr_i32)(tab + s);
-    return UStripe{p[0], p[1], p[2], p[3], static_cast<uint32_t>(p[4])};
-}
-
-// lane masks of a row from its packed word (npr_sched.h tile_row_word): mask_r = (~0 << lo_r) & (~0 >> sh_r), six-bit
-// fields -- the 64-bit shifts take six bits of their count, so the fields need no masking
-__device__ __forceinline__ Masks<2> row_masks(uint32_t w) {
-    Masks<2> m;
-    m.cell[0] = (~0ull << (w & 63u)) & (~0ull >> ((w >> 6) & 63u));
-    m.cell[1] = (~0ull << ((w >> 12) & 63u)) & (~0ull >> ((w >> 18) & 63u));
-    m.lanes = m.cell[0] | m.cell[1];
-    m.l0 = 0;
-    return m;
-}
-
-// progress words: volatile LDS accesses (the pointer has to say LDS, or the compiler emits flat loads)
-typedef __attribute__((address_space(3))) int lds_int;
-__device__ __forceinline__ int lds_peek(const int *p) { return *(const volatile lds_int *)(p); }
-__device__ __forceinline__ void lds_poke(int *p, int v) { *(volatile lds_int *)(p) = v; }
-
 // One row per anti-diagonal of a stripe: 64*R cells of 8 bytes, lane l at 8*R*l.  The descriptor is the stripe's (its
-// first row); `vo` = this lane's byte offset in the row + 8 * 64 * R * (row - first row), in a VGPR: nothing per row on the
-// scalar unit, and no scalar offset operand (npr_frame.h store_row explains why).
-template <int R>
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t stripe_rsrc(char *base, uint32_t row0, int row_bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(base + static_cast<int64_t>(row0) * row_bytes, 0, -1, 0x00020000);
-}
+// first row, stripe_rsrc); `vo` = this lane's byte offset in the row + 8 * 64 * R * (row - first row), in a VGPR.
 template <int R>
 __device__ __forceinline__ void tile_store_row(__amdgpu_buffer_rsrc_t rs, int vo, const Diag<R> &C, const Masks<R> &mk) {
     static_assert(R == 2, "k_dp_tile: two slots per lane");
@@ -92,6 +67,15 @@ __device__ __forceinline__ void tile_load_row(__amdgpu_buffer_rsrc_t rs, int vo,
     if (__builtin_amdgcn_inverse_ballot_w64(mk.lanes)) {
         const v4i q = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 0);
         f.v[0] = bitsf(q.x), f.e[0] = q.y, f.v[1] = bitsf(q.z), f.e[1] = q.w;
+    }
+}
+// the other four states of a row (k_em_tile): a second row of 16 bytes per cell
+template <int R>
+__device__ __forceinline__ void tile_store_planes(__amdgpu_buffer_rsrc_t rs, int vo, const Diag<R> &C, const Masks<R> &mk) {
+    static_assert(R == 2, "k_em_tile: two slots per lane");
+    if (__builtin_amdgcn_inverse_ballot_w64(mk.lanes)) {
+        __builtin_amdgcn_raw_buffer_store_b128(v4i{fbits(C.c[0].sx), fbits(C.c[0].sy), fbits(C.c[0].lx), fbits(C.c[0].ly)}, rs, vo, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(v4i{fbits(C.c[1].sx), fbits(C.c[1].sy), fbits(C.c[1].lx), fbits(C.c[1].ly)}, rs, vo + 16, 0, 0);
     }
 }
 
@@ -120,27 +104,6 @@ __device__ __forceinline__ Cell edge_get(const float *stage, int k) {
     return Cell{q.x, q.y, q.z, q.w, g.x, fbits(g.y)};
 }
 
-__device__ __forceinline__ Cell dpp_cell_from_below(const Cell &v, const Cell &edge) {
-    Cell o;
-    o.m = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.m), fbits(v.m), 0x138, 0xf, 0xf, false));
-    o.sx = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.sx), fbits(v.sx), 0x138, 0xf, 0xf, false));
-    o.sy = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.sy), fbits(v.sy), 0x138, 0xf, 0xf, false));
-    o.lx = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.lx), fbits(v.lx), 0x138, 0xf, 0xf, false));
-    o.ly = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.ly), fbits(v.ly), 0x138, 0xf, 0xf, false));
-    o.e = __builtin_amdgcn_update_dpp(edge.e, v.e, 0x138, 0xf, 0xf, false);
-    return o;
-}
-__device__ __forceinline__ Cell dpp_cell_from_above(const Cell &v, const Cell &edge) {
-    Cell o;
-    o.m = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.m), fbits(v.m), 0x130, 0xf, 0xf, false));
-    o.sx = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.sx), fbits(v.sx), 0x130, 0xf, 0xf, false));
-    o.sy = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.sy), fbits(v.sy), 0x130, 0xf, 0xf, false));
-    o.lx = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.lx), fbits(v.lx), 0x130, 0xf, 0xf, false));
-    o.ly = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.ly), fbits(v.ly), 0x130, 0xf, 0xf, false));
-    o.e = __builtin_amdgcn_update_dpp(edge.e, v.e, 0x130, 0xf, 0xf, false);
-    return o;
-}
-
 // One forward anti-diagonal of a stripe.  `io`: d-2 on entry, d on exit; `p1`: d-1; `carry`: the slot-below copy of
 // d-2's top register (made by the step before) on entry, that of d-1 on exit; `edge`: the left stripe's last column on
 // d-1 (every lane holds it, lane 0 uses it).  bx / by: X[x-1]*4 and Y[y-1]*4 of every slot.
@@ -159,7 +122,7 @@ __device__ __forceinline__ void tile_emissions(const StepEnv &E, const Bases<R> 
 template <int R, bool FLAT = false>
 __device__ __forceinline__ void tile_fwd_step(int d, const StepEnv &E, Diag<R> &io, const Diag<R> &p1, Cell &carry, const Cell &edge,
                                               const Bases<R> &bx, const Bases<R> &by, const Masks<R> &mk) {
-    const Cell Le = dpp_cell_from_below(p1.c[R - 1], edge);  // (x-1, y) of every lane's register 0
+    const Cell Le = cell_from_below(p1.c[R - 1], edge);  // (x-1, y) of every lane's register 0
     Diag<R> o;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -176,7 +139,7 @@ __device__ __forceinline__ void tile_fwd_step(int d, const StepEnv &E, Diag<R> &
 template <int R, bool FLAT = false>
 __device__ __forceinline__ void tile_bwd_step(int d, const StepEnv &E, Diag<R> &io, const Diag<R> &s1, Cell &carry, const Cell &edge,
                                               const Bases<R> &bx, const Bases<R> &by, const Masks<R> &mk) {
-    const Cell Xe = dpp_cell_from_above(s1.c[0], edge);  // (x+1, y) of every lane's top register
+    const Cell Xe = cell_from_above(s1.c[0], edge);  // (x+1, y) of every lane's top register
     Diag<R> o;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -189,197 +152,298 @@ __device__ __forceinline__ void tile_bwd_step(int d, const StepEnv &E, Diag<R> &
     carry = Xe;
 }
 
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// =====================================================================================================================
+// What k_dp_tile and k_em_tile share: the task, the hand-over between neighbour stripes, the forward sweep, the totals.
+
+// The dynamic LDS of a workgroup: the model, then misc ([0..3] totals, [4] pair counter, [5] next task), one progress word per
+// wavefront, one staging block of neighbour cells per wavefront (k_em_tile: its bins behind those, em_tile_lds_bytes)
+struct TileLds {
+    float *model;
+    int *misc, *prog;
+    float *stage;  // this wavefront's
+};
+__device__ __forceinline__ TileLds tile_lds(char *smem, int wv) {
+    TileLds L;
+    L.model = reinterpret_cast<float *>(smem);
+    L.misc = reinterpret_cast<int *>(L.model + MODEL_FLOATS);
+    L.prog = L.misc + 8;
+    L.stage = reinterpret_cast<float *>(L.prog + TILE_MAX_NW) + wv * (TILE_BLOCK * EDGE_FLOATS);
+    return L;
+}
+
+// One task, everything wave-uniform.
+struct TileTask {
+    const uint8_t *X, *Y;
+    int64_t pair_off;
+    int lX, lY, D, pair_cap, model, xs, ys;
+    int rs, re;          // rows of the model's start / end vectors
+    cptr32 rowmask;      // one packed word per row, through the scalar cache
+    const Stripe *tab;   // stripe s of S
+    int S;
+    char *Ef, *Eb;       // neighbour cells of the forward / the backward sweep, behind the rows in the task's scratch
+};
+template <int R>
+__device__ __forceinline__ TileTask tile_task(const KernelArgs &a, int t, char *F) {
+    const Task *tp = a.tasks + t;
+    const int64_t tile_off = uni64(tp->tile_off), rowmask_off = uni64(tp->rowmask_off);
+    const int flags = uni(tp->flags);
+    TileTask T;
+    T.X = a.seq + uni64(tp->x_off), T.Y = a.seq + uni64(tp->y_off), T.pair_off = uni64(tp->pair_off);
+    T.lX = uni(tp->lX), T.lY = uni(tp->lY), T.D = uni(tp->D), T.pair_cap = uni(tp->pair_cap), T.model = uni(tp->model);
+    T.xs = uni(tp->xs), T.ys = uni(tp->ys);
+    T.rs = flags & 1, T.re = (flags >> 1) & 1;
+    T.rowmask = (cptr32)(a.rowmask + rowmask_off);
+    const Stripe *tab = a.stripes + tile_off;
+    const UStripe hd = load_stripe(tab, 0);  // the table's header: stripes, rows
+    T.S = hd.X;
+    T.tab = tab + 1;
+    const uint32_t rows = static_cast<uint32_t>(hd.K);
+    T.Ef = F + static_cast<int64_t>(rows) * (64 * R * 8);
+    T.Eb = T.Ef + static_cast<int64_t>(rows) * (4 * EDGE_FLOATS);
+    return T;
+}
+// The workgroup takes the task up: the model into LDS, totals / pair counter / progress words reset (and BIN_ROWS rows of this
+// wavefront's `lbins`, k_em_tile), between two barriers.  Returns the step environment with the transitions in VGPRs.
+template <int BIN_ROWS>
+__device__ __forceinline__ StepEnv tile_task_begin(const KernelArgs &a, const TileTask &T, const TileLds &L, int lane, float *lbins) {
+    __syncthreads();
+    {
+        const float *gm = reinterpret_cast<const float *>(a.models + T.model);
+        for (int i = threadIdx.x; i < MODEL_FLOATS; i += blockDim.x) L.model[i] = gm[i];
+        if (threadIdx.x == 0) L.misc[0] = 0, L.misc[1] = E_DEAD, L.misc[2] = 0, L.misc[3] = E_DEAD, L.misc[4] = 0;
+        if (threadIdx.x < TILE_MAX_NW) L.prog[threadIdx.x] = 0;
+        if constexpr (BIN_ROWS > 0)
+            for (int i = 0; i < BIN_ROWS; ++i) lbins[i * WAVE + lane] = 0.f;
+    }
+    __syncthreads();
+    StepEnv E;
+    E.mdl = reinterpret_cast<const DevModel *>(L.model);
+    E.ltab = reinterpret_cast<const char *>(L.model);
+    E.X = T.X, E.Y = T.Y, E.lX = T.lX, E.lY = T.lY, E.lane = lane;
+    E.tr = load_trans(E.mdl->T);
+    return E;
+}
+
+// The start cell (0, 0) / the end cell (lX, lY) from the model's start / end vector
+__device__ __forceinline__ Cell corner_cell(const float *v) {
+    Cell c;
+    c.m = v[0], c.sx = v[1], c.sy = v[2], c.lx = v[3], c.ly = v[4];
+    normalise(c, 0);
+    return c;
+}
+// A sweep's total, <v, c> at its last corner, as (mantissa, exponent) into misc[slot], misc[slot + 1] (by the one lane that holds c)
+__device__ __forceinline__ void capture_total(int *misc, int slot, const float *v, const Cell &c) {
+    const float raw = dot5(v, c);
+    if (raw > 0.f) {
+        int k;
+        reinterpret_cast<float *>(misc)[slot] = __builtin_frexpf(raw, &k);
+        misc[slot + 1] = c.e + k;
+    }
+}
+// A stripe's neighbour cells up to here are in memory: tell the wavefront that sweeps the neighbour stripe
+__device__ __forceinline__ void publish_progress(int *word, int v, int lane) {
+    wait_vm();
+    if (lane == 0) lds_poke(word, v);
+}
+
+// The stripe next to the one a wavefront sweeps and the block of its neighbour cells this wavefront has staged in LDS.
+// DIR = +1, the forward sweep: the stripe to the LEFT, whose last column slot 0 needs; its wavefront's progress word counts the rows
+// whose neighbour cells are out.  DIR = -1, the backward sweep: the stripe to the RIGHT, whose first column the top slot needs; the
+// progress word is the LOWEST row whose cell is out.  Entry q of the neighbour is its anti-diagonal df + q, row row0 + q.
+// THE hand-over: a consumer never reads a cell before the producer's progress word covers it (the wait has no bound: the planner's
+// stripe tables promise every row a wavefront that writes it), and the loads that follow bypass the vector L1 (edge_stage).
+template <int DIR>
+struct TileEdge {
+    int df, len;         // the neighbour's first anti-diagonal and how many it has (0: no neighbour)
+    uint32_t row0;
+    const int *prog;     // the progress word of the wavefront that sweeps it
+    char *cells;         // its neighbour cells in the task's scratch (Ef / Eb)
+    float *stage;
+    int lane;
+    int blk_lo, blk_hi;  // staged: entries [blk_lo, blk_hi)
+};
+template <int DIR>
+__device__ __forceinline__ TileEdge<DIR> edge_open(const TileTask &T, const TileLds &L, int s, int NW, int lane) {
+    TileEdge<DIR> e;
+    int df = 1, dl = 0, w = 0;
+    e.row0 = 0;
+    if (DIR > 0 ? s > 0 : s + 1 < T.S) {
+        const UStripe n = load_stripe(T.tab, s - DIR);
+        df = n.df, dl = n.dl, e.row0 = n.row0;
+        w = (s - DIR) % NW;
+    }
+    e.df = df, e.len = dl - df + 1;
+    e.prog = L.prog + w, e.cells = DIR > 0 ? T.Ef : T.Eb, e.stage = L.stage, e.lane = lane;
+    e.blk_lo = e.blk_hi = DIR > 0 ? 0 : e.len;
+    return e;
+}
+// wait for the block of TILE_BLOCK entries that begins (forward) / ends (backward) with entry q, and stage it
+template <int DIR>
+__device__ __forceinline__ void edge_fetch(TileEdge<DIR> &e, int q) {
+    const int lo = DIR > 0 ? q : max(q - TILE_BLOCK + 1, 0), hi = DIR > 0 ? min(q + TILE_BLOCK, e.len) : q + 1;
+    const int need = static_cast<int>(e.row0) + (DIR > 0 ? hi : lo);
+    while (DIR > 0 ? uni(lds_peek(e.prog)) < need : uni(lds_peek(e.prog)) > need) __builtin_amdgcn_s_sleep(2);
+    asm volatile("" ::: "memory");
+    edge_stage(e.cells, e.row0 + lo, hi - lo, e.stage, e.lane);
+    e.blk_lo = lo, e.blk_hi = hi;
+}
+// `carry` for a stripe's first anti-diagonal d0: (x-1, y-1) of slot 0 / (x+1, y+1) of the top slot is the neighbour's cell on d0 -+ 2
+template <int DIR>
+__device__ __forceinline__ void edge_seed(TileEdge<DIR> &e, int d0, Cell &carry) {
+    const int q0 = d0 - 2 * DIR - e.df;
+    if (q0 >= 0 && q0 < e.len) {
+        edge_fetch(e, q0);
+        const Cell c0 = edge_get(e.stage, q0 - e.blk_lo);
+        if (e.lane == (DIR > 0 ? 0 : WAVE - 1)) carry = c0;
+    }
+}
+// the neighbour's cell that the step of anti-diagonal d needs (its cell on d -+ 1; dead where it has none), in every lane
+template <int DIR>
+__device__ __forceinline__ Cell edge_at(TileEdge<DIR> &e, int d) {
+    Cell c = dead_cell();
+    const int q = d - DIR - e.df;
+    if (static_cast<unsigned>(q) < static_cast<unsigned>(e.len)) {  // uniform; 0 <= q < len (len >= 0)
+        if (DIR > 0 ? q >= e.blk_hi : q < e.blk_lo) edge_fetch(e, q);
+        c = edge_get(e.stage, q - e.blk_lo);
+    }
+    return c;
+}
+
+// The forward sweep over this wavefront's stripes (s == wv mod NW).  PLANES: the other four states of every cell go to Fx too
+// (k_em_tile, tile_store_planes).  Leaves the total in misc[0..1].
+template <int R, bool FLAT, bool PLANES>
+__device__ __forceinline__ void tile_forward_sweep(const TileTask &T, const StepEnv &E, const TileLds &L, int wv, int NW, char *F, char *Fx) {
+    constexpr int K = 64 * R;
+    const int lane = E.lane, lX = T.lX, lY = T.lY;
+    const int voff = 8 * R * lane;
+    int jr[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) jr[r] = R * lane + r;
+    for (int s = wv; s < T.S; s += NW) {
+        const UStripe st = load_stripe(T.tab, s);
+        if (st.dl < st.df) continue;
+        TileEdge<+1> left = edge_open<+1>(T, L, s, NW, lane);
+        Bases<R> bx, by;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            bx.b[r] = base4(E.X, lX, st.X + jr[r] - 1);
+            by.b[r] = base4(E.Y, lY, (st.df - 1) - st.X - jr[r] - 1);  // as of anti-diagonal df - 1
+        }
+        Feed fy;
+        feed_init<+1>(fy, E.Y, lY, st.df - st.X - 1, lane);
+        Diag<R> A = dead_diag<R>(), B = dead_diag<R>();
+        Cell carry = dead_cell();
+        const uint64_t out_lane = 1ull << (st.K / R - 1);  // holds the stripe's last column in its top register
+        cptr32 rm = T.rowmask + st.row0;                    // walked by pointer: the word of the row in hand
+        uint32_t w_n = rm[0];                               // mask word one row ahead
+        const __amdgpu_buffer_rsrc_t rsF = stripe_rsrc(F, st.row0, K * 8), rsE = stripe_rsrc(T.Ef, st.row0, 4 * EDGE_FLOATS);
+        [[maybe_unused]] const __amdgpu_buffer_rsrc_t rsX = PLANES ? stripe_rsrc(Fx, st.row0, K * 16) : rsF;
+        edge_seed(left, st.df, carry);
+
+        auto step = [&](int d, Diag<R> &io, const Diag<R> &p1) {
+            const int k = d - st.df;
+            const Masks<R> mk = row_masks(w_n);
+            if (d < st.dl) w_n = rm[1];
+            rm += 1;
+            const Cell edge = edge_at(left, d);
+            bases_down<R>(by, feed_get<+1>(fy, E.Y, lY, d - st.X - 1, lane));
+            tile_fwd_step<R, FLAT>(d, E, io, p1, carry, edge, bx, by, mk);
+            if (d == 0) {  // the start cell (0, 0): slot 0 of the first stripe
+                if (lane == 0) io.c[0] = corner_cell(E.mdl->start + T.rs * 5);
+            }
+            tile_store_row<R>(rsF, voff + k * (K * 8), io, mk);
+            if constexpr (PLANES) tile_store_planes<R>(rsX, 2 * voff + k * (K * 16), io, mk);
+            edge_store(rsE, k, io.c[R - 1], out_lane);
+            if ((k & (TILE_BLOCK - 1)) == TILE_BLOCK - 1 || d == st.dl) publish_progress(L.prog + wv, static_cast<int>(st.row0) + k + 1, lane);
+        };
+        int d = st.df;
+        for (; d + 1 <= st.dl; d += 2) {
+            step(d, B, A);
+            step(d + 1, A, B);
+        }
+        if (d <= st.dl) step(d, B, A);
+        if (s == T.S - 1) {  // total probability at the end corner (lX, lY), anti-diagonal D = this stripe's last row
+            const bool inB = ((st.dl - st.df) & 1) == 0;
+            const int je = lX - st.X;
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (jr[r] == je) capture_total(L.misc, 0, E.mdl->end + T.re * 5, inB ? B.c[r] : A.c[r]);
+        }
+    }
+}
+// Every wavefront is through its forward sweep: what the task reports so far (the backward total and the pairs come later)
+__device__ __forceinline__ TaskOut tile_forward_out(const int *misc) {
+    __syncthreads();
+    TaskOut out;
+    out.tot_m = unif(reinterpret_cast<const float *>(misc)[0]), out.tot_e = uni(misc[1]);
+    out.btot_m = 0.f, out.btot_e = E_DEAD, out.npairs = 0;
+    out.status = out.tot_m > 0.f ? NPR_OK : NPR_ERR_ZERO_PROB;
+    return out;
+}
+// Before the backward sweep: the progress words now mean the LOWEST row whose neighbour cell is out.  Returns the last stripe of
+// this wavefront (s == wv mod NW).
+__device__ __forceinline__ int tile_backward_begin(const TileLds &L, int S, int wv, int NW) {
+    if (threadIdx.x < TILE_MAX_NW) L.prog[threadIdx.x] = 0x7fffffff;
+    __syncthreads();
+    return S - 1 - ((S - 1 - wv) % NW + NW) % NW;
+}
+// ... and after it: the total from the backward side, which the sweep of stripe 0 left in misc[2..3]
+__device__ __forceinline__ void tile_backward_out(TaskOut &out, const int *misc) {
+    __syncthreads();
+    out.btot_m = unif(reinterpret_cast<const float *>(misc)[2]);
+    out.btot_e = uni(misc[3]);
+}
+// The task's result out, the next task in: returns its index (uniform over the workgroup)
+__device__ __forceinline__ int tile_task_end(const KernelArgs &a, int t, const TaskOut &out, int *misc) {
+    if (threadIdx.x == 0) {
+        a.outs[t] = out;
+        misc[5] = atomicAdd(a.queue, 1);
+    }
+    __syncthreads();
+    return uni(misc[5]) + static_cast<int>(gridDim.x);
+}
 
 template <int R, bool FLAT>
 __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves_per_eu(R == 2 ? 6 : 1))) k_dp_tile(KernelArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float *lmodel = reinterpret_cast<float *>(smem);
-    int *lmisc = reinterpret_cast<int *>(lmodel + MODEL_FLOATS);  // [0..3] totals, [4] pair counter, [5] next task
-    int *prog = lmisc + 8;                                        // [TILE_MAX_NW] rows whose neighbour cells are out
     constexpr int K = 64 * R;
 
     const int lane = threadIdx.x & (WAVE - 1);
     const int wv = uni(static_cast<int>(threadIdx.x) >> 6);
     const int NW = static_cast<int>(blockDim.x) >> 6;
-    float *const stage = reinterpret_cast<float *>(prog + TILE_MAX_NW) + wv * (TILE_BLOCK * EDGE_FLOATS);
+    const TileLds L = tile_lds(smem, wv);
     char *const F = a.F + uni64(a.region[blockIdx.x]) * 8;
     const int voff = 8 * R * lane;
     int jr[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) jr[r] = R * lane + r;
 
-
     int t = blockIdx.x;
     while (t < a.ntasks) {
-        const Task *tp = a.tasks + t;
-        const int64_t x_off = uni64(tp->x_off), y_off = uni64(tp->y_off), pair_off = uni64(tp->pair_off),
-                      tile_off = uni64(tp->tile_off), rowmask_off = uni64(tp->rowmask_off);
-        const int lX = uni(tp->lX), lY = uni(tp->lY), D = uni(tp->D), pair_cap = uni(tp->pair_cap),
-                  flags = uni(tp->flags), model = uni(tp->model), xs = uni(tp->xs), ys = uni(tp->ys);
-        cptr32 rowmask = (cptr32)(a.rowmask + rowmask_off);  // one packed word per row, through the scalar cache
-        const Stripe *tab = a.stripes + tile_off;
-        const UStripe hd = load_stripe(tab, 0);
-        const int S = hd.X;
-        const uint32_t rows = static_cast<uint32_t>(hd.K);
-        tab += 1;
-        char *const Ef = F + static_cast<int64_t>(rows) * (K * 8);           // neighbour cells of the forward sweep
-        char *const Eb = Ef + static_cast<int64_t>(rows) * (4 * EDGE_FLOATS);  // ... of the backward sweep
-        const int rs = flags & 1, re = (flags >> 1) & 1;
-
-        __syncthreads();
-        {
-            const float *gm = reinterpret_cast<const float *>(a.models + model);
-            for (int i = threadIdx.x; i < MODEL_FLOATS; i += blockDim.x) lmodel[i] = gm[i];
-            if (threadIdx.x == 0) lmisc[0] = 0, lmisc[1] = E_DEAD, lmisc[2] = 0, lmisc[3] = E_DEAD, lmisc[4] = 0;
-            if (threadIdx.x < TILE_MAX_NW) prog[threadIdx.x] = 0;
+        const TileTask T = tile_task<R>(a, t, F);
+        StepEnv E = tile_task_begin<0>(a, T, L, lane, nullptr);
+        if constexpr (R >= T_SGPR_MIN_R) {
+            Trans &tr = E.tr;
+            tr.mm = unif(tr.mm), tr.sxm = unif(tr.sxm), tr.sym = unif(tr.sym), tr.lxm = unif(tr.lxm), tr.lym = unif(tr.lym);
+            tr.msx = unif(tr.msx), tr.sxsx = unif(tr.sxsx), tr.sysx = unif(tr.sysx);
+            tr.msy = unif(tr.msy), tr.sysy = unif(tr.sysy), tr.sxsy = unif(tr.sxsy);
+            tr.mlx = unif(tr.mlx), tr.lxlx = unif(tr.lxlx), tr.mly = unif(tr.mly), tr.lyly = unif(tr.lyly);
         }
-        __syncthreads();
-        StepEnv E;
-        E.mdl = reinterpret_cast<const DevModel *>(lmodel);
-        E.ltab = reinterpret_cast<const char *>(lmodel);
-        E.X = a.seq + x_off, E.Y = a.seq + y_off, E.lX = lX, E.lY = lY, E.lane = lane;
-        {
-            Trans tr = load_trans(E.mdl->T);
-            if constexpr (R >= T_SGPR_MIN_R) {
-                tr.mm = unif(tr.mm), tr.sxm = unif(tr.sxm), tr.sym = unif(tr.sym), tr.lxm = unif(tr.lxm), tr.lym = unif(tr.lym);
-                tr.msx = unif(tr.msx), tr.sxsx = unif(tr.sxsx), tr.sysx = unif(tr.sysx);
-                tr.msy = unif(tr.msy), tr.sysy = unif(tr.sysy), tr.sxsy = unif(tr.sxsy);
-                tr.mlx = unif(tr.mlx), tr.lxlx = unif(tr.lxlx), tr.mly = unif(tr.mly), tr.lyly = unif(tr.lyly);
-            }
-            E.tr = tr;
-        }
-        const DevModel *mdl = E.mdl;
+        const int lX = T.lX, lY = T.lY;
 
-        // =============================== forward ===============================
-        for (int s = wv; s < S; s += NW) {
-            const UStripe st = load_stripe(tab, s);
-            if (st.dl >= st.df) {
-            // the stripe to the left: its rows, and which wavefront sweeps it
-            int dfL = 1, dlL = 0, wL = 0;
-            uint32_t row0L = 0;
-            if (s > 0) {
-                const UStripe sl = load_stripe(tab, s - 1);
-                dfL = sl.df, dlL = sl.dl, row0L = sl.row0;
-                wL = (s - 1) % NW;
-            }
-            const int lenL = dlL - dfL + 1;
-            Bases<R> bx, by;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                bx.b[r] = base4(E.X, lX, st.X + jr[r] - 1);
-                by.b[r] = base4(E.Y, lY, (st.df - 1) - st.X - jr[r] - 1);  // as of anti-diagonal df - 1
-            }
-            Feed fy;
-            feed_init<+1>(fy, E.Y, lY, st.df - st.X - 1, lane);
-            Diag<R> A = dead_diag<R>(), B = dead_diag<R>();
-            Cell carry = dead_cell();
-            const uint64_t out_lane = 1ull << (st.K / R - 1);  // holds the stripe's last column in its top register
-            int blk_lo = 0, blk_hi = 0;                         // staged cells of the left stripe: [blk_lo, blk_hi) past dfL
-            cptr32 rm = rowmask + st.row0;                      // walked by pointer: the word of the row in hand
-            uint32_t w_n = rm[0];                               // mask word one row ahead
-            const __amdgpu_buffer_rsrc_t rsF = stripe_rsrc<R>(F, st.row0, K * 8), rsE = stripe_rsrc<R>(Ef, st.row0, 4 * EDGE_FLOATS);
-            {   // (x-1, y-1) of slot 0 on the first anti-diagonal: the left stripe's cell on df - 2
-                const int q0 = st.df - 2 - dfL;
-                if (q0 >= 0 && q0 < lenL) {
-                    const int hi = min(q0 + TILE_BLOCK, lenL);
-                    const int need = static_cast<int>(row0L) + hi;
-                    while (uni(lds_peek(prog + wL)) < need) __builtin_amdgcn_s_sleep(2);
-                    asm volatile("" ::: "memory");
-                    edge_stage(Ef, row0L + q0, hi - q0, stage, lane);
-                    blk_lo = q0, blk_hi = hi;
-                    const Cell c0 = edge_get(stage, 0);
-                    if (lane == 0) carry = c0;
-                }
-            }
-
-            auto step = [&](int d, Diag<R> &io, const Diag<R> &p1) {
-                const int k = d - st.df;
-                const Masks<R> mk = row_masks(w_n);
-                if (d < st.dl) w_n = rm[1];
-                rm += 1;
-                Cell edge = dead_cell();
-                const int q = d - 1 - dfL;
-                if (static_cast<unsigned>(q) < static_cast<unsigned>(lenL)) {  // uniform; 0 <= q < lenL (lenL >= 0)
-                    if (q >= blk_hi) {
-                        const int hi = min(q + TILE_BLOCK, lenL);
-                        const int need = static_cast<int>(row0L) + hi;
-                        while (uni(lds_peek(prog + wL)) < need) __builtin_amdgcn_s_sleep(2);
-                        asm volatile("" ::: "memory");
-                        edge_stage(Ef, row0L + q, hi - q, stage, lane);
-                        blk_lo = q, blk_hi = hi;
-                    }
-                    edge = edge_get(stage, q - blk_lo);
-                }
-                bases_down<R>(by, feed_get<+1>(fy, E.Y, lY, d - st.X - 1, lane));
-                tile_fwd_step<R, FLAT>(d, E, io, p1, carry, edge, bx, by, mk);
-                if (d == 0) {  // the start cell (0, 0): slot 0 of the first stripe
-                    if (lane == 0) {
-                        Cell c;
-                        c.m = mdl->start[rs * 5 + 0], c.sx = mdl->start[rs * 5 + 1], c.sy = mdl->start[rs * 5 + 2];
-                        c.lx = mdl->start[rs * 5 + 3], c.ly = mdl->start[rs * 5 + 4];
-                        normalise(c, 0);
-                        io.c[0] = c;
-                    }
-                }
-                tile_store_row<R>(rsF, voff + k * (K * 8), io, mk);
-                edge_store(rsE, k, io.c[R - 1], out_lane);
-                if ((k & (TILE_BLOCK - 1)) == TILE_BLOCK - 1 || d == st.dl) {
-                    wait_vm();
-                    if (lane == 0) lds_poke(prog + wv, static_cast<int>(st.row0) + k + 1);
-                }
-            };
-            int d = st.df;
-            for (; d + 1 <= st.dl; d += 2) {
-                step(d, B, A);
-                step(d + 1, A, B);
-            }
-            if (d <= st.dl) step(d, B, A);
-            if (s == S - 1) {  // total probability at the end corner (lX, lY), anti-diagonal D = this stripe's last row
-                const bool inB = ((st.dl - st.df) & 1) == 0;
-                const int je = lX - st.X;
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                    if (jr[r] == je) {
-                        const Cell c = inB ? B.c[r] : A.c[r];
-                        const float raw = dot5(mdl->end + re * 5, c);
-                        if (raw > 0.f) {
-                            int k;
-                            reinterpret_cast<float *>(lmisc)[0] = __builtin_frexpf(raw, &k);
-                            lmisc[1] = c.e + k;
-                        }
-                    }
-            }
-            }
-        }
-        __syncthreads();
-        const float tot_m = unif(reinterpret_cast<float *>(lmisc)[0]);
-        const int tot_e = uni(lmisc[1]);
-
-        TaskOut out;
-        out.tot_m = tot_m, out.tot_e = tot_e, out.btot_m = 0.f, out.btot_e = E_DEAD, out.npairs = 0;
-        out.status = NPR_OK;
-        const bool alive = tot_m > 0.f;
-        if (!alive) out.status = NPR_ERR_ZERO_PROB;
+        tile_forward_sweep<R, FLAT, false>(T, E, L, wv, NW, F, nullptr);
+        TaskOut out = tile_forward_out(L.misc);
 
         // =============================== backward + posteriors ===============================
-        if (alive) {
-            const float inv_tot = 1.0f / tot_m;
-            const PairSink sink{a.px, a.py, a.pp, pair_off, pair_cap, xs, ys, a.threshold};
-            if (threadIdx.x < TILE_MAX_NW) prog[threadIdx.x] = 0x7fffffff;  // now: the LOWEST row whose neighbour cell is out
-            __syncthreads();
-            int s_top = S - 1 - ((S - 1 - wv) % NW + NW) % NW;  // the last stripe of this wavefront (s == wv mod NW)
+        if (out.tot_m > 0.f) {
+            const int tot_e = out.tot_e;
+            const float inv_tot = 1.0f / out.tot_m;
+            const PairSink sink{a.px, a.py, a.pp, T.pair_off, T.pair_cap, T.xs, T.ys, a.threshold};
+            const int s_top = tile_backward_begin(L, T.S, wv, NW);
             for (int s = s_top; s >= 0; s -= NW) {
-                const UStripe st = load_stripe(tab, s);
-                if (st.dl >= st.df) {
-                int dfR = 1, dlR = 0, wR = 0;
-                uint32_t row0R = 0;
-                if (s + 1 < S) {
-                    const UStripe sr = load_stripe(tab, s + 1);
-                    dfR = sr.df, dlR = sr.dl, row0R = sr.row0;
-                    wR = (s + 1) % NW;
-                }
-                const int lenR = dlR - dfR + 1;
+                const UStripe st = load_stripe(T.tab, s);
+                if (st.dl < st.df) continue;
+                TileEdge<-1> right = edge_open<-1>(T, L, s, NW, lane);
                 const int X0 = st.X;  // every stripe is 64*R columns wide (npr_sched.h stripe_fill): slot j is column X0 + j
                 Bases<R> bx, by;
 #pragma unroll
@@ -392,29 +456,15 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
                 Diag<R> A = dead_diag<R>(), B = dead_diag<R>();
                 Cell carry = dead_cell();
                 const uint64_t out_lane = 1ull;  // lane 0 holds the stripe's first column in its register 0
-                int blk_lo = 0, blk_hi = 0;                     // staged cells of the right stripe: entries (blk_lo, blk_hi] ... see below
                 FRow<R> fa, fb;
 #pragma unroll
                 for (int r = 0; r < R; ++r) fa.v[r] = fb.v[r] = 0.f, fa.e[r] = fb.e[r] = E_DEAD;
-                cptr32 rm = rowmask + st.row0 + static_cast<uint32_t>(st.dl - st.df);  // walked by pointer: the word of the row in hand
-                const __amdgpu_buffer_rsrc_t rsF = stripe_rsrc<R>(F, st.row0, K * 8), rsE = stripe_rsrc<R>(Eb, st.row0, 4 * EDGE_FLOATS);
+                cptr32 rm = T.rowmask + st.row0 + static_cast<uint32_t>(st.dl - st.df);  // walked by pointer: the word of the row in hand
+                const __amdgpu_buffer_rsrc_t rsF = stripe_rsrc(F, st.row0, K * 8), rsE = stripe_rsrc(T.Eb, st.row0, 4 * EDGE_FLOATS);
                 // forward row of the first anti-diagonal (the later ones are loaded one step ahead, with their masks)
                 Masks<R> mk_n = row_masks(rm[0]);
                 tile_load_row<R>(rsF, voff + (st.dl - st.df) * (K * 8), fb, mk_n);
-                blk_lo = lenR, blk_hi = lenR;  // staged: entries [blk_lo, blk_hi) of the right stripe (entry = d' - dfR); empty
-                {   // (x+1, y+1) of the top slot on the first anti-diagonal: the right stripe's cell on dl + 2
-                    const int q0 = st.dl + 2 - dfR;
-                    if (q0 >= 0 && q0 < lenR) {
-                        const int lo = max(q0 - TILE_BLOCK + 1, 0);
-                        const int need = static_cast<int>(row0R) + lo;
-                        while (uni(lds_peek(prog + wR)) > need) __builtin_amdgcn_s_sleep(2);
-                        asm volatile("" ::: "memory");
-                        edge_stage(Eb, row0R + lo, q0 - lo + 1, stage, lane);
-                        blk_lo = lo, blk_hi = q0 + 1;
-                        const Cell c0 = edge_get(stage, q0 - lo);
-                        if (lane == WAVE - 1) carry = c0;
-                    }
-                }
+                edge_seed(right, st.dl, carry);
 
                 // f: the forward row of d (loaded a step ago); fnext: where the row of d-1 goes
                 auto step = [&](int d, Diag<R> &io, const Diag<R> &s1, FRow<R> &f, FRow<R> &fnext) {
@@ -425,31 +475,13 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
                         mk_n = row_masks(rm[0]);
                         tile_load_row<R>(rsF, voff + (k - 1) * (K * 8), fnext, mk_n);
                     }
-                    Cell edge = dead_cell();
-                    const int q = d + 1 - dfR;
-                    if (static_cast<unsigned>(q) < static_cast<unsigned>(lenR)) {  // uniform; 0 <= q < lenR (lenR >= 0)
-                        if (q < blk_lo) {
-                            const int lo = max(q - TILE_BLOCK + 1, 0);
-                            const int need = static_cast<int>(row0R) + lo;
-                            while (uni(lds_peek(prog + wR)) > need) __builtin_amdgcn_s_sleep(2);
-                            asm volatile("" ::: "memory");
-                            edge_stage(Eb, row0R + lo, q - lo + 1, stage, lane);
-                            blk_lo = lo, blk_hi = q + 1;
-                        }
-                        edge = edge_get(stage, q - blk_lo);
-                    }
+                    const Cell edge = edge_at(right, d);
                     bases_up<R>(by, feed_get<-1>(fy, E.Y, lY, d - X0 - (K - 1), lane));
                     tile_bwd_step<R, FLAT>(d, E, io, s1, carry, edge, bx, by, mk);
-                    if (d == D) {  // the end corner (lX, lY)
+                    if (d == T.D) {  // the end corner (lX, lY)
 #pragma unroll
                         for (int r = 0; r < R; ++r)
-                            if (X0 + jr[r] == lX) {
-                                Cell c;
-                                c.m = mdl->end[re * 5 + 0], c.sx = mdl->end[re * 5 + 1], c.sy = mdl->end[re * 5 + 2];
-                                c.lx = mdl->end[re * 5 + 3], c.ly = mdl->end[re * 5 + 4];
-                                normalise(c, 0);
-                                io.c[r] = c;
-                            }
+                            if (X0 + jr[r] == lX) io.c[r] = corner_cell(E.mdl->end + T.re * 5);
                     }
                     edge_store(rsE, k, io.c[0], out_lane);
                     // posteriors of this anti-diagonal, slots claimed from the workgroup's LDS counter
@@ -465,7 +497,7 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
                         }
                         if (d >= 2 && total) {
                             int base = 0;
-                            if (lane == 0) base = atomicAdd(lmisc + 4, total);
+                            if (lane == 0) base = atomicAdd(L.misc + 4, total);
                             base = uni(base);
                             const int y0 = d - X0;
 #pragma unroll
@@ -484,10 +516,7 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
                             }
                         }
                     }
-                    if (((st.dl - d) & (TILE_BLOCK - 1)) == TILE_BLOCK - 1 || d == st.df) {
-                        wait_vm();
-                        if (lane == 0) lds_poke(prog + wv, static_cast<int>(st.row0) + k);
-                    }
+                    if (((st.dl - d) & (TILE_BLOCK - 1)) == TILE_BLOCK - 1 || d == st.df) publish_progress(L.prog + wv, static_cast<int>(st.row0) + k, lane);
                 };
                 int d = st.dl;
                 for (; d - 1 >= st.df; d -= 2) {
@@ -499,34 +528,18 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
                     const bool inB = ((st.dl - st.df) & 1) == 0;
 #pragma unroll
                     for (int r = 0; r < R; ++r)
-                        if (X0 + jr[r] == 0) {
-                            const Cell cz = inB ? B.c[r] : A.c[r];
-                            const float raw = dot5(mdl->start + rs * 5, cz);
-                            if (raw > 0.f) {
-                                int k;
-                                reinterpret_cast<float *>(lmisc)[2] = __builtin_frexpf(raw, &k);
-                                lmisc[3] = cz.e + k;
-                            }
-                        }
-                }
+                        if (X0 + jr[r] == 0) capture_total(L.misc, 2, E.mdl->start + T.rs * 5, inB ? B.c[r] : A.c[r]);
                 }
             }
-            __syncthreads();
-            out.btot_m = unif(reinterpret_cast<float *>(lmisc)[2]);
-            out.btot_e = uni(lmisc[3]);
+            tile_backward_out(out, L.misc);
         }
         if (threadIdx.x == 0) {
-            const int cnt = lmisc[4];
-            out.npairs = cnt;
-            if (cnt > pair_cap) out.status = NPR_ERR_CAPACITY;
-            a.outs[t] = out;
-            lmisc[5] = atomicAdd(a.queue, 1);
+            out.npairs = L.misc[4];
+            if (out.npairs > T.pair_cap) out.status = NPR_ERR_CAPACITY;
         }
-        __syncthreads();
-        t = uni(lmisc[5]) + static_cast<int>(gridDim.x);
+        t = tile_task_end(a, t, out, L.misc);
     }
 }
-
 
 // =====================================================================================================================
 // k_em_tile<2>: the Baum-Welch E-step on column stripes -- the trainer's own band (anchors, splitMatrixBiggerThanThis 300,
@@ -540,14 +553,6 @@ __global__ void __launch_bounds__(WAVE *TILE_MAX_NW) __attribute__((amdgpu_waves
 // stripe's last column, which the forward sweep left in the task's scratch for its neighbour.
 constexpr int EM_TILE_NW = 4;
 
-template <int R>
-__device__ __forceinline__ void tile_store_planes(__amdgpu_buffer_rsrc_t rs, int vo, const Diag<R> &C, const Masks<R> &mk) {
-    static_assert(R == 2, "k_em_tile: two slots per lane");
-    if (__builtin_amdgcn_inverse_ballot_w64(mk.lanes)) {
-        __builtin_amdgcn_raw_buffer_store_b128(v4i{fbits(C.c[0].sx), fbits(C.c[0].sy), fbits(C.c[0].lx), fbits(C.c[0].ly)}, rs, vo, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(v4i{fbits(C.c[1].sx), fbits(C.c[1].sy), fbits(C.c[1].lx), fbits(C.c[1].ly)}, rs, vo + 16, 0, 0);
-    }
-}
 // all five states of a row back into registers; lanes outside the row keep what they held (every use is masked)
 template <int R>
 __device__ __forceinline__ void tile_load_full(__amdgpu_buffer_rsrc_t rsF, __amdgpu_buffer_rsrc_t rsX, int voF, int voX, Diag<R> &G,
@@ -569,7 +574,6 @@ __device__ __forceinline__ Cell edge_load(char *Eb, uint32_t row) {
 }
 
 constexpr int EM_SKIP = -40;
-__device__ __forceinline__ int Fm_e_of(const Cell &c) { return c.e; }
 __device__ __forceinline__ float &tile_bin_at(float *lbins, int byte_off) {
     return *reinterpret_cast<float *>(reinterpret_cast<char *>(lbins) + byte_off);
 }
@@ -591,7 +595,7 @@ __device__ __forceinline__ void tile_em_cells(const StepEnv &E, const Diag<R> &i
         float bM = 0.f, bXs = 0.f, bXl = 0.f, bYs = 0.f, bYl = 0.f;  // this cell's emission posteriors
         // (round 6) A region whose every lane's F * B / total is below 2^EM_SKIP contributes nothing a count can see (2.7e8 terms of 2^-40 each are
         // 2.4e-4 of a count): the wavefront steps over it -- a stripe row that lies off the alignment's path, a third of the rows of the trainer's band.
-        const int s_m = Fm_e_of(Gm.c[r]) + c.e - tot_e, s_l = Fm_e_of(Gl.c[r]) + c.e - tot_e, s_u = Fm_e_of(Gu.c[r]) + c.e - tot_e;
+        const int s_m = Gm.c[r].e + c.e - tot_e, s_l = Gl.c[r].e + c.e - tot_e, s_u = Gu.c[r].e + c.e - tot_e;
         const uint64_t live_m = here & vm[r] & __ballot(s_m > EM_SKIP), live_l = here & vl[r] & __ballot(s_l > EM_SKIP), live_u = here & vu[r] & __ballot(s_u > EM_SKIP);
         if (lanes_of(live_m)) {
             const Cell &Fm = Gm.c[r];
@@ -648,16 +652,13 @@ constexpr int EM_TILE_WPE = 3;  // wavefronts per SIMD the register allocation a
 template <int R>
 __global__ void __launch_bounds__(WAVE *EM_TILE_NW) __attribute__((amdgpu_waves_per_eu(EM_TILE_WPE))) k_em_tile(KernelArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float *lmodel = reinterpret_cast<float *>(smem);
-    int *lmisc = reinterpret_cast<int *>(lmodel + MODEL_FLOATS);  // [0..3] totals, [5] next task
-    int *prog = lmisc + 8;
     constexpr int K = 64 * R;
 
     const int lane = threadIdx.x & (WAVE - 1);
     const int wv = uni(static_cast<int>(threadIdx.x) >> 6);
     const int NW = static_cast<int>(blockDim.x) >> 6;
-    float *const stage = reinterpret_cast<float *>(prog + TILE_MAX_NW) + wv * (TILE_BLOCK * EDGE_FLOATS);
-    float *const lbins = reinterpret_cast<float *>(prog + TILE_MAX_NW) + NW * (TILE_BLOCK * EDGE_FLOATS) + wv * ((EM_BINS + 1) * WAVE);
+    const TileLds L = tile_lds(smem, wv);
+    float *const lbins = reinterpret_cast<float *>(L.prog + TILE_MAX_NW) + NW * (TILE_BLOCK * EDGE_FLOATS) + wv * ((EM_BINS + 1) * WAVE);
     char *const F = a.F + uni64(a.region[blockIdx.x]) * 8;
     char *const Fx = reinterpret_cast<char *>(a.Fx) + uni64(a.region[blockIdx.x]) * 16;  // the other four states: 16 bytes per cell
     const int voff = 8 * R * lane;
@@ -667,173 +668,27 @@ __global__ void __launch_bounds__(WAVE *EM_TILE_NW) __attribute__((amdgpu_waves_
 
     int t = blockIdx.x;
     while (t < a.ntasks) {
-        const Task *tp = a.tasks + t;
-        const int64_t x_off = uni64(tp->x_off), y_off = uni64(tp->y_off), tile_off = uni64(tp->tile_off), rowmask_off = uni64(tp->rowmask_off);
-        const int lX = uni(tp->lX), lY = uni(tp->lY), D = uni(tp->D), flags = uni(tp->flags), model = uni(tp->model);
-        cptr32 rowmask = (cptr32)(a.rowmask + rowmask_off);
-        const Stripe *tab = a.stripes + tile_off;
-        const UStripe hd = load_stripe(tab, 0);
-        const int S = hd.X;
-        const uint32_t rows = static_cast<uint32_t>(hd.K);
-        tab += 1;
-        char *const Ef = F + static_cast<int64_t>(rows) * (K * 8);
-        char *const Eb = Ef + static_cast<int64_t>(rows) * (4 * EDGE_FLOATS);
-        const int rs = flags & 1, re = (flags >> 1) & 1;
+        const TileTask T = tile_task<R>(a, t, F);
+        const StepEnv E = tile_task_begin<EM_BINS + 1>(a, T, L, lane, lbins);  // transitions in VGPRs, as in k_em_stair: every count multiplies by one
+        const int lX = T.lX, lY = T.lY, model = T.model;
 
-        __syncthreads();
-        {
-            const float *gm = reinterpret_cast<const float *>(a.models + model);
-            for (int i = threadIdx.x; i < MODEL_FLOATS; i += blockDim.x) lmodel[i] = gm[i];
-            if (threadIdx.x == 0) lmisc[0] = 0, lmisc[1] = E_DEAD, lmisc[2] = 0, lmisc[3] = E_DEAD, lmisc[4] = 0;
-            if (threadIdx.x < TILE_MAX_NW) prog[threadIdx.x] = 0;
-            for (int i = 0; i <= EM_BINS; ++i) lbins[i * WAVE + lane] = 0.f;
-        }
-        __syncthreads();
-        StepEnv E;
-        E.mdl = reinterpret_cast<const DevModel *>(lmodel);
-        E.ltab = reinterpret_cast<const char *>(lmodel);
-        E.X = a.seq + x_off, E.Y = a.seq + y_off, E.lX = lX, E.lY = lY, E.lane = lane;
-        E.tr = load_trans(E.mdl->T);  // in VGPRs, as in k_em_stair: every count multiplies by one
-        const DevModel *mdl = E.mdl;
-
-        // =============================== forward: as k_dp_tile, all five states stored ===============================
-        for (int s = wv; s < S; s += NW) {
-            const UStripe st = load_stripe(tab, s);
-            if (st.dl >= st.df) {
-            int dfL = 1, dlL = 0, wL = 0;
-            uint32_t row0L = 0;
-            if (s > 0) {
-                const UStripe sl = load_stripe(tab, s - 1);
-                dfL = sl.df, dlL = sl.dl, row0L = sl.row0;
-                wL = (s - 1) % NW;
-            }
-            const int lenL = dlL - dfL + 1;
-            Bases<R> bx, by;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                bx.b[r] = base4(E.X, lX, st.X + jr[r] - 1);
-                by.b[r] = base4(E.Y, lY, (st.df - 1) - st.X - jr[r] - 1);
-            }
-            Feed fy;
-            feed_init<+1>(fy, E.Y, lY, st.df - st.X - 1, lane);
-            Diag<R> A = dead_diag<R>(), B = dead_diag<R>();
-            Cell carry = dead_cell();
-            const uint64_t out_lane = 1ull << (st.K / R - 1);
-            int blk_lo = 0, blk_hi = 0;
-            cptr32 rm = rowmask + st.row0;
-            uint32_t w_n = rm[0];
-            const __amdgpu_buffer_rsrc_t rsF = stripe_rsrc<R>(F, st.row0, K * 8), rsE = stripe_rsrc<R>(Ef, st.row0, 4 * EDGE_FLOATS),
-                                         rsX = stripe_rsrc<R>(Fx, st.row0, K * 16);
-            {
-                const int q0 = st.df - 2 - dfL;
-                if (q0 >= 0 && q0 < lenL) {
-                    const int hi = min(q0 + TILE_BLOCK, lenL);
-                    const int need = static_cast<int>(row0L) + hi;
-                    while (uni(lds_peek(prog + wL)) < need) __builtin_amdgcn_s_sleep(2);
-                    asm volatile("" ::: "memory");
-                    edge_stage(Ef, row0L + q0, hi - q0, stage, lane);
-                    blk_lo = q0, blk_hi = hi;
-                    const Cell c0 = edge_get(stage, 0);
-                    if (lane == 0) carry = c0;
-                }
-            }
-            auto step = [&](int d, Diag<R> &io, const Diag<R> &p1) {
-                const int k = d - st.df;
-                const Masks<R> mk = row_masks(w_n);
-                if (d < st.dl) w_n = rm[1];
-                rm += 1;
-                Cell edge = dead_cell();
-                const int q = d - 1 - dfL;
-                if (static_cast<unsigned>(q) < static_cast<unsigned>(lenL)) {
-                    if (q >= blk_hi) {
-                        const int hi = min(q + TILE_BLOCK, lenL);
-                        const int need = static_cast<int>(row0L) + hi;
-                        while (uni(lds_peek(prog + wL)) < need) __builtin_amdgcn_s_sleep(2);
-                        asm volatile("" ::: "memory");
-                        edge_stage(Ef, row0L + q, hi - q, stage, lane);
-                        blk_lo = q, blk_hi = hi;
-                    }
-                    edge = edge_get(stage, q - blk_lo);
-                }
-                bases_down<R>(by, feed_get<+1>(fy, E.Y, lY, d - st.X - 1, lane));
-                tile_fwd_step<R>(d, E, io, p1, carry, edge, bx, by, mk);
-                if (d == 0) {
-                    if (lane == 0) {
-                        Cell c;
-                        c.m = mdl->start[rs * 5 + 0], c.sx = mdl->start[rs * 5 + 1], c.sy = mdl->start[rs * 5 + 2];
-                        c.lx = mdl->start[rs * 5 + 3], c.ly = mdl->start[rs * 5 + 4];
-                        normalise(c, 0);
-                        io.c[0] = c;
-                    }
-                }
-                tile_store_row<R>(rsF, voff + k * (K * 8), io, mk);
-                tile_store_planes<R>(rsX, 2 * voff + k * (K * 16), io, mk);
-                edge_store(rsE, k, io.c[R - 1], out_lane);
-                if ((k & (TILE_BLOCK - 1)) == TILE_BLOCK - 1 || d == st.dl) {
-                    wait_vm();
-                    if (lane == 0) lds_poke(prog + wv, static_cast<int>(st.row0) + k + 1);
-                }
-            };
-            int d = st.df;
-            for (; d + 1 <= st.dl; d += 2) {
-                step(d, B, A);
-                step(d + 1, A, B);
-            }
-            if (d <= st.dl) step(d, B, A);
-            if (s == S - 1) {
-                const bool inB = ((st.dl - st.df) & 1) == 0;
-                const int je = lX - st.X;
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                    if (jr[r] == je) {
-                        const Cell c = inB ? B.c[r] : A.c[r];
-                        const float raw = dot5(mdl->end + re * 5, c);
-                        if (raw > 0.f) {
-                            int k;
-                            reinterpret_cast<float *>(lmisc)[0] = __builtin_frexpf(raw, &k);
-                            lmisc[1] = c.e + k;
-                        }
-                    }
-            }
-            }
-        }
-        __syncthreads();
-        const float tot_m = unif(reinterpret_cast<float *>(lmisc)[0]);
-        const int tot_e = uni(lmisc[1]);
-
-        TaskOut out;
-        out.tot_m = tot_m, out.tot_e = tot_e, out.btot_m = 0.f, out.btot_e = E_DEAD, out.npairs = 0;
-        out.status = NPR_OK;
-        const bool alive = tot_m > 0.f;
-        if (!alive) out.status = NPR_ERR_ZERO_PROB;
+        // forward: as k_dp_tile, all five states stored
+        tile_forward_sweep<R, false, true>(T, E, L, wv, NW, F, Fx);
+        TaskOut out = tile_forward_out(L.misc);
 
         // =============================== backward + expected counts ===============================
         float acc[15];
 #pragma unroll
         for (int i = 0; i < 15; ++i) acc[i] = 0.f;
-        if (alive) {
-            const float inv_tot = 1.0f / tot_m;
-            if (threadIdx.x < TILE_MAX_NW) prog[threadIdx.x] = 0x7fffffff;
-            __syncthreads();
-            int s_top = S - 1 - ((S - 1 - wv) % NW + NW) % NW;
+        if (out.tot_m > 0.f) {
+            const int tot_e = out.tot_e;
+            const float inv_tot = 1.0f / out.tot_m;
+            const int s_top = tile_backward_begin(L, T.S, wv, NW);
             for (int s = s_top; s >= 0; s -= NW) {
-                const UStripe st = load_stripe(tab, s);
-                if (st.dl >= st.df) {
-                int dfR = 1, dlR = 0, wR = 0;
-                uint32_t row0R = 0;
-                if (s + 1 < S) {
-                    const UStripe sr = load_stripe(tab, s + 1);
-                    dfR = sr.df, dlR = sr.dl, row0R = sr.row0;
-                    wR = (s + 1) % NW;
-                }
-                const int lenR = dlR - dfR + 1;
-                int dfL = 1, dlL = 0;
-                uint32_t row0L = 0;
-                if (s > 0) {
-                    const UStripe sl = load_stripe(tab, s - 1);
-                    dfL = sl.df, dlL = sl.dl, row0L = sl.row0;
-                }
-                const int lenL = dlL - dfL + 1;
+                const UStripe st = load_stripe(T.tab, s);
+                if (st.dl < st.df) continue;
+                TileEdge<-1> right = edge_open<-1>(T, L, s, NW, lane);
+                const TileEdge<+1> left = edge_open<+1>(T, L, s, NW, lane);  // its cells are all out: read straight from memory (edge_load)
                 const int X0 = st.X;
                 Bases<R> bx, by, bxm, bym;  // X[x], Y[y] of every slot (the backward cell) and X[x-1], Y[y-1] (the symbols emitted INTO it)
 #pragma unroll
@@ -849,10 +704,9 @@ __global__ void __launch_bounds__(WAVE *EM_TILE_NW) __attribute__((amdgpu_waves_
                 Diag<R> A = dead_diag<R>(), B = dead_diag<R>();
                 Cell carry = dead_cell();
                 const uint64_t out_lane = 1ull;
-                int blk_lo = lenR, blk_hi = lenR;
-                cptr32 rm0 = rowmask + st.row0;
-                const __amdgpu_buffer_rsrc_t rsF = stripe_rsrc<R>(F, st.row0, K * 8), rsE = stripe_rsrc<R>(Eb, st.row0, 4 * EDGE_FLOATS),
-                                             rsX = stripe_rsrc<R>(Fx, st.row0, K * 16);
+                cptr32 rm0 = T.rowmask + st.row0;
+                const __amdgpu_buffer_rsrc_t rsF = stripe_rsrc(F, st.row0, K * 8), rsE = stripe_rsrc(T.Eb, st.row0, 4 * EDGE_FLOATS),
+                                             rsX = stripe_rsrc(Fx, st.row0, K * 16);
                 // forward rows of d-1 and d-2 (all five states), the masks of their lanes, and the left stripe's last column on them
                 Diag<R> G1 = dead_diag<R>(), G2 = dead_diag<R>();
                 Masks<R> m1{}, m2{};
@@ -865,61 +719,31 @@ __global__ void __launch_bounds__(WAVE *EM_TILE_NW) __attribute__((amdgpu_waves_
                         tile_load_full<R>(rsF, rsX, voff + k * (K * 8), 2 * voff + k * (K * 16), G, m);
                     }
                     eL = dead_cell();
-                    const int q = dd - dfL;
-                    if (static_cast<unsigned>(q) < static_cast<unsigned>(lenL)) eL = edge_load(Ef, row0L + static_cast<uint32_t>(q));
+                    const int q = dd - left.df;
+                    if (static_cast<unsigned>(q) < static_cast<unsigned>(left.len)) eL = edge_load(T.Ef, left.row0 + static_cast<uint32_t>(q));
                 };
                 fetch_row(st.dl - 1, G1, m1, eL1);
                 fetch_row(st.dl - 2, G2, m2, eL2);
                 Masks<R> mk_n = row_masks(rm0[st.dl - st.df]);
-                {
-                    const int q0 = st.dl + 2 - dfR;
-                    if (q0 >= 0 && q0 < lenR) {
-                        const int lo = max(q0 - TILE_BLOCK + 1, 0);
-                        const int need = static_cast<int>(row0R) + lo;
-                        while (uni(lds_peek(prog + wR)) > need) __builtin_amdgcn_s_sleep(2);
-                        asm volatile("" ::: "memory");
-                        edge_stage(Eb, row0R + lo, q0 - lo + 1, stage, lane);
-                        blk_lo = lo, blk_hi = q0 + 1;
-                        const Cell c0 = edge_get(stage, q0 - lo);
-                        if (lane == WAVE - 1) carry = c0;
-                    }
-                }
+                edge_seed(right, st.dl, carry);
                 auto step = [&](int d, Diag<R> &io, const Diag<R> &s1) {
                     const int k = d - st.df;
                     const Masks<R> mk = mk_n;
                     if (d > st.df) mk_n = row_masks(rm0[k - 1]);
-                    Cell edge = dead_cell();
-                    const int q = d + 1 - dfR;
-                    if (static_cast<unsigned>(q) < static_cast<unsigned>(lenR)) {
-                        if (q < blk_lo) {
-                            const int lo = max(q - TILE_BLOCK + 1, 0);
-                            const int need = static_cast<int>(row0R) + lo;
-                            while (uni(lds_peek(prog + wR)) > need) __builtin_amdgcn_s_sleep(2);
-                            asm volatile("" ::: "memory");
-                            edge_stage(Eb, row0R + lo, q - lo + 1, stage, lane);
-                            blk_lo = lo, blk_hi = q + 1;
-                        }
-                        edge = edge_get(stage, q - blk_lo);
-                    }
+                    const Cell edge = edge_at(right, d);
                     bases_up<R>(by, feed_get<-1>(fy, E.Y, lY, d - X0 - (K - 1), lane));
                     bases_up<R>(bym, feed_get<-1>(fym, E.Y, lY, d - X0 - (K - 1) - 1, lane));
                     tile_bwd_step<R>(d, E, io, s1, carry, edge, bx, by, mk);
-                    if (d == D) {
+                    if (d == T.D) {
 #pragma unroll
                         for (int r = 0; r < R; ++r)
-                            if (X0 + jr[r] == lX) {
-                                Cell c;
-                                c.m = mdl->end[re * 5 + 0], c.sx = mdl->end[re * 5 + 1], c.sy = mdl->end[re * 5 + 2];
-                                c.lx = mdl->end[re * 5 + 3], c.ly = mdl->end[re * 5 + 4];
-                                normalise(c, 0);
-                                io.c[r] = c;
-                            }
+                            if (X0 + jr[r] == lX) io.c[r] = corner_cell(E.mdl->end + T.re * 5);
                     }
                     edge_store(rsE, k, io.c[0], out_lane);
                     if (d >= 1) {  // expected counts of the transitions into the cells of d
                         Diag<R> Gl, Gm;
-                        Gl.c[1] = G1.c[0], Gl.c[0] = dpp_cell_from_below(G1.c[1], eL1);
-                        Gm.c[1] = G2.c[0], Gm.c[0] = dpp_cell_from_below(G2.c[1], eL2);
+                        Gl.c[1] = G1.c[0], Gl.c[0] = cell_from_below(G1.c[1], eL1);
+                        Gm.c[1] = G2.c[0], Gm.c[0] = cell_from_below(G2.c[1], eL2);
                         const uint64_t vu[R] = {m1.cell[0], m1.cell[1]};
                         const uint64_t vl[R] = {(m1.cell[1] << 1) | (uni(eL1.e) != E_DEAD ? 1ull : 0ull), m1.cell[0]};
                         const uint64_t vm[R] = {(m2.cell[1] << 1) | (uni(eL2.e) != E_DEAD ? 1ull : 0ull), m2.cell[0]};
@@ -928,10 +752,7 @@ __global__ void __launch_bounds__(WAVE *EM_TILE_NW) __attribute__((amdgpu_waves_
                     // the rows the next anti-diagonal needs: d-2 moves up, d-3 comes from memory
                     G1 = G2, m1 = m2, eL1 = eL2;
                     fetch_row(d - 3, G2, m2, eL2);
-                    if (((st.dl - d) & (TILE_BLOCK - 1)) == TILE_BLOCK - 1 || d == st.df) {
-                        wait_vm();
-                        if (lane == 0) lds_poke(prog + wv, static_cast<int>(st.row0) + k);
-                    }
+                    if (((st.dl - d) & (TILE_BLOCK - 1)) == TILE_BLOCK - 1 || d == st.df) publish_progress(L.prog + wv, static_cast<int>(st.row0) + k, lane);
                 };
                 int d = st.dl;
                 for (; d - 1 >= st.df; d -= 2) {
@@ -943,21 +764,10 @@ __global__ void __launch_bounds__(WAVE *EM_TILE_NW) __attribute__((amdgpu_waves_
                     const bool inB = ((st.dl - st.df) & 1) == 0;
 #pragma unroll
                     for (int r = 0; r < R; ++r)
-                        if (X0 + jr[r] == 0) {
-                            const Cell cz = inB ? B.c[r] : A.c[r];
-                            const float raw = dot5(mdl->start + rs * 5, cz);
-                            if (raw > 0.f) {
-                                int k;
-                                reinterpret_cast<float *>(lmisc)[2] = __builtin_frexpf(raw, &k);
-                                lmisc[3] = cz.e + k;
-                            }
-                        }
-                }
+                        if (X0 + jr[r] == 0) capture_total(L.misc, 2, E.mdl->start + T.rs * 5, inB ? B.c[r] : A.c[r]);
                 }
             }
-            __syncthreads();
-            out.btot_m = unif(reinterpret_cast<float *>(lmisc)[2]);
-            out.btot_e = uni(lmisc[3]);
+            tile_backward_out(out, L.misc);
             // every wavefront adds up its own bins, then its transition accumulators through the same rows
             if (lane < EM_BINS) {
                 double sum = 0.0;
@@ -975,12 +785,7 @@ __global__ void __launch_bounds__(WAVE *EM_TILE_NW) __attribute__((amdgpu_waves_
                 atomicAdd(a.em_T + model * 25 + map[lane], sum);
             }
         }
-        if (threadIdx.x == 0) {
-            a.outs[t] = out;
-            lmisc[5] = atomicAdd(a.queue, 1);
-        }
-        __syncthreads();
-        t = uni(lmisc[5]) + static_cast<int>(gridDim.x);
+        t = tile_task_end(a, t, out, L.misc);
     }
 }
 

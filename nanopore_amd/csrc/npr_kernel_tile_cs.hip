@@ -26,6 +26,8 @@
 //     2^-89 of the total; a task with a lane above that (TCS_S_LIMIT) runs again in k_dp_tile (TASK_RERUN, npr_device.h).
 // Scaling by powers of two is exact: wherever nothing leaves fp32's range relative to its lane the results are those of the
 // per-cell-exponent kernels bit for bit, and the parity tests compare them with that mirror (tests/test_gpu_tile.py).
+// What this kernel has word for word in common with k_dp_tile / k_em_tile -- stripe table entries, row masks, progress words, stripe
+// descriptors, the DPP shift of a cell -- lives in npr_stripe.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +36,7 @@
 #include "npr_device.h"
 #include "npr_frame.h"
 #include "npr_rs.h"
+#include "npr_stripe.h"
 
 namespace npr {
 
@@ -53,33 +56,8 @@ constexpr int TCS_BIAS = 1 << 25;       // makes every exponent a positive numbe
 constexpr int TCS_S_LIMIT = 126 - 60 - 28 - (TCS_TOP + 6) - 1;
 static_assert(TCS_TOP + 6 + TCS_REACH * TCS_C < 127, "a value that crosses TCS_REACH lanes inside a block must stay finite");
 
-typedef const __attribute__((address_space(4))) int32_t *cptr_i32;
-
-struct UStripe {
-    int X, K, df, dl;
-    uint32_t row0;
-};
-__device__ __forceinline__ UStripe load_stripe(const Stripe *tab, int s) {
-    cptr_i32 p = (cptr_i32)(tab + s);
-    return UStripe{p[0], p[1], p[2], p[3], static_cast<uint32_t>(p[4])};
-}
-__device__ __forceinline__ Masks<2> row_masks(uint32_t w) {
-    Masks<2> m;
-    m.cell[0] = (~0ull << (w & 63u)) & (~0ull >> ((w >> 6) & 63u));
-    m.cell[1] = (~0ull << ((w >> 12) & 63u)) & (~0ull >> ((w >> 18) & 63u));
-    m.lanes = m.cell[0] | m.cell[1];
-    m.l0 = 0;
-    return m;
-}
-typedef __attribute__((address_space(3))) int lds_int;
-__device__ __forceinline__ int lds_peek(const int *p) { return *(const volatile lds_int *)(p); }
-__device__ __forceinline__ void lds_poke(int *p, int v) { *(volatile lds_int *)(p) = v; }
-
 // One row per anti-diagonal of a stripe: 128 cells of 4 bytes, lane l at 8 l, in the first half of the row's space (the region is laid
 // out for k_dp_tile's 8-byte cells, which may have to run the task again); bytes 512 + 8 l of a block's first row: (e, e^) of lane l.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t stripe_rsrc(char *base, uint32_t row0, int row_bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(base + static_cast<int64_t>(row0) * row_bytes, 0, -1, 0x00020000);
-}
 constexpr int TCS_ROW_BYTES = 1024, TCS_EXP_AT = 512;
 
 // `cnt` neighbour cells of the rows [first, first + 16) of the neighbour stripe into this wavefront's LDS staging, record i = row first + i;
@@ -106,25 +84,6 @@ __device__ __forceinline__ RCell tcs_edge_get(const float *stage, int i) {
     const float4 q = *reinterpret_cast<const float4 *>(stage + TCS_EDGE * i);
     const float g = stage[TCS_EDGE * i + 4];
     return RCell{q.x, q.y, q.z, q.w, g};
-}
-
-__device__ __forceinline__ RCell dpp_rcell_from_below(const RCell &v, const RCell &edge) {
-    RCell o;
-    o.m = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.m), fbits(v.m), 0x138, 0xf, 0xf, false));
-    o.sx = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.sx), fbits(v.sx), 0x138, 0xf, 0xf, false));
-    o.sy = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.sy), fbits(v.sy), 0x138, 0xf, 0xf, false));
-    o.lx = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.lx), fbits(v.lx), 0x138, 0xf, 0xf, false));
-    o.ly = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.ly), fbits(v.ly), 0x138, 0xf, 0xf, false));
-    return o;
-}
-__device__ __forceinline__ RCell dpp_rcell_from_above(const RCell &v, const RCell &edge) {
-    RCell o;
-    o.m = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.m), fbits(v.m), 0x130, 0xf, 0xf, false));
-    o.sx = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.sx), fbits(v.sx), 0x130, 0xf, 0xf, false));
-    o.sy = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.sy), fbits(v.sy), 0x130, 0xf, 0xf, false));
-    o.lx = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.lx), fbits(v.lx), 0x130, 0xf, 0xf, false));
-    o.ly = bitsf(__builtin_amdgcn_update_dpp(fbits(edge.ly), fbits(v.ly), 0x130, 0xf, 0xf, false));
-    return o;
 }
 
 // 2^k, k clamped to [-127, 127]; 2^-127 and below: 0 (what is that far down is flushed)
@@ -240,10 +199,9 @@ __device__ __forceinline__ int tcs_renorm(CsState &Q, int lane, int e_in, int eh
     return eb;
 }
 
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
 // Waiting for a neighbour stripe's progress word.  Bounded: a table that promised rows no wavefront will ever write must not hang the device --
-// after ~2^22 polls (seconds) the wait gives up and the task is reported for the second pass (TASK_RERUN), whose kernel has the same bound.
+// after ~2^22 polls (seconds) the wait gives up and the task is reported for the second pass (TASK_RERUN).  The second-pass kernel's waits
+// (k_dp_tile, npr_kernel_tile.hip TileEdge) have NO such bound: it relies on the planner's stripe tables being consistent.
 constexpr int TCS_SPIN_LIMIT = 1 << 22;
 __device__ __forceinline__ void tcs_wait_at_least(const int *p, int need, int &stuck) {
     int spins = 0;
@@ -259,8 +217,6 @@ __device__ __forceinline__ void tcs_wait_at_most(const int *p, int need, int &st
 }
 
 // ---- one anti-diagonal of a stripe, the part every step has ----
-__device__ __forceinline__ float tcs_dpp_below(float v, float edge) { return bitsf(__builtin_amdgcn_update_dpp(fbits(edge), fbits(v), 0x138, 0xf, 0xf, false)); }
-__device__ __forceinline__ float tcs_dpp_above(float v, float edge) { return bitsf(__builtin_amdgcn_update_dpp(fbits(edge), fbits(v), 0x130, 0xf, 0xf, false)); }
 // the transitions into match applied to a cell: what the cell diagonally above-right of it starts from (rs_fwd_cell's first five operations)
 __device__ __forceinline__ float tcs_into_match(const Trans &t, const RCell &c) {
     float a = t.mm * c.m;
@@ -278,10 +234,10 @@ __device__ __forceinline__ void tcs_fwd_core(const StepEnv &E, RDiag<2> &io, con
                                              const float *erec, const Bases<2> &bx, Bases<2> &by, int inject) {
     const float4 edge = *reinterpret_cast<const float4 *>(erec);
     bases_down<2>(by, inject);
-    const float um_s = tcs_dpp_below(um_p1, edge.x) * c;  // (x-1, y-1)'s share of the NEXT anti-diagonal's slot 0, in this lane's units from here on
-    const float Lm = tcs_dpp_below(p1.c[1].m, edge.y), Lsx = tcs_dpp_below(p1.c[1].sx, edge.z), Llx = tcs_dpp_below(p1.c[1].lx, edge.w);  // (x-1, y), the neighbour's units
+    const float um_s = dppf_from_below(um_p1, edge.x) * c;  // (x-1, y-1)'s share of the NEXT anti-diagonal's slot 0, in this lane's units from here on
+    const float Lm = dppf_from_below(p1.c[1].m, edge.y), Lsx = dppf_from_below(p1.c[1].sx, edge.z), Llx = dppf_from_below(p1.c[1].lx, edge.w);  // (x-1, y), the neighbour's units
     float Lsy = 0.f;
-    if constexpr (SW) Lsy = tcs_dpp_below(p1.c[1].sy, erec[4]);
+    if constexpr (SW) Lsy = dppf_from_below(p1.c[1].sy, erec[4]);
     float em[2], exs[2], exl[2], eys[2], eyl[2];
 #pragma unroll
     for (int r = 0; r < 2; ++r) rs_cell_emissions<FULL ? 4 : 2, FLAT>(E.ltab, mk.cell[r], bx.b[r], by.b[r], em[r], exs[r], exl[r], eys[r], eyl[r]);
@@ -320,8 +276,8 @@ __device__ __forceinline__ void tcs_bwd_core(const StepEnv &E, RDiag<2> &io, con
                                              const Bases<2> &bx, Bases<2> &by, int inject) {
     const float4 edge = *reinterpret_cast<const float4 *>(erec);
     bases_up<2>(by, inject);
-    const float Xm = tcs_dpp_above(s1.c[0].m, edge.x) * c;  // becomes (x+1, y+1) of the next anti-diagonal
-    const float Xsx = tcs_dpp_above(s1.c[0].sx, edge.y), Xlx = tcs_dpp_above(s1.c[0].lx, edge.z);  // (x+1, y), the neighbour's units
+    const float Xm = dppf_from_above(s1.c[0].m, edge.x) * c;  // becomes (x+1, y+1) of the next anti-diagonal
+    const float Xsx = dppf_from_above(s1.c[0].sx, edge.y), Xlx = dppf_from_above(s1.c[0].lx, edge.z);  // (x+1, y), the neighbour's units
     float em[2], exs[2], exl[2], eys[2], eyl[2];
 #pragma unroll
     for (int r = 0; r < 2; ++r) rs_cell_emissions<FULL ? 4 : 2, FLAT>(E.ltab, mk.cell[r], bx.b[r], by.b[r], em[r], exs[r], exl[r], eys[r], eyl[r]);
@@ -860,7 +816,7 @@ __global__ void __launch_bounds__(WAVE *(EM ? TCS_EM_NW : TCS_MAX_NW)) __attribu
                 };
                 auto em_take = [&](int row, const EmRow &S, RDiag<R> &G, RCell &Gbelow) __attribute__((always_inline)) {  // a fetched row, and the lane below's top cell of it in this lane's units (lane 0: cb = 1)
                     G = em_scaled(row, S);
-                    Gbelow = dpp_rcell_from_below(G.c[R - 1], em_left(row));
+                    Gbelow = cell_from_below(G.c[R - 1], em_left(row));
                     rcell_scale(Gbelow, cb);
                 };
                 {

@@ -469,6 +469,46 @@ def test_base_dependent_gap_emissions(gpu_ctx):
             assert o["status"] == 0 and o["ops"] == m["ops"]
             order = np.lexsort((m["py"], m["px"]))
             assert np.array_equal(o["p"], m["pp"].astype(np.float32)[order])
+
+    # ... and the stripe kernel's instance for such a model, k_dp_tile<2, FLAT = false> (tile_rs = 2), against the frame kernels (no_tile):
+    # the same bits.  With one wavefront per task a stripe takes its left neighbour's cells from the same wavefront, with three from
+    # another one.  fixed_width = 400 is 201 cells per anti-diagonal: one wavefront's four-slot frame holds it, so that batch stays in
+    # the frame class either way.  fixed_width = 700 is 351 cells per anti-diagonal, more than any one-wavefront frame: those tasks go to
+    # the stripes, five to eight of 128 columns each -- the width that runs the kernel.
+    wide = [random_pair(rng, int(rng.integers(600, 901))) for _ in range(3)]
+    wrefs = [bytes(b"ACGT"[c] for c in X) for X, _, _ in wide]
+    wreads = [bytes(b"ACGT"[c] for c in Y) for _, Y, _ in wide]
+
+    def run(W):
+        b = gpu_ctx.stage(R.make_params(band_mode=1, fixed_width=W), wrefs, wreads, [g for _, _, g in wide])
+        tasks, _ = b.class_stats()
+        b.run(), b.finish()
+        got = (b.results(), b.ops(), b.pairs(), tasks)
+        b.close()
+        return got
+
+    try:
+        for W in (400, 700):
+            gpu_ctx.set_option(_lib.OPTIONS["tile_rs"], 0)
+            gpu_ctx.set_option(_lib.OPTIONS["tile_waves"], 0)
+            gpu_ctx.set_option(_lib.OPTIONS["no_tile"], 1)
+            ref = run(W)
+            gpu_ctx.set_option(_lib.OPTIONS["no_tile"], 0)
+            assert (ref[0]["status"] == 0).all() and ref[3][11] == 0
+            gpu_ctx.set_option(_lib.OPTIONS["tile_rs"], 2)
+            for nw in (1, 3):
+                gpu_ctx.set_option(_lib.OPTIONS["tile_waves"], nw)
+                got = run(W)
+                if W == 700:  # every task in the stripe class, run by k_dp_tile
+                    assert got[3][11] == got[3].sum() > 0 and ref[3][3:11].sum() == got[3][11]
+                for f in ("cells", "status", "loglik", "loglik_bwd", "score"):
+                    assert np.array_equal(got[0][f], ref[0][f])
+                assert all(np.array_equal(a, c) for a, c in zip(got[1], ref[1]))
+                assert all(np.array_equal(a, c) for a, c in zip(got[2], ref[2]))
+    finally:
+        gpu_ctx.set_option(_lib.OPTIONS["no_tile"], 0)
+        gpu_ctx.set_option(_lib.OPTIONS["tile_rs"], 0)
+        gpu_ctx.set_option(_lib.OPTIONS["tile_waves"], 0)
     gpu_ctx.set_hmm(_hmm_obj("blasr_hmm_0.txt"))
 
 
