@@ -118,7 +118,7 @@ __global__ void __launch_bounds__(2 * WAVE) __attribute__((amdgpu_waves_per_eu(R
         }
         if (threadIdx.x < 16) lmisc[threadIdx.x] = threadIdx.x == 1 || threadIdx.x == 3 ? E_DEAD : (threadIdx.x == 7 || threadIdx.x == 13 ? -(1 << 30) : 0);
         __syncthreads();
-        if (new_model) rs_build_tables(ltab, reinterpret_cast<const DevModel *>(lmodel), threadIdx.x, 2 * WAVE);
+        if (new_model) rs_build_tables<!FLAT>(ltab, reinterpret_cast<const DevModel *>(lmodel), threadIdx.x, 2 * WAVE);
         last_model = model;
         StepEnv E;
         E.mdl = reinterpret_cast<const DevModel *>(lmodel);
@@ -138,6 +138,7 @@ __global__ void __launch_bounds__(2 * WAVE) __attribute__((amdgpu_waves_per_eu(R
         __syncthreads();
         {
             Trans tr = load_trans(E.mdl->T);
+            if constexpr (rs_folds<R, FLAT>()) rs_fold_gap_emission(tr);  // (the gap states' flat 2^-2, once per task: npr_rs.h)
             if constexpr (R >= RS_T_SGPR_MIN_R) {
                 tr.mm = unif(tr.mm), tr.sxm = unif(tr.sxm), tr.sym = unif(tr.sym), tr.lxm = unif(tr.lxm), tr.lym = unif(tr.lym);
                 tr.msx = unif(tr.msx), tr.sxsx = unif(tr.sxsx), tr.sysx = unif(tr.sysx);

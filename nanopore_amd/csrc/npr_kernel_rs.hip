@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(R == 
             for (int i = lane; i < MODEL_FLOATS; i += WAVE) lmodel[i] = gm[i];
         }
         __syncthreads();
-        rs_build_tables(ltab, reinterpret_cast<const DevModel *>(lmodel), lane, WAVE);
+        rs_build_tables<!FLAT>(ltab, reinterpret_cast<const DevModel *>(lmodel), lane, WAVE);
         __syncthreads();
         StepEnv E;
         E.mdl = reinterpret_cast<const DevModel *>(lmodel);
@@ -61,6 +61,7 @@ __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(R == 
         E.X = a.seq + x_off, E.Y = a.seq + y_off, E.lX = lX, E.lY = lY, E.lane = lane;
         {
             Trans tr = load_trans(E.mdl->T);
+            if constexpr (rs_folds<R, FLAT>()) rs_fold_gap_emission(tr);  // (the gap states' flat 2^-2, once per task: npr_rs.h)
             if constexpr (R >= RS_T_SGPR_MIN_R) {
                 tr.mm = unif(tr.mm), tr.sxm = unif(tr.sxm), tr.sym = unif(tr.sym), tr.lxm = unif(tr.lxm), tr.lym = unif(tr.lym);
                 tr.msx = unif(tr.msx), tr.sxsx = unif(tr.sxsx), tr.sysx = unif(tr.sysx);

@@ -137,11 +137,13 @@ constexpr int RS_DEADCODE_MAX_R = 2;  // slots per lane up to which it is used: 
                                       // gain since round 4 (no switch terms, seven wavefronts per SIMD): a 1/8 shard of config 3 -- a launch that is its longest read's
                                       // serial chain -- 44.5 -> 42.1 ms (two lane-mask regions and their branches fewer per step), the headline batch 139.0 -> 138.5
 constexpr int RS_TABLE_FLOATS = sizeof(RsTables) / sizeof(float);
+template <bool GAPS = true>  // (false: the match table alone -- a FLAT frame kernel looks up nothing else)
 __device__ __forceinline__ void rs_build_tables(RsTables *t, const DevModel *m, int tid, int nthreads) {
     for (int i = tid; i < 36; i += nthreads) {
         const int x = i / 6, y = i % 6;
         t->em4[i] = (x < 5 && y < 5) ? m->em[5 * x + y] : 0.f;
     }
+    if constexpr (!GAPS) return;
     for (int i = tid; i < 6; i += nthreads) {
         t->ex2[i][0] = i < 5 ? m->ex[5 + i] : 0.f, t->ex2[i][1] = i < 5 ? m->ex[15 + i] : 0.f;
         t->eys[i] = i < 5 ? m->ey[10 + i] : 0.f, t->eyl[i] = i < 5 ? m->ey[20 + i] : 0.f;
@@ -155,11 +157,40 @@ __device__ __forceinline__ void rs_emissions(const char *tab, int bx, int by, fl
     eys = *reinterpret_cast<const float *>(tab + OFF_EYS + by), eyl = *reinterpret_cast<const float *>(tab + OFF_EYL + by);
 }
 
-// The emissions of one cell of a step.  Slots outside the band: up to RS_DEADCODE_MAX_R slots per lane they take the dead base code (every
-// emission 0: the cell comes out as exact zeros), above that the step runs under the band's lane mask.
 // FLAT: every loaded model emits every base from every gap state with probability exactly 2^-2 (all shipped ones do: blasr_hmm_0 / _20 / _40;
-// a model trained by EM does not).  The four gap emissions then carry one bit -- in the band or not -- and come from a select instead of two
-// 8-byte LDS loads per cell and direction; the same factor 0.25f or 0.f multiplies the same sums, so not a bit changes.
+// a model trained by EM does not).  The frame kernels of two slots per lane (the headline class) then FOLD that factor into the ten transitions
+// that lead into a gap state, once per task (rs_fold_gap_emission), and a cell keeps its four gap sums as they come: no gap emission is looked
+// up, selected or multiplied.  A power of two commutes with every rounding of the chain -- 0.25f * fmaf(t2, s, t1 * m) = fmaf(0.25f * t2, s,
+// (0.25f * t1) * m) --, so the bits are those of the table-driven instance WHEREVER NO PRODUCT OR SUM IS SUBNORMAL.  Where one is (a cell more
+// than 210 binary orders below its row's maximum, at the far edge of a band) the table-driven form rounds twice and the folded one once.  That
+// is an ulp of a subnormal when it happens, but not for long: when the band jumps, the rows' maximum falls, the renormalisation lifts such
+// cells back among the normal numbers with the few bits they had, and two forms that differed by 2^-149 differ in most of the mantissa.
+// RS_FOLD_R: the slots per lane (a bit each) whose FLAT instances fold; the others keep the select and the multiply by 0.25f / 0.f.
+//   4: no.  A band of 201 cells reaches 210 binary orders below the row maximum on ordinary reads, and the forward rows of the folded
+//      k_dp_rs<4> were NOT the table-driven instance's after a jump of the band (2 867 of 122 910 cells, the largest 2e-25 next to a row maximum
+//      held near 2^84; pairs, totals and cigars still agreed; tests/test_gpu_flat_fold.py).
+//   2: yes.  Every cell identical in that test (101 cells); the headline launch 138.6 -> 132.1 ms, a launch that is one read's chain 28.5 -> 27.8.
+//   1: no.  Identical too (51 cells), but the lane-mask region costs a one-slot step more than the multiplies did: config 2's launch
+//      0.752 -> 0.770 ms (RS_DEADCODE_MAX_R above: what the dead base code gained there in round 3).
+// With the factor gone nothing multiplies a slot outside the band by zero, so a folding instance computes its rows under the band's lane mask.
+constexpr int RS_FOLD_R = 2;
+template <int R, bool FLAT>
+constexpr bool rs_folds() { return FLAT && (RS_FOLD_R & R) != 0; }
+// Slots outside the band: a step either gives them the dead base code (every emission 0: the cell comes out as exact zeros) or runs under the
+// band's lane mask and clears what the band left behind.
+template <int R, bool FLAT>
+constexpr bool rs_dead_codes() { return R <= RS_DEADCODE_MAX_R && !rs_folds<R, FLAT>(); }
+__device__ __forceinline__ void rs_fold_gap_emission(Trans &t) {
+    constexpr float G = 0x1p-2f;
+    t.msx *= G, t.sxsx *= G, t.sysx *= G, t.mlx *= G, t.lxlx *= G;
+    t.msy *= G, t.sysy *= G, t.sxsy *= G, t.mly *= G, t.lyly *= G;
+}
+__device__ __forceinline__ float rs_match_emission(const char *tab, int bx, int by) { return *reinterpret_cast<const float *>(tab + (bx + by)); }
+
+// The emissions of one cell of a step that does not fold (and of the stripe kernels, npr_kernel_tile_cs.hip, which fold theirs into a column
+// scale).  Slots outside the band: up to RS_DEADCODE_MAX_R slots per lane they take the dead base code, above that the step runs under the
+// band's lane mask.  FLAT here: the four gap emissions carry one bit -- in the band or not -- and come from a select instead of two 8-byte
+// LDS loads per cell and direction; the same factor 0.25f or 0.f multiplies the same sums, so not a bit changes.
 template <int R, bool FLAT>
 __device__ __forceinline__ void rs_cell_emissions(const char *tab, uint64_t in_band, int bx, int by, float &em, float &exs, float &exl, float &eys, float &eyl) {
     if constexpr (R <= RS_DEADCODE_MAX_R) {
@@ -185,9 +216,9 @@ __device__ __forceinline__ void rs_cell_emissions(const char *tab, uint64_t in_b
 // SW: whether the model has short-gap switches (shortGapX <-> shortGapY).  None of the shipped models has (13 of cPecan's 15
 // transitions); their two multiply-adds with a zero transition add exact zeros, so leaving them out changes no bit
 // (the kernels are instantiated both ways, npr_batch_run picks by the loaded models).
+// The five sums of a forward cell, before any emission.
 template <bool SW = true>
-__device__ __forceinline__ RCell rs_fwd_cell(const Trans &t, const RCell &L, const RCell &M, const RCell &U, float em, float exs, float exl,
-                                             float eys, float eyl) {
+__device__ __forceinline__ RCell rs_fwd_sums(const Trans &t, const RCell &L, const RCell &M, const RCell &U) {
     RCell c;
     float a;
     a = t.mm * M.m;
@@ -195,32 +226,40 @@ __device__ __forceinline__ RCell rs_fwd_cell(const Trans &t, const RCell &L, con
     a = __builtin_fmaf(t.sym, M.sy, a);
     a = __builtin_fmaf(t.lxm, M.lx, a);
     a = __builtin_fmaf(t.lym, M.ly, a);
-    c.m = em * a;
+    c.m = a;
     a = t.msx * L.m;
     a = __builtin_fmaf(t.sxsx, L.sx, a);
     if constexpr (SW) a = __builtin_fmaf(t.sysx, L.sy, a);
-    c.sx = exs * a;
+    c.sx = a;
     a = t.mlx * L.m;
     a = __builtin_fmaf(t.lxlx, L.lx, a);
-    c.lx = exl * a;
+    c.lx = a;
     a = t.msy * U.m;
     a = __builtin_fmaf(t.sysy, U.sy, a);
     if constexpr (SW) a = __builtin_fmaf(t.sxsy, U.sx, a);
-    c.sy = eys * a;
+    c.sy = a;
     a = t.mly * U.m;
     a = __builtin_fmaf(t.lyly, U.ly, a);
-    c.ly = eyl * a;
+    c.ly = a;
     return c;
 }
-// backward: Ms = (x+1, y+1), Xs = (x+1, y), Ys = (x, y+1)
 template <bool SW = true>
-__device__ __forceinline__ RCell rs_bwd_cell(const Trans &t, const RCell &Ms, const RCell &Xs, const RCell &Ys, float em, float exs, float exl,
+__device__ __forceinline__ RCell rs_fwd_cell(const Trans &t, const RCell &L, const RCell &M, const RCell &U, float em, float exs, float exl,
                                              float eys, float eyl) {
-    const float am = em * Ms.m;
-    const float asx = exs * Xs.sx;
-    const float alx = exl * Xs.lx;
-    const float asy = eys * Ys.sy;
-    const float aly = eyl * Ys.ly;
+    RCell c = rs_fwd_sums<SW>(t, L, M, U);
+    c.m = em * c.m, c.sx = exs * c.sx, c.lx = exl * c.lx, c.sy = eys * c.sy, c.ly = eyl * c.ly;
+    return c;
+}
+// ... of a folding instance: `t` went through rs_fold_gap_emission
+template <bool SW = true>
+__device__ __forceinline__ RCell rs_fwd_cell(const Trans &t, const RCell &L, const RCell &M, const RCell &U, float em) {
+    RCell c = rs_fwd_sums<SW>(t, L, M, U);
+    c.m = em * c.m;
+    return c;
+}
+// backward: Ms = (x+1, y+1), Xs = (x+1, y), Ys = (x, y+1); the sums over the successors' values, each already times its emission
+template <bool SW = true>
+__device__ __forceinline__ RCell rs_bwd_sums(const Trans &t, float am, float asx, float alx, float asy, float aly) {
     RCell c;
     float b;
     b = t.mm * am;
@@ -244,6 +283,15 @@ __device__ __forceinline__ RCell rs_bwd_cell(const Trans &t, const RCell &Ms, co
     b = __builtin_fmaf(t.lyly, aly, b);
     c.ly = b;
     return c;
+}
+template <bool SW = true>
+__device__ __forceinline__ RCell rs_bwd_cell(const Trans &t, const RCell &Ms, const RCell &Xs, const RCell &Ys, float em, float exs, float exl,
+                                             float eys, float eyl) {
+    return rs_bwd_sums<SW>(t, em * Ms.m, exs * Xs.sx, exl * Xs.lx, eys * Ys.sy, eyl * Ys.ly);
+}
+template <bool SW = true>
+__device__ __forceinline__ RCell rs_bwd_cell(const Trans &t, const RCell &Ms, const RCell &Xs, const RCell &Ys, float em) {
+    return rs_bwd_sums<SW>(t, em * Ms.m, Xs.sx, Xs.lx, Ys.sy, Ys.ly);
 }
 __device__ __forceinline__ float rs_dot5(const float *w, const RCell &c) {
     float a = w[0] * c.m;
@@ -643,16 +691,17 @@ __device__ __forceinline__ void rs_fwd_x_step(const StepEnv &E, RDiag<R> &io, co
     RDiag<R> o;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        float em, exs, exl, eys, eyl;
-        if constexpr (R <= RS_DEADCODE_MAX_R) {
-            rs_cell_emissions<R, FLAT>(E.ltab, mk.cell[r], S.X.b[r], S.Y.b[r], em, exs, exl, eys, eyl);
-            o.c[r] = rs_fwd_cell<SW>(E.tr, p1.c[r], io.c[r], U.c[r], em, exs, exl, eys, eyl);
+        if constexpr (rs_folds<R, FLAT>()) {
+            const float em = rs_match_emission(E.ltab, S.X.b[r], S.Y.b[r]);
+            rs_put(io.c[r], mk.cell[r], [&] { return rs_fwd_cell<SW>(E.tr, p1.c[r], io.c[r], U.c[r], em); });
         } else {
+            float em, exs, exl, eys, eyl;
             rs_cell_emissions<R, FLAT>(E.ltab, mk.cell[r], S.X.b[r], S.Y.b[r], em, exs, exl, eys, eyl);
-            rs_put(io.c[r], mk.cell[r], [&] { return rs_fwd_cell<SW>(E.tr, p1.c[r], io.c[r], U.c[r], em, exs, exl, eys, eyl); });
+            if constexpr (rs_dead_codes<R, FLAT>()) o.c[r] = rs_fwd_cell<SW>(E.tr, p1.c[r], io.c[r], U.c[r], em, exs, exl, eys, eyl);
+            else rs_put(io.c[r], mk.cell[r], [&] { return rs_fwd_cell<SW>(E.tr, p1.c[r], io.c[r], U.c[r], em, exs, exl, eys, eyl); });
         }
     }
-    if constexpr (R <= RS_DEADCODE_MAX_R) io = o;
+    if constexpr (rs_dead_codes<R, FLAT>()) io = o;
     else rs_clear_outside<R>(io, mk, moved);
 }
 template <int R, bool CHK = true, bool SW = true, bool FLAT = false>
@@ -665,16 +714,17 @@ __device__ __forceinline__ void rs_fwd_y_step(const StepEnv &E, RDiag<R> &io, co
     RDiag<R> o;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        float em, exs, exl, eys, eyl;
-        if constexpr (R <= RS_DEADCODE_MAX_R) {
-            rs_cell_emissions<R, FLAT>(E.ltab, mk.cell[r], S.X.b[r], S.Y.b[r], em, exs, exl, eys, eyl);
-            o.c[r] = rs_fwd_cell<SW>(E.tr, L.c[r], io.c[r], p1.c[r], em, exs, exl, eys, eyl);
+        if constexpr (rs_folds<R, FLAT>()) {
+            const float em = rs_match_emission(E.ltab, S.X.b[r], S.Y.b[r]);
+            rs_put(io.c[r], mk.cell[r], [&] { return rs_fwd_cell<SW>(E.tr, L.c[r], io.c[r], p1.c[r], em); });
         } else {
+            float em, exs, exl, eys, eyl;
             rs_cell_emissions<R, FLAT>(E.ltab, mk.cell[r], S.X.b[r], S.Y.b[r], em, exs, exl, eys, eyl);
-            rs_put(io.c[r], mk.cell[r], [&] { return rs_fwd_cell<SW>(E.tr, L.c[r], io.c[r], p1.c[r], em, exs, exl, eys, eyl); });
+            if constexpr (rs_dead_codes<R, FLAT>()) o.c[r] = rs_fwd_cell<SW>(E.tr, L.c[r], io.c[r], p1.c[r], em, exs, exl, eys, eyl);
+            else rs_put(io.c[r], mk.cell[r], [&] { return rs_fwd_cell<SW>(E.tr, L.c[r], io.c[r], p1.c[r], em, exs, exl, eys, eyl); });
         }
     }
-    if constexpr (R <= RS_DEADCODE_MAX_R) io = o;
+    if constexpr (rs_dead_codes<R, FLAT>()) io = o;
     else rs_clear_outside<R>(io, mk, moved);
 }
 // One backward anti-diagonal d: `io` holds d+2 on entry and d on exit, `s1` holds d+1.  S.X / S.Y: X[x]*8, Y[y]*8.
@@ -688,16 +738,17 @@ __device__ __forceinline__ void rs_bwd_x_step(const StepEnv &E, RDiag<R> &io, co
     RDiag<R> o;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        float em, exs, exl, eys, eyl;
-        if constexpr (R <= RS_DEADCODE_MAX_R) {
-            rs_cell_emissions<R, FLAT>(E.ltab, mk.cell[r], S.X.b[r], S.Y.b[r], em, exs, exl, eys, eyl);
-            o.c[r] = rs_bwd_cell<SW>(E.tr, io.c[r], s1.c[r], Ys.c[r], em, exs, exl, eys, eyl);
+        if constexpr (rs_folds<R, FLAT>()) {
+            const float em = rs_match_emission(E.ltab, S.X.b[r], S.Y.b[r]);
+            rs_put(io.c[r], mk.cell[r], [&] { return rs_bwd_cell<SW>(E.tr, io.c[r], s1.c[r], Ys.c[r], em); });
         } else {
+            float em, exs, exl, eys, eyl;
             rs_cell_emissions<R, FLAT>(E.ltab, mk.cell[r], S.X.b[r], S.Y.b[r], em, exs, exl, eys, eyl);
-            rs_put(io.c[r], mk.cell[r], [&] { return rs_bwd_cell<SW>(E.tr, io.c[r], s1.c[r], Ys.c[r], em, exs, exl, eys, eyl); });
+            if constexpr (rs_dead_codes<R, FLAT>()) o.c[r] = rs_bwd_cell<SW>(E.tr, io.c[r], s1.c[r], Ys.c[r], em, exs, exl, eys, eyl);
+            else rs_put(io.c[r], mk.cell[r], [&] { return rs_bwd_cell<SW>(E.tr, io.c[r], s1.c[r], Ys.c[r], em, exs, exl, eys, eyl); });
         }
     }
-    if constexpr (R <= RS_DEADCODE_MAX_R) io = o;
+    if constexpr (rs_dead_codes<R, FLAT>()) io = o;
     else rs_clear_outside<R>(io, mk, moved);
 }
 template <int R, bool CHK = true, bool SW = true, bool FLAT = false>
@@ -710,16 +761,17 @@ __device__ __forceinline__ void rs_bwd_y_step(const StepEnv &E, RDiag<R> &io, co
     RDiag<R> o;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        float em, exs, exl, eys, eyl;
-        if constexpr (R <= RS_DEADCODE_MAX_R) {
-            rs_cell_emissions<R, FLAT>(E.ltab, mk.cell[r], S.X.b[r], S.Y.b[r], em, exs, exl, eys, eyl);
-            o.c[r] = rs_bwd_cell<SW>(E.tr, io.c[r], Xs.c[r], s1.c[r], em, exs, exl, eys, eyl);
+        if constexpr (rs_folds<R, FLAT>()) {
+            const float em = rs_match_emission(E.ltab, S.X.b[r], S.Y.b[r]);
+            rs_put(io.c[r], mk.cell[r], [&] { return rs_bwd_cell<SW>(E.tr, io.c[r], Xs.c[r], s1.c[r], em); });
         } else {
+            float em, exs, exl, eys, eyl;
             rs_cell_emissions<R, FLAT>(E.ltab, mk.cell[r], S.X.b[r], S.Y.b[r], em, exs, exl, eys, eyl);
-            rs_put(io.c[r], mk.cell[r], [&] { return rs_bwd_cell<SW>(E.tr, io.c[r], Xs.c[r], s1.c[r], em, exs, exl, eys, eyl); });
+            if constexpr (rs_dead_codes<R, FLAT>()) o.c[r] = rs_bwd_cell<SW>(E.tr, io.c[r], Xs.c[r], s1.c[r], em, exs, exl, eys, eyl);
+            else rs_put(io.c[r], mk.cell[r], [&] { return rs_bwd_cell<SW>(E.tr, io.c[r], Xs.c[r], s1.c[r], em, exs, exl, eys, eyl); });
         }
     }
-    if constexpr (R <= RS_DEADCODE_MAX_R) io = o;
+    if constexpr (rs_dead_codes<R, FLAT>()) io = o;
     else rs_clear_outside<R>(io, mk, moved);
 }
 
