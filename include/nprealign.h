@@ -462,6 +462,32 @@ int64_t npr_seed_chain_sam_text(int64_t n_reads, const uint8_t *text, const int6
                                 const char *rnames, const int64_t *rname_off, int64_t n_refs, const int64_t *chain_off, const int32_t *chains,
                                 const int64_t *ops_off, const int32_t *ops, int64_t *rec_off, char *out, int64_t cap);
 
+/* ---- reads to rows, chains and guides in one call, the rows never leaving the device ----
+ * npr_seed_matches followed by npr_seed_chains, as one object that owns its device buffers: the reads are encoded and matched as
+ * npr_seed_matches does, and what that call and npr_seed_chains do on the host between the kernels happens on the device
+ * (csrc/npr_seedmap.hip): the reads' row counts are scanned into hit_off, every read's rows are sorted by (strand, reference index, a, b)
+ * where the match kernel wrote them -- a read of at most NPR_SEED_MAP_LDS_ROWS rows in the LDS of one workgroup, a longer one by the same
+ * workgroup in global memory; no read length and no row count is refused -- and the (read, reference) chain spans are found in the
+ * sorted rows; then the chain kernels run on the rows where they lie.  The host reads back three totals (rows, chains, op pairs).
+ * The arrays are DEFINED by the two calls: hit_off, hits are what npr_seed_matches returns for the same index, min_len, strands and
+ * reads; chain_off, chains, ops_off, ops are what npr_seed_chains returns for those rows with read_len[i] = end[i] - begin[i], the
+ * index's own sequence lengths as ref_len, and max_gap.  The rows are valid by construction and are not looked at again.
+ * Errors are those of the two calls (a bad min_len, strands or max_gap, a span that ends before it begins, 2^31 - 64 read bases and
+ * reads together or more): NPR_ERR_INVALID, *out = NULL, nothing launched.  n_reads == 0, empty reads, reads shorter than k and reads
+ * without a match are legal: the result then has chain_off all zero and ops_off[0] == 0.
+ * The map belongs to the index's context (not to the index) and must be destroyed before it; calls on it count as calls on the
+ * context.  npr_seed_map_counts: counts[0..2] = rows, chains, guide op pairs.  npr_seed_map_fetch copies what is asked for to the host
+ * -- hit_off [n_reads + 1], hits [rows][4], chain_off [n_reads + 1], chains [chains][4], ops_off [chains + 1], ops [pairs][2]; a NULL
+ * pointer is not fetched -- any number of times. */
+#define NPR_SEED_MAP_LDS_ROWS 4096 /* 16 bytes a row: 64 KB of LDS */
+typedef struct npr_seed_map npr_seed_map;
+int32_t npr_seed_map_create(npr_seed_index *index, int64_t min_len, int32_t strands, int64_t max_gap, int64_t n_reads, const uint8_t *text,
+                            const int64_t *begin, const int64_t *end, npr_seed_map **out);
+int32_t npr_seed_map_counts(const npr_seed_map *m, int64_t counts[3]);
+int32_t npr_seed_map_fetch(npr_seed_map *m, int64_t *hit_off, int32_t *hits, int64_t *chain_off, int32_t *chains, int64_t *ops_off,
+                           int32_t *ops);
+void npr_seed_map_destroy(npr_seed_map *m);
+
 /* Expected base counts per reference position from the posterior pairs of a finished batch, on the device (SURVEY.md 8f
  * next #4): what marginAlignSnpCaller.py:150-155 collates from the --outputAllPosteriorProbs files, one text line at a time:
  * every pair (refPos, readPos, p) of a selected read adds p to expect[(first row of its reference + refPos) * 4 + base] for

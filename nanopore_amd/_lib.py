@@ -51,6 +51,7 @@ KMER_MAX_K = 6    # the k-mer tables: 4^k + 1 bins, the last one for k-mers with
 KMER_MAX_GROUPS = 64  # npr_kmer_counts_groups: tables of one call
 SAM_COLS = 16     # NPR_SAM_COLS
 SEED_MIN_K, SEED_MAX_K = 8, 32  # npr_seed_index_create: the k of a seed index
+SEED_MAP_LDS_ROWS = 4096  # NPR_SEED_MAP_LDS_ROWS: a read of at most so many rows is sorted in LDS by npr_seed_map_create, a longer one in global memory
 PILEUP_WORDS = 8  # NPR_PILEUP_WORDS: M columns by read base A C G T other, deletion columns, insertion runs, record starts
 SNP_BINS, SNP_MAX_MODELS = 101, 4  # NPR_SNP_BINS, NPR_SNP_MAX_MODELS
 MAX_MODELS = 8
@@ -165,6 +166,10 @@ SIGNATURES = {
     "npr_seed_sam_text": (i64, [i64] + [vp] * 6 + [i64] + [vp] * 4 + [i64]),
     "npr_seed_chains": (i64, [vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64]),
     "npr_seed_chain_sam_text": (i64, [i64] + [vp] * 6 + [i64] + [vp] * 6 + [i64]),
+    "npr_seed_map_create": (i32, [vp, i64, i32, i64, i64, vp, vp, vp, _out]),
+    "npr_seed_map_counts": (i32, [vp, vp]),
+    "npr_seed_map_fetch": (i32, [vp] * 7),
+    "npr_seed_map_destroy": (None, [vp]),
     "npr_batch_base_expectations": (i32, [vp, vp, i64, vp, vp, vp]),
     "npr_snp_calls_table": (i32, [vp, i64, vp, vp, vp, vp, i32, vp, vp, vp]),
     "npr_batch_snp_calls": (i32, [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp]),

@@ -306,7 +306,11 @@ def realignSamFile(samFile, outputSamFile, readFastqFile, referenceFastaFile, hm
                                group=group, gpu=None if ctx is None else ctx.device)
     if "results" not in out:
         return None
-    results = out["results"]
+    return raiseForFailedRecords(out["results"], outputSamFile)
+
+
+def raiseForFailedRecords(results, outputSamFile):
+    """The per-record results of a job that wrote outputSamFile, handed back when every record's status is 0."""
     failed = np.nonzero(results["status"] != 0)[0]
     if len(failed):
         # the reference's system() raises on a non-zero exit of cactus_realign and the job tree reports failed jobs

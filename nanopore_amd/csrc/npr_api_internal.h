@@ -7,6 +7,8 @@
 //   npr_aux.cpp     post-alignment statistics, k-mer tables, base expectations and SNP calls, the device pileup, the planner cross-check
 //   npr_text.cpp    cigar and SAM record text (the transport forms a job ships)
 //   npr_seed_api.cpp  exact-match seeding (npr_seed.hip): the index, the matches, their SAM records
+//   npr_seedchain_api.cpp  the chains of seed rows given on the host as guides (npr_seedchain.hip), their SAM records
+//   npr_seedmap_api.cpp  reads -> rows, chains and guides in one device-resident object (npr_seedmap.hip between the two above)
 //   npr_cigtext_api.cpp  cigar text made on the device (npr_cigtext.hip): npr_cigar_text_packed, npr_batch_cigar_text, NPR_OPT_FINISH_TEXT
 #pragma once
 #include <hip/hip_runtime.h>
@@ -185,6 +187,13 @@ struct DevBuf {
         p = ptr, count = n, borrowed = true;
     }
     size_t bytes() const { return count * sizeof(T); }
+    // what `o` holds becomes this buffer's, and `o` is left empty (an object that keeps a result its maker allocated)
+    void take(DevBuf &o) {
+        release();
+        p = o.p, count = o.count, cap = o.cap, borrowed = o.borrowed, owner = o.owner, held = o.held;
+        o.p = nullptr;
+        o.release();
+    }
     // a buffer from the context's cache of released ones (the smallest that fits without wasting more than half), else a
     // fresh one; it goes back to the cache when released
     npr_ctx *owner = nullptr;
@@ -382,6 +391,26 @@ struct npr_pileup {
     DevBuf<int32_t> bad;         // one word: a record of the current call ran past what it has
 };
 
+// the index of one reference set (npr_seed_api.cpp): lives on the device from npr_seed_index_create to npr_seed_index_destroy
+struct npr_seed_index {
+    npr_ctx *ctx = nullptr;
+    int32_t k = 0, kb = 0;
+    int64_t n_refs = 0, bytes = 0;  // bytes of the code buffer
+    std::vector<int32_t> ref_len;   // [n_refs] bases of every sequence (what the chain kernels take as ref_len)
+    DevBuf<uint8_t> codes;
+    DevBuf<int64_t> off;            // [n_refs + 1] ASCII offsets of the sequences
+    DevBuf<int32_t> table, pos;
+};
+
+// the rows, chains and guides of one call's reads (npr_seedmap_api.cpp): on the device from npr_seed_map_create to npr_seed_map_destroy.
+// Without a row there is no buffer at all (rows > 0 means chains > 0 and op pairs > 0: every row lies in a chain, every chain has an M)
+struct npr_seed_map {
+    npr_ctx *ctx = nullptr;
+    int64_t n_reads = 0, rows = 0, chains = 0, pairs = 0;
+    DevBuf<int64_t> hit_off, chain_off, ops_off;  // [n_reads + 1], [n_reads + 1], [chains + 1]
+    DevBuf<int32_t> hits, chain_rows, ops;        // [rows][4], [chains][4], [pairs][2]
+};
+
 // --------------------------------------------------------------------------------------------------
 // Frame schedule of the register kernel (npr_kernel_stair.hip).  The wavefront holds a frame of C = 64*R slots of the
 // current anti-diagonal (times NW wavefronts for k_dp_wide), slot j = lattice point (x0 + j, y0 - j); the frame takes an X-step (x0 += 1) into every odd
@@ -525,4 +554,23 @@ struct PiecedFetch {
 };
 int32_t fetch_pieced(npr_ctx *ctx, const PiecedFetch &f);
 int32_t fetch_device_words(npr_batch *b);                  // npr_cigtext_api.cpp: the packed words such a finish left on the device, while they are there
+// npr_seedchain_api.cpp: the chain kernels on rows and chain spans that lie on the device, wherever they came from (npr_seed_chains uploads
+// them, npr_seed_map_create made them there).  count: k_chain_dp, k_chain_trace<false>, k_chain_scan; `chains` and `n_ops` (the guides'
+// offsets) are final and `pairs` is on the host.  write: k_chain_trace<true> into `ops`; queued on the context's stream, not waited for.
+// `what`: the caller's text for a failed hipMalloc.
+struct SeedChainRun {
+    DevBuf<int32_t> node, back, run_end, chains, ops;
+    DevBuf<int64_t> n_ops;
+    SeedChainArgs a{};
+    int64_t pairs = 0;
+    int32_t count(npr_ctx *ctx, const char *what, const int32_t *d_hits, int64_t rows, const SeedChainSpan *d_span, int64_t n_chains, int64_t max_gap,
+                  const int32_t *d_ref_len, const int32_t *d_read_len);
+    int32_t write(npr_ctx *ctx, const char *what);
+};
+// npr_seed_api.cpp: the steps npr_seed_matches and npr_seed_map_create share (`who`: the entry point, for the error text)
+int32_t seed_check_reads(npr_ctx *ctx, const char *who, int64_t n_reads, const uint8_t *text, const int64_t *begin, const int64_t *end, std::vector<int64_t> &off);
+int32_t seed_stage_reads(npr_ctx *ctx, const char *who, int32_t strands, int64_t n_reads, const uint8_t *text, const int64_t *begin, const int64_t *end,
+                         const std::vector<int64_t> &off, DevBuf<uint8_t> &fwd, DevBuf<uint8_t> &rev, DevBuf<int64_t> &d_off);
+SeedMatchArgs seed_match_args(const npr_seed_index *ix, int64_t min_len, const std::vector<int64_t> &off, const int64_t *d_off, uint32_t *d_count, const int64_t *d_hit_off);
+int32_t seed_match_pass(npr_ctx *ctx, SeedMatchArgs &a, int32_t strands, const uint8_t *fwd, const uint8_t *rev, bool emit);
 }  // namespace npr_impl

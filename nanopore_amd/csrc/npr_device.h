@@ -379,6 +379,19 @@ struct SeedChainArgs {
 };
 int launch_seed_chain_dp(const SeedChainArgs &a, void *stream);     // k_chain_dp, k_chain_trace<false>, k_chain_scan
 int launch_seed_chain_write(const SeedChainArgs &a, void *stream);  // k_chain_trace<true>
+// from the rows k_seed_match emitted to the chain spans k_chain_dp takes, on the device (npr_seedmap.hip)
+// (the tier boundary of k_map_sort is NPR_SEED_MAP_LDS_ROWS of include/nprealign.h: a read of at most so many rows is sorted in LDS, one of more in global memory)
+struct SeedMapArgs {
+    int64_t n_reads;
+    const uint32_t *count;   // [n_reads] what k_seed_match<false> counted
+    int64_t *hit_off;        // [n_reads + 1]: k_map_scan<uint32_t> makes it of count
+    int32_t *hits;           // [hit_off[n_reads]][4]: k_map_sort sorts every read's rows by (strand, reference index, a, b) in place
+    int64_t *chain_off;      // [n_reads + 1]: k_map_spans<false> writes every read's number of chains, k_map_scan<int64_t> turns them into offsets in place
+    SeedChainSpan *span;     // [chain_off[n_reads]]: k_map_spans<true>
+};
+int launch_seedmap_offsets(const SeedMapArgs &a, void *stream);  // k_map_scan<uint32_t>
+int launch_seedmap_chains(const SeedMapArgs &a, void *stream);   // k_map_sort, k_map_spans<false>, k_map_scan<int64_t>
+int launch_seedmap_spans(const SeedMapArgs &a, void *stream);    // k_map_spans<true>
 // SAM CIGAR text of packed cigars on the device (npr_cigtext.hip): list i = words[word_off[i] .. word_off[i] + n_ops[i])
 struct CigTextArgs {
     int64_t n;

@@ -6,17 +6,7 @@
 
 #include <array>
 
-// the index of one reference set: lives on the device from npr_seed_index_create to npr_seed_index_destroy
-struct npr_seed_index {
-    npr_ctx *ctx = nullptr;
-    int32_t k = 0, kb = 0;
-    int64_t n_refs = 0, bytes = 0;  // bytes of the code buffer
-    DevBuf<uint8_t> codes;
-    DevBuf<int64_t> off;            // [n_refs + 1] ASCII offsets of the sequences
-    DevBuf<int32_t> table, pos;
-};
-
-namespace {
+namespace npr_impl {
 
 // n ASCII sequences lying back to back on the host (`bases` bytes at `ascii`, offsets off[n + 1] from 0) -> their code buffer on the device, and
 // the buffer of their reverse complements when rc is given; d_off receives the offsets
@@ -36,6 +26,57 @@ int32_t encode_on_device(npr_ctx *ctx, const uint8_t *ascii, const std::vector<i
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the ASCII copy on the device goes when this returns)
     return NPR_OK;
 }
+
+// what npr_seed_matches and npr_seed_map_create (npr_seedmap_api.cpp) do alike, `who` being the one that asks: the reads' spans looked at and
+// summed into off[n_reads + 1] (nothing is launched when they are refused) ...
+int32_t seed_check_reads(npr_ctx *ctx, const char *who, int64_t n_reads, const uint8_t *text, const int64_t *begin, const int64_t *end, std::vector<int64_t> &off) {
+    off.assign(static_cast<size_t>(n_reads) + 1, 0);
+    for (int64_t i = 0; i < n_reads; ++i) {
+        if (end[i] < begin[i] || begin[i] < 0) return fail(ctx, NPR_ERR_INVALID, (std::string(who) + ": a span that ends before it begins").c_str());
+        off[i + 1] = off[i] + (end[i] - begin[i]);
+    }
+    if (off[n_reads] && !text) return NPR_ERR_INVALID;
+    if (seed_code_bytes(off[n_reads], n_reads) >= (int64_t(1) << 31))
+        return fail(ctx, NPR_ERR_INVALID, (std::string(who) + ": 2^31 read positions and more in one call (give the reads in several)").c_str());
+    return NPR_OK;
+}
+
+// ... the reads back to back in the pinned staging, then as code buffers on the device (both orientations when the reverse strand is asked for) ...
+int32_t seed_stage_reads(npr_ctx *ctx, const char *who, int32_t strands, int64_t n_reads, const uint8_t *text, const int64_t *begin, const int64_t *end,
+                         const std::vector<int64_t> &off, DevBuf<uint8_t> &fwd, DevBuf<uint8_t> &rev, DevBuf<int64_t> &d_off) {
+    const int64_t bases = off[n_reads];
+    const int32_t grown = grow_pin_stage(ctx, static_cast<size_t>(bases), (std::string(who) + ": hipHostMalloc").c_str());
+    if (grown != NPR_OK) return grown;
+    uint8_t *const h_ascii = static_cast<uint8_t *>(ctx->pin_stage);
+    parallel_for((n_reads + 255) / 256, ctx->host_threads, [&](int64_t c) {
+        for (int64_t i = c * 256, hi = std::min(n_reads, (c + 1) * 256); i < hi; ++i)
+            std::memcpy(h_ascii + off[i], text + begin[i], static_cast<size_t>(end[i] - begin[i]));
+    });
+    return encode_on_device(ctx, h_ascii, off, NPR_SEED_READ_OTHER, NPR_SEED_READ_SEP, fwd, (strands & 2) ? &rev : nullptr, d_off, (std::string(who) + ": hipMalloc").c_str());
+}
+
+// ... the arguments of k_seed_match for them (the orientation, and the rows once they have a buffer, are filled in later) ...
+SeedMatchArgs seed_match_args(const npr_seed_index *ix, int64_t min_len, const std::vector<int64_t> &off, const int64_t *d_off, uint32_t *d_count, const int64_t *d_hit_off) {
+    const int64_t n_reads = static_cast<int64_t>(off.size()) - 1;
+    return SeedMatchArgs{ix->codes.p, ix->table.p, ix->pos.p, ix->off.p, ix->n_refs, ix->k, ix->kb, static_cast<int32_t>(min_len), nullptr, seed_code_bytes(off[n_reads], n_reads),
+                         d_off, n_reads, 0u, d_count, d_hit_off, nullptr};
+}
+
+// ... and one pass of it, counting or emitting, over the orientations asked for
+int32_t seed_match_pass(npr_ctx *ctx, SeedMatchArgs &a, int32_t strands, const uint8_t *fwd, const uint8_t *rev, bool emit) {
+    HIP_TRY(ctx, hipMemsetAsync(a.count, 0, static_cast<size_t>(a.n_reads) * sizeof(uint32_t), ctx->stream));
+    for (uint32_t strand = 0; strand < 2; ++strand) {
+        if (!(strands & (1 << strand))) continue;
+        a.read = strand ? rev : fwd, a.strand = strand;
+        const int r = launch_seed_match(a, emit, ctx->stream);
+        if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_seed_match launch", static_cast<hipError_t>(r));
+    }
+    return NPR_OK;
+}
+
+}  // namespace npr_impl
+
+namespace {
 
 struct HitLess {  // (strand, reference index, a, b)
     bool operator()(const std::array<int32_t, 4> &x, const std::array<int32_t, 4> &y) const {
@@ -68,6 +109,8 @@ int32_t npr_seed_index_create(npr_ctx *ctx, int32_t k, int64_t n_refs, const uin
         std::unique_ptr<npr_seed_index> ix(new npr_seed_index);
         ix->ctx = ctx, ix->k = k, ix->kb = std::min<int32_t>(k, NPR_SEED_MAX_KB), ix->n_refs = n_refs;
         ix->bytes = seed_code_bytes(off[n_refs], n_refs);
+        ix->ref_len.resize(static_cast<size_t>(n_refs));
+        for (int64_t i = 0; i < n_refs; ++i) ix->ref_len[i] = static_cast<int32_t>(off[i + 1] - off[i]);
         const int32_t rc = encode_on_device(ctx, n_refs ? ref + ref_off[0] : nullptr, off, NPR_SEED_REF_OTHER, NPR_SEED_REF_SEP, ix->codes, nullptr, ix->off,
                                             "npr_seed_index_create: hipMalloc");
         if (rc != NPR_OK) return rc;
@@ -103,48 +146,25 @@ int64_t npr_seed_matches(npr_seed_index *ix, int64_t min_len, int32_t strands, i
     if (strands < 1 || strands > 3) return fail(ctx, NPR_ERR_INVALID, "npr_seed_matches: strands outside 1 .. 3");
     if (n_reads < 0 || cap < 0 || !hit_off || (n_reads && (!begin || !end))) return NPR_ERR_INVALID;
     try {
-        std::vector<int64_t> off(n_reads + 1, 0);
-        for (int64_t i = 0; i < n_reads; ++i) {
-            if (end[i] < begin[i] || begin[i] < 0) return fail(ctx, NPR_ERR_INVALID, "npr_seed_matches: a span that ends before it begins");
-            off[i + 1] = off[i] + (end[i] - begin[i]);
-        }
+        std::vector<int64_t> off;
+        int32_t rs = seed_check_reads(ctx, "npr_seed_matches", n_reads, text, begin, end, off);
+        if (rs != NPR_OK) return rs;
         const int64_t bases = off[n_reads];
-        if (bases && !text) return NPR_ERR_INVALID;
-        if (seed_code_bytes(bases, n_reads) >= (int64_t(1) << 31))
-            return fail(ctx, NPR_ERR_INVALID, "npr_seed_matches: 2^31 read positions and more in one call (give the reads in several)");
         std::fill(hit_off, hit_off + n_reads + 1, int64_t(0));
         if (bases == 0) return 0;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        // the reads back to back in the pinned staging, then as code buffers on the device (both orientations when the reverse strand is asked for)
-        const int32_t grown = grow_pin_stage(ctx, static_cast<size_t>(bases), "npr_seed_matches: hipHostMalloc");
-        if (grown != NPR_OK) return grown;
-        uint8_t *const h_ascii = static_cast<uint8_t *>(ctx->pin_stage);
-        parallel_for((n_reads + 255) / 256, ctx->host_threads, [&](int64_t c) {
-            for (int64_t i = c * 256, hi = std::min(n_reads, (c + 1) * 256); i < hi; ++i)
-                std::memcpy(h_ascii + off[i], text + begin[i], static_cast<size_t>(end[i] - begin[i]));
-        });
         DevBuf<uint8_t> fwd, rev;
         DevBuf<int64_t> d_off, d_hit_off;
         DevBuf<uint32_t> d_count;
         DevBuf<int32_t> d_hits;
-        const int32_t rc = encode_on_device(ctx, h_ascii, off, NPR_SEED_READ_OTHER, NPR_SEED_READ_SEP, fwd, (strands & 2) ? &rev : nullptr, d_off, "npr_seed_matches: hipMalloc");
-        if (rc != NPR_OK) return rc;
+        rs = seed_stage_reads(ctx, "npr_seed_matches", strands, n_reads, text, begin, end, off, fwd, rev, d_off);
+        if (rs != NPR_OK) return rs;
         hipError_t e;
         if ((e = d_count.alloc(static_cast<size_t>(n_reads))) != hipSuccess || (e = d_hit_off.alloc(static_cast<size_t>(n_reads) + 1)) != hipSuccess)
             return fail(ctx, NPR_ERR_NOMEM, "npr_seed_matches: hipMalloc", e);
-        SeedMatchArgs a{ix->codes.p, ix->table.p, ix->pos.p, ix->off.p, ix->n_refs, ix->k, ix->kb, static_cast<int32_t>(min_len), nullptr, seed_code_bytes(bases, n_reads),
-                        d_off.p, n_reads, 0u, d_count.p, d_hit_off.p, nullptr};
-        auto both_strands = [&](bool emit) -> int32_t {  // the pass over the orientations asked for
-            HIP_TRY(ctx, hipMemsetAsync(d_count.p, 0, d_count.bytes(), ctx->stream));
-            for (uint32_t strand = 0; strand < 2; ++strand) {
-                if (!(strands & (1 << strand))) continue;
-                a.read = strand ? rev.p : fwd.p, a.strand = strand;
-                const int r = launch_seed_match(a, emit, ctx->stream);
-                if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_seed_match launch", static_cast<hipError_t>(r));
-            }
-            return NPR_OK;
-        };
-        int32_t rs = both_strands(false);
+        SeedMatchArgs a = seed_match_args(ix, min_len, off, d_off.p, d_count.p, d_hit_off.p);
+        auto both_strands = [&](bool emit) { return seed_match_pass(ctx, a, strands, fwd.p, rev.p, emit); };  // the pass over the orientations asked for
+        rs = both_strands(false);
         if (rs != NPR_OK) return rs;
         std::vector<uint32_t> count(n_reads);
         HIP_TRY(ctx, hipMemcpyAsync(count.data(), d_count.p, d_count.bytes(), hipMemcpyDeviceToHost, ctx->stream));

@@ -4,6 +4,35 @@
 #include "npr_api_internal.h"
 #include "npr_textout.h"
 
+namespace npr_impl {
+
+int32_t SeedChainRun::count(npr_ctx *ctx, const char *what, const int32_t *d_hits, int64_t rows, const SeedChainSpan *d_span, int64_t n_chains, int64_t max_gap,
+                            const int32_t *d_ref_len, const int32_t *d_read_len) {
+    hipError_t e;
+    if ((e = node.alloc(static_cast<size_t>(rows) * 4)) != hipSuccess || (e = back.alloc(static_cast<size_t>(rows))) != hipSuccess ||
+        (e = run_end.alloc(static_cast<size_t>(n_chains) * 4)) != hipSuccess || (e = chains.alloc(static_cast<size_t>(n_chains) * 4)) != hipSuccess ||
+        (e = n_ops.alloc(static_cast<size_t>(n_chains) + 1)) != hipSuccess)
+        return fail(ctx, NPR_ERR_NOMEM, what, e);
+    a = SeedChainArgs{d_hits, d_span, n_chains, static_cast<uint32_t>(std::min<int64_t>(max_gap, UINT32_MAX)), d_ref_len, d_read_len, node.p, back.p,
+                      run_end.p, chains.p, n_ops.p, nullptr};
+    const int r = launch_seed_chain_dp(a, ctx->stream);
+    if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_chain_dp launch", static_cast<hipError_t>(r));
+    HIP_TRY(ctx, hipMemcpyAsync(&pairs, n_ops.p + n_chains, sizeof(pairs), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return NPR_OK;
+}
+
+int32_t SeedChainRun::write(npr_ctx *ctx, const char *what) {
+    const hipError_t e = ops.alloc(static_cast<size_t>(pairs) * 2);
+    if (e != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, what, e);
+    a.ops = ops.p;
+    const int r = launch_seed_chain_write(a, ctx->stream);
+    if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_chain_trace launch", static_cast<hipError_t>(r));
+    return NPR_OK;
+}
+
+}  // namespace npr_impl
+
 namespace {
 
 inline uint32_t strand_of(const int32_t *h) { return static_cast<uint32_t>(h[2]) >> 31; }
@@ -94,39 +123,29 @@ int64_t npr_seed_chains(npr_ctx *ctx, int64_t max_gap, int64_t n_reads, const in
         std::copy(ref_len, ref_len + n_refs, len32.begin());
         std::copy(read_len, read_len + n_reads, len32.begin() + n_refs);
 
+        // the upload, then the chain kernels on rows that lie on the device
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        DevBuf<int32_t> d_hits, d_len, d_node, d_back, d_run_end, d_chains, d_ops;
+        DevBuf<int32_t> d_hits, d_len;
         DevBuf<SeedChainSpan> d_span;
-        DevBuf<int64_t> d_n_ops;
         hipError_t e;
-        if ((e = d_hits.alloc(static_cast<size_t>(total) * 4)) != hipSuccess || (e = d_len.alloc(len32.size())) != hipSuccess ||
-            (e = d_node.alloc(static_cast<size_t>(total) * 4)) != hipSuccess || (e = d_back.alloc(static_cast<size_t>(total))) != hipSuccess ||
-            (e = d_run_end.alloc(static_cast<size_t>(n_chains) * 4)) != hipSuccess || (e = d_chains.alloc(static_cast<size_t>(n_chains) * 4)) != hipSuccess ||
-            (e = d_span.alloc(span.size())) != hipSuccess || (e = d_n_ops.alloc(static_cast<size_t>(n_chains) + 1)) != hipSuccess)
+        if ((e = d_hits.alloc(static_cast<size_t>(total) * 4)) != hipSuccess || (e = d_len.alloc(len32.size())) != hipSuccess || (e = d_span.alloc(span.size())) != hipSuccess)
             return fail(ctx, NPR_ERR_NOMEM, "npr_seed_chains: hipMalloc", e);
         HIP_TRY(ctx, hipMemcpyAsync(d_hits.p, hits, d_hits.bytes(), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(d_len.p, len32.data(), d_len.bytes(), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(d_span.p, span.data(), d_span.bytes(), hipMemcpyHostToDevice, ctx->stream));
-        SeedChainArgs a{d_hits.p, d_span.p, n_chains, static_cast<uint32_t>(std::min<int64_t>(max_gap, UINT32_MAX)), d_len.p, d_len.p + n_refs, d_node.p, d_back.p,
-                        d_run_end.p, d_chains.p, d_n_ops.p, nullptr};
-        int r = launch_seed_chain_dp(a, ctx->stream);
-        if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_chain_dp launch", static_cast<hipError_t>(r));
-        std::vector<int64_t> off(static_cast<size_t>(n_chains) + 1);
-        HIP_TRY(ctx, hipMemcpyAsync(off.data(), d_n_ops.p, d_n_ops.bytes(), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        const int64_t pairs = off[n_chains];
-        if (pairs > cap_ops || (pairs && !ops)) {
-            ops_off[0] = pairs;
+        SeedChainRun run;
+        int32_t rc = run.count(ctx, "npr_seed_chains: hipMalloc", d_hits.p, total, d_span.p, n_chains, max_gap, d_len.p, d_len.p + n_refs);
+        if (rc != NPR_OK) return rc;
+        if (run.pairs > cap_ops || (run.pairs && !ops)) {
+            ops_off[0] = run.pairs;
             return fail(ctx, NPR_ERR_CAPACITY, "npr_seed_chains: more op pairs than the buffer holds (ops_off[0] says how many)");
         }
-        if ((e = d_ops.alloc(static_cast<size_t>(pairs) * 2)) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_seed_chains: hipMalloc", e);
-        a.ops = d_ops.p;
-        r = launch_seed_chain_write(a, ctx->stream);
-        if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_chain_trace launch", static_cast<hipError_t>(r));
-        HIP_TRY(ctx, hipMemcpyAsync(chains, d_chains.p, d_chains.bytes(), hipMemcpyDeviceToHost, ctx->stream));
-        if (pairs) HIP_TRY(ctx, hipMemcpyAsync(ops, d_ops.p, d_ops.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        rc = run.write(ctx, "npr_seed_chains: hipMalloc");
+        if (rc != NPR_OK) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(chains, run.chains.p, run.chains.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        if (run.pairs) HIP_TRY(ctx, hipMemcpyAsync(ops, run.ops.p, run.ops.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ops_off, run.n_ops.p, run.n_ops.bytes(), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::copy(off.begin(), off.end(), ops_off);
         return n_chains;
     } catch (const std::exception &) {
         return fail(ctx, NPR_ERR_NOMEM, "npr_seed_chains: out of host memory");

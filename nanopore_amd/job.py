@@ -193,6 +193,74 @@ class SamSource(ArraySource):
         return self.sam.splice_text(self.span[lo:hi], self.fields[lo:hi], str_off, text, take=_take)
 
 
+_COMPLEMENT = np.arange(256, dtype=np.uint8)  # A <-> T, C <-> G in either case, everything else kept (npr_seed_chain_sam_text's letter rule)
+_COMPLEMENT[np.frombuffer(b"ACGTacgt", dtype=np.uint8)] = np.frombuffer(b"TGCAtgca", dtype=np.uint8)
+
+
+def _gather_spans(text, begin, end):
+    """The spans text[begin[i]:end[i]] back to back: (uint8 array, offsets[n + 1])."""
+    lens = end - begin
+    off = np.zeros(len(lens) + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    return text[np.repeat(begin - off[:-1], lens) + np.arange(int(off[-1]), dtype=np.int64)], off
+
+
+class SeedSource(ArraySource):
+    """The chains of a SeedMapper (SeedIndex.map, or SeedIndex.matches + Context.seed_chains) as records, with no SAM text in between: one
+    record per chain, in the file order of chainSamFile -- by (reference index, QNAME as bytes), npr_seed_chain_sam_text's -- the chain's
+    guide as the record's guide, and as output the record that call writes with the realigned CIGAR in place of the guide's.
+    fa, fq: ingest.FastaTable, ingest.FastqTable; chain c belongs to the read i with chain_off[i] <= c < chain_off[i + 1], is (reference
+    index, strand, ...) and has the guide ops[ops_off[c]:ops_off[c + 1]].  Reads of strand-0 chains are the spans of the FASTQ text; reads
+    of strand-1 chains are spans of a side buffer that holds their reverse complements, made once here and lying behind a copy of the FASTQ
+    text (a batch is staged from ONE text).  Two reads of one name are refused, as npr_seed_chain_sam_text refuses them: their order
+    would be undefined."""
+
+    def __init__(self, fa, fq, chain_off, chains, ops_off, ops, model_slot=None):
+        chain_off, ops_off = np.ascontiguousarray(chain_off, dtype=np.int64), np.ascontiguousarray(ops_off, dtype=np.int64)
+        chains, ops = np.ascontiguousarray(chains, dtype=np.int32).reshape(-1, 4), np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 2)
+        text, span = np.ascontiguousarray(fq.text, dtype=np.uint8), np.ascontiguousarray(fq.seq_span, dtype=np.int64).reshape(-1, 2)
+        names = [text[a:b].tobytes() for a, b in np.asarray(fq.name_span, dtype=np.int64).reshape(-1, 2)]
+        n_reads = len(names)
+        if len(chain_off) != n_reads + 1 or int(chain_off[-1]) != len(chains) or len(ops_off) != len(chains) + 1 or int(ops_off[-1]) != len(ops):
+            raise ValueError("chain_off[reads + 1], one row per chain, ops_off[chains + 1], one pair per op")
+        if len(chains) and (int(chains[:, 0].min()) < 0 or int(chains[:, 0].max()) >= len(fa.names) or not np.isin(chains[:, 1], (0, 1)).all()):
+            raise _lib.NprError(_lib.ERR_INVALID, "SeedSource", "a chain outside the reference list, or a strand other than 0 / 1")
+        by_name = sorted(range(n_reads), key=names.__getitem__)  # (bytes compare as memcmp does, a shorter name before its extensions)
+        if any(names[a] == names[b] for a, b in zip(by_name, by_name[1:])):
+            raise _lib.NprError(_lib.ERR_INVALID, "SeedSource", "two reads of one name: the order of their records would be undefined")
+        rank = np.empty(n_reads, dtype=np.int64)
+        rank[by_name] = np.arange(n_reads)
+        read_of = np.repeat(np.arange(n_reads, dtype=np.int64), np.diff(chain_off))
+        order = np.lexsort((rank[read_of], chains[:, 0]))  # record k is chain order[k]
+        self.read, self.strand = read_of[order], chains[order, 1]
+        # the guides in record order
+        k = ops_off[order + 1] - ops_off[order]
+        guide_off = np.zeros(len(order) + 1, dtype=np.int64)
+        np.cumsum(k, out=guide_off[1:])
+        guide_ops = ops[np.repeat(ops_off[order] - guide_off[:-1], k) + np.arange(int(guide_off[-1]), dtype=np.int64)]
+        # the reverse complements of the reads that have a strand-1 chain, each once: byte t of one is the complement of the read's byte end - 1 - t
+        rev = np.unique(self.read[self.strand == 1])
+        lens = span[rev, 1] - span[rev, 0]
+        rc_off = np.zeros(len(rev) + 1, dtype=np.int64)
+        np.cumsum(lens, out=rc_off[1:])
+        rc = _COMPLEMENT[text[np.repeat(span[rev, 1] - 1 + rc_off[:-1], lens) - np.arange(int(rc_off[-1]), dtype=np.int64)]]
+        slot = np.zeros(n_reads, dtype=np.int64)
+        slot[rev] = np.arange(len(rev))
+        begin = np.where(self.strand == 1, len(text) + rc_off[slot[self.read]], span[self.read, 0])
+        ArraySource.__init__(self, fa.seq, fa.off, np.concatenate([text, rc]), begin, begin + (span[self.read, 1] - span[self.read, 0]), guide_ops,
+                             guide_off, ref_index=chains[order, 0], model_slot=model_slot)
+        self.names, self.ref_names = names, [name.encode() for name in fa.names]
+        self.header = b"".join(("@SQ\tSN:%s\tLN:%d\n" % (name, length)).encode() for name, length in zip(fa.names, np.diff(fa.off)))
+
+    def format_block(self, lo, hi, ops_off, words):
+        from . import realign
+        nops = np.asarray(ops_off[1:]) - np.asarray(ops_off[:-1])
+        seq, seq_off = _gather_spans(self.text, self.read_begin[lo:hi], self.read_end[lo:hi])
+        buf, _ = realign.format_sam_records([self.names[i] for i in self.read[lo:hi]], self.ref_names, self.ref_index[lo:hi], np.ones(hi - lo, dtype=np.int64),
+                                            ops_off[:-1], nops, words, seq, seq_off, flag=16 * self.strand[lo:hi])
+        return buf
+
+
 # ---------------------------------------------------------------------------------------------------------
 # the per-rank pipeline
 # ---------------------------------------------------------------------------------------------------------
@@ -814,6 +882,38 @@ def run_source(src, params, bounds, out_path, ctxs=None, gpu=None, group=None, w
     return out
 
 
+_KEEP_MODELS = object()  # _job_setup: the contexts keep the models they have
+
+
+def _job_setup(gpu, workers, hmm, model_slot, params, gapGamma, matchGamma):
+    """What a files -> file job needs before its records run: (the GPU, its contexts with the model `hmm` -- a nanopore_amd.hmm.Hmm, a model
+    file path, None for the stock model -- in `model_slot`, params or the reference's call parameters: anchors +- 10, trim 14, split 3000)."""
+    from . import realign
+    from .hmm import Hmm
+    gpu = default_gpu() if gpu is None else gpu
+    ctxs = contexts(gpu, workers or WORKERS)
+    if hmm is not _KEEP_MODELS:
+        model = Hmm.loadHmm(hmm) if isinstance(hmm, str) else hmm
+        for c in ctxs:
+            c.set_hmm(model, slot=model_slot)
+    if params is None:
+        params = realign.make_params(band_mode=realign.BAND_ANCHOR, diagonal_expansion=10, constraint_trim=14, split_threshold=3000,
+                                     gap_gamma=gapGamma, match_gamma=matchGamma, mode=realign.MODE_REALIGN)
+    return gpu, ctxs, params
+
+
+def realign_source(src, outputSamFile, hmm=None, gapGamma=0.5, matchGamma=0.0, gpu=None, model_slot=0):
+    """realign_sam_file for records that are arrays already (a SeedSource): the same contexts, model and call parameters, the same
+    pipeline, `outputSamFile` = src.header + the records.  One process: such a source is not sharded over the ranks of a process group, and
+    under an initialised one this raises rather than let every rank write the whole file."""
+    if _dist_state(None)[0] is not None:
+        raise RuntimeError("realign_source runs in one process: a record source made of arrays is not sharded over a torch.distributed process group")
+    gpu, ctxs, params = _job_setup(gpu, None, hmm, model_slot, None, gapGamma, matchGamma)
+    out = run_source(src, params, np.array([0, src.n], dtype=np.int64), outputSamFile, ctxs=ctxs, gpu=gpu, group=SOLO)
+    out["records"] = len(out["results"])
+    return out
+
+
 def realign_sam_file(samFile, outputSamFile, referenceFastaFile, hmm=None, gapGamma=0.5, matchGamma=0.0, params=None, group=None,
                      gpu=None, want_stats=False, model_slot=0, chunk_bases=None, workers=None, coll_device=None, set_models=True,
                      device_text=False):
@@ -827,14 +927,12 @@ def realign_sam_file(samFile, outputSamFile, referenceFastaFile, hmm=None, gapGa
     csrc/npr_cigtext.hip) and spliced in as they are (npr_sam_splice_text); the file is the same byte for byte.  One process only: under a
     process group the job keeps the packed words (what the ranks' payloads are made of) and refuses the keyword; and not with want_stats,
     whose table is reduced from the packed words."""
-    from . import ingest, realign
-    from .hmm import Hmm
+    from . import ingest
     dist, world, rank = _dist_state(group)
     if device_text and dist is not None:
         raise ValueError("device_text=True is for the single-process job: a job sharded over a process group keeps the packed cigars")
     if device_text and want_stats:
         raise ValueError("device_text=True: the statistics are reduced from the packed cigars, which such a job does not fetch")
-    gpu = default_gpu() if gpu is None else gpu
     t0 = time.perf_counter()
     sam = ingest.SamText(samFile)
     fasta = ingest.FastaTable(referenceFastaFile)
@@ -850,14 +948,7 @@ def realign_sam_file(samFile, outputSamFile, referenceFastaFile, hmm=None, gapGa
         fields, span = fields[keep], span[keep]
     src = SamSource(sam, fasta, span, fields, model_slot=None if not model_slot else np.full(len(fields), model_slot, dtype=np.int32))
     t2 = time.perf_counter()
-    ctxs = contexts(gpu, workers or WORKERS)
-    if set_models:
-        model = Hmm.loadHmm(hmm) if isinstance(hmm, str) else hmm
-        for c in ctxs:
-            c.set_hmm(model, slot=model_slot)
-    if params is None:
-        params = realign.make_params(band_mode=realign.BAND_ANCHOR, diagonal_expansion=10, constraint_trim=14, split_threshold=3000,
-                                     gap_gamma=gapGamma, match_gamma=matchGamma, mode=realign.MODE_REALIGN)
+    gpu, ctxs, params = _job_setup(gpu, workers, hmm if set_models else _KEEP_MODELS, model_slot, params, gapGamma, matchGamma)
     local = np.array([0] * (rank + 1) + [len(fields)] * (world - rank), dtype=np.int64)  # src holds this rank's records only
     for c in ctxs if device_text else ():
         c.set_option(_lib.OPT_FINISH_TEXT, 1)

@@ -92,15 +92,16 @@ def _snp_calls(fn, where, ctx, head, rows, ref_code, true_code, evolution, error
 
 
 class _Handle(object):
-    """An object of the library that belongs to a Context (Batch, Pileup, SeedIndex): destroyed once, by close(), by the context's
+    """An object of the library that belongs to a Context (Batch, Pileup, SeedIndex, SeedMap): destroyed once, by close(), by the context's
     close() or when it is collected, whichever comes first."""
     _destroy = None  # the entry point that destroys the handle
 
-    def _create(self, ctx, create, where, *args):
-        """self._h = the handle `create`(ctx, *args, &handle) makes."""
+    def _create(self, ctx, create, where, *args, made_from=None):
+        """self._h = the handle `create`(ctx, *args, &handle) makes -- or `create`(made_from, *args, &handle), for an object the library
+        makes from another handle of the same context."""
         self._L, self.ctx, self._h = _lib.load(), ctx, None
         h = C.c_void_p()
-        check(getattr(self._L, create)(ctx._h, *args, C.byref(h)), where, ctx)
+        check(getattr(self._L, create)((made_from or ctx)._h, *args, C.byref(h)), where, ctx)
         self._h = h
         ctx._open.add(self)
 
@@ -365,23 +366,57 @@ class SeedIndex(_Handle):
         self.n_refs = len(ref_off) - 1
         self._create(ctx, "npr_seed_index_create", "npr_seed_index_create", self.k, self.n_refs, ptr(ref), ptr(ref_off))
 
+    @staticmethod
+    def _chunks(where, text, begin, end, chunk_bases):
+        """The reads as the library takes them, and how they go to the device: (text, begin, end, [(lo, hi), ...]) with reads lo .. hi of a
+        chunk staying within chunk_bases bases (one read at least); one empty chunk when there are no reads."""
+        text, begin, end = _arr(text, np.uint8), _arr(begin, np.int64), _arr(end, np.int64)
+        n = len(begin)
+        if len(end) != n or (n and (int(begin.min()) < 0 or int(end.max()) > len(text))):
+            raise NprError(_lib.ERR_INVALID, where, "begin and end differ in number, or a span lies outside the text")
+        first = np.zeros(n + 1, dtype=np.int64)  # bases before read i
+        np.cumsum(end - begin, out=first[1:])
+        chunks = []
+        while not chunks or chunks[-1][1] < n:
+            lo = chunks[-1][1] if chunks else 0
+            chunks.append((lo, min(n, max(int(np.searchsorted(first, first[lo] + chunk_bases, side="right")) - 1, lo + 1))))
+        return text, begin, end, chunks
+
+    def map(self, text, begin, end, min_len=20, strands=3, max_gap=200, chunk_bases=1 << 26, rows=False):
+        """matches() followed by Context.seed_chains() on its rows, in one call per chunk of reads and with the rows never leaving the
+        device (include/nprealign.h: npr_seed_map_*; csrc/npr_seedmap.hip): (chain_off, chains, ops_off, ops) as seed_chains returns them
+        for read lengths end - begin and the index's own sequence lengths, and with rows=True (hit_off, hits, chain_off, chains, ops_off,
+        ops), the first two as matches returns them.  Chunks as matches cuts them; their arrays are joined with the offsets rebased."""
+        text, begin, end, chunks = self._chunks("npr_seed_map_create", text, begin, end, chunk_bases)
+        n = len(begin)
+        hit_off, chain_off = np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+        hits, chains, ops_off, ops = [], [], [np.zeros(1, dtype=np.int64)], []
+        n_ops = 0
+        for lo, hi in chunks:
+            m = SeedMap(self, text, begin[lo:hi], end[lo:hi], min_len, strands, max_gap)
+            try:
+                part = m.fetch(rows)
+            finally:
+                m.close()
+            if rows:
+                hit_off[lo + 1:hi + 1] = hit_off[lo] + part[0][1:]
+                hits.append(part[1])
+            chain_off[lo + 1:hi + 1] = chain_off[lo] + part[-4][1:]
+            chains.append(part[-3])
+            ops_off.append(n_ops + part[-2][1:])
+            ops.append(part[-1])
+            n_ops += len(part[-1])
+        out = (chain_off, np.concatenate(chains), np.concatenate(ops_off), np.concatenate(ops))
+        return (hit_off, np.concatenate(hits)) + out if rows else out
+
     def matches(self, text, begin, end, min_len=20, strands=3, chunk_bases=1 << 26):
         """All maximal exact matches of at least min_len bases of the reads text[begin[i]:end[i]] (spans inside a larger uint8 text, e.g.
         FastqTable.text / .seq_span) on the strands asked for (1 forward, 2 reverse, 3 both): (hit_off int64 [n + 1], hits int32 [m, 4]) --
         the rows of read i are hits[hit_off[i]:hit_off[i + 1]], each (reference index, a, b | strand << 31, L), sorted by (strand,
         reference index, a, b).  The reads go to the device in chunks of about chunk_bases bases, each counted first and then fetched
         into a buffer of exactly its size."""
-        text, begin, end = _arr(text, np.uint8), _arr(begin, np.int64), _arr(end, np.int64)
-        n = len(begin)
-        if len(end) != n or (n and (int(begin.min()) < 0 or int(end.max()) > len(text))):
-            raise NprError(_lib.ERR_INVALID, "npr_seed_matches", "begin and end differ in number, or a span lies outside the text")
-        hit_off = np.zeros(n + 1, dtype=np.int64)
-        first = np.zeros(n + 1, dtype=np.int64)  # bases before read i
-        np.cumsum(end - begin, out=first[1:])
-        chunks = []  # reads lo .. hi whose bases stay within chunk_bases (one read at least); one empty call when there are no reads
-        while not chunks or chunks[-1][1] < n:
-            lo = chunks[-1][1] if chunks else 0
-            chunks.append((lo, min(n, max(int(np.searchsorted(first, first[lo] + chunk_bases, side="right")) - 1, lo + 1))))
+        text, begin, end, chunks = self._chunks("npr_seed_matches", text, begin, end, chunk_bases)
+        hit_off = np.zeros(len(begin) + 1, dtype=np.int64)
         parts = []
         for lo, hi in chunks:
             off = np.zeros(hi - lo + 1, dtype=np.int64)
@@ -394,6 +429,34 @@ class SeedIndex(_Handle):
             check(total, "npr_seed_matches", self.ctx)
             hit_off[lo + 1:hi + 1] = hit_off[lo] + off[1:]
         return hit_off, (np.concatenate(parts) if parts else np.zeros((0, 4), dtype=np.int32))
+
+
+class SeedMap(_Handle):
+    """The rows, chains and guides of one call's reads on the device (include/nprealign.h: npr_seed_map_*): made by one call on a
+    SeedIndex, fetched as often as wanted, destroyed like every other object of its context (it does not need its index any more)."""
+    _destroy = "npr_seed_map_destroy"
+
+    def __init__(self, index, text, begin, end, min_len=20, strands=3, max_gap=200):
+        begin, end = _arr(begin, np.int64), _arr(end, np.int64)
+        self.n_reads = len(begin)
+        self._create(index.ctx, "npr_seed_map_create", "npr_seed_map_create", int(min_len), int(strands), int(max_gap), self.n_reads,
+                     ptr(_arr(text, np.uint8)), ptr(begin), ptr(end), made_from=index)
+
+    def counts(self):
+        """(rows, chains, guide op pairs)"""
+        c = np.zeros(3, dtype=np.int64)
+        check(self._L.npr_seed_map_counts(self._h, ptr(c)), "npr_seed_map_counts", self.ctx)
+        return tuple(int(v) for v in c)
+
+    def fetch(self, rows=True):
+        """(hit_off, hits, chain_off, chains, ops_off, ops), the first two only with rows=True."""
+        n_rows, n_chains, n_pairs = self.counts()
+        hit_off, hits = (np.zeros(self.n_reads + 1, dtype=np.int64), np.empty((n_rows, 4), dtype=np.int32)) if rows else (None, None)
+        chain_off, chains = np.zeros(self.n_reads + 1, dtype=np.int64), np.empty((n_chains, 4), dtype=np.int32)
+        ops_off, ops = np.zeros(n_chains + 1, dtype=np.int64), np.empty((n_pairs, 2), dtype=np.int32)
+        out = (hit_off, hits, chain_off, chains, ops_off, ops)
+        check(self._L.npr_seed_map_fetch(self._h, *map(ptr, out)), "npr_seed_map_fetch", self.ctx)
+        return out if rows else out[2:]
 
 
 class Context(object):
