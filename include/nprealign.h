@@ -537,6 +537,39 @@ int32_t npr_batch_snp_calls(npr_batch *b, const uint8_t *use, int64_t n_refs, co
 int32_t npr_pileup_snp_calls(npr_pileup *pl, const uint8_t *ref_code, const uint8_t *true_code, int32_t n_models,
                              const double *evolution16, const double *error16, npr_snp_calls *out);
 
+/* ---- SNP variants on the device: the calls themselves and a consensus, from the same posteriors ----
+ * The tables, the row layout, evolution16 and the posterior are those of the npr_*_snp_calls block above, for ONE error model
+ * (error16 [candidate][observed], 16 entries) and without a truth.  Instead of histograms two things leave the device
+ * (csrc/npr_snpcall.hip: k_snp_variants_count, _scan, _emit): a best base and its quality per row, and the list of calls.
+ * A row is CALLABLE when it is seen, total = ((w0+w1)+w2)+w3 != 0 and its reference base is A/C/G/T.  For a callable row, in fp64:
+ *   lp[c]  = log evolution[ref][c] + sum_o (w[o] / total) log error[c][o]     (o = 0..3 added in that order, starting from 0)
+ *   e[c]   = exp(lp[c] - max_c lp[c]),   sum = ((e0+e1)+e2)+e3,   p[c] = e[c] / sum
+ * BEST.  best[row] = the candidate of largest lp; among candidates whose lp are exactly equal, the reference base if it is one of
+ * them, else the one of lowest code.  qual[row] = min(93, floor(-10 log10(q))) with q = (the e of the three other candidates, added
+ * in ascending code) / sum; q == 0 gives 93.  A row that is not callable has best = 4 and qual = 0.
+ * CALLS.  Every candidate c != ref of a callable row with p[c] >= threshold is one call (row, c, p[c]).  The calls come in ascending
+ * (row, candidate code) order in call_row / call_alt / call_p; the arrays are the same from run to run.  threshold is a finite number
+ * in [0, 1].  A zero in evolution16 makes p[c] = 0: such a candidate is no call at any threshold above 0 and IS a call at threshold
+ * 0, where every callable row has its three calls.
+ * OUTPUT AND CAPACITY, as npr_seed_matches.  best and qual ([rows] each) may be NULL and are then not copied.  The return value is the
+ * number of calls (>= 0), which *n_calls receives too; the call arrays hold cap entries (they may be NULL with cap 0).  More calls
+ * than cap: NPR_ERR_CAPACITY, *n_calls says how many, the call arrays are not touched -- best and qual are filled in both cases.
+ * rows == 0 is legal (no calls).  NPR_ERR_INVALID, with EVERY output untouched: a threshold outside [0, 1] or not a number, cap < 0,
+ * n_calls NULL, an error16 entry that is not a finite number above zero, an evolution16 entry that is negative or not finite or a row
+ * of it that is all zero -- and whatever the npr_*_snp_calls call on the same table refuses (a weight that is negative or not finite,
+ * missing base codes; npr_batch_snp_variants before npr_batch_finish: NPR_ERR_STATE). */
+int64_t npr_snp_variants_table(npr_ctx *ctx, int64_t rows, const double *weights, const uint8_t *seen, const uint8_t *ref_code,
+                               const double *evolution16, const double *error16 /* [16] */, double threshold, uint8_t *best, uint8_t *qual,
+                               int64_t *call_row, uint8_t *call_alt, double *call_p, int64_t cap, int64_t *n_calls);
+/* the posterior expectations of a finished all-posteriors batch (table and arguments as for npr_batch_snp_calls) */
+int64_t npr_batch_snp_variants(npr_batch *b, const uint8_t *use, int64_t n_refs, const int64_t *ref_len, const uint8_t *ref_code,
+                               const double *evolution16, const double *error16, double threshold, uint8_t *best, uint8_t *qual,
+                               int64_t *call_row, uint8_t *call_alt, double *call_p, int64_t cap, int64_t *n_calls);
+/* the aligned-base frequencies of a pileup (table as for npr_pileup_snp_calls) */
+int64_t npr_pileup_snp_variants(npr_pileup *pl, const uint8_t *ref_code, const double *evolution16, const double *error16,
+                                double threshold, uint8_t *best, uint8_t *qual, int64_t *call_row, uint8_t *call_alt, double *call_p,
+                                int64_t cap, int64_t *n_calls);
+
 /* Baum-Welch E-step over the staged batch with the models currently installed: what
  * `cactus_realign --outputExpectations` produces per alignment and cactus_expectationMaximisation sums over all of
  * them in every EM iteration (nanopore/analyses/utils.py:509-528).  T_exp[slot*25 + from*5 + to] and

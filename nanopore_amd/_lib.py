@@ -174,6 +174,9 @@ SIGNATURES = {
     "npr_snp_calls_table": (i32, [vp, i64, vp, vp, vp, vp, i32, vp, vp, vp]),
     "npr_batch_snp_calls": (i32, [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp]),
     "npr_pileup_snp_calls": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+    "npr_snp_variants_table": (i64, [vp, i64, vp, vp, vp, vp, vp, dbl] + [vp] * 5 + [i64, C.POINTER(i64)]),
+    "npr_batch_snp_variants": (i64, [vp, vp, i64, vp, vp, vp, vp, dbl] + [vp] * 5 + [i64, C.POINTER(i64)]),
+    "npr_pileup_snp_variants": (i64, [vp, vp, vp, vp, dbl] + [vp] * 5 + [i64, C.POINTER(i64)]),
     "npr_batch_expectations": (i32, [vp, vp, vp, vp, C.POINTER(C.c_float)]),
     "npr_batch_dense": (i32, [vp, i64, vp, vp, vp, vp, i64]),
     "npr_batch_rs_forward": (i32, [vp, i64, vp, vp, i64]),

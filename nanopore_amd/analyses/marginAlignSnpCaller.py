@@ -224,26 +224,16 @@ class MarginAlignSnpCaller(AbstractAnalysis):
         """What callsOnDevice needs of the SAM records and the references, made once per run: the records as Pileup.add_csr takes them
         (the alignments the host path counts its frequencies of aligned bases from), the aligned pairs of every record, and the reference /
         true base codes of every table row (npr_encode_bases' codes; rows in the order of refNames)."""
-        from ..realign import _csr, _csr_ops
-        from .utils import _guideOf
+        from .utils import stageRecordsForPileup
         for aR in records:
             assert all(op in (0, 1, 2) for op, _ in aR.cigar), "callsOnDevice: %s has cigar operations other than M / I / D" % aR.qname
-        guides = [_guideOf(aR) for aR in records]
-        refLengths = [len(refSequences[n]) for n in refNames]
-        refRows = np.concatenate([[0], np.cumsum(refLengths)])
-        code = np.where(_BASE_CODE < 0, 4, _BASE_CODE).astype(np.uint8)
-        refCodes = code[np.frombuffer("".join(refSequences[n] for n in refNames).encode(), dtype=np.uint8)]
-        trueCodes = refCodes.copy()
+        # (a record is global, asserted in run(): every M column lies on the reference)
+        staged = stageRecordsForPileup(sam, records, refSequences, refNames)
+        trueCodes = staged["refCodes"].copy()
         for (name, i), base in snpSet.items():
-            trueCodes[refRows[refIndex[name]] + i] = code[ord(base)]
-        read, readOff = _csr([aR.query for aR in records])
-        ops, opsOff = _csr_ops(guides)
-        return {"read": read, "readOff": readOff, "ops": ops, "opsOff": opsOff,
-                "refIndex": np.array([refIndex[sam.getrname(aR.rname)] for aR in records], dtype=np.int32),
-                "start": np.array([(aR.pos, 0) for aR in records], dtype=np.int64).reshape(-1, 2),
-                # (a record is global, asserted in run(): every M column lies on the reference)
-                "alignedPairs": [sum(length for op, length in g if op == 0) for g in guides],
-                "refCodes": refCodes, "trueCodes": trueCodes}
+            trueCodes[staged["refRows"][refIndex[name]] + i] = staged["baseCode"][ord(base)]
+        staged["trueCodes"] = trueCodes
+        return staged
 
     def _callSetsOnDevice(self, batch, staged, sampled, refLengths, hmmErrorMatrix, totalHeldOut):
         """The four call sets of one sample, in the order of the element tags, counted on the device: the two error models over the posterior

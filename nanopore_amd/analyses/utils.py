@@ -245,6 +245,28 @@ def _guideOf(aR):
     return [(op, length) for op, length in aR.cigar if op in (0, 1, 2)]
 
 
+def stageRecordsForPileup(sam, records, refSequences, refNames):
+    """The SAM records and the references as the device takes them for a pileup and for calls made on it (MarginAlignSnpCaller with
+    callsOnDevice, Consensus), made once per run: the records as Pileup.add_csr takes them -- read i = its SEQ without the soft-clipped
+    ends, its cigar's M / I / D runs, starting at (POS, 0) --, the aligned pairs of every record, the row of every reference sequence's
+    first position and the reference base code of every table row (npr_encode_bases' codes; rows in the order of refNames)."""
+    from ..realign import _csr, _csr_ops
+    guides = [_guideOf(aR) for aR in records]
+    refIndex = {n: i for i, n in enumerate(refNames)}
+    refLengths = [len(refSequences[n]) for n in refNames]
+    code = np.full(256, 4, dtype=np.uint8)
+    for k, c in enumerate("ACGT"):
+        code[ord(c)] = code[ord(c.lower())] = k
+    read, readOff = _csr([aR.query for aR in records])
+    ops, opsOff = _csr_ops(guides)
+    return {"read": read, "readOff": readOff, "ops": ops, "opsOff": opsOff,
+            "refIndex": np.array([refIndex[sam.getrname(aR.rname)] for aR in records], dtype=np.int32),
+            "start": np.array([(aR.pos, 0) for aR in records], dtype=np.int64).reshape(-1, 2),
+            "alignedPairs": [sum(length for op, length in g if op == 0) for g in guides],
+            "refLengths": refLengths, "refRows": np.concatenate([[0], np.cumsum(refLengths)]).astype(np.int64), "baseCode": code,
+            "refCodes": code[np.frombuffer("".join(refSequences[n] for n in refNames).encode(), dtype=np.uint8)]}
+
+
 def realignRecords(sam, records, refSequences, gapGamma, matchGamma, hmmFile, mode=None, splitThreshold=None,
                    ctx=None, want_pairs=False):
     """All records to the GPU in one batched call.  Returns the list of per-record result dicts in input

@@ -549,6 +549,60 @@ int32_t run_snp_calls(npr_ctx *ctx, int64_t rows, int32_t source, const void *d_
     return NPR_OK;
 }
 
+// The device half of the three SNP-variant entry points, the table as for run_snp_calls: k_snp_variants_count and the scan, the one word
+// the capacity decision needs, then k_snp_variants_emit when the calls fit.  Scratch from the context's cache of released buffers.
+// *n_calls and best / qual (each when given) are written in both outcomes, the call arrays only when everything has worked.
+int64_t run_snp_variants(npr_ctx *ctx, int64_t rows, int32_t source, const void *d_table, const uint8_t *d_seen, const uint8_t *ref_code,
+                         const double *log_evolution, const double *log_error, double threshold, uint8_t *best, uint8_t *qual, int64_t *call_row,
+                         uint8_t *call_alt, double *call_p, int64_t cap, int64_t *n_calls) {
+    if (rows == 0) return *n_calls = 0;
+    const int64_t tiles = snp_variant_tiles(rows);
+    DevBuf<uint8_t> d_bytes, d_alt;  // ref_code, best, qual, mask: [4][rows]
+    DevBuf<uint32_t> d_tile_calls;
+    DevBuf<int64_t> d_tile_off, d_row;
+    DevBuf<double> d_p;
+    hipError_t e;
+    if ((e = d_bytes.alloc_from(ctx, 4 * static_cast<size_t>(rows))) != hipSuccess || (e = d_tile_calls.alloc_from(ctx, tiles)) != hipSuccess ||
+        (e = d_tile_off.alloc_from(ctx, tiles + 1)) != hipSuccess)
+        return fail(ctx, NPR_ERR_NOMEM, "SNP variants: hipMalloc", e);
+    HIP_TRY(ctx, hipMemcpyAsync(d_bytes.p, ref_code, rows, hipMemcpyHostToDevice, ctx->stream));
+    SnpCallArgs a{};
+    a.rows = rows, a.source = source, a.n_models = 1, a.table = d_table, a.seen = d_seen, a.ref_code = d_bytes.p, a.threshold = threshold;
+    a.best = d_bytes.p + rows, a.qual = d_bytes.p + 2 * rows, a.mask = d_bytes.p + 3 * rows, a.tile_calls = d_tile_calls.p, a.tile_off = d_tile_off.p;
+    std::memcpy(a.log_evolution, log_evolution, sizeof(a.log_evolution));
+    std::memcpy(a.log_error, log_error, 16 * sizeof(double));
+    int rc = launch_snp_variants_count(a, ctx->stream);
+    if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_snp_variants_count launch", static_cast<hipError_t>(rc));
+    int64_t total = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&total, d_tile_off.p + tiles, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const bool fits = total <= cap && (total == 0 || (call_row && call_alt && call_p));
+    if (fits && total) {
+        if ((e = d_row.alloc_from(ctx, total)) != hipSuccess || (e = d_alt.alloc_from(ctx, total)) != hipSuccess || (e = d_p.alloc_from(ctx, total)) != hipSuccess)
+            return fail(ctx, NPR_ERR_NOMEM, "SNP variants: hipMalloc", e);
+        a.n_calls = total, a.call_row = d_row.p, a.call_alt = d_alt.p, a.call_p = d_p.p;
+        rc = launch_snp_variants_emit(a, ctx->stream);
+        if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_snp_variants_emit launch", static_cast<hipError_t>(rc));
+        HIP_TRY(ctx, hipMemcpyAsync(call_row, d_row.p, d_row.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(call_alt, d_alt.p, d_alt.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(call_p, d_p.p, d_p.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (best) HIP_TRY(ctx, hipMemcpyAsync(best, a.best, rows, hipMemcpyDeviceToHost, ctx->stream));
+    if (qual) HIP_TRY(ctx, hipMemcpyAsync(qual, a.qual, rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *n_calls = total;
+    if (!fits) return fail(ctx, NPR_ERR_CAPACITY, "SNP variants: more calls than the arrays hold (*n_calls says how many)");
+    return total;
+}
+
+// what the three entry points check of their model and outputs before anything else: the matrices' logs, or false
+bool snp_variant_model(const double *evolution16, const double *error16, double threshold, int64_t cap, const int64_t *n_calls, double *log_evolution,
+                       double *log_error) {
+    return n_calls && cap >= 0 && threshold >= 0.0 && threshold <= 1.0 && snp_log_matrices(1, evolution16, error16, log_evolution, log_error);
+}
+const char *const kSnpVariantModel =
+    ": a threshold outside [0, 1], a negative capacity, no n_calls, an error probability that is not a finite number above zero, or an evolution matrix with a negative entry or an all-zero row";
+
 }  // namespace
 
 int32_t npr_batch_base_expectations(npr_batch *b, const uint8_t *use, int64_t n_refs, const int64_t *ref_len, double *expect, uint8_t *seen) {
@@ -645,6 +699,78 @@ int32_t npr_pileup_snp_calls(npr_pileup *pl, const uint8_t *ref_code, const uint
         return run_snp_calls(ctx, pl->rows, SNP_SRC_PILEUP, pl->tab.p, nullptr, ref_code, true_code, n_models, log_evolution, log_error, out);
     } catch (const std::exception &) {
         return fail(ctx, NPR_ERR_NOMEM, "npr_pileup_snp_calls: out of host memory");
+    }
+}
+
+int64_t npr_snp_variants_table(npr_ctx *ctx, int64_t rows, const double *weights, const uint8_t *seen, const uint8_t *ref_code, const double *evolution16,
+                               const double *error16, double threshold, uint8_t *best, uint8_t *qual, int64_t *call_row, uint8_t *call_alt, double *call_p,
+                               int64_t cap, int64_t *n_calls) {
+    if (!ctx) return NPR_ERR_INVALID;
+    if (rows < 0 || (rows && (!weights || !seen || !ref_code))) return fail(ctx, NPR_ERR_INVALID, "npr_snp_variants_table: bad argument");
+    double log_evolution[16], log_error[16];
+    if (!snp_variant_model(evolution16, error16, threshold, cap, n_calls, log_evolution, log_error))
+        return fail(ctx, NPR_ERR_INVALID, (std::string("npr_snp_variants_table") + kSnpVariantModel).c_str());
+    try {
+        for (int64_t i = 0; i < 4 * rows; ++i)
+            if (!(weights[i] >= 0.0) || !std::isfinite(weights[i])) return fail(ctx, NPR_ERR_INVALID, "npr_snp_variants_table: a weight is negative or not finite");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        DevBuf<double> d_w;
+        DevBuf<uint8_t> d_seen;
+        hipError_t e;
+        if ((e = d_w.alloc_from(ctx, 4 * rows)) != hipSuccess || (e = d_seen.alloc_from(ctx, rows)) != hipSuccess)
+            return fail(ctx, NPR_ERR_NOMEM, "npr_snp_variants_table: hipMalloc", e);
+        if (rows) {
+            HIP_TRY(ctx, hipMemcpyAsync(d_w.p, weights, d_w.bytes(), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(d_seen.p, seen, d_seen.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        }
+        return run_snp_variants(ctx, rows, SNP_SRC_DOUBLE, d_w.p, d_seen.p, ref_code, log_evolution, log_error, threshold, best, qual, call_row, call_alt, call_p,
+                                cap, n_calls);
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_snp_variants_table: out of host memory");
+    }
+}
+
+int64_t npr_batch_snp_variants(npr_batch *b, const uint8_t *use, int64_t n_refs, const int64_t *ref_len, const uint8_t *ref_code, const double *evolution16,
+                               const double *error16, double threshold, uint8_t *best, uint8_t *qual, int64_t *call_row, uint8_t *call_alt, double *call_p,
+                               int64_t cap, int64_t *n_calls) {
+    if (!b || n_refs < 0 || (n_refs && !ref_len)) return NPR_ERR_INVALID;
+    if (!b->finished) return NPR_ERR_STATE;
+    npr_ctx *ctx = b->ctx;
+    double log_evolution[16], log_error[16];
+    if (!snp_variant_model(evolution16, error16, threshold, cap, n_calls, log_evolution, log_error))
+        return fail(ctx, NPR_ERR_INVALID, (std::string("npr_batch_snp_variants") + kSnpVariantModel).c_str());
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        std::vector<int64_t> base;
+        if (!row_bases(n_refs, ref_len, base)) return NPR_ERR_INVALID;
+        const int64_t rows = base[n_refs];
+        if (rows && !ref_code) return fail(ctx, NPR_ERR_INVALID, "npr_batch_snp_variants: no reference base codes");
+        DeviceExpectations d;
+        if (rows) {
+            const int32_t rc = accumulate_base_expectations(b, use, n_refs, ref_len, base, "npr_batch_snp_variants: a read's window does not fit its reference", d);
+            if (rc != NPR_OK) return rc;
+        }
+        return run_snp_variants(ctx, rows, SNP_SRC_FIXED, d.e.p, d.seen.p, ref_code, log_evolution, log_error, threshold, best, qual, call_row, call_alt, call_p,
+                                cap, n_calls);
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_batch_snp_variants: out of host memory");
+    }
+}
+
+int64_t npr_pileup_snp_variants(npr_pileup *pl, const uint8_t *ref_code, const double *evolution16, const double *error16, double threshold, uint8_t *best,
+                                uint8_t *qual, int64_t *call_row, uint8_t *call_alt, double *call_p, int64_t cap, int64_t *n_calls) {
+    if (!pl) return NPR_ERR_INVALID;
+    npr_ctx *ctx = pl->ctx;
+    if (pl->rows && !ref_code) return fail(ctx, NPR_ERR_INVALID, "npr_pileup_snp_variants: no reference base codes");
+    double log_evolution[16], log_error[16];
+    if (!snp_variant_model(evolution16, error16, threshold, cap, n_calls, log_evolution, log_error))
+        return fail(ctx, NPR_ERR_INVALID, (std::string("npr_pileup_snp_variants") + kSnpVariantModel).c_str());
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return run_snp_variants(ctx, pl->rows, SNP_SRC_PILEUP, pl->tab.p, nullptr, ref_code, log_evolution, log_error, threshold, best, qual, call_row, call_alt,
+                                call_p, cap, n_calls);
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_pileup_snp_variants: out of host memory");
     }
 }
 

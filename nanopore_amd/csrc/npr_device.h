@@ -437,8 +437,22 @@ struct SnpCallArgs {
     double log_evolution[16];   // [reference][candidate]
     double log_error[4][16];    // [model][candidate][observed]
     unsigned long long *out;    // [n_models][SNP_OUT_WORDS], added to
+    // The variant kernels alone (include/nprealign.h: npr_*_snp_variants): error model 0, no true_code, no `out`.
+    double threshold;           // a candidate c != ref of a callable row is a call when p[c] >= threshold
+    uint8_t *best, *qual;       // [rows]: the most probable base (4: the row is not callable) and its quality 0..93
+    uint8_t *mask;              // [rows] scratch: bit j = the j-th candidate other than the reference base, in ascending code, is a call
+    uint32_t *tile_calls;       // [tiles]: the set mask bits of SNP_VARIANT_TILE consecutive rows
+    int64_t *tile_off;          // [tiles + 1]: their exclusive scan; the last entry is the number of calls
+    int64_t n_calls;            // emit: what tile_off[tiles] said, the length of the three arrays below
+    int64_t *call_row;          // [n_calls] ascending (row, candidate code)
+    uint8_t *call_alt;
+    double *call_p;
 };
 int launch_snp_calls(const SnpCallArgs &a, void *stream);
+constexpr int SNP_VARIANT_TILE = 256;  // rows of one workgroup of the variant kernels, one per thread
+constexpr int64_t snp_variant_tiles(int64_t rows) { return (rows + SNP_VARIANT_TILE - 1) / SNP_VARIANT_TILE; }
+int launch_snp_variants_count(const SnpCallArgs &a, void *stream);  // best, qual, mask, tile_calls, then the scan: tile_off
+int launch_snp_variants_emit(const SnpCallArgs &a, void *stream);   // the calls of a.n_calls = tile_off[tiles] <= the arrays' length
 // NPR_MODE_RESCORE_ORIGINAL on the device (npr_stats.hip; cactus_realign --rescoreOriginalAlignment, nanopore/analyses/alignmentUncertainty.py:41):
 // the mean posterior over the M columns of the guide.  k_rescore_table spreads the guide's M runs into a table of one entry per reference
 // position of the read's window (the read position the guide aligns it to, -1: none); k_rescore_sum looks every posterior pair up in it where the

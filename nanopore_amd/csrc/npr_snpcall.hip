@@ -1,5 +1,6 @@
-// npr_snpcall.hip -- k_snp_calls: the calling step of MarginAlignSnpCaller on the device (include/nprealign.h: npr_snp_calls_table,
-// npr_batch_snp_calls, npr_pileup_snp_calls; nanopore/analyses/marginAlignSnpCaller.py:18-23 and :163-197).
+// npr_snpcall.hip -- the calling step of MarginAlignSnpCaller on the device (nanopore/analyses/marginAlignSnpCaller.py:18-23 and :163-197):
+// k_snp_calls counts the calls into histograms (include/nprealign.h: npr_snp_calls_table, npr_batch_snp_calls, npr_pileup_snp_calls),
+// k_snp_variants_count / _scan / _emit return them (npr_snp_variants_table, npr_batch_snp_variants, npr_pileup_snp_variants).
 //
 // The host path copies a [positions][4] fp64 table over PCIe, computes the posterior of the four candidate bases at every position and
 // appends one (probability, position) tuple per non-reference candidate to a Python list -- which is then reduced to two histograms of
@@ -9,6 +10,14 @@
 // in LDS.  A workgroup flushes its histograms once, after its grid-stride loop, with 64-bit atomics in global memory; counts are
 // integers, so the result is the same from run to run.  Per row 35 bytes are read (two 16-byte loads and three bytes) against 4 exp per
 // model: the kernel is memory-bound and nothing was spent on its arithmetic.  Not yet timed on hardware.
+//
+// The variant kernels share the per-row arithmetic (row_frequencies, candidate_weights) and work on one error model.  A workgroup owns
+// tiles of SNP_VARIANT_TILE consecutive rows, one row per thread.  k_snp_variants_count reads the table once and writes three bytes per
+// row -- the best base, its quality, and which candidates are calls -- and one count per tile; k_snp_variants_scan, one workgroup, turns
+// the counts into offsets and leaves the total for the host, which decides whether the calls fit; k_snp_variants_emit reads the mask
+// bytes, skips a tile without calls, and lets only the rows that call recompute their posteriors.  A call's place is its tile's offset
+// plus its rank in the tile (wavefront ballots, then the wavefronts before it): the arrays are in ascending (row, candidate) order
+// whatever order the workgroups run in.  The whole call on a 4.6 Mb pileup: profiles/snp_variants_time.json (tools/snp_variants_time.py).
 #include <hip/hip_runtime.h>
 
 #include "npr_device.h"
@@ -56,6 +65,38 @@ __device__ __forceinline__ bool load_row(const SnpCallArgs &a, int64_t r, double
     }
 }
 
+// What a table row is to a caller (include/nprealign.h: CALLABLE), and for a callable row the share of each observed base.
+enum { ROW_UNSEEN = 0, ROW_SILENT = 1, ROW_CALLABLE = 2 };
+template <int SRC>
+__device__ __forceinline__ int row_frequencies(const SnpCallArgs &a, int64_t r, int ref, double (&f)[4]) {
+    double w[4];
+    const bool seen = load_row<SRC>(a, r, w);
+    const double total = ((w[0] + w[1]) + w[2]) + w[3];
+    if (!seen) return ROW_UNSEEN;
+    if (!(total != 0.0 && ref <= 3)) return ROW_SILENT;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) f[o] = w[o] / total;
+    return ROW_CALLABLE;
+}
+
+// The four candidates of a callable row under one error model: lp[c] = log evolution[ref][c] + sum_o f[o] log error[c][o], e[c] =
+// exp(lp[c] - the largest lp); returns ((e0 + e1) + e2) + e3: the posterior of candidate c is e[c] / that.  evo_row: the reference
+// base's row of log_evolution.  Every kernel of this file takes its posteriors from here, in this order of operations.
+__device__ __forceinline__ double candidate_weights(const double (&f)[4], const double *evo_row, const double (&log_error)[16], double (&lp)[4],
+                                                    double (&e)[4]) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        double s = 0.0;
+#pragma unroll
+        for (int o = 0; o < 4; ++o) s += f[o] * log_error[4 * c + o];
+        lp[c] = evo_row[c] + s;
+    }
+    const double top = fmax(fmax(lp[0], lp[1]), fmax(lp[2], lp[3]));  // finite: some candidate of every reference base is possible
+#pragma unroll
+    for (int c = 0; c < 4; ++c) e[c] = exp(lp[c] - top);
+    return ((e[0] + e[1]) + e[2]) + e[3];
+}
+
 template <int SRC>
 __global__ void __launch_bounds__(THREADS) k_snp_calls(SnpCallArgs a) {
     __shared__ unsigned int hist[kSnpMaxModels * 2 * SNP_BINS];  // [model][true / false][bin]
@@ -91,29 +132,16 @@ __global__ void __launch_bounds__(THREADS) k_snp_calls(SnpCallArgs a) {
     for (int64_t r0 = static_cast<int64_t>(blockIdx.x) * THREADS; r0 < a.rows; r0 += static_cast<int64_t>(gridDim.x) * THREADS) {
         const int64_t r = r0 + tid;
         if (r < a.rows) {
-            double w[4];
-            const bool seen = load_row<SRC>(a, r, w);
             const int ref = a.ref_code[r];
             const int tru = a.true_code ? a.true_code[r] : ref;
-            const double total = ((w[0] + w[1]) + w[2]) + w[3];
-            if (!seen) {
+            double f[4];
+            const int state = row_frequencies<SRC>(a, r, ref, f);
+            if (state == ROW_UNSEEN) {
                 ++unseen;
-            } else if (total != 0.0 && ref <= 3) {
-                const double f[4] = {w[0] / total, w[1] / total, w[2] / total, w[3] / total};
+            } else if (state == ROW_CALLABLE) {
                 for (int m = 0; m < a.n_models; ++m) {
-                    double lp[4];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        double s = 0.0;
-#pragma unroll
-                        for (int o = 0; o < 4; ++o) s += f[o] * a.log_error[m][4 * c + o];
-                        lp[c] = evo[4 * ref + c] + s;
-                    }
-                    const double top = fmax(fmax(lp[0], lp[1]), fmax(lp[2], lp[3]));  // finite: some candidate of every reference base is possible
-                    double e[4];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) e[c] = exp(lp[c] - top);
-                    const double sum = ((e[0] + e[1]) + e[2]) + e[3];
+                    double lp[4], e[4];
+                    const double sum = candidate_weights(f, evo + 4 * ref, a.log_error[m], lp, e);
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         if (c == ref) continue;
@@ -133,6 +161,149 @@ __global__ void __launch_bounds__(THREADS) k_snp_calls(SnpCallArgs a) {
     flush();
 }
 
+// ---- the calls themselves and a consensus: best base, quality and the list of calls (include/nprealign.h: npr_snp_variants_table) ----
+constexpr int TILE = SNP_VARIANT_TILE;
+constexpr int WAVES = THREADS / WAVE;
+static_assert(TILE == THREADS, "a thread owns one row of its workgroup's tile");
+// Eight workgroups a CU hide the table's latency; a workgroup takes tiles blockIdx.x, + gridDim.x, ... and loads the evolution rows once.
+constexpr int VARIANT_GRID = 2048;
+
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int64_t uniform(int64_t v) {
+    const unsigned int lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned int>(v));
+    const unsigned int hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned int>(static_cast<unsigned long long>(v) >> 32));
+    return static_cast<int64_t>(static_cast<unsigned long long>(hi) << 32 | lo);
+}
+
+template <int SRC>
+__global__ void __launch_bounds__(THREADS) k_snp_variants_count(SnpCallArgs a) {
+    __shared__ double evo[16];
+    __shared__ unsigned int wave_calls[WAVES];
+    const int tid = threadIdx.x, wave = uniform(tid >> 6);
+    if (tid < 16) evo[tid] = a.log_evolution[tid];
+    __syncthreads();
+    const int64_t tiles = snp_variant_tiles(a.rows);
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t r = tile * TILE + tid;
+        unsigned int mask = 0u;
+        if (r < a.rows) {
+            const int ref = a.ref_code[r];
+            int best = 4, qual = 0;
+            double f[4];
+            if (row_frequencies<SRC>(a, r, ref, f) == ROW_CALLABLE) {
+                double lp[4], e[4];
+                const double sum = candidate_weights(f, evo + 4 * ref, a.log_error[0], lp, e);
+                const double top = fmax(fmax(lp[0], lp[1]), fmax(lp[2], lp[3]));
+                // the candidate of largest lp; among equals the reference base, else the lowest code
+                bool ref_on_top = false;
+#pragma unroll
+                for (int c = 3; c >= 0; --c) {
+                    if (lp[c] == top) best = c;
+                    ref_on_top = ref_on_top || (c == ref && lp[c] == top);
+                }
+                if (ref_on_top) best = ref;
+                double others = 0.0;  // the three other e in ascending code (0.0 + x is x)
+                int j = 0;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (c != best) others += e[c];
+                    if (c != ref) {
+                        if (e[c] / sum >= a.threshold) mask |= 1u << j;
+                        ++j;
+                    }
+                }
+                const double q = others / sum;
+                qual = q == 0.0 ? 93 : static_cast<int>(fmin(floor(-10.0 * log10(q)), 93.0));  // (q <= 3/4: never negative)
+            }
+            a.best[r] = static_cast<uint8_t>(best), a.qual[r] = static_cast<uint8_t>(qual), a.mask[r] = static_cast<uint8_t>(mask);
+        }
+        const unsigned int in_wave = wave_sum(__popc(mask));
+        if ((tid & (WAVE - 1)) == 0) wave_calls[wave] = in_wave;
+        __syncthreads();
+        if (tid == 0) a.tile_calls[tile] = (wave_calls[0] + wave_calls[1]) + (wave_calls[2] + wave_calls[3]);
+        __syncthreads();
+    }
+}
+static_assert(WAVES == 4, "k_snp_variants_count adds four wavefront counts");
+
+// tile_off[t] = the calls of the tiles before t, tile_off[tiles] = all of them: one workgroup, THREADS tiles a trip.  4.6 Mb of reference are
+// 18 k tiles, 71 trips.
+__global__ void __launch_bounds__(THREADS) k_snp_variants_scan(const uint32_t *__restrict__ tile_calls, int64_t tiles, int64_t *__restrict__ tile_off) {
+    __shared__ int64_t wave_total[WAVES];
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = uniform(tid >> 6);
+    int64_t carry = 0;
+    for (int64_t t0 = 0; t0 < tiles; t0 += THREADS) {
+        const int64_t t = t0 + tid;
+        const int64_t v = t < tiles ? static_cast<int64_t>(tile_calls[t]) : 0;
+        int64_t upto = v;  // inclusive, within the wavefront
+#pragma unroll
+        for (int o = 1; o < WAVE; o <<= 1) {
+            const int64_t u = __shfl_up(upto, o, WAVE);
+            if (lane >= o) upto += u;
+        }
+        if (lane == WAVE - 1) wave_total[wave] = upto;
+        __syncthreads();
+        int64_t before = carry, all = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            const int64_t n = wave_total[w];
+            if (w < wave) before += n;
+            all += n;
+        }
+        if (t < tiles) tile_off[t] = before + (upto - v);
+        carry += all;
+        __syncthreads();
+    }
+    if (tid == 0) tile_off[tiles] = carry;
+}
+
+template <int SRC>
+__global__ void __launch_bounds__(THREADS) k_snp_variants_emit(SnpCallArgs a) {
+    __shared__ double evo[16];
+    __shared__ unsigned int wave_calls[WAVES];
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = uniform(tid >> 6);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (tid < 16) evo[tid] = a.log_evolution[tid];
+    __syncthreads();
+    const int64_t tiles = snp_variant_tiles(a.rows);
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t first = uniform(a.tile_off[tile]), end = uniform(a.tile_off[tile + 1]);
+        if (first == end) continue;  // (the whole workgroup: no barrier is skipped by some)
+        const int64_t r = tile * TILE + tid;
+        const unsigned int mask = r < a.rows ? a.mask[r] : 0u;
+        // calls of the rows before this one: in the wavefront by ballots, then the wavefronts before
+        unsigned int before = 0u, in_wave = 0u;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const unsigned long long has = __ballot((mask >> j) & 1u);
+            before += __popcll(has & below), in_wave += __popcll(has);
+        }
+        if (lane == 0) wave_calls[wave] = in_wave;
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < WAVES - 1; ++w)
+            if (w < wave) before += wave_calls[w];
+        if (mask) {
+            const int ref = a.ref_code[r];
+            double f[4], lp[4], e[4];
+            (void)row_frequencies<SRC>(a, r, ref, f);  // callable: the count kernel set a mask bit
+            const double sum = candidate_weights(f, evo + 4 * ref, a.log_error[0], lp, e);
+            int64_t at = first + before;
+            int j = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (c == ref) continue;
+                if ((mask >> j) & 1u) {
+                    if (at < a.n_calls) a.call_row[at] = r, a.call_alt[at] = static_cast<uint8_t>(c), a.call_p[at] = e[c] / sum;
+                    ++at;
+                }
+                ++j;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 int launch_snp_calls(const SnpCallArgs &a, void *stream) {
@@ -147,6 +318,44 @@ int launch_snp_calls(const SnpCallArgs &a, void *stream) {
         hipLaunchKernelGGL(k_snp_calls<SNP_SRC_PILEUP>, dim3(grid), dim3(THREADS), 0, s, a);
     else if (a.source == SNP_SRC_DOUBLE)
         hipLaunchKernelGGL(k_snp_calls<SNP_SRC_DOUBLE>, dim3(grid), dim3(THREADS), 0, s, a);
+    else
+        return static_cast<int>(hipErrorInvalidValue);
+    return static_cast<int>(hipGetLastError());
+}
+
+namespace {
+int variant_grid(int64_t rows) {
+    const int64_t tiles = snp_variant_tiles(rows);
+    return static_cast<int>(tiles < VARIANT_GRID ? tiles : VARIANT_GRID);
+}
+}  // namespace
+
+int launch_snp_variants_count(const SnpCallArgs &a, void *stream) {
+    if (a.rows <= 0) return static_cast<int>(hipErrorInvalidValue);
+    const int grid = variant_grid(a.rows);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (a.source == SNP_SRC_FIXED)
+        hipLaunchKernelGGL(k_snp_variants_count<SNP_SRC_FIXED>, dim3(grid), dim3(THREADS), 0, s, a);
+    else if (a.source == SNP_SRC_PILEUP)
+        hipLaunchKernelGGL(k_snp_variants_count<SNP_SRC_PILEUP>, dim3(grid), dim3(THREADS), 0, s, a);
+    else if (a.source == SNP_SRC_DOUBLE)
+        hipLaunchKernelGGL(k_snp_variants_count<SNP_SRC_DOUBLE>, dim3(grid), dim3(THREADS), 0, s, a);
+    else
+        return static_cast<int>(hipErrorInvalidValue);
+    hipLaunchKernelGGL(k_snp_variants_scan, dim3(1), dim3(THREADS), 0, s, a.tile_calls, snp_variant_tiles(a.rows), a.tile_off);
+    return static_cast<int>(hipGetLastError());
+}
+
+int launch_snp_variants_emit(const SnpCallArgs &a, void *stream) {
+    if (a.rows <= 0 || a.n_calls <= 0) return static_cast<int>(hipErrorInvalidValue);
+    const int grid = variant_grid(a.rows);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (a.source == SNP_SRC_FIXED)
+        hipLaunchKernelGGL(k_snp_variants_emit<SNP_SRC_FIXED>, dim3(grid), dim3(THREADS), 0, s, a);
+    else if (a.source == SNP_SRC_PILEUP)
+        hipLaunchKernelGGL(k_snp_variants_emit<SNP_SRC_PILEUP>, dim3(grid), dim3(THREADS), 0, s, a);
+    else if (a.source == SNP_SRC_DOUBLE)
+        hipLaunchKernelGGL(k_snp_variants_emit<SNP_SRC_DOUBLE>, dim3(grid), dim3(THREADS), 0, s, a);
     else
         return static_cast<int>(hipErrorInvalidValue);
     return static_cast<int>(hipGetLastError());

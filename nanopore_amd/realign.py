@@ -91,6 +91,33 @@ def _snp_calls(fn, where, ctx, head, rows, ref_code, true_code, evolution, error
     return [(np.array(o.true_pos, dtype=np.int64), np.array(o.false_pos, dtype=np.int64), int(o.not_called), int(o.rows_called)) for o in out[:n_models]]
 
 
+def _snp_variants(fn, where, ctx, head, rows, ref_code, evolution, error, threshold):
+    """The call the three SNP-variant entry points share (include/nprealign.h: npr_snp_variants_table): fn(*head, ref_code, evolution16,
+    error16, threshold, best, qual, call_row, call_alt, call_p, cap, n_calls) with the 4 x 4 `error` [candidate, observed] and `evolution`
+    [reference, candidate], both as probabilities.  -> (best uint8[rows]: base code, 4 = no call possible; qual uint8[rows]: 0..93;
+    call_row int64[n], call_alt uint8[n], call_p float64[n]: the calls in ascending (row, candidate) order).  Room for one call in
+    sixteen rows is offered first; when there are more the library says how many and the call is made once more with that room."""
+    ref_code = _arr(ref_code, np.uint8)
+    if ref_code is None or ref_code.shape != (rows,):
+        raise ValueError("one reference base code per table row")
+    evolution, error = _arr(evolution, np.float64), _arr(error, np.float64)
+    if evolution.size != 16 or error.size != 16:
+        raise ValueError("evolution and error are one 4 x 4 matrix each")
+    best, qual = np.empty(rows, dtype=np.uint8), np.empty(rows, dtype=np.uint8)
+    n = C.c_int64(0)
+
+    def call(cap):
+        row, alt, p = np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.uint8), np.empty(cap, dtype=np.float64)
+        rc = fn(*head, ptr(ref_code), ptr(evolution), ptr(error), float(threshold), ptr(best), ptr(qual), ptr(row), ptr(alt), ptr(p), cap, C.byref(n))
+        return rc, row, alt, p
+
+    rc, row, alt, p = call(rows // 16 + 64)
+    if rc == ERR_CAPACITY:
+        rc, row, alt, p = call(n.value)
+    count = int(check(rc, where, ctx))
+    return best, qual, row[:count], alt[:count], p[:count]
+
+
 class _Handle(object):
     """An object of the library that belongs to a Context (Batch, Pileup, SeedIndex, SeedMap): destroyed once, by close(), by the context's
     close() or when it is collected, whichever comes first."""
@@ -251,6 +278,15 @@ class Batch(_Handle):
         return _snp_calls(self._L.npr_batch_snp_calls, "npr_batch_snp_calls", self.ctx, (self._h, ptr(u), len(ref_lengths), ptr(ref_lengths)),
                           int(ref_lengths.sum()), ref_code, true_code, evolution, errors)
 
+    def snp_variants(self, ref_lengths, ref_code, evolution, error, threshold, use=None):
+        """The SNP calls themselves and a best base with its quality per position, from the posterior-weighted base counts of the (selected)
+        reads where k_base_expectations leaves them (include/nprealign.h: npr_batch_snp_variants; _snp_variants for what comes back)."""
+        ref_lengths, u = _arr(ref_lengths, np.int64), _arr(use, np.uint8)
+        if u is not None and len(u) != self.n_reads:
+            raise ValueError("use must have one entry per read of the batch")
+        return _snp_variants(self._L.npr_batch_snp_variants, "npr_batch_snp_variants", self.ctx, (self._h, ptr(u), len(ref_lengths), ptr(ref_lengths)),
+                             int(ref_lengths.sum()), ref_code, evolution, error, threshold)
+
     def plan_check(self):
         """Tasks whose device-made band rows / schedules / stripe tables differ from the host planner's (test aid;
         include/nprealign.h: npr_batch_plan_check)."""
@@ -345,6 +381,11 @@ class Pileup(_Handle):
         """SNP calls from the aligned-base frequencies of the table so far (words 0-3; a row is seen when words 0-4 are not all zero), made
         on the device (include/nprealign.h: npr_pileup_snp_calls; _snp_calls for the matrices and what comes back)."""
         return _snp_calls(self._L.npr_pileup_snp_calls, "npr_pileup_snp_calls", self.ctx, (self._h,), self.rows, ref_code, true_code, evolution, errors)
+
+    def snp_variants(self, ref_code, evolution, error, threshold):
+        """The SNP calls themselves and a best base with its quality per position, from the aligned-base frequencies of the table so far
+        (include/nprealign.h: npr_pileup_snp_variants; _snp_variants for what comes back)."""
+        return _snp_variants(self._L.npr_pileup_snp_variants, "npr_pileup_snp_variants", self.ctx, (self._h,), self.rows, ref_code, evolution, error, threshold)
 
     def depth(self):
         """(depth int32 [rows], covered bool [rows]): what `samtools depth` prints (M columns) and which positions it prints a line for
@@ -588,6 +629,15 @@ class Context(object):
             raise ValueError("one seen flag per table row")
         return _snp_calls(self._L.npr_snp_calls_table, "npr_snp_calls_table", self, (self._h, len(weights), ptr(weights), ptr(seen)), len(weights),
                           ref_code, true_code, evolution, errors)
+
+    def snp_variants_table(self, weights, seen, ref_code, evolution, error, threshold):
+        """The SNP calls themselves and a best base with its quality per row of any table of four non-negative base weights, uploaded and
+        called on the device (include/nprealign.h: npr_snp_variants_table; _snp_variants for what comes back)."""
+        weights, seen = _arr(weights, np.float64, 4), _arr(seen, np.uint8)
+        if seen.shape != (len(weights),):
+            raise ValueError("one seen flag per table row")
+        return _snp_variants(self._L.npr_snp_variants_table, "npr_snp_variants_table", self, (self._h, len(weights), ptr(weights), ptr(seen)),
+                             len(weights), ref_code, evolution, error, threshold)
 
     def seed_index(self, refs, k=16):
         """The exact-match seed index of the ASCII sequences `refs` (SeedIndex; include/nprealign.h: npr_seed_index_create)."""
