@@ -335,6 +335,58 @@ int32_t npr_align_indel_kmers(npr_ctx *ctx, int32_t k, int64_t n_reads, int64_t 
  * failed add nothing. */
 int32_t npr_batch_indel_kmers(npr_batch *b, int32_t k, int64_t *read_counts, int64_t *ref_counts /* [4^k + 1] each */);
 
+/* ---- read-quality tables on the device (the reference's FastQC analysis, nanopore/analyses/fastqc.py) ----
+ * The reference shells out to the Java FastQC; here the statistics are defined in exact integer terms and counted in one
+ * pass over the reads' base and quality bytes.  Read i has the bases text[seq_begin[i] .. seq_end[i]) and the quality
+ * bytes text[qual_begin[i] .. qual_end[i]).
+ *
+ * Spans and groups.  Spans are positions inside a larger text, as npr_kmer_counts_groups takes them (columns 2-3 of
+ * npr_fastq_index and the pairs of npr_fastq_qual_index fit directly); they may come in any order.  group[i] in
+ * [0, n_groups) picks the tables, -1 leaves the read out.  1 <= n_groups <= NPR_RQ_MAX_GROUPS (8).
+ *
+ * Invalid input.  NPR_ERR_INVALID for any of: a group outside the range, a span that ends before it begins,
+ * qual_end - qual_begin != seq_end - seq_begin for a read whose group is not -1, a bad n_groups.  Nothing is counted and
+ * no table is touched then; this is checked on the host before any launch.
+ *
+ * Legal input that adds nothing.  n_reads == 0 is legal: the tables are written as for empty groups.  Empty reads are legal.
+ *
+ * Position bin, NPR_RQ_POS_BINS = 336.  bin(p) = p for p < 16; otherwise, with e = floor(log2 p),
+ * bin(p) = 16 * (e - 3) + ((p >> (e - 4)) & 15): sixteen bins per octave, width 1 below 32, width 2 below 64, and so on.
+ * Any p >= 2^24 goes to bin 335.  The inverse: bin b >= 16 starts at (16 + b % 16) << (b / 16 - 1) and is
+ * 1 << (b / 16 - 1) wide.  The device computes bin(p) from a count-leading-zeros, without table or search.
+ *
+ * Quality column, NPR_RQ_QUAL_COLS = 95.  A byte c with 33 <= c <= 126 goes to column c - 33, any other byte to column 94.
+ *
+ * Base column.  npr_encode_bases' codes: A C G T -> 0..3 in either letter case, anything else -> 4.
+ *
+ * pos_qual and pos_base.  Every position p of every counted read adds one at [bin(p)][column].
+ *
+ * len_hist.  One count per read at bin(length); an empty read lands in bin 0.
+ *
+ * meanq_hist.  One count per non-empty read, in column floor(sum of (c - 33) / length) when every quality byte is in
+ * 33..126, else in column 94.
+ *
+ * gc_hist.  One count per non-empty read.  With n the read's A + C + G + T count and gc its G + C count, the column is
+ * (200 * gc + n) / (2 * n), integer division -- the percentage rounded half up, 0..100 -- and 101 when n == 0.
+ *
+ * totals, NPR_RQ_TOTALS = 8.  reads, bases, shortest length, longest length, smallest quality byte, largest quality byte,
+ * empty reads, reads with a quality byte outside 33..126.  Shortest and longest length are -1 when the group has no read,
+ * smallest and largest quality byte are -1 when the group has no base.
+ *
+ * All counts are exact and the same from run to run; the tables are overwritten. */
+#define NPR_RQ_POS_BINS 336
+#define NPR_RQ_QUAL_COLS 95
+#define NPR_RQ_GC_COLS 102
+#define NPR_RQ_TOTALS 8
+#define NPR_RQ_MAX_GROUPS 8
+#define NPR_RQ_TILE 2048 /* positions of one read a workgroup takes per step */
+int32_t npr_read_quality(npr_ctx *ctx, int64_t n_reads, const uint8_t *text, const int64_t *seq_begin, const int64_t *seq_end,
+                         const int64_t *qual_begin, const int64_t *qual_end, const int32_t *group, int32_t n_groups,
+                         int64_t *pos_qual /* [n_groups][NPR_RQ_POS_BINS][NPR_RQ_QUAL_COLS] */,
+                         int64_t *pos_base /* [n_groups][NPR_RQ_POS_BINS][5] */, int64_t *len_hist /* [n_groups][NPR_RQ_POS_BINS] */,
+                         int64_t *meanq_hist /* [n_groups][NPR_RQ_QUAL_COLS] */, int64_t *gc_hist /* [n_groups][102] */,
+                         int64_t *totals /* [n_groups][NPR_RQ_TOTALS] */);
+
 /* ---- the device pileup: per-position depth and base counts of a set of alignments ----
  * What the reference gets from samtools after writing the realigned SAM, converting it to BAM, sorting and indexing it:
  * `samtools depth` (nanopore/metaAnalyses/coverageDepth.py:49-65) and `samtools mpileup` (analyses/consensus.py).  A table of
@@ -755,6 +807,11 @@ int32_t npr_fasta_pack(const char *text, const int64_t *rec, int64_t n, const in
  * word after '@') and [start, end) of the sequence line.  rec == NULL: only count.  NPR_ERR_INVALID for a record that does
  * not start with '@' or whose third line does not start with '+'. */
 int64_t npr_fastq_index(const char *text, int64_t len, int64_t *rec, int64_t cap);
+/* ... and where the quality lines are: for the n records npr_fastq_index found (rec as it filled it), qual[2 * k ..] =
+ * [start, end) of record k's fourth line, by the same line rules (the line ends at '\n' or at the end of the text, '\r' before
+ * it left out).  A last record whose fourth line is missing gets an empty span at the end of the text.  NPR_ERR_INVALID when a
+ * record's sequence span lies outside the text or its third line does not start with '+'. */
+int32_t npr_fastq_qual_index(const char *text, int64_t len, const int64_t *rec, int64_t n, int64_t *qual /* [2 n] */);
 /* Which of n names a SAM file maps (abstractUnmappedAnalysis.py:39-43: samIterator, then `not record.is_unmapped`): name i is
  * names_text[name_span[2 * i] .. name_span[2 * i + 1]); span / fields are the m alignment lines as npr_sam_index and
  * npr_sam_parse give them.  mark[i] is set to 1 when some line has QNAME bytes equal to name i (case-sensitive), column 15

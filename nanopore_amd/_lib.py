@@ -49,6 +49,8 @@ KERNEL_GENERIC, ARITH_CELL, PAIR_NEVER, PAIR_LONG, PAIR_ALL = 1, 1, 1, 2, 3
 STATS_WORDS = 40  # NPR_STATS_WORDS
 KMER_MAX_K = 6    # the k-mer tables: 4^k + 1 bins, the last one for k-mers with a base outside ACGT
 KMER_MAX_GROUPS = 64  # npr_kmer_counts_groups: tables of one call
+RQ_POS_BINS, RQ_QUAL_COLS, RQ_GC_COLS, RQ_TOTALS = 336, 95, 102, 8  # NPR_RQ_*: the read-quality tables (npr_read_quality)
+RQ_MAX_GROUPS, RQ_TILE = 8, 2048  # NPR_RQ_MAX_GROUPS; NPR_RQ_TILE: positions of one read a workgroup of its kernel takes per step
 SAM_COLS = 16     # NPR_SAM_COLS
 SEED_MIN_K, SEED_MAX_K = 8, 32  # npr_seed_index_create: the k of a seed index
 SEED_MAP_LDS_ROWS = 4096  # NPR_SEED_MAP_LDS_ROWS: a read of at most so many rows is sorted in LDS by npr_seed_map_create, a longer one in global memory
@@ -154,6 +156,7 @@ SIGNATURES = {
     "npr_kmer_counts_groups": (i32, [vp, i32, i64, vp, vp, vp, vp, i32, vp]),
     "npr_align_indel_kmers": (i32, [vp, i32, i64, i64] + [vp] * 10),
     "npr_batch_indel_kmers": (i32, [vp, i32, vp, vp]),
+    "npr_read_quality": (i32, [vp, i64] + [vp] * 6 + [i32] + [vp] * 6),
     "npr_pileup_create": (i32, [vp, i64, vp, _out]),
     "npr_pileup_destroy": (None, [vp]),
     "npr_pileup_add_batch": (i32, [vp, vp, vp]),
@@ -207,6 +210,7 @@ SIGNATURES = {
     "npr_fasta_index": (i64, [vp, i64, vp, vp, i64]),
     "npr_fasta_pack": (i32, [vp, vp, i64, vp, vp]),
     "npr_fastq_index": (i64, [vp, i64, vp, i64]),
+    "npr_fastq_qual_index": (i32, [vp, i64, vp, i64, vp]),
     "npr_names_mark": (i64, [vp, vp, i64, vp, vp, vp, i64, vp]),
     "npr_batch_create_spans": (i32, [vp, _params, i64, i64] + [vp] * 10 + [_out]),
 }

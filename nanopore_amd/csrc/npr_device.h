@@ -281,6 +281,27 @@ struct IndelKmerArgs {  // k_indel_kmers: `s` as for k_align_stats, but every re
     int32_t *bad;            // set to 1 when a record's cigar runs past its piece (the record adds nothing)
 };
 int launch_indel_kmers(const IndelKmerArgs &a, void *stream);
+// read-quality tables (npr_readqual.hip; the definitions: include/nprealign.h, npr_read_quality)
+constexpr int RQ_POS_BINS = 336, RQ_QUAL_COLS = 95, RQ_BASE_COLS = 5, RQ_GC_COLS = 102, RQ_TOTALS = 8, RQ_MAX_GROUPS = 8;
+constexpr int RQ_TILE = 2048;     // positions of one read per work item
+constexpr int RQ_ALIGN = 16;      // a staged read starts on a multiple of it and RQ_ALIGN bytes past the last read are readable: a lane loads 8 bytes at a time
+constexpr int RQ_ROW = 6;         // per-read scratch row: quality sum, G + C, A + C + G + T, bad quality bytes, 255 - smallest quality byte, largest quality byte
+constexpr int RQ_TILE_CLASSES = (1 << 24) / RQ_TILE + 1;  // tiles from position 2^24 on all count into bin 335: one class
+constexpr unsigned long long RQ_LEN_TOP = 1ull << 62;     // the shortest length is kept as the largest RQ_LEN_TOP - length
+constexpr size_t RQ_GROUP_WORDS = static_cast<size_t>(RQ_POS_BINS) * (RQ_QUAL_COLS + RQ_BASE_COLS + 1) + RQ_QUAL_COLS + RQ_GC_COLS + RQ_TOTALS;
+struct ReadQualArgs {
+    const uint8_t *seq, *qual;    // the counted reads' bytes: read r's at [start[r], start[r] + len[r])
+    const int64_t *start, *len;   // [n]
+    const int32_t *group;         // [n], 0 .. n_groups - 1
+    const unsigned long long *items;  // [n_items] (read << 32 | tile), ordered by (group, min(tile, RQ_TILE_CLASSES - 1))
+    int64_t n, n_items;
+    int32_t n_groups;
+    unsigned long long *rows;     // [n][RQ_ROW], zeroed
+    // zeroed, added to; totals as the device keeps them: reads, bases, largest RQ_LEN_TOP - length, largest length, largest 255 - quality byte,
+    // largest quality byte, empty reads, reads with a bad quality byte
+    unsigned long long *pos_qual, *pos_base, *len_hist, *meanq_hist, *gc_hist, *totals;
+};
+int launch_read_quality(const ReadQualArgs &a, void *stream);
 // the device pileup (npr_pileup.hip): NPR_PILEUP_WORDS int32 per reference position, a difference array for the deletion columns
 struct PileupRec {
     int64_t row0;    // table row of the record's first reference position

@@ -369,6 +369,25 @@ int64_t npr_fastq_index(const char *text, int64_t len, int64_t *rec, int64_t cap
     return n;
 }
 
+int32_t npr_fastq_qual_index(const char *text, int64_t len, const int64_t *rec, int64_t n, int64_t *qual) {
+    if (len < 0 || n < 0 || (len && !text) || (n && (!rec || !qual))) return NPR_ERR_INVALID;
+    const char *const end = text + len;
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t sa = rec[4 * k + 2], sb = rec[4 * k + 3];
+        if (sa < 0 || sb < sa || sb > len) return NPR_ERR_INVALID;
+        auto next_line = [&](const char *p) {  // the start of the line after the one p lies in
+            const char *nl = find(p, end, '\n');
+            return nl < end ? nl + 1 : end;
+        };
+        const char *plus = next_line(text + sb);
+        if (plus >= end || *plus != '+') return NPR_ERR_INVALID;
+        const char *a = next_line(plus), *b = find(a, end, '\n');
+        while (b > a && b[-1] == '\r') --b;
+        qual[2 * k] = a - text, qual[2 * k + 1] = b - text;
+    }
+    return NPR_OK;
+}
+
 int64_t npr_names_mark(const char *names_text, const int64_t *name_span, int64_t n, const char *sam_text, const int64_t *span, const int64_t *fields,
                        int64_t m, uint8_t *mark) {
     if (n < 0 || m < 0 || (n && (!names_text || !name_span || !mark)) || (m && (!sam_text || !span || !fields))) return NPR_ERR_INVALID;

@@ -195,9 +195,19 @@ class FastqTable(object):
         self.name_span = np.ascontiguousarray(rec[:, 0:2])
         self.seq_span = np.ascontiguousarray(rec[:, 2:4])
         self.lengths = self.seq_span[:, 1] - self.seq_span[:, 0]
+        self._rec, self._qual_span = rec, None
 
     def __len__(self):
         return len(self.lengths)
+
+    @property
+    def qual_span(self):
+        """int64 [n, 2]: [start, end) of each record's quality line inside `text` (npr_fastq_qual_index), made when first asked for."""
+        if self._qual_span is None:
+            qual = np.zeros((len(self), 2), dtype=np.int64)
+            check(_lib.load().npr_fastq_qual_index(ptr(self.text), len(self.text), ptr(self._rec), len(self), ptr(qual)), "npr_fastq_qual_index")
+            self._qual_span = qual
+        return self._qual_span
 
     def name(self, i):
         return bytes(self.text[self.name_span[i, 0]:self.name_span[i, 1]]).decode("ascii", errors="replace")

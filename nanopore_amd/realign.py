@@ -45,6 +45,28 @@ def _ragged(items):
     return _csr(items, pad=True)
 
 
+class ReadQuality(object):
+    """The six int64 tables of npr_read_quality (include/nprealign.h defines them), first axis = group: pos_qual [G, 336, 95],
+    pos_base [G, 336, 5], len_hist [G, 336], meanq_hist [G, 95], gc_hist [G, 102], totals [G, 8]."""
+    FIELDS = ("pos_qual", "pos_base", "len_hist", "meanq_hist", "gc_hist", "totals")
+    TILE = _lib.RQ_TILE  # positions of one read a workgroup of the kernel takes per step
+
+    def __init__(self, pos_qual, pos_base, len_hist, meanq_hist, gc_hist, totals):
+        self.pos_qual, self.pos_base, self.len_hist, self.meanq_hist, self.gc_hist, self.totals = pos_qual, pos_base, len_hist, meanq_hist, gc_hist, totals
+
+    @classmethod
+    def zeros(cls, n_groups):
+        B, Q = _lib.RQ_POS_BINS, _lib.RQ_QUAL_COLS
+        return cls(*[np.zeros((n_groups,) + shape, dtype=np.int64) for shape in ((B, Q), (B, 5), (B,), (Q,), (_lib.RQ_GC_COLS,), (_lib.RQ_TOTALS,))])
+
+    def arrays(self):
+        return [getattr(self, f) for f in self.FIELDS]
+
+    def group(self, g):
+        """The tables of one group (no group axis), as fastqc.writeFastqcData takes them."""
+        return ReadQuality(*[a[g] for a in self.arrays()])
+
+
 def _csr_ops(guides):
     lens = np.fromiter((len(g) for g in guides), dtype=np.int64, count=len(guides))
     off = np.zeros(len(guides) + 1, dtype=np.int64)
@@ -606,6 +628,22 @@ class Context(object):
         out = np.zeros((n_groups, 4 ** k + 1) if ok else (1, 1), dtype=np.int64)
         check(self._L.npr_kmer_counts_groups(self._h, int(k), len(begin), ptr(text), ptr(begin), ptr(end), ptr(group), int(n_groups), ptr(out)),
               "npr_kmer_counts_groups", self)
+        return out
+
+    def read_quality(self, text, seq_span, qual_span, group, n_groups):
+        """The read-quality tables of the FastQC analysis, counted on the device in one pass (include/nprealign.h: npr_read_quality, which
+        defines every table): read i has the bases text[seq_span[i, 0]:seq_span[i, 1]] and the quality bytes
+        text[qual_span[i, 0]:qual_span[i, 1]] -- FastqTable.text / .seq_span / .qual_span as they are --, group[i] in 0 .. n_groups - 1
+        picks its tables and -1 leaves it out.  -> ReadQuality."""
+        text, group = _arr(text, np.uint8), _arr(group, np.int32)
+        seq_span, qual_span = _arr(seq_span, np.int64).reshape(-1, 2), _arr(qual_span, np.int64).reshape(-1, 2)
+        n = len(group)
+        if not (len(seq_span) == len(qual_span) == n) or (n and (min(int(seq_span.min()), int(qual_span.min())) < 0 or
+                                                                 max(int(seq_span.max()), int(qual_span.max())) > len(text))):
+            raise NprError(_lib.ERR_INVALID, "npr_read_quality", "spans and groups differ in number, or a span lies outside the text")
+        out = ReadQuality.zeros(n_groups if 1 <= n_groups <= _lib.RQ_MAX_GROUPS else 1)
+        cols = [np.ascontiguousarray(a) for a in (seq_span[:, 0], seq_span[:, 1], qual_span[:, 0], qual_span[:, 1])]
+        check(self._L.npr_read_quality(self._h, n, ptr(text), *map(ptr, cols), ptr(group), int(n_groups), *map(ptr, out.arrays())), "npr_read_quality", self)
         return out
 
     def align_indel_kmers(self, refs, reads, cigars, k=5, ref_index=None, start=None):
