@@ -1,10 +1,12 @@
 // npr_api_internal.h -- what the translation units of the C ABI share (round 6: npr_api.cpp was one file of 3 000 lines):
 // the context and batch structures, device buffers, the kernel class table, error plumbing.  Internal to libnprealign; not installed.
 //   npr_api.cpp     context, options, models, the plan-inspection entry points, the small public helpers
-//   npr_stage.cpp   npr_batch_create*: plan points, packing, H2D, the device planner, kernel classes and launch geometry
+//   npr_stage.cpp   npr_batch_create*: plan points, packing, H2D, the device planner and its cross-check, kernel classes and launch geometry
 //   npr_run.cpp     npr_batch_run (launch policy, second pass of tasks without a range certificate), the E-step, the dense dumps
 //   npr_finish.cpp  npr_batch_finish and what reads its results: the device MEA stage and its pieced D2H, the rescore sums, the host stage, ops / pairs
-//   npr_aux.cpp     post-alignment statistics, k-mer tables, base expectations and SNP calls, the device pileup, the planner cross-check
+//   npr_stats_api.cpp  post-alignment statistics, k-mer and indel-k-mer tables (npr_stats.hip, npr_kmer.hip)
+//   npr_snp_api.cpp  base expectations, SNP calls and variants (npr_stats.hip, npr_snpcall.hip)
+//   npr_pileup_api.cpp  the device pileup (npr_pileup.hip)
 //   npr_text.cpp    cigar and SAM record text (the transport forms a job ships)
 //   npr_seed_api.cpp  exact-match seeding (npr_seed.hip): the index, the matches, their SAM records
 //   npr_seedchain_api.cpp  the chains of seed rows given on the host as guides (npr_seedchain.hip), their SAM records
@@ -21,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -28,6 +31,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "npr_device.h"
@@ -270,6 +274,88 @@ inline int32_t fail(npr_ctx *ctx, int32_t code, const char *what, hipError_t e =
         if (_e != hipSuccess) return fail((ctx), NPR_ERR_HIP, #expr, _e);   \
     } while (0)
 
+// ---- the analysis entry points (everything but the hot path, which keeps HIP_TRY): one guard at the ABI boundary, one vocabulary for device steps ----
+// what a failed step or a refused argument throws once ctx->last_error says why; guarded() turns it into the entry point's return value
+struct EntryFailure {
+    int32_t code;
+};
+
+// The device steps of one entry point, all on the context's stream.  A step that fails records "<entry>: <step>: <hip error>" through fail(), waits
+// for the stream -- a copy or kernel queued earlier may still use a DevBuf or host vector of the frames about to unwind -- and throws.
+struct Call {
+    npr_ctx *ctx;
+    const char *entry;
+    [[noreturn]] void failed(int32_t code, const char *step, hipError_t e) const {
+        char text[160];
+        std::snprintf(text, sizeof(text), "%s: %s", entry, step);
+        code = fail(ctx, code, text, e);
+        (void)hipStreamSynchronize(ctx->stream);
+        throw EntryFailure{code};
+    }
+    void check(hipError_t e, const char *step) const {
+        if (e != hipSuccess) failed(NPR_ERR_HIP, step, e);
+    }
+    // a refused argument: `text` as it is (none: last_error stays)
+    [[noreturn]] void refuse(int32_t code, const char *text = nullptr) const { throw EntryFailure{text ? fail(ctx, code, text) : code}; }
+    // a step of the hot-path units, which report through fail() themselves
+    void passed(int32_t rc) const {
+        if (rc == NPR_OK) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        throw EntryFailure{rc};
+    }
+    template <typename T>
+    void alloc(DevBuf<T> &b, size_t n) const {
+        const hipError_t e = b.alloc(n);
+        if (e != hipSuccess) failed(NPR_ERR_NOMEM, "hipMalloc", e);
+    }
+    template <typename T>
+    void alloc_cached(DevBuf<T> &b, size_t n) const {  // from the context's cache of released buffers
+        const hipError_t e = b.alloc_from(ctx, n);
+        if (e != hipSuccess) failed(NPR_ERR_NOMEM, "hipMalloc", e);
+    }
+    void copy_up(void *dst, const void *src, size_t bytes) const {
+        if (bytes) check(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream), "H2D");
+    }
+    template <typename T>
+    void upload(DevBuf<T> &b, const T *src, size_t n) const {
+        alloc(b, n);
+        copy_up(b.p, src, b.bytes());
+    }
+    template <typename T>
+    void upload(DevBuf<T> &b, const std::vector<T> &v) const { upload(b, v.data(), v.size()); }
+    void zero(void *p, size_t bytes) const {
+        if (bytes) check(hipMemsetAsync(p, 0, bytes, ctx->stream), "memset");
+    }
+    template <typename T>
+    void zero(DevBuf<T> &b) const { zero(b.p, b.bytes()); }
+    void fetch(void *dst, const void *src, size_t bytes) const {
+        if (bytes) check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream), "D2H");
+    }
+    void launched(int rc, const char *kernel) const {
+        if (rc != 0) failed(NPR_ERR_HIP, kernel, static_cast<hipError_t>(rc));
+    }
+    void sync() const { check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"); }
+};
+
+// An entry point's body behind the C ABI: guarded(ctx, "npr_entry", [&](const Call &dev) -> T { ... }), T the int32_t or int64_t it returns.  Sets the
+// device, runs the body; an EntryFailure becomes its code, any other exception NPR_ERR_NOMEM.  ctx may be null for host code (no device, no text).
+template <typename F>
+auto guarded(npr_ctx *ctx, const char *entry, F &&body) -> decltype(body(std::declval<const Call &>())) {
+    using T = decltype(body(std::declval<const Call &>()));
+    static_assert(std::is_same<T, int32_t>::value || std::is_same<T, int64_t>::value, "an entry point returns a status or a count");
+    const Call dev{ctx, entry};
+    try {
+        if (ctx) dev.check(hipSetDevice(ctx->device), "hipSetDevice");
+        return body(dev);
+    } catch (const EntryFailure &f) {
+        return f.code;
+    } catch (const std::exception &) {
+        char text[160];
+        std::snprintf(text, sizeof(text), "%s: out of host memory", entry);
+        return fail(ctx, NPR_ERR_NOMEM, text);
+    }
+}
+
 // NPR_TIMING=1 prints host-stage wall times to stderr (bring-up / DESIGN.md host-inclusive numbers)
 struct StageTimer {
     bool on;
@@ -377,7 +463,7 @@ struct npr_batch {
     bool text_ready = false, words_on_device = false;
 };
 
-// the device pileup (npr_aux.cpp, npr_pileup.hip): the table and the difference array of its deletion columns live on the device from
+// the device pileup (npr_pileup_api.cpp, npr_pileup.hip): the table and the difference array of its deletion columns live on the device from
 // npr_pileup_create to npr_pileup_destroy and are added to by every npr_pileup_add / npr_pileup_add_batch
 struct npr_pileup {
     npr_ctx *ctx = nullptr;
@@ -557,20 +643,31 @@ int32_t fetch_device_words(npr_batch *b);                  // npr_cigtext_api.cp
 // npr_seedchain_api.cpp: the chain kernels on rows and chain spans that lie on the device, wherever they came from (npr_seed_chains uploads
 // them, npr_seed_map_create made them there).  count: k_chain_dp, k_chain_trace<false>, k_chain_scan; `chains` and `n_ops` (the guides'
 // offsets) are final and `pairs` is on the host.  write: k_chain_trace<true> into `ops`; queued on the context's stream, not waited for.
-// `what`: the caller's text for a failed hipMalloc.
 struct SeedChainRun {
     DevBuf<int32_t> node, back, run_end, chains, ops;
     DevBuf<int64_t> n_ops;
     SeedChainArgs a{};
     int64_t pairs = 0;
-    int32_t count(npr_ctx *ctx, const char *what, const int32_t *d_hits, int64_t rows, const SeedChainSpan *d_span, int64_t n_chains, int64_t max_gap,
-                  const int32_t *d_ref_len, const int32_t *d_read_len);
-    int32_t write(npr_ctx *ctx, const char *what);
+    void count(const Call &dev, const int32_t *d_hits, int64_t rows, const SeedChainSpan *d_span, int64_t n_chains, int64_t max_gap, const int32_t *d_ref_len,
+               const int32_t *d_read_len);
+    void write(const Call &dev);
 };
-// npr_seed_api.cpp: the steps npr_seed_matches and npr_seed_map_create share (`who`: the entry point, for the error text)
-int32_t seed_check_reads(npr_ctx *ctx, const char *who, int64_t n_reads, const uint8_t *text, const int64_t *begin, const int64_t *end, std::vector<int64_t> &off);
-int32_t seed_stage_reads(npr_ctx *ctx, const char *who, int32_t strands, int64_t n_reads, const uint8_t *text, const int64_t *begin, const int64_t *end,
-                         const std::vector<int64_t> &off, DevBuf<uint8_t> &fwd, DevBuf<uint8_t> &rev, DevBuf<int64_t> &d_off);
+// npr_seed_api.cpp: the steps npr_seed_matches and npr_seed_map_create share
+void seed_check_reads(const Call &dev, int64_t n_reads, const uint8_t *text, const int64_t *begin, const int64_t *end, std::vector<int64_t> &off);
+void seed_stage_reads(const Call &dev, int32_t strands, int64_t n_reads, const uint8_t *text, const int64_t *begin, const int64_t *end, const std::vector<int64_t> &off,
+                      DevBuf<uint8_t> &fwd, DevBuf<uint8_t> &rev, DevBuf<int64_t> &d_off);
 SeedMatchArgs seed_match_args(const npr_seed_index *ix, int64_t min_len, const std::vector<int64_t> &off, const int64_t *d_off, uint32_t *d_count, const int64_t *d_hit_off);
-int32_t seed_match_pass(npr_ctx *ctx, SeedMatchArgs &a, int32_t strands, const uint8_t *fwd, const uint8_t *rev, bool emit);
+void seed_match_pass(const Call &dev, SeedMatchArgs &a, int32_t strands, const uint8_t *fwd, const uint8_t *rev, bool emit);
+// npr_stats_api.cpp: a set of reads' cigars packed on the device (one word per operation, off[n + 1]), with the upload it may own ...
+struct DeviceCigars {
+    const uint32_t *ops = nullptr;
+    const int64_t *off = nullptr;
+    DevBuf<uint32_t> own_ops;
+    DevBuf<int64_t> own_off;
+};
+// ... made from the host form (off.back() words at `ops`), queued on the context's stream ...
+void cigars_from_host(const Call &dev, const uint32_t *ops, const std::vector<int64_t> &off, DeviceCigars &c);
+// ... and the ones npr_batch_finish produced handed to `run`: where the device MEA stage left them (in the arena, whose lock is held until `run`
+// returns: it waits for its kernels), else uploaded from the batch's packed host form
+void with_batch_cigars(const Call &dev, npr_batch *b, const std::function<void(const DeviceCigars &)> &run);
 }  // namespace npr_impl

@@ -14,39 +14,37 @@ struct TextBufs {
     char *text_p = nullptr;
 };
 
-// Lengths, offsets and (want_text) the text of n lists whose words are on the device.  str_off[n + 1] on the host when the call returns
-// NPR_OK; the text stays on the device at bufs.text_p -- in `lend` (lend_bytes) when it fits there.  NPR_ERR_INVALID: an op outside M I D,
-// NPR_ERR_CAPACITY: want_text and the total is above cap (the offsets are valid then); nothing is written in either case.
-int32_t run_cigtext(npr_ctx *ctx, int64_t n, const int64_t *d_word_off, const int64_t *d_n_ops, const uint32_t *d_words, bool want_text,
-                    int64_t cap, char *lend, size_t lend_bytes, TextBufs &bufs, int64_t *str_off) {
-    hipError_t e;
-    if ((e = bufs.off.alloc_from(ctx, n + 1)) != hipSuccess || (e = bufs.tile.alloc_from(ctx, cigtext_scan_tiles(n + 1))) != hipSuccess ||
-        (e = bufs.bad.alloc_from(ctx, 1)) != hipSuccess)
-        return fail(ctx, NPR_ERR_NOMEM, "cigar text: hipMalloc", e);
-    HIP_TRY(ctx, hipMemsetAsync(bufs.bad.p, 0, sizeof(int32_t), ctx->stream));
+// Lengths, offsets and (want_text) the text of n lists whose words are on the device.  str_off[n + 1] is on the host when the call returns;
+// the text stays on the device at bufs.text_p -- in `lend` (lend_bytes) when it fits there.  An op outside M I D is refused (NPR_ERR_INVALID);
+// false: want_text and the total is above cap (the offsets are valid then).  Nothing is written in either case.
+bool run_cigtext(const Call &dev, int64_t n, const int64_t *d_word_off, const int64_t *d_n_ops, const uint32_t *d_words, bool want_text, int64_t cap, char *lend,
+                 size_t lend_bytes, TextBufs &bufs, int64_t *str_off) {
+    dev.alloc_cached(bufs.off, n + 1);
+    dev.alloc_cached(bufs.tile, cigtext_scan_tiles(n + 1));
+    dev.alloc_cached(bufs.bad, 1);
+    dev.zero(bufs.bad.p, sizeof(int32_t));
     CigTextArgs a{n, d_word_off, d_n_ops, d_words, bufs.off.p, bufs.tile.p, bufs.bad.p, nullptr};
-    int rc = launch_cigtext_offsets(a, ctx->stream);
-    if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_cigtext_len / scan launch", static_cast<hipError_t>(rc));
+    dev.launched(launch_cigtext_offsets(a, dev.ctx->stream), "k_cigtext_len / scan");
     int32_t bad = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(str_off, bufs.off.p, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&bad, bufs.bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (bad) return fail(ctx, NPR_ERR_INVALID, "cigar text: an operation outside M / I / D");
-    if (!want_text) return NPR_OK;
+    dev.fetch(str_off, bufs.off.p, sizeof(int64_t) * (n + 1));
+    dev.fetch(&bad, bufs.bad.p, sizeof(int32_t));
+    dev.sync();
+    if (bad) dev.refuse(NPR_ERR_INVALID, "cigar text: an operation outside M / I / D");
+    if (!want_text) return true;
     const int64_t total = str_off[n];
-    if (cap < total) return NPR_ERR_CAPACITY;
+    if (cap < total) return false;
     if (static_cast<size_t>(total) <= lend_bytes) {
         bufs.text_p = lend;
     } else {
-        if ((e = bufs.text.alloc_from(ctx, total)) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "cigar text: hipMalloc", e);
+        dev.alloc_cached(bufs.text, total);
         bufs.text_p = bufs.text.p;
     }
     a.out = bufs.text_p;
-    if ((rc = launch_cigtext_write(a, ctx->stream)) != 0) return fail(ctx, NPR_ERR_HIP, "k_cigtext_write launch", static_cast<hipError_t>(rc));
-    return NPR_OK;
+    dev.launched(launch_cigtext_write(a, dev.ctx->stream), "k_cigtext_write");
+    return true;
 }
 
-int32_t keep_text(npr_batch *b, const TextBufs &bufs, std::vector<int64_t> &off) {
+void keep_text(const Call &dev, npr_batch *b, const TextBufs &bufs, std::vector<int64_t> &off) {
     const int64_t total = off[b->n_reads];
     if (total > b->text_cap) b->text.reset(new char[total + total / 8]), b->text_cap = total + total / 8;
     // through the context's pinned staging in pieces of 4 MiB
@@ -55,73 +53,71 @@ int32_t keep_text(npr_batch *b, const TextBufs &bufs, std::vector<int64_t> &off)
                                 std::memcpy(static_cast<char *>(dst) + lo, static_cast<const char *>(pin) + lo, static_cast<size_t>(hi - lo));
                             },
                             "cigar text: hipHostMalloc", "cigar text: D2H"};
-    const int32_t rc = fetch_pieced(b->ctx, fetch);
-    if (rc != NPR_OK) return rc;
+    dev.passed(fetch_pieced(b->ctx, fetch));
     b->text_off.swap(off);
     b->text_ready = true;
-    return NPR_OK;
 }
-
-}  // namespace
 
 // The text of a batch whose packed words (offsets d_off[n + 1]) are on the device, to b->text and b->text_off.  `lend`: device memory the text
 // may use (lend_bytes).  The stream is drained when it returns.
-int32_t device_words_text(npr_batch *b, const int64_t *d_off, const uint32_t *d_words, char *lend, size_t lend_bytes) {
+void words_text(const Call &dev, npr_batch *b, const int64_t *d_off, const uint32_t *d_words, char *lend, size_t lend_bytes) {
     std::vector<int64_t> off(b->n_reads + 1, 0);
     TextBufs bufs;
-    const int32_t rc = run_cigtext(b->ctx, b->n_reads, d_off, nullptr, d_words, true, INT64_MAX, lend, lend_bytes, bufs, off.data());
-    return rc != NPR_OK ? rc : keep_text(b, bufs, off);
+    run_cigtext(dev, b->n_reads, d_off, nullptr, d_words, true, INT64_MAX, lend, lend_bytes, bufs, off.data());
+    keep_text(dev, b, bufs, off);
 }
-
-namespace {
 
 // the text of a finished batch on the host (b->text, b->text_off), made once: from the packed words where the device MEA stage left them
 // while they are still there, else from the batch's host form, uploaded
-int32_t ensure_text(npr_batch *b) {
-    if (b->text_ready) return NPR_OK;
+void ensure_text(const Call &dev, npr_batch *b) {
+    if (b->text_ready) return;
     npr_ctx *ctx = b->ctx;
     const int64_t n = b->n_reads;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n == 0) {
         std::vector<int64_t> off(1, 0);
-        return keep_text(b, TextBufs{}, off);
+        return keep_text(dev, b, TextBufs{}, off);
     }
     {
         std::unique_lock<std::mutex> arena_lock(ctx->arena->mu);  // the resident cigars lie in the arena
-        if (b->dev_ops && b->dev_ops_epoch == ctx->arena->epoch) return device_words_text(b, b->dev_od, b->dev_ops, nullptr, 0);  // (the lock goes after it)
+        if (b->dev_ops && b->dev_ops_epoch == ctx->arena->epoch) return words_text(dev, b, b->dev_od, b->dev_ops, nullptr, 0);  // (the lock goes after it)
     }
-    if (b->words_on_device && !b->have_packed_form) {
-        const int32_t rc = fetch_device_words(b);  // (fails: the words are gone)
-        if (rc != NPR_OK) return rc;
-    }
+    if (b->words_on_device && !b->have_packed_form) dev.passed(fetch_device_words(b));  // (fails: the words are gone)
     ensure_packed_form(b);
     const int64_t words = b->ops_off[n];
     DevBuf<uint32_t> d_words;
     DevBuf<int64_t> d_off;
-    hipError_t e;
-    if ((e = d_words.alloc_from(ctx, std::max<int64_t>(words, 1))) != hipSuccess || (e = d_off.alloc_from(ctx, n + 1)) != hipSuccess)
-        return fail(ctx, NPR_ERR_NOMEM, "npr_batch_cigar_text: hipMalloc", e);
-    if (words) HIP_TRY(ctx, hipMemcpyAsync(d_words.p, b->packed.get(), sizeof(uint32_t) * static_cast<size_t>(words), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_off.p, b->ops_off.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
-    return device_words_text(b, d_off.p, d_words.p, nullptr, 0);
+    dev.alloc_cached(d_words, std::max<int64_t>(words, 1));
+    dev.alloc_cached(d_off, n + 1);
+    dev.copy_up(d_words.p, b->packed.get(), sizeof(uint32_t) * static_cast<size_t>(words));
+    dev.copy_up(d_off.p, b->ops_off.data(), sizeof(int64_t) * (n + 1));
+    words_text(dev, b, d_off.p, d_words.p, nullptr, 0);
 }
 
 }  // namespace
 
+// what npr_finish.cpp calls under NPR_OPT_FINISH_TEXT
+int32_t device_words_text(npr_batch *b, const int64_t *d_off, const uint32_t *d_words, char *lend, size_t lend_bytes) {
+    return guarded(b->ctx, "cigar text", [&](const Call &dev) -> int32_t {
+        words_text(dev, b, d_off, d_words, lend, lend_bytes);
+        return NPR_OK;
+    });
+}
+
 // a batch finished with NPR_OPT_FINISH_TEXT has its packed words on the device only: to the host while they are still there
 int32_t fetch_device_words(npr_batch *b) {
     npr_ctx *ctx = b->ctx;
-    const int64_t total = b->ops_off[b->n_reads];
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::unique_lock<std::mutex> arena_lock(ctx->arena->mu);
-    if (!(b->dev_ops && b->dev_ops_epoch == ctx->arena->epoch))
-        return fail(ctx, NPR_ERR_STATE, "the batch was finished with NPR_OPT_FINISH_TEXT and its packed cigars have since been overwritten on the device: "
-                                        "fetch them before the next batch is finished, or use npr_batch_cigar_text");
-    if (total > b->packed_cap) b->packed.reset(new uint32_t[total]), b->packed_cap = total;
-    if (total) HIP_TRY(ctx, hipMemcpyAsync(b->packed.get(), b->dev_ops, sizeof(uint32_t) * static_cast<size_t>(total), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    b->have_packed_form = true;
-    return NPR_OK;
+    return guarded(ctx, "packed cigars", [&](const Call &dev) -> int32_t {
+        const int64_t total = b->ops_off[b->n_reads];
+        std::unique_lock<std::mutex> arena_lock(ctx->arena->mu);
+        if (!(b->dev_ops && b->dev_ops_epoch == ctx->arena->epoch))
+            return fail(ctx, NPR_ERR_STATE, "the batch was finished with NPR_OPT_FINISH_TEXT and its packed cigars have since been overwritten on the device: "
+                                            "fetch them before the next batch is finished, or use npr_batch_cigar_text");
+        if (total > b->packed_cap) b->packed.reset(new uint32_t[total]), b->packed_cap = total;
+        dev.fetch(b->packed.get(), b->dev_ops, sizeof(uint32_t) * static_cast<size_t>(total));
+        dev.sync();
+        b->have_packed_form = true;
+        return NPR_OK;
+    });
 }
 
 }  // namespace npr_impl
@@ -132,7 +128,7 @@ int64_t npr_cigar_text_packed(npr_ctx *ctx, int64_t n, const int64_t *word_off, 
                               char *out, int64_t cap) {
     if (!ctx) return NPR_ERR_INVALID;
     if (n < 0 || (n && (!word_off || !n_ops || !str_off || !words))) return fail(ctx, NPR_ERR_INVALID, "npr_cigar_text_packed: bad argument");
-    try {
+    return guarded(ctx, "npr_cigar_text_packed", [&](const Call &dev) -> int64_t {
         if (n == 0) {
             if (str_off) str_off[0] = 0;
             return 0;
@@ -146,51 +142,43 @@ int64_t npr_cigar_text_packed(npr_ctx *ctx, int64_t n, const int64_t *word_off, 
         if (hi == 0) lo = 0;
         std::vector<int64_t> rel(n);
         for (int64_t i = 0; i < n; ++i) rel[i] = n_ops[i] ? word_off[i] - lo : 0;
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
         DevBuf<uint32_t> d_words;
         DevBuf<int64_t> d_off, d_nops;
-        hipError_t e;
-        if ((e = d_words.alloc_from(ctx, std::max<int64_t>(hi - lo, 1))) != hipSuccess || (e = d_off.alloc_from(ctx, n)) != hipSuccess ||
-            (e = d_nops.alloc_from(ctx, n)) != hipSuccess)
-            return fail(ctx, NPR_ERR_NOMEM, "npr_cigar_text_packed: hipMalloc", e);
-        if (hi > lo) HIP_TRY(ctx, hipMemcpyAsync(d_words.p, words + lo, sizeof(uint32_t) * static_cast<size_t>(hi - lo), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_off.p, rel.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_nops.p, n_ops, sizeof(int64_t) * n, hipMemcpyHostToDevice, ctx->stream));
+        dev.alloc_cached(d_words, std::max<int64_t>(hi - lo, 1));
+        dev.alloc_cached(d_off, n);
+        dev.alloc_cached(d_nops, n);
+        dev.copy_up(d_words.p, words + lo, sizeof(uint32_t) * static_cast<size_t>(hi - lo));
+        dev.copy_up(d_off.p, rel.data(), sizeof(int64_t) * n);
+        dev.copy_up(d_nops.p, n_ops, sizeof(int64_t) * n);
         std::vector<int64_t> off(n + 1, 0);
         TextBufs bufs;
-        const int32_t rc = run_cigtext(ctx, n, d_off.p, d_nops.p, d_words.p, out != nullptr, cap, nullptr, 0, bufs, off.data());
-        if (rc != NPR_OK && rc != NPR_ERR_CAPACITY) return rc;  // (an op outside M I D: str_off is not written either)
+        const bool fits = run_cigtext(dev, n, d_off.p, d_nops.p, d_words.p, out != nullptr, cap, nullptr, 0, bufs, off.data());  // (an op outside M I D: str_off is not written either)
         std::copy(off.begin(), off.end(), str_off);
-        if (rc == NPR_ERR_CAPACITY) return rc;
+        if (!fits) return NPR_ERR_CAPACITY;
         if (out) {
-            if (off[n]) HIP_TRY(ctx, hipMemcpyAsync(out, bufs.text_p, static_cast<size_t>(off[n]), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            dev.fetch(out, bufs.text_p, static_cast<size_t>(off[n]));
+            dev.sync();
         }
         return off[n];
-    } catch (const std::exception &) {
-        return fail(ctx, NPR_ERR_NOMEM, "npr_cigar_text_packed: out of host memory");
-    }
+    });
 }
 
 int64_t npr_batch_cigar_text(npr_batch *b, int64_t *str_off, char *out, int64_t cap) {
     if (!b || !str_off) return NPR_ERR_INVALID;
     if (!b->finished) return fail(b->ctx, NPR_ERR_STATE, "npr_batch_cigar_text before npr_batch_finish");
-    try {
-        const int32_t rc = ensure_text(b);
-        if (rc != NPR_OK) return rc;
-    } catch (const std::exception &) {
-        return fail(b->ctx, NPR_ERR_NOMEM, "npr_batch_cigar_text: out of host memory");
-    }
-    std::copy(b->text_off.begin(), b->text_off.end(), str_off);
-    const int64_t total = b->text_off[b->n_reads];
-    if (!out) return total;
-    if (cap < total) return NPR_ERR_CAPACITY;
-    const char *src = b->text.get();
-    const int64_t chunk = 4 << 20, nchunks = (total + chunk - 1) / chunk;
-    parallel_for(nchunks, b->ctx->host_threads, [&](int64_t c) {
-        std::memcpy(out + c * chunk, src + c * chunk, static_cast<size_t>(std::min(total, (c + 1) * chunk) - c * chunk));
+    return guarded(b->ctx, "npr_batch_cigar_text", [&](const Call &dev) -> int64_t {
+        ensure_text(dev, b);
+        std::copy(b->text_off.begin(), b->text_off.end(), str_off);
+        const int64_t total = b->text_off[b->n_reads];
+        if (!out) return total;
+        if (cap < total) return NPR_ERR_CAPACITY;
+        const char *src = b->text.get();
+        const int64_t chunk = 4 << 20, nchunks = (total + chunk - 1) / chunk;
+        parallel_for(nchunks, b->ctx->host_threads, [&](int64_t c) {
+            std::memcpy(out + c * chunk, src + c * chunk, static_cast<size_t>(std::min(total, (c + 1) * chunk) - c * chunk));
+        });
+        return total;
     });
-    return total;
 }
 
 }  // extern "C"

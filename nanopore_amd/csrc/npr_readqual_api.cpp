@@ -32,7 +32,7 @@ int32_t npr_read_quality(npr_ctx *ctx, int64_t n_reads, const uint8_t *text, con
         (n_reads && (!seq_begin || !seq_end || !qual_begin || !qual_end || !group)))
         return NPR_ERR_INVALID;
     const size_t G = static_cast<size_t>(n_groups);
-    try {
+    return guarded(ctx, "npr_read_quality", [&](const Call &dev) -> int32_t {
         // nothing is counted and no table touched when an argument is wrong
         int64_t n = 0, bytes = 0, n_items = 0;
         for (int64_t i = 0; i < n_reads; ++i) {
@@ -80,9 +80,7 @@ int32_t npr_read_quality(npr_ctx *ctx, int64_t n_reads, const uint8_t *text, con
                 items[f[std::min<int64_t>(t, RQ_TILE_CLASSES - 1)]++] = (static_cast<unsigned long long>(r) << 32) | static_cast<unsigned long long>(t);
         }
 
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const int32_t grown = grow_pin_stage(ctx, 2 * static_cast<size_t>(bytes), "npr_read_quality: hipHostMalloc");
-        if (grown != NPR_OK) return grown;
+        dev.passed(grow_pin_stage(ctx, 2 * static_cast<size_t>(bytes), "npr_read_quality: hipHostMalloc"));
         uint8_t *const h_seq = static_cast<uint8_t *>(ctx->pin_stage), *const h_qual = h_seq + bytes;
         parallel_for((n + 255) / 256, ctx->host_threads, [&](int64_t c) {
             for (int64_t r = c * 256, hi = std::min(n, (c + 1) * 256); r < hi; ++r) {
@@ -95,18 +93,15 @@ int32_t npr_read_quality(npr_ctx *ctx, int64_t n_reads, const uint8_t *text, con
         DevBuf<int64_t> d_meta;
         DevBuf<int32_t> d_grp;
         DevBuf<unsigned long long> d_items, d_rows, d_tab;
-        hipError_t e;
         const size_t tab_words = G * RQ_GROUP_WORDS;
-        if ((e = d_bytes.alloc(2 * static_cast<size_t>(bytes))) != hipSuccess || (e = d_meta.alloc(meta.size())) != hipSuccess ||
-            (e = d_grp.alloc(grp.size())) != hipSuccess || (e = d_items.alloc(items.size())) != hipSuccess ||
-            (e = d_rows.alloc(static_cast<size_t>(n) * RQ_ROW)) != hipSuccess || (e = d_tab.alloc(tab_words)) != hipSuccess)
-            return fail(ctx, NPR_ERR_NOMEM, "npr_read_quality: hipMalloc", e);
-        HIP_TRY(ctx, hipMemcpyAsync(d_bytes.p, h_seq, d_bytes.bytes(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_meta.p, meta.data(), d_meta.bytes(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_grp.p, grp.data(), d_grp.bytes(), hipMemcpyHostToDevice, ctx->stream));
-        if (!items.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_items.p, items.data(), d_items.bytes(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(d_rows.p, 0, d_rows.bytes(), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(d_tab.p, 0, d_tab.bytes(), ctx->stream));
+        dev.upload(d_bytes, h_seq, 2 * static_cast<size_t>(bytes));
+        dev.upload(d_meta, meta);
+        dev.upload(d_grp, grp);
+        dev.upload(d_items, items);
+        dev.alloc(d_rows, static_cast<size_t>(n) * RQ_ROW);
+        dev.alloc(d_tab, tab_words);
+        dev.zero(d_rows);
+        dev.zero(d_tab);
         ReadQualArgs a{};
         a.seq = d_bytes.p, a.qual = d_bytes.p + bytes, a.start = d_meta.p, a.len = d_meta.p + n, a.group = d_grp.p, a.items = d_items.p;
         a.n = n, a.n_items = n_items, a.n_groups = n_groups, a.rows = d_rows.p;
@@ -116,11 +111,10 @@ int32_t npr_read_quality(npr_ctx *ctx, int64_t n_reads, const uint8_t *text, con
         a.meanq_hist = a.len_hist + G * RQ_POS_BINS;
         a.gc_hist = a.meanq_hist + G * RQ_QUAL_COLS;
         a.totals = a.gc_hist + G * RQ_GC_COLS;
-        const int rc = launch_read_quality(a, ctx->stream);
-        if (rc != 0) return fail(ctx, NPR_ERR_HIP, "k_read_quality launch", static_cast<hipError_t>(rc));
+        dev.launched(launch_read_quality(a, ctx->stream), "k_read_quality");
         std::vector<int64_t> tab(tab_words);
-        HIP_TRY(ctx, hipMemcpyAsync(tab.data(), d_tab.p, d_tab.bytes(), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        dev.fetch(tab.data(), d_tab.p, d_tab.bytes());
+        dev.sync();
         const int64_t *p = tab.data();
         auto take = [&](int64_t *dst, size_t words) { std::copy(p, p + words, dst), p += words; };
         take(pos_qual, G * RQ_POS_BINS * RQ_QUAL_COLS), take(pos_base, G * RQ_POS_BINS * RQ_BASE_COLS), take(len_hist, G * RQ_POS_BINS);
@@ -133,9 +127,7 @@ int32_t npr_read_quality(npr_ctx *ctx, int64_t n_reads, const uint8_t *text, con
             if (t[1]) o[4] = 255 - t[4], o[5] = t[5];
         }
         return NPR_OK;
-    } catch (const std::exception &) {
-        return fail(ctx, NPR_ERR_NOMEM, "npr_read_quality: out of host memory");
-    }
+    });
 }
 
 }  // extern "C"

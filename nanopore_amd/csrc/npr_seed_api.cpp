@@ -10,49 +10,42 @@ namespace npr_impl {
 
 // n ASCII sequences lying back to back on the host (`bases` bytes at `ascii`, offsets off[n + 1] from 0) -> their code buffer on the device, and
 // the buffer of their reverse complements when rc is given; d_off receives the offsets
-int32_t encode_on_device(npr_ctx *ctx, const uint8_t *ascii, const std::vector<int64_t> &off, uint8_t other, uint8_t sep, DevBuf<uint8_t> &codes,
-                         DevBuf<uint8_t> *rc, DevBuf<int64_t> &d_off, const char *what) {
+void encode_on_device(const Call &dev, const uint8_t *ascii, const std::vector<int64_t> &off, uint8_t other, uint8_t sep, DevBuf<uint8_t> &codes, DevBuf<uint8_t> *rc,
+                      DevBuf<int64_t> &d_off) {
     const int64_t n = static_cast<int64_t>(off.size()) - 1, bases = off[n], bytes = seed_code_bytes(bases, n);
     DevBuf<uint8_t> d_ascii;
-    hipError_t e;
-    if ((e = d_ascii.alloc(static_cast<size_t>(bases))) != hipSuccess || (e = codes.alloc(static_cast<size_t>(bytes))) != hipSuccess ||
-        (rc && (e = rc->alloc(static_cast<size_t>(bytes))) != hipSuccess) || (e = d_off.alloc(off.size())) != hipSuccess)
-        return fail(ctx, NPR_ERR_NOMEM, what, e);
-    if (bases) HIP_TRY(ctx, hipMemcpyAsync(d_ascii.p, ascii, static_cast<size_t>(bases), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_off.p, off.data(), d_off.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    dev.upload(d_ascii, ascii, static_cast<size_t>(bases));
+    dev.alloc(codes, static_cast<size_t>(bytes));
+    if (rc) dev.alloc(*rc, static_cast<size_t>(bytes));
+    dev.upload(d_off, off);
     const SeedEncodeArgs a{d_ascii.p, d_off.p, n, bytes, other, sep, codes.p, rc ? rc->p : nullptr};
-    const int r = launch_seed_encode(a, ctx->stream);
-    if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_seed_encode launch", static_cast<hipError_t>(r));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the ASCII copy on the device goes when this returns)
-    return NPR_OK;
+    dev.launched(launch_seed_encode(a, dev.ctx->stream), "k_seed_encode");
+    dev.sync();  // (the ASCII copy on the device goes when this returns)
 }
 
-// what npr_seed_matches and npr_seed_map_create (npr_seedmap_api.cpp) do alike, `who` being the one that asks: the reads' spans looked at and
-// summed into off[n_reads + 1] (nothing is launched when they are refused) ...
-int32_t seed_check_reads(npr_ctx *ctx, const char *who, int64_t n_reads, const uint8_t *text, const int64_t *begin, const int64_t *end, std::vector<int64_t> &off) {
+// what npr_seed_matches and npr_seed_map_create (npr_seedmap_api.cpp) do alike: the reads' spans looked at and summed into off[n_reads + 1]
+// (nothing is launched when they are refused) ...
+void seed_check_reads(const Call &dev, int64_t n_reads, const uint8_t *text, const int64_t *begin, const int64_t *end, std::vector<int64_t> &off) {
     off.assign(static_cast<size_t>(n_reads) + 1, 0);
     for (int64_t i = 0; i < n_reads; ++i) {
-        if (end[i] < begin[i] || begin[i] < 0) return fail(ctx, NPR_ERR_INVALID, (std::string(who) + ": a span that ends before it begins").c_str());
+        if (end[i] < begin[i] || begin[i] < 0) dev.refuse(NPR_ERR_INVALID, (std::string(dev.entry) + ": a span that ends before it begins").c_str());
         off[i + 1] = off[i] + (end[i] - begin[i]);
     }
-    if (off[n_reads] && !text) return NPR_ERR_INVALID;
+    if (off[n_reads] && !text) dev.refuse(NPR_ERR_INVALID);
     if (seed_code_bytes(off[n_reads], n_reads) >= (int64_t(1) << 31))
-        return fail(ctx, NPR_ERR_INVALID, (std::string(who) + ": 2^31 read positions and more in one call (give the reads in several)").c_str());
-    return NPR_OK;
+        dev.refuse(NPR_ERR_INVALID, (std::string(dev.entry) + ": 2^31 read positions and more in one call (give the reads in several)").c_str());
 }
 
 // ... the reads back to back in the pinned staging, then as code buffers on the device (both orientations when the reverse strand is asked for) ...
-int32_t seed_stage_reads(npr_ctx *ctx, const char *who, int32_t strands, int64_t n_reads, const uint8_t *text, const int64_t *begin, const int64_t *end,
-                         const std::vector<int64_t> &off, DevBuf<uint8_t> &fwd, DevBuf<uint8_t> &rev, DevBuf<int64_t> &d_off) {
-    const int64_t bases = off[n_reads];
-    const int32_t grown = grow_pin_stage(ctx, static_cast<size_t>(bases), (std::string(who) + ": hipHostMalloc").c_str());
-    if (grown != NPR_OK) return grown;
-    uint8_t *const h_ascii = static_cast<uint8_t *>(ctx->pin_stage);
-    parallel_for((n_reads + 255) / 256, ctx->host_threads, [&](int64_t c) {
+void seed_stage_reads(const Call &dev, int32_t strands, int64_t n_reads, const uint8_t *text, const int64_t *begin, const int64_t *end, const std::vector<int64_t> &off,
+                      DevBuf<uint8_t> &fwd, DevBuf<uint8_t> &rev, DevBuf<int64_t> &d_off) {
+    dev.passed(grow_pin_stage(dev.ctx, static_cast<size_t>(off[n_reads]), (std::string(dev.entry) + ": hipHostMalloc").c_str()));
+    uint8_t *const h_ascii = static_cast<uint8_t *>(dev.ctx->pin_stage);
+    parallel_for((n_reads + 255) / 256, dev.ctx->host_threads, [&](int64_t c) {
         for (int64_t i = c * 256, hi = std::min(n_reads, (c + 1) * 256); i < hi; ++i)
             std::memcpy(h_ascii + off[i], text + begin[i], static_cast<size_t>(end[i] - begin[i]));
     });
-    return encode_on_device(ctx, h_ascii, off, NPR_SEED_READ_OTHER, NPR_SEED_READ_SEP, fwd, (strands & 2) ? &rev : nullptr, d_off, (std::string(who) + ": hipMalloc").c_str());
+    encode_on_device(dev, h_ascii, off, NPR_SEED_READ_OTHER, NPR_SEED_READ_SEP, fwd, (strands & 2) ? &rev : nullptr, d_off);
 }
 
 // ... the arguments of k_seed_match for them (the orientation, and the rows once they have a buffer, are filled in later) ...
@@ -63,15 +56,13 @@ SeedMatchArgs seed_match_args(const npr_seed_index *ix, int64_t min_len, const s
 }
 
 // ... and one pass of it, counting or emitting, over the orientations asked for
-int32_t seed_match_pass(npr_ctx *ctx, SeedMatchArgs &a, int32_t strands, const uint8_t *fwd, const uint8_t *rev, bool emit) {
-    HIP_TRY(ctx, hipMemsetAsync(a.count, 0, static_cast<size_t>(a.n_reads) * sizeof(uint32_t), ctx->stream));
+void seed_match_pass(const Call &dev, SeedMatchArgs &a, int32_t strands, const uint8_t *fwd, const uint8_t *rev, bool emit) {
+    dev.zero(a.count, static_cast<size_t>(a.n_reads) * sizeof(uint32_t));
     for (uint32_t strand = 0; strand < 2; ++strand) {
         if (!(strands & (1 << strand))) continue;
         a.read = strand ? rev : fwd, a.strand = strand;
-        const int r = launch_seed_match(a, emit, ctx->stream);
-        if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_seed_match launch", static_cast<hipError_t>(r));
+        dev.launched(launch_seed_match(a, emit, dev.ctx->stream), "k_seed_match");
     }
-    return NPR_OK;
 }
 
 }  // namespace npr_impl
@@ -97,7 +88,7 @@ int32_t npr_seed_index_create(npr_ctx *ctx, int32_t k, int64_t n_refs, const uin
     *out = nullptr;
     if (k < NPR_SEED_MIN_K || k > NPR_SEED_MAX_K) return fail(ctx, NPR_ERR_INVALID, "npr_seed_index_create: k outside 8 .. 32");
     if (n_refs < 0 || (n_refs && !ref_off)) return NPR_ERR_INVALID;
-    try {
+    return guarded(ctx, "npr_seed_index_create", [&](const Call &dev) -> int32_t {
         std::vector<int64_t> off(n_refs + 1, 0);
         for (int64_t i = 1; i <= n_refs; ++i) {
             off[i] = ref_off[i] - ref_off[0];
@@ -105,31 +96,24 @@ int32_t npr_seed_index_create(npr_ctx *ctx, int32_t k, int64_t n_refs, const uin
         }
         if (off[n_refs] && !ref) return NPR_ERR_INVALID;
         if (seed_code_bytes(off[n_refs], n_refs) >= (int64_t(1) << 31)) return fail(ctx, NPR_ERR_INVALID, "npr_seed_index_create: 2^31 reference positions and more");
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
         std::unique_ptr<npr_seed_index> ix(new npr_seed_index);
         ix->ctx = ctx, ix->k = k, ix->kb = std::min<int32_t>(k, NPR_SEED_MAX_KB), ix->n_refs = n_refs;
         ix->bytes = seed_code_bytes(off[n_refs], n_refs);
         ix->ref_len.resize(static_cast<size_t>(n_refs));
         for (int64_t i = 0; i < n_refs; ++i) ix->ref_len[i] = static_cast<int32_t>(off[i + 1] - off[i]);
-        const int32_t rc = encode_on_device(ctx, n_refs ? ref + ref_off[0] : nullptr, off, NPR_SEED_REF_OTHER, NPR_SEED_REF_SEP, ix->codes, nullptr, ix->off,
-                                            "npr_seed_index_create: hipMalloc");
-        if (rc != NPR_OK) return rc;
+        encode_on_device(dev, n_refs ? ref + ref_off[0] : nullptr, off, NPR_SEED_REF_OTHER, NPR_SEED_REF_SEP, ix->codes, nullptr, ix->off);
         const size_t entries = static_cast<size_t>(seed_table_entries(ix->kb));
         DevBuf<int32_t> tile;
-        hipError_t e;
-        if ((e = ix->table.alloc(entries)) != hipSuccess || (e = ix->pos.alloc(static_cast<size_t>(ix->bytes))) != hipSuccess ||
-            (e = tile.alloc(entries / NPR_SEED_SCAN_TILE)) != hipSuccess)
-            return fail(ctx, NPR_ERR_NOMEM, "npr_seed_index_create: hipMalloc", e);
-        HIP_TRY(ctx, hipMemsetAsync(ix->table.p, 0, ix->table.bytes(), ctx->stream));
+        dev.alloc(ix->table, entries);
+        dev.alloc(ix->pos, static_cast<size_t>(ix->bytes));
+        dev.alloc(tile, entries / NPR_SEED_SCAN_TILE);
+        dev.zero(ix->table);
         const SeedIndexArgs a{ix->codes.p, ix->bytes, ix->k, ix->kb, ix->table.p, tile.p, ix->pos.p};
-        const int r = launch_seed_index(a, ctx->stream);
-        if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_seed_bucket launch", static_cast<hipError_t>(r));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        dev.launched(launch_seed_index(a, ctx->stream), "k_seed_bucket");
+        dev.sync();
         *out = ix.release();
         return NPR_OK;
-    } catch (const std::exception &) {
-        return fail(ctx, NPR_ERR_NOMEM, "npr_seed_index_create: out of host memory");
-    }
+    });
 }
 
 void npr_seed_index_destroy(npr_seed_index *ix) {
@@ -145,41 +129,33 @@ int64_t npr_seed_matches(npr_seed_index *ix, int64_t min_len, int32_t strands, i
     if (min_len < ix->k || min_len >= (int64_t(1) << 31)) return fail(ctx, NPR_ERR_INVALID, "npr_seed_matches: min_len outside k .. 2^31 - 1");
     if (strands < 1 || strands > 3) return fail(ctx, NPR_ERR_INVALID, "npr_seed_matches: strands outside 1 .. 3");
     if (n_reads < 0 || cap < 0 || !hit_off || (n_reads && (!begin || !end))) return NPR_ERR_INVALID;
-    try {
+    return guarded(ctx, "npr_seed_matches", [&](const Call &dev) -> int64_t {
         std::vector<int64_t> off;
-        int32_t rs = seed_check_reads(ctx, "npr_seed_matches", n_reads, text, begin, end, off);
-        if (rs != NPR_OK) return rs;
-        const int64_t bases = off[n_reads];
+        seed_check_reads(dev, n_reads, text, begin, end, off);
         std::fill(hit_off, hit_off + n_reads + 1, int64_t(0));
-        if (bases == 0) return 0;
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (off[n_reads] == 0) return 0;
         DevBuf<uint8_t> fwd, rev;
         DevBuf<int64_t> d_off, d_hit_off;
         DevBuf<uint32_t> d_count;
         DevBuf<int32_t> d_hits;
-        rs = seed_stage_reads(ctx, "npr_seed_matches", strands, n_reads, text, begin, end, off, fwd, rev, d_off);
-        if (rs != NPR_OK) return rs;
-        hipError_t e;
-        if ((e = d_count.alloc(static_cast<size_t>(n_reads))) != hipSuccess || (e = d_hit_off.alloc(static_cast<size_t>(n_reads) + 1)) != hipSuccess)
-            return fail(ctx, NPR_ERR_NOMEM, "npr_seed_matches: hipMalloc", e);
+        seed_stage_reads(dev, strands, n_reads, text, begin, end, off, fwd, rev, d_off);
+        dev.alloc(d_count, static_cast<size_t>(n_reads));
+        dev.alloc(d_hit_off, static_cast<size_t>(n_reads) + 1);
         SeedMatchArgs a = seed_match_args(ix, min_len, off, d_off.p, d_count.p, d_hit_off.p);
-        auto both_strands = [&](bool emit) { return seed_match_pass(ctx, a, strands, fwd.p, rev.p, emit); };  // the pass over the orientations asked for
-        rs = both_strands(false);
-        if (rs != NPR_OK) return rs;
+        seed_match_pass(dev, a, strands, fwd.p, rev.p, false);
         std::vector<uint32_t> count(n_reads);
-        HIP_TRY(ctx, hipMemcpyAsync(count.data(), d_count.p, d_count.bytes(), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        dev.fetch(count.data(), d_count.p, d_count.bytes());
+        dev.sync();
         for (int64_t i = 0; i < n_reads; ++i) hit_off[i + 1] = hit_off[i] + count[i];
         const int64_t total = hit_off[n_reads];
         if (total == 0) return 0;
         if (!hits || total > cap) return fail(ctx, NPR_ERR_CAPACITY, "npr_seed_matches: more matches than the buffer holds (hit_off says how many)");
-        if ((e = d_hits.alloc(static_cast<size_t>(total) * 4)) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, "npr_seed_matches: hipMalloc", e);
-        HIP_TRY(ctx, hipMemcpyAsync(d_hit_off.p, hit_off, d_hit_off.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        dev.alloc(d_hits, static_cast<size_t>(total) * 4);
+        dev.copy_up(d_hit_off.p, hit_off, d_hit_off.bytes());
         a.hits = d_hits.p;
-        rs = both_strands(true);
-        if (rs != NPR_OK) return rs;
-        HIP_TRY(ctx, hipMemcpyAsync(hits, d_hits.p, d_hits.bytes(), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        seed_match_pass(dev, a, strands, fwd.p, rev.p, true);
+        dev.fetch(hits, d_hits.p, d_hits.bytes());
+        dev.sync();
         // a read's matches arrive in the order the lanes found them: sorted here, the result is the same from run to run
         static_assert(sizeof(std::array<int32_t, 4>) == 4 * sizeof(int32_t), "a match is four int32");
         parallel_for((n_reads + 63) / 64, ctx->host_threads, [&](int64_t c) {
@@ -194,9 +170,7 @@ int64_t npr_seed_matches(npr_seed_index *ix, int64_t min_len, int32_t strands, i
             }
         });
         return total;
-    } catch (const std::exception &) {
-        return fail(ctx, NPR_ERR_NOMEM, "npr_seed_matches: out of host memory");
-    }
+    });
 }
 
 int64_t npr_seed_sam_text(int64_t n_reads, const uint8_t *text, const int64_t *name_span, const int64_t *begin, const int64_t *end, const char *rnames,
@@ -204,7 +178,7 @@ int64_t npr_seed_sam_text(int64_t n_reads, const uint8_t *text, const int64_t *n
     if (n_reads < 0 || n_refs < 0 || !hit_off || !rec_off || (n_reads && (!text || !name_span || !begin || !end))) return NPR_ERR_INVALID;
     const int64_t total = hit_off[n_reads];
     if (hit_off[0] != 0 || total < 0 || (total && (!hits || !rnames || !rname_off))) return NPR_ERR_INVALID;
-    try {
+    return guarded(nullptr, "npr_seed_sam_text", [&](const Call &) -> int64_t {  // (host code)
         for (int64_t i = 0; i < n_reads; ++i)
             if (hit_off[i + 1] < hit_off[i] || end[i] < begin[i] || name_span[2 * i + 1] < name_span[2 * i]) return NPR_ERR_INVALID;
         // qname, flag, rname, pos, "255", cigar, "*", "0", "0", seq, "*"
@@ -235,9 +209,7 @@ int64_t npr_seed_sam_text(int64_t n_reads, const uint8_t *text, const int64_t *n
             s.lit("\t*\n");
             return true;
         });
-    } catch (const std::exception &) {
-        return NPR_ERR_NOMEM;
-    }
+    });
 }
 
 }  // extern "C"

@@ -6,29 +6,24 @@
 
 namespace npr_impl {
 
-int32_t SeedChainRun::count(npr_ctx *ctx, const char *what, const int32_t *d_hits, int64_t rows, const SeedChainSpan *d_span, int64_t n_chains, int64_t max_gap,
-                            const int32_t *d_ref_len, const int32_t *d_read_len) {
-    hipError_t e;
-    if ((e = node.alloc(static_cast<size_t>(rows) * 4)) != hipSuccess || (e = back.alloc(static_cast<size_t>(rows))) != hipSuccess ||
-        (e = run_end.alloc(static_cast<size_t>(n_chains) * 4)) != hipSuccess || (e = chains.alloc(static_cast<size_t>(n_chains) * 4)) != hipSuccess ||
-        (e = n_ops.alloc(static_cast<size_t>(n_chains) + 1)) != hipSuccess)
-        return fail(ctx, NPR_ERR_NOMEM, what, e);
+void SeedChainRun::count(const Call &dev, const int32_t *d_hits, int64_t rows, const SeedChainSpan *d_span, int64_t n_chains, int64_t max_gap, const int32_t *d_ref_len,
+                         const int32_t *d_read_len) {
+    dev.alloc(node, static_cast<size_t>(rows) * 4);
+    dev.alloc(back, static_cast<size_t>(rows));
+    dev.alloc(run_end, static_cast<size_t>(n_chains) * 4);
+    dev.alloc(chains, static_cast<size_t>(n_chains) * 4);
+    dev.alloc(n_ops, static_cast<size_t>(n_chains) + 1);
     a = SeedChainArgs{d_hits, d_span, n_chains, static_cast<uint32_t>(std::min<int64_t>(max_gap, UINT32_MAX)), d_ref_len, d_read_len, node.p, back.p,
                       run_end.p, chains.p, n_ops.p, nullptr};
-    const int r = launch_seed_chain_dp(a, ctx->stream);
-    if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_chain_dp launch", static_cast<hipError_t>(r));
-    HIP_TRY(ctx, hipMemcpyAsync(&pairs, n_ops.p + n_chains, sizeof(pairs), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return NPR_OK;
+    dev.launched(launch_seed_chain_dp(a, dev.ctx->stream), "k_chain_dp");
+    dev.fetch(&pairs, n_ops.p + n_chains, sizeof(pairs));
+    dev.sync();
 }
 
-int32_t SeedChainRun::write(npr_ctx *ctx, const char *what) {
-    const hipError_t e = ops.alloc(static_cast<size_t>(pairs) * 2);
-    if (e != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, what, e);
+void SeedChainRun::write(const Call &dev) {
+    dev.alloc(ops, static_cast<size_t>(pairs) * 2);
     a.ops = ops.p;
-    const int r = launch_seed_chain_write(a, ctx->stream);
-    if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_chain_trace launch", static_cast<hipError_t>(r));
-    return NPR_OK;
+    dev.launched(launch_seed_chain_write(a, dev.ctx->stream), "k_chain_trace");
 }
 
 }  // namespace npr_impl
@@ -78,7 +73,7 @@ int64_t npr_seed_chains(npr_ctx *ctx, int64_t max_gap, int64_t n_reads, const in
     if (!ctx) return NPR_ERR_INVALID;
     if (max_gap < 0) return fail(ctx, NPR_ERR_INVALID, "npr_seed_chains: a negative max_gap");
     if (n_reads < 0 || n_refs < 0 || cap_chains < 0 || cap_ops < 0 || !hit_off || !chain_off || (n_reads && !read_len) || (n_refs && !ref_len)) return NPR_ERR_INVALID;
-    try {
+    return guarded(ctx, "npr_seed_chains", [&](const Call &dev) -> int64_t {
         // everything is checked before anything is written or indexed with: the offsets, the lengths, then the rows read by read
         if (hit_off[0] != 0) return fail(ctx, NPR_ERR_INVALID, "npr_seed_chains: hit_off does not start at 0");
         for (int64_t i = 0; i < n_reads; ++i)
@@ -124,32 +119,24 @@ int64_t npr_seed_chains(npr_ctx *ctx, int64_t max_gap, int64_t n_reads, const in
         std::copy(read_len, read_len + n_reads, len32.begin() + n_refs);
 
         // the upload, then the chain kernels on rows that lie on the device
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
         DevBuf<int32_t> d_hits, d_len;
         DevBuf<SeedChainSpan> d_span;
-        hipError_t e;
-        if ((e = d_hits.alloc(static_cast<size_t>(total) * 4)) != hipSuccess || (e = d_len.alloc(len32.size())) != hipSuccess || (e = d_span.alloc(span.size())) != hipSuccess)
-            return fail(ctx, NPR_ERR_NOMEM, "npr_seed_chains: hipMalloc", e);
-        HIP_TRY(ctx, hipMemcpyAsync(d_hits.p, hits, d_hits.bytes(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_len.p, len32.data(), d_len.bytes(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_span.p, span.data(), d_span.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        dev.upload(d_hits, hits, static_cast<size_t>(total) * 4);
+        dev.upload(d_len, len32);
+        dev.upload(d_span, span);
         SeedChainRun run;
-        int32_t rc = run.count(ctx, "npr_seed_chains: hipMalloc", d_hits.p, total, d_span.p, n_chains, max_gap, d_len.p, d_len.p + n_refs);
-        if (rc != NPR_OK) return rc;
+        run.count(dev, d_hits.p, total, d_span.p, n_chains, max_gap, d_len.p, d_len.p + n_refs);
         if (run.pairs > cap_ops || (run.pairs && !ops)) {
             ops_off[0] = run.pairs;
             return fail(ctx, NPR_ERR_CAPACITY, "npr_seed_chains: more op pairs than the buffer holds (ops_off[0] says how many)");
         }
-        rc = run.write(ctx, "npr_seed_chains: hipMalloc");
-        if (rc != NPR_OK) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(chains, run.chains.p, run.chains.bytes(), hipMemcpyDeviceToHost, ctx->stream));
-        if (run.pairs) HIP_TRY(ctx, hipMemcpyAsync(ops, run.ops.p, run.ops.bytes(), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ops_off, run.n_ops.p, run.n_ops.bytes(), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        run.write(dev);
+        dev.fetch(chains, run.chains.p, run.chains.bytes());
+        dev.fetch(ops, run.ops.p, run.ops.bytes());
+        dev.fetch(ops_off, run.n_ops.p, run.n_ops.bytes());
+        dev.sync();
         return n_chains;
-    } catch (const std::exception &) {
-        return fail(ctx, NPR_ERR_NOMEM, "npr_seed_chains: out of host memory");
-    }
+    });
 }
 
 int64_t npr_seed_chain_sam_text(int64_t n_reads, const uint8_t *text, const int64_t *name_span, const int64_t *begin, const int64_t *end, const char *rnames,
@@ -159,7 +146,7 @@ int64_t npr_seed_chain_sam_text(int64_t n_reads, const uint8_t *text, const int6
     const int64_t total = chain_off[n_reads];
     if (chain_off[0] != 0 || total < 0 || (total && (!chains || !ops_off || !rnames || !rname_off))) return NPR_ERR_INVALID;
     if (total && (ops_off[0] != 0 || (ops_off[total] && !ops))) return NPR_ERR_INVALID;
-    try {
+    return guarded(nullptr, "npr_seed_chain_sam_text", [&](const Call &) -> int64_t {  // (host code)
         const int threads = usable_cpus();
         for (int64_t i = 0; i < n_reads; ++i)
             if (chain_off[i + 1] < chain_off[i] || end[i] < begin[i] || name_span[2 * i + 1] < name_span[2 * i]) return NPR_ERR_INVALID;
@@ -215,9 +202,7 @@ int64_t npr_seed_chain_sam_text(int64_t n_reads, const uint8_t *text, const int6
             s.lit("\t*\n");
             return true;
         });
-    } catch (const std::exception &) {
-        return NPR_ERR_NOMEM;
-    }
+    });
 }
 
 }  // extern "C"

@@ -8,42 +8,38 @@
 namespace {
 
 // one int64 from the device, waited for
-int32_t fetch_total(npr_ctx *ctx, const int64_t *d, int64_t &v) {
-    HIP_TRY(ctx, hipMemcpyAsync(&v, d, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return NPR_OK;
+int64_t fetch_total(const Call &dev, const int64_t *d) {
+    int64_t v = 0;
+    dev.fetch(&v, d, sizeof(v));
+    dev.sync();
+    return v;
 }
 
-int32_t fill_map(npr_seed_map *m, npr_seed_index *ix, int64_t min_len, int32_t strands, int64_t max_gap, const uint8_t *text, const int64_t *begin, const int64_t *end,
-                 const std::vector<int64_t> &off) {
-    npr_ctx *ctx = m->ctx;
+void fill_map(const Call &dev, npr_seed_map *m, npr_seed_index *ix, int64_t min_len, int32_t strands, int64_t max_gap, const uint8_t *text, const int64_t *begin,
+              const int64_t *end, const std::vector<int64_t> &off) {
+    const hipStream_t stream = dev.ctx->stream;
     const int64_t n_reads = m->n_reads;
-    const char *const what = "npr_seed_map_create: hipMalloc";
     DevBuf<uint8_t> fwd, rev;
     DevBuf<int64_t> d_off;
     DevBuf<uint32_t> d_count;
-    int32_t rc = seed_stage_reads(ctx, "npr_seed_map_create", strands, n_reads, text, begin, end, off, fwd, rev, d_off);
-    if (rc != NPR_OK) return rc;
-    hipError_t e;
-    if ((e = d_count.alloc(static_cast<size_t>(n_reads))) != hipSuccess || (e = m->hit_off.alloc(static_cast<size_t>(n_reads) + 1)) != hipSuccess)
-        return fail(ctx, NPR_ERR_NOMEM, what, e);
+    seed_stage_reads(dev, strands, n_reads, text, begin, end, off, fwd, rev, d_off);
+    dev.alloc(d_count, static_cast<size_t>(n_reads));
+    dev.alloc(m->hit_off, static_cast<size_t>(n_reads) + 1);
     // count, offsets by a scan on the device, emit
     SeedMatchArgs match = seed_match_args(ix, min_len, off, d_off.p, d_count.p, m->hit_off.p);
     SeedMapArgs a{n_reads, d_count.p, m->hit_off.p, nullptr, nullptr, nullptr};
-    if ((rc = seed_match_pass(ctx, match, strands, fwd.p, rev.p, false)) != NPR_OK) return rc;
-    int r = launch_seedmap_offsets(a, ctx->stream);
-    if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_map_scan launch", static_cast<hipError_t>(r));
-    if ((rc = fetch_total(ctx, m->hit_off.p + n_reads, m->rows)) != NPR_OK) return rc;
-    if (m->rows == 0) return NPR_OK;
-    if ((e = m->hits.alloc(static_cast<size_t>(m->rows) * 4)) != hipSuccess || (e = m->chain_off.alloc(static_cast<size_t>(n_reads) + 1)) != hipSuccess)
-        return fail(ctx, NPR_ERR_NOMEM, what, e);
+    seed_match_pass(dev, match, strands, fwd.p, rev.p, false);
+    dev.launched(launch_seedmap_offsets(a, stream), "k_map_scan");
+    m->rows = fetch_total(dev, m->hit_off.p + n_reads);
+    if (m->rows == 0) return;
+    dev.alloc(m->hits, static_cast<size_t>(m->rows) * 4);
+    dev.alloc(m->chain_off, static_cast<size_t>(n_reads) + 1);
     match.hits = m->hits.p;
-    if ((rc = seed_match_pass(ctx, match, strands, fwd.p, rev.p, true)) != NPR_OK) return rc;
+    seed_match_pass(dev, match, strands, fwd.p, rev.p, true);
     // every read's rows sorted where they lie, its chains counted and the counts scanned
     a.hits = m->hits.p, a.chain_off = m->chain_off.p;
-    r = launch_seedmap_chains(a, ctx->stream);
-    if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_map_sort launch", static_cast<hipError_t>(r));
-    if ((rc = fetch_total(ctx, m->chain_off.p + n_reads, m->chains)) != NPR_OK) return rc;
+    dev.launched(launch_seedmap_chains(a, stream), "k_map_sort");
+    m->chains = fetch_total(dev, m->chain_off.p + n_reads);
     fwd.release(), rev.release();  // (the reads' codes have served; the kernels that read them have finished)
     // the chain spans, then the chain kernels on the rows where they lie
     DevBuf<SeedChainSpan> d_span;
@@ -51,18 +47,16 @@ int32_t fill_map(npr_seed_map *m, npr_seed_index *ix, int64_t min_len, int32_t s
     std::vector<int32_t> len32(ix->ref_len);  // reference lengths, then read lengths
     len32.resize(static_cast<size_t>(ix->n_refs + n_reads));
     for (int64_t i = 0; i < n_reads; ++i) len32[static_cast<size_t>(ix->n_refs + i)] = static_cast<int32_t>(off[i + 1] - off[i]);
-    if ((e = d_span.alloc(static_cast<size_t>(m->chains))) != hipSuccess || (e = d_len.alloc(len32.size())) != hipSuccess) return fail(ctx, NPR_ERR_NOMEM, what, e);
-    HIP_TRY(ctx, hipMemcpyAsync(d_len.p, len32.data(), d_len.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    dev.alloc(d_span, static_cast<size_t>(m->chains));
+    dev.upload(d_len, len32);
     a.span = d_span.p;
-    r = launch_seedmap_spans(a, ctx->stream);
-    if (r != 0) return fail(ctx, NPR_ERR_HIP, "k_map_spans launch", static_cast<hipError_t>(r));
+    dev.launched(launch_seedmap_spans(a, stream), "k_map_spans");
     SeedChainRun run;
-    if ((rc = run.count(ctx, what, m->hits.p, m->rows, d_span.p, m->chains, max_gap, d_len.p, d_len.p + ix->n_refs)) != NPR_OK) return rc;
-    if ((rc = run.write(ctx, what)) != NPR_OK) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the scratch of the chain kernels and the spans go when this returns)
+    run.count(dev, m->hits.p, m->rows, d_span.p, m->chains, max_gap, d_len.p, d_len.p + ix->n_refs);
+    run.write(dev);
+    dev.sync();  // (the scratch of the chain kernels and the spans go when this returns)
     m->pairs = run.pairs;
     m->chain_rows.take(run.chains), m->ops_off.take(run.n_ops), m->ops.take(run.ops);
-    return NPR_OK;
 }
 
 }  // namespace
@@ -78,22 +72,15 @@ int32_t npr_seed_map_create(npr_seed_index *ix, int64_t min_len, int32_t strands
     if (strands < 1 || strands > 3) return fail(ctx, NPR_ERR_INVALID, "npr_seed_map_create: strands outside 1 .. 3");
     if (max_gap < 0) return fail(ctx, NPR_ERR_INVALID, "npr_seed_map_create: a negative max_gap");
     if (n_reads < 0 || (n_reads && (!begin || !end))) return NPR_ERR_INVALID;
-    try {
+    return guarded(ctx, "npr_seed_map_create", [&](const Call &dev) -> int32_t {
         std::vector<int64_t> off;
-        int32_t rc = seed_check_reads(ctx, "npr_seed_map_create", n_reads, text, begin, end, off);
-        if (rc != NPR_OK) return rc;
+        seed_check_reads(dev, n_reads, text, begin, end, off);
         std::unique_ptr<npr_seed_map> m(new npr_seed_map);
         m->ctx = ctx, m->n_reads = n_reads;
-        if (off[n_reads] != 0) {  // (without a base there is no row: nothing to launch)
-            HIP_TRY(ctx, hipSetDevice(ctx->device));
-            rc = fill_map(m.get(), ix, min_len, strands, max_gap, text, begin, end, off);
-            if (rc != NPR_OK) return rc;
-        }
+        if (off[n_reads] != 0) fill_map(dev, m.get(), ix, min_len, strands, max_gap, text, begin, end, off);  // (without a base there is no row: nothing to launch)
         *out = m.release();
         return NPR_OK;
-    } catch (const std::exception &) {
-        return fail(ctx, NPR_ERR_NOMEM, "npr_seed_map_create: out of host memory");
-    }
+    });
 }
 
 int32_t npr_seed_map_counts(const npr_seed_map *m, int64_t counts[3]) {
@@ -104,23 +91,25 @@ int32_t npr_seed_map_counts(const npr_seed_map *m, int64_t counts[3]) {
 
 int32_t npr_seed_map_fetch(npr_seed_map *m, int64_t *hit_off, int32_t *hits, int64_t *chain_off, int32_t *chains, int64_t *ops_off, int32_t *ops) {
     if (!m) return NPR_ERR_INVALID;
-    npr_ctx *ctx = m->ctx;
     if (m->rows == 0) {  // no buffer on the device: the empty, well-formed result
         if (hit_off) std::fill(hit_off, hit_off + m->n_reads + 1, int64_t(0));
         if (chain_off) std::fill(chain_off, chain_off + m->n_reads + 1, int64_t(0));
         if (ops_off) ops_off[0] = 0;
         return NPR_OK;
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto fetch = [&](void *dst, const void *src, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
-    HIP_TRY(ctx, fetch(hit_off, m->hit_off.p, m->hit_off.bytes()));
-    HIP_TRY(ctx, fetch(hits, m->hits.p, m->hits.bytes()));
-    HIP_TRY(ctx, fetch(chain_off, m->chain_off.p, m->chain_off.bytes()));
-    HIP_TRY(ctx, fetch(chains, m->chain_rows.p, m->chain_rows.bytes()));
-    HIP_TRY(ctx, fetch(ops_off, m->ops_off.p, m->ops_off.bytes()));
-    HIP_TRY(ctx, fetch(ops, m->ops.p, m->ops.bytes()));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return NPR_OK;
+    return guarded(m->ctx, "npr_seed_map_fetch", [&](const Call &dev) -> int32_t {
+        auto fetch = [&](void *dst, const void *src, size_t bytes) {
+            if (dst) dev.fetch(dst, src, bytes);
+        };
+        fetch(hit_off, m->hit_off.p, m->hit_off.bytes());
+        fetch(hits, m->hits.p, m->hits.bytes());
+        fetch(chain_off, m->chain_off.p, m->chain_off.bytes());
+        fetch(chains, m->chain_rows.p, m->chain_rows.bytes());
+        fetch(ops_off, m->ops_off.p, m->ops_off.bytes());
+        fetch(ops, m->ops.p, m->ops.bytes());
+        dev.sync();
+        return NPR_OK;
+    });
 }
 
 void npr_seed_map_destroy(npr_seed_map *m) {

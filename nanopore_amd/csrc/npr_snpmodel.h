@@ -7,7 +7,7 @@
 
 namespace npr {
 
-constexpr int kSnpMaxModels = 4;  // NPR_SNP_MAX_MODELS (npr_aux.cpp asserts that they agree)
+constexpr int kSnpMaxModels = 4;  // NPR_SNP_MAX_MODELS (npr_snp_api.cpp asserts that they agree)
 
 // log_evolution[16] = log evolution16 ([reference][candidate]; a zero gives -inf: that candidate gets p = 0),
 // log_error[n_models][16] = log error16 ([candidate][observed]).  false, with nothing written: n_models outside 1..kSnpMaxModels, a null

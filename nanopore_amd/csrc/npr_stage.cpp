@@ -894,4 +894,103 @@ int32_t npr_batch_create(npr_ctx *ctx, const npr_params *params, int64_t n_reads
                                nullptr, model_slot, out);
 }
 
+
+// the planner cross-check: what the device planner staged for every task against the host planner's plan of the same guide; the number of tasks that differ
+int64_t npr_batch_plan_check(npr_batch *b, const int32_t *guide_ops) {
+    if (!b || (b->n_reads && b->guide_off[b->n_reads] && !guide_ops)) return NPR_ERR_INVALID;
+    npr_ctx *ctx = b->ctx;
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        {
+            const int32_t rc = ensure_coff(b);
+            if (rc != NPR_OK) return rc;
+        }
+        const int64_t n = b->n_reads;
+        int64_t mismatches = 0;
+        std::vector<int32_t> lo, nn;
+        std::vector<uint32_t> co, ctl, want_ctl;
+        std::vector<Stripe> st, want_st;
+        for (int64_t i = 0; i < n; ++i) {
+            if (b->read_status[i] != NPR_OK && b->read_ntasks[i] == 0) continue;
+            Plan plan;
+            const int32_t rc = build_plan(b->params, b->ref_len[i], b->read_len[i], guide_ops + 2 * b->guide_off[i],
+                                          b->guide_off[i + 1] - b->guide_off[i], plan);
+            if (rc != NPR_OK || static_cast<int32_t>(plan.segs.size()) != b->read_ntasks[i]) {
+                ++mismatches;
+                continue;
+            }
+            for (int32_t s = 0; s < b->read_ntasks[i]; ++s) {
+                const int32_t k = b->task_of[b->read_first_task[i] + s];
+                const Task &t = b->tasks[k];
+                const Segment &sg = plan.segs[s];
+                bool ok = t.D == sg.D() && t.xs == sg.xs && t.ys == sg.ys && t.lX == sg.xe - sg.xs && t.lY == sg.ye - sg.ys &&
+                          t.flags == ((sg.ragged_start ? 1 : 0) | (sg.ragged_end ? 2 : 0)) && b->task_cells[k] == sg.cells;
+                if (ok) {
+                    const size_t rows = static_cast<size_t>(t.D) + 1;
+                    lo.resize(rows), nn.resize(rows), co.resize(rows);
+                    HIP_TRY(ctx, hipMemcpy(lo.data(), b->d_lo.p + t.band_off, rows * 4, hipMemcpyDeviceToHost));
+                    HIP_TRY(ctx, hipMemcpy(nn.data(), b->d_n.p + t.band_off, rows * 4, hipMemcpyDeviceToHost));
+                    HIP_TRY(ctx, hipMemcpy(co.data(), b->d_coff.p + t.band_off, rows * 4, hipMemcpyDeviceToHost));
+                    uint64_t off = 0;
+                    for (size_t d = 0; d < rows && ok; ++d) {
+                        ok = lo[d] == sg.lo[d] && nn[d] == sg.n[d] && co[d] == static_cast<uint32_t>(off);
+                        if (!ok && std::getenv("NPR_TIMING"))
+                            std::fprintf(stderr, "[npr plan check] row %zu: device lo %d n %d coff %u | host lo %d n %d coff %u\n", d, lo[d], nn[d], co[d], sg.lo[d],
+                                         sg.n[d], static_cast<uint32_t>(off));
+                        off += (static_cast<uint64_t>(sg.n[d]) + 3) & ~uint64_t(3);
+                    }
+                    if (ok && t.ctl_off >= 0) {
+                        int cls = -1;  // the class the task was sorted into
+                        for (const auto &L : b->launches)
+                            if (k >= L.first && k < L.first + L.count) cls = L.cls;
+                        ctl.resize(2 * rows), want_ctl.assign(2 * rows, 0);
+                        HIP_TRY(ctx, hipMemcpy(ctl.data(), b->d_ctl.p + 2 * t.ctl_off, rows * 8, hipMemcpyDeviceToHost));
+                        int64_t cells = 0;
+                        ok = cls >= 0 && is_register_class(cls) && build_stair_schedule(sg, kClassTab[cls].R, kClassTab[cls].NW, want_ctl.data(), &cells) &&
+                             ctl == want_ctl;
+                        if (!ok && std::getenv("NPR_TIMING")) {
+                            size_t q = 0;
+                            while (q < 2 * rows && ctl[q] == want_ctl[q]) ++q;
+                            std::fprintf(stderr, "[npr plan check] class %d, control word %zu of %zu: device %08x host %08x\n", cls, q, 2 * rows,
+                                         q < 2 * rows ? ctl[q] : 0u, q < 2 * rows ? want_ctl[q] : 0u);
+                        }
+                    }
+                    if (ok && t.tile_off >= 0) {
+                        const int R = kClassTab[kTileClass].R;
+                        const size_t S = static_cast<size_t>(stripes_of(sg, R)) + 1;
+                        st.resize(S), want_st.assign(S, Stripe{});
+                        HIP_TRY(ctx, hipMemcpy(st.data(), b->d_stripes.p + t.tile_off, S * sizeof(Stripe), hipMemcpyDeviceToHost));
+                        build_stripes(sg, R, want_st.data(), nullptr);
+                        ok = std::memcmp(st.data(), want_st.data(), S * sizeof(Stripe)) == 0;
+                        if (ok && R == 2) {  // the packed lane masks of every row
+                            const size_t nrows = static_cast<size_t>(want_st[0].K);
+                            std::vector<uint32_t> rm(nrows), want_rm(nrows, 0);
+                            if (nrows) HIP_TRY(ctx, hipMemcpy(rm.data(), b->d_rowmask.p + t.rowmask_off, nrows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                            for (size_t q = 1; q < S; ++q)
+                                for (int32_t d = want_st[q].df; d <= want_st[q].dl; ++d)
+                                    want_rm[want_st[q].row0 + static_cast<uint32_t>(d - want_st[q].df)] = tile_row_word(d, sg.lo[d], sg.n[d], want_st[q].X);
+                            ok = rm == want_rm;
+                            if (!ok && std::getenv("NPR_TIMING")) std::fprintf(stderr, "[npr plan check] row masks differ (%zu rows)\n", nrows);
+                        }
+                        if (!ok && std::getenv("NPR_TIMING"))
+                            for (size_t q = 0; q < S; ++q)
+                                if (std::memcmp(&st[q], &want_st[q], sizeof(Stripe)) != 0) {
+                                    std::fprintf(stderr, "[npr plan check] stripe entry %zu of %zu: device X %d K %d df %d dl %d row0 %u | host X %d K %d df %d dl %d row0 %u\n", q, S,
+                                                 st[q].X, st[q].K, st[q].df, st[q].dl, st[q].row0, want_st[q].X, want_st[q].K, want_st[q].df, want_st[q].dl, want_st[q].row0);
+                                    break;
+                                }
+                    }
+                }
+                if (!ok && mismatches < 4 && std::getenv("NPR_TIMING"))
+                    std::fprintf(stderr, "[npr plan check] read %lld segment %d differs (D %d, widest band row n/a, ctl %lld, stripes %lld)\n", (long long)i, s,
+                                 t.D, (long long)t.ctl_off, (long long)t.tile_off);
+                mismatches += ok ? 0 : 1;
+            }
+        }
+        return mismatches;
+    } catch (const std::exception &) {
+        return fail(ctx, NPR_ERR_NOMEM, "npr_batch_plan_check: out of host memory");
+    }
+}
+
 }  // extern "C"
