@@ -432,6 +432,82 @@ int32_t npr_pileup_counts(npr_pileup *pl, int32_t *counts /* [sum ref_len][NPR_P
  * cross PCIe instead of 32. */
 int32_t npr_pileup_depth(npr_pileup *pl, int32_t *depth /* [sum ref_len] */, uint8_t *covered /* [sum ref_len] */);
 
+/* ---- alignment-quality tables on the device (the reference's QualiMap analysis, nanopore/analyses/qualimap.py) ----
+ * The reference converts the SAM file to BAM, sorts it and shells out to the Java `qualimap bamqc`.  Here the statistics are
+ * defined in exact integer terms and counted where the data already lies: npr_pileup_coverage reduces a pileup's table,
+ * npr_align_quality makes one pass over the records with the reference bases beside them.
+ *
+ * Rows.  Reference positions are rows of the concatenated sequences, as for npr_pileup_create; T is the sum of ref_len.
+ *
+ * Windows.  W = n_windows, 1 <= W <= NPR_AQ_MAX_WINDOWS (65536).  Window w holds the rows [w * T / W, (w + 1) * T / W),
+ * integer division; equivalently row r lies in window ((r + 1) * W - 1) / T.  Windows ignore sequence boundaries, as
+ * QualiMap's do.  When W > T some windows are empty; T == 0 is legal (every window is empty).
+ *
+ * Bins.  bin(v) is the position bin of npr_read_quality (NPR_RQ_POS_BINS = 336: exact below 16, then sixteen per octave,
+ * everything from 2^24 on in bin 335).
+ *
+ * Base codes.  npr_encode_bases': A C G T -> 0..3 in either letter case, anything else -> 4.
+ *
+ * Output.  Every table is int64, exact, overwritten, and the same from run to run.
+ *
+ * npr_pileup_coverage runs over the table of `pl` as npr_pileup_counts would return it (the difference array summed).
+ * ref / ref_off are the ASCII reference sequences in the pileup's order: sequence k = ref[ref_off[k] .. ref_off[k + 1]),
+ * and ref_off[k + 1] - ref_off[k] must be the pileup's ref_len[k].  With depth = words 0-4 of a row summed:
+ *   win[w][NPR_AQ_WIN_WORDS = 8] over the rows of window w:  [0] rows  [1] sum of depth  [2] sum of depth^2
+ *     [3] rows with depth >= 1  [4] reference G + C  [5] reference A + C + G + T  [6] record starts (word 7 of the table)
+ *     [7] deletion columns (word 5)
+ *   depth_hist[336]: one count per row at bin(depth), depth 0 included.
+ *   start_hist[336]: one count per row at bin(word 7) -- the duplication table: how many positions begin k records.
+ *   totals[NPR_AQ_TOTALS = 8]: rows, depth sum, largest depth, rows with depth >= 1, largest start count, records (sum of
+ *     word 7), deletion columns (sum of word 5), insertion markers (sum of word 6).  The two largest values are 0 when T == 0.
+ * The largest depth is reduced first: when largest depth^2 x rows of the longest window >= 2^63 the call returns
+ * NPR_ERR_CAPACITY and writes nothing (word 2 of a window is the first sum that could leave int64).  A bad n_windows, a null
+ * pointer or a length that is not the pileup's: NPR_ERR_INVALID, checked on the host before any launch, nothing written.
+ *
+ * npr_align_quality takes the records exactly as npr_pileup_add takes them (ref_index .. use), and with them mapq[i], an
+ * int32 in 0..255, and clip[2 * i], clip[2 * i + 1] in [0, 2^42), the soft-clipped bases before and after
+ * read[read_begin[i] .. read_end[i]).  ref / ref_off are the n_refs reference sequences as ASCII (ref_off[0] may be any
+ * position of `ref`; ref_off never decreases); they give the rows.  A record's position in its read counts from the start
+ * of SEQ: p = clip[2 * i] + start[2 * i + 1] + offset, offset = the read bases its cigar has consumed.  A run is a cigar
+ * operation of length >= 1; every run is taken alone (2I3I is two I runs).  Over the counted records:
+ *   mapq_hist[256]: one count per record.
+ *   win_mapq[W][2]: [0] the M columns in the window, [1] the sum of the record's MAPQ over those columns; an M run adds
+ *     overlap and overlap x mapq to each window it overlaps.
+ *   pos_base[336][5]: every read base an M or I run consumes, at [bin(p)][code].
+ *   clip_hist[336]: every soft-clipped read position at bin(p): the positions [0, clip[2 * i]) and the clip[2 * i + 1]
+ *     positions from clip[2 * i] + (read_end[i] - read_begin[i]) on.
+ *   gc_hist[102]: one count per record whose read[read_begin[i] .. read_end[i]) is not empty, over those bases, by the
+ *     column rule of npr_read_quality's gc_hist.
+ *   indel[2][5]: kind (0 an I run, 1 a D run) by class, below.      indel_len[2][336]: kind by bin(run length).
+ *   totals[NPR_AQ_TOTALS = 8]: records counted, M columns, I runs, inserted bases, D runs, deleted bases, soft-clipped
+ *     bases, records with a clip.
+ * Classes (NPR_AQ_HOMOPOLYMER = 3): 0..3 = inside a homopolymer of A C G T, 4 = everything else.  x = the reference row of
+ * the next column at the run (for an I run before the record's first column: the record's start).  For a code b < 4,
+ * l = how many of the rows x - 1, x - 2, ... in a row hold code b, r = how many rows in a row hold b to the right, from x
+ * for an I run and from x + length for a D run; both are counted inside the record's own sequence only and stop at
+ * NPR_AQ_HOMOPOLYMER.  An I run whose inserted read bases all have one code b < 4 is class b when l + r >= 3; a D run whose
+ * deleted reference bases all have one code b < 4 is class b when l + length + r >= 3; every other run is class 4.
+ * Invalid records, the rule of npr_pileup_add: a selected record that is malformed (as there; also a MAPQ outside 0..255 or
+ * a clip outside its range) or whose cigar runs past its read or its reference sequence adds NOTHING -- it is checked before its
+ * first add -- and makes the call return NPR_ERR_INVALID; the other records are counted and every table is written.
+ * Checked on the host, nothing written: a bad n_windows, n_refs < 0 or ref_off that decreases, a null pointer the call
+ * needs, operation offsets that decrease.  n_reads == 0 is legal (zero tables). */
+#define NPR_AQ_MAX_WINDOWS 65536
+#define NPR_AQ_WIN_WORDS 8
+#define NPR_AQ_TOTALS 8
+#define NPR_AQ_HOMOPOLYMER 3
+#define NPR_AQ_TILE 2048 /* consecutive rows a workgroup of the coverage kernel takes */
+int32_t npr_pileup_coverage(npr_pileup *pl, const uint8_t *ref, const int64_t *ref_off, int32_t n_windows,
+                            int64_t *win /* [n_windows][NPR_AQ_WIN_WORDS] */, int64_t *depth_hist /* [NPR_RQ_POS_BINS] */,
+                            int64_t *start_hist /* [NPR_RQ_POS_BINS] */, int64_t *totals /* [NPR_AQ_TOTALS] */);
+int32_t npr_align_quality(npr_ctx *ctx, int64_t n_reads, const int32_t *ref_index, const uint8_t *read, const int64_t *read_begin,
+                          const int64_t *read_end, const int32_t *ops, const int64_t *ops_off, const int64_t *start, const uint8_t *use,
+                          const int32_t *mapq, const int64_t *clip /* [n_reads][2] */, int64_t n_refs, const uint8_t *ref,
+                          const int64_t *ref_off, int32_t n_windows, int64_t *mapq_hist /* [256] */,
+                          int64_t *win_mapq /* [n_windows][2] */, int64_t *pos_base /* [NPR_RQ_POS_BINS][5] */,
+                          int64_t *clip_hist /* [NPR_RQ_POS_BINS] */, int64_t *gc_hist /* [NPR_RQ_GC_COLS] */, int64_t *indel /* [2][5] */,
+                          int64_t *indel_len /* [2][NPR_RQ_POS_BINS] */, int64_t *totals /* [NPR_AQ_TOTALS] */);
+
 /* ---- exact-match seeding on the device: the local hits a base mapper hands to chainSamFile ----
  * The reference's base mappers (last, bwa, lastz, blasr) are external binaries and not part of this build; this is the build's own
  * mapper (nanopore_amd/mappers/seedMapper.py), behind the C ABI like every other stage.  Base codes are npr_encode_bases': A C G T ->

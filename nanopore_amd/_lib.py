@@ -51,6 +51,8 @@ KMER_MAX_K = 6    # the k-mer tables: 4^k + 1 bins, the last one for k-mers with
 KMER_MAX_GROUPS = 64  # npr_kmer_counts_groups: tables of one call
 RQ_POS_BINS, RQ_QUAL_COLS, RQ_GC_COLS, RQ_TOTALS = 336, 95, 102, 8  # NPR_RQ_*: the read-quality tables (npr_read_quality)
 RQ_MAX_GROUPS, RQ_TILE = 8, 2048  # NPR_RQ_MAX_GROUPS; NPR_RQ_TILE: positions of one read a workgroup of its kernel takes per step
+AQ_MAX_WINDOWS, AQ_WIN_WORDS, AQ_TOTALS, AQ_HOMOPOLYMER = 65536, 8, 8, 3  # NPR_AQ_*: the alignment-quality tables (npr_pileup_coverage, npr_align_quality)
+AQ_TILE = 2048    # NPR_AQ_TILE: consecutive rows a workgroup of the coverage kernel takes
 SAM_COLS = 16     # NPR_SAM_COLS
 SEED_MIN_K, SEED_MAX_K = 8, 32  # npr_seed_index_create: the k of a seed index
 SEED_MAP_LDS_ROWS = 4096  # NPR_SEED_MAP_LDS_ROWS: a read of at most so many rows is sorted in LDS by npr_seed_map_create, a longer one in global memory
@@ -163,6 +165,8 @@ SIGNATURES = {
     "npr_pileup_add": (i32, [vp, i64] + [vp] * 8),
     "npr_pileup_counts": (i32, [vp, vp]),
     "npr_pileup_depth": (i32, [vp, vp, vp]),
+    "npr_pileup_coverage": (i32, [vp, vp, vp, i32] + [vp] * 4),
+    "npr_align_quality": (i32, [vp, i64] + [vp] * 10 + [i64, vp, vp, i32] + [vp] * 8),
     "npr_seed_index_create": (i32, [vp, i32, i64, vp, vp, _out]),
     "npr_seed_index_destroy": (None, [vp]),
     "npr_seed_matches": (i64, [vp, i64, i32, i64, vp, vp, vp, vp, vp, i64]),

@@ -53,6 +53,49 @@ def pileup_of_sam(ctx, samFile, referenceFastaFile):
     return names, lengths, pileup
 
 
+def alignment_quality_of_sam(ctx, samFile, referenceFastaFile, n_windows=400):
+    """-> (names, ref_lengths, Coverage, AlignQuality): the alignment-quality tables of the QualiMap analysis (include/nprealign.h:
+    npr_pileup_coverage, npr_align_quality) over the records pileup_of_sam keeps -- samtools' flag mask, records with a reference --
+    from ONE parse of the file: the pileup is built and reduced to windows, and the same arrays go through the per-record pass with
+    MAPQ and the soft clips of either end.  Rows and windows are in the order of the header's @SQ lines."""
+    sam = ingest.SamText(samFile)
+    names, lengths = list(sam.references), np.asarray(sam.lengths, dtype=np.int64)
+    fasta = ingest.FastaTable(referenceFastaFile)
+    ref_off = np.zeros(len(names) + 1, dtype=np.int64)
+    np.cumsum(lengths, out=ref_off[1:])
+    ref_text = np.zeros(max(int(ref_off[-1]), 1), dtype=np.uint8)
+    for i, (name, length) in enumerate(zip(names, lengths)):
+        if name not in fasta.index:
+            raise KeyError("%s: @SQ sequence %r is not in %s" % (samFile, name, referenceFastaFile))
+        k = fasta.index[name]
+        if int(fasta.off[k + 1] - fasta.off[k]) != int(length):
+            raise ValueError("%s: @SQ sequence %r has LN %d, %s holds %d bases" % (samFile, name, length, referenceFastaFile, fasta.off[k + 1] - fasta.off[k]))
+        ref_text[ref_off[i]:ref_off[i + 1]] = fasta.seq[fasta.off[k]:fasta.off[k + 1]]
+    fields = sam.parse()
+    n = len(fields)
+    with_reference = sam.records_with_a_reference(fields, sam.span) if n else np.zeros(0, dtype=bool)
+    use = with_reference & kept_by_samtools(fields[:, ingest.F_FLAG])
+    ops_off, ops = sam.guides(fields)
+    start = np.zeros((n, 2), dtype=np.int64)
+    start[:, 0] = fields[:, ingest.F_POS]
+    tid = np.where(with_reference, fields[:, ingest.F_TID], 0)
+    # the clips as the parse gives them; an unselected record's may be anything: they are not looked at
+    clip = np.zeros((n, 2), dtype=np.int64)
+    clip[:, 0] = np.where(use, fields[:, ingest.F_QUERY_LO] - fields[:, ingest.F_SEQ_LO], 0)
+    clip[:, 1] = np.where(use, fields[:, ingest.F_SEQ_HI] - fields[:, ingest.F_QUERY_HI], 0)
+    mapq = np.where(use, fields[:, ingest.F_MAPQ], 0)
+    pileup = ctx.pileup(lengths)
+    try:
+        if n:
+            pileup.add_csr(sam.text, fields[:, ingest.F_QUERY_LO], fields[:, ingest.F_QUERY_HI], ops, ops_off, tid, start=start, use=use)
+        coverage = pileup.coverage(ref_text, ref_off, n_windows)
+    finally:
+        pileup.close()
+    quality = ctx.align_quality(sam.text, fields[:, ingest.F_QUERY_LO], fields[:, ingest.F_QUERY_HI], ops, ops_off, tid, mapq, clip, ref_text, ref_off,
+                                start=start, use=use, n_windows=n_windows)
+    return names, lengths, coverage, quality
+
+
 def depth_text(names, ref_lengths, depth, covered):
     """The text of `samtools depth`: `name\\t1-based position\\tdepth\\n` for every covered position (one with an M or a
     deletion column; a position under deletions alone has depth 0), sequences in the given order."""

@@ -332,6 +332,45 @@ int launch_pileup_add(const PileupArgs &a, void *stream);
 int64_t pileup_scan_tiles(int64_t n_slots);
 int launch_pileup_scan(const PileupScanArgs &a, void *stream);
 int launch_pileup_depth(const int32_t *tab, int64_t rows, int32_t *depth, uint8_t *covered, void *stream);
+// alignment-quality tables (npr_alnqual.hip; the definitions: include/nprealign.h, npr_pileup_coverage and npr_align_quality)
+constexpr int AQ_WIN_WORDS = 8, AQ_TOTALS = 8, AQ_HOMOPOLYMER = 3, AQ_MAX_WINDOWS = 65536, AQ_MAPQ_COLS = 256, AQ_CLASSES = 5;
+constexpr int AQ_TILE = 2048;  // consecutive rows of the pileup's table one workgroup of k_pileup_coverage takes
+struct CoverageArgs {  // k_coverage_max, then k_pileup_coverage
+    const int32_t *tab;      // [rows][NPR_PILEUP_WORDS], word 5 summed
+    const uint8_t *ref;      // [rows] ASCII, the sequences back to back
+    int64_t rows;            // T
+    int32_t n_windows;       // W
+    unsigned long long *max_depth;  // one word, zeroed: k_coverage_max
+    // zeroed, added to: win [W][AQ_WIN_WORDS], depth_hist / start_hist [RQ_POS_BINS], totals [AQ_TOTALS] (word 2 is left to the host)
+    unsigned long long *win, *depth_hist, *start_hist, *totals;
+};
+int launch_coverage_max(const CoverageArgs &a, void *stream);
+int launch_pileup_coverage(const CoverageArgs &a, void *stream);
+struct AlnQualRec {
+    int64_t row0;      // table row of the record's first reference position
+    int64_t s0, s1;    // rows of the record's reference sequence: [s0, s1)
+    int64_t y_off;     // read[read_begin] of the record in AlnQualArgs::seq
+    int64_t clip0, clip1;
+    int32_t xlen;      // reference positions from row0 to the end of the sequence; < 0: the record is not selected
+    int32_t span;      // read_end - read_begin
+    int32_t sy;        // read position the cigar starts at (<= span)
+    int32_t mapq;
+};
+constexpr size_t AQ_TABLE_WORDS = AQ_MAPQ_COLS + static_cast<size_t>(RQ_POS_BINS) * RQ_BASE_COLS + RQ_POS_BINS + RQ_GC_COLS + 2 * AQ_CLASSES + 2 * RQ_POS_BINS + AQ_TOTALS;
+struct AlnQualArgs {  // k_align_quality
+    int64_t n;
+    const int64_t *ops_off;  // [n + 1]
+    const uint32_t *ops;     // one word per cigar op: length << 2 | op
+    const AlnQualRec *recs;
+    const uint8_t *seq;      // read bases, ASCII
+    const uint8_t *ref;      // [rows] ASCII, the sequences back to back
+    int64_t rows;            // T
+    int32_t n_windows;       // W
+    unsigned long long *tab; // [AQ_TABLE_WORDS] zeroed, added to: mapq_hist, pos_base, clip_hist, gc_hist, indel, indel_len, totals in this order
+    unsigned long long *win_mapq;  // [W][2] zeroed, added to
+    int32_t *bad;            // set to 1 when a record's cigar runs past what it has (the record adds nothing)
+};
+int launch_align_quality(const AlnQualArgs &a, void *stream);
 // exact-match seeding (npr_seed.hip).  A set of sequences lies in a CODE BUFFER: one separator byte, then every sequence followed by one
 // separator, then NPR_SEED_PAD more separators; sequence s of ASCII offsets off[] starts at off[s] + s + 1.  Bases A C G T are 0..3; every
 // other byte of the two buffers that meet has a value of its own side (reference: other base 4, separator 6; read: 5 and 7), so that

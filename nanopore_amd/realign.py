@@ -67,6 +67,45 @@ class ReadQuality(object):
         return ReadQuality(*[a[g] for a in self.arrays()])
 
 
+class _Tables(object):
+    """A set of int64 tables an entry point fills: FIELDS names them, in the order of its signature."""
+    FIELDS = ()
+
+    def __init__(self, *arrays):
+        if len(arrays) != len(self.FIELDS):
+            raise ValueError("one array per field: %s" % ", ".join(self.FIELDS))
+        for f, a in zip(self.FIELDS, arrays):
+            setattr(self, f, a)
+
+    def arrays(self):
+        return [getattr(self, f) for f in self.FIELDS]
+
+
+class Coverage(_Tables):
+    """The four int64 tables of npr_pileup_coverage (include/nprealign.h defines them): win [W, 8], depth_hist [336], start_hist [336],
+    totals [8]."""
+    FIELDS = ("win", "depth_hist", "start_hist", "totals")
+    TILE = _lib.AQ_TILE  # consecutive rows a workgroup of the kernel takes
+
+    @classmethod
+    def zeros(cls, n_windows):
+        B = _lib.RQ_POS_BINS
+        return cls(*[np.zeros(shape, dtype=np.int64) for shape in ((n_windows, _lib.AQ_WIN_WORDS), (B,), (B,), (_lib.AQ_TOTALS,))])
+
+
+class AlignQuality(_Tables):
+    """The eight int64 tables of npr_align_quality (include/nprealign.h defines them): mapq_hist [256], win_mapq [W, 2], pos_base [336, 5],
+    clip_hist [336], gc_hist [102], indel [2, 5], indel_len [2, 336], totals [8].  `invalid`: some record was malformed or ran past its
+    sequences and was left out (only a call with allow_invalid hands such tables back)."""
+    FIELDS = ("mapq_hist", "win_mapq", "pos_base", "clip_hist", "gc_hist", "indel", "indel_len", "totals")
+    invalid = False
+
+    @classmethod
+    def zeros(cls, n_windows):
+        B = _lib.RQ_POS_BINS
+        return cls(*[np.zeros(shape, dtype=np.int64) for shape in ((256,), (n_windows, 2), (B, 5), (B,), (_lib.RQ_GC_COLS,), (2, 5), (2, B), (_lib.AQ_TOTALS,))])
+
+
 def _csr_ops(guides):
     lens = np.fromiter((len(g) for g in guides), dtype=np.int64, count=len(guides))
     off = np.zeros(len(guides) + 1, dtype=np.int64)
@@ -417,6 +456,19 @@ class Pileup(_Handle):
         check(self._L.npr_pileup_depth(self._h, ptr(depth), ptr(covered)), "npr_pileup_depth", self.ctx)
         return depth, covered.astype(bool)
 
+    def coverage(self, ref_text, ref_off, n_windows=400, out=None):
+        """The table so far reduced on the device to windows of the concatenated reference, a depth histogram, the histogram of record
+        starts per position and totals (include/nprealign.h: npr_pileup_coverage, which defines every word).  ref_text / ref_off: the ASCII
+        reference sequences in the pileup's order, sequence k = ref_text[ref_off[k]:ref_off[k + 1]] (FastaTable.seq / .off when the file
+        holds them in that order).  -> Coverage; `out`: a Coverage to fill."""
+        ref_text, ref_off = _arr(ref_text, np.uint8), _arr(ref_off, np.int64)
+        if len(ref_off) != len(self.ref_lengths) + 1 or (len(ref_off) and (int(ref_off[0]) < 0 or int(ref_off[-1]) > len(ref_text))):
+            raise NprError(_lib.ERR_INVALID, "npr_pileup_coverage", "one offset per sequence and the end, inside the reference text")
+        if out is None:
+            out = Coverage.zeros(n_windows if 1 <= n_windows <= _lib.AQ_MAX_WINDOWS else 1)
+        check(self._L.npr_pileup_coverage(self._h, ptr(ref_text), ptr(ref_off), int(n_windows), *map(ptr, out.arrays())), "npr_pileup_coverage", self.ctx)
+        return out
+
 
 class SeedIndex(_Handle):
     """The exact-match seed index of a set of reference sequences on the device (include/nprealign.h: npr_seed_*; csrc/npr_seed.hip):
@@ -644,6 +696,33 @@ class Context(object):
         out = ReadQuality.zeros(n_groups if 1 <= n_groups <= _lib.RQ_MAX_GROUPS else 1)
         cols = [np.ascontiguousarray(a) for a in (seq_span[:, 0], seq_span[:, 1], qual_span[:, 0], qual_span[:, 1])]
         check(self._L.npr_read_quality(self._h, n, ptr(text), *map(ptr, cols), ptr(group), int(n_groups), *map(ptr, out.arrays())), "npr_read_quality", self)
+        return out
+
+    def align_quality(self, read, read_begin, read_end, ops, ops_off, ref_index, mapq, clip, ref_text, ref_off, start=None, use=None, n_windows=400,
+                      out=None, allow_invalid=False):
+        """The per-record alignment-quality tables of the QualiMap analysis, counted on the device in one pass over the records
+        (include/nprealign.h: npr_align_quality, which defines every table).  The records as Pileup.add_csr takes them; mapq[i] = MAPQ of
+        record i, clip[i] = (soft-clipped bases before, after read[read_begin[i]:read_end[i]]); ref_text / ref_off = the ASCII reference
+        sequences ref_index points into.  A record that is malformed or runs past its sequences is left out and raises NprError, unless
+        allow_invalid: then the tables of the other records come back with .invalid set.  -> AlignQuality; `out`: an AlignQuality to fill."""
+        read, read_begin, read_end = _arr(read, np.uint8), _arr(read_begin, np.int64), _arr(read_end, np.int64)
+        ops, ops_off = _arr(ops, np.int32, 2), _arr(ops_off, np.int64)
+        n = len(ops_off) - 1
+        ri, st, u = _arr(ref_index, np.int32), _arr(start, np.int64, 2), _arr(use, np.uint8)
+        mq, cl = _arr(mapq, np.int32), _arr(clip, np.int64, 2)
+        ref_text, ref_off = _arr(ref_text, np.uint8), _arr(ref_off, np.int64)
+        if n < 0 or len(ri) != n or len(read_begin) != (n + 1 if read_end is None else n) or (read_end is not None and len(read_end) != n) or \
+                (st is not None and len(st) != n) or (u is not None and len(u) != n) or len(mq) != n or len(cl) != n:
+            raise ValueError("one reference index, read, start, use, mapq and clip entry per cigar")
+        if len(ref_off) < 1 or int(ref_off[0]) < 0 or int(ref_off[-1]) > len(ref_text):
+            raise NprError(_lib.ERR_INVALID, "npr_align_quality", "the reference offsets lie outside the reference text")
+        if out is None:
+            out = AlignQuality.zeros(n_windows if 1 <= n_windows <= _lib.AQ_MAX_WINDOWS else 1)
+        rc = self._L.npr_align_quality(self._h, n, ptr(ri), ptr(read), ptr(read_begin), ptr(read_end), ptr(ops), ptr(ops_off), ptr(st), ptr(u), ptr(mq),
+                                       ptr(cl), len(ref_off) - 1, ptr(ref_text), ptr(ref_off), int(n_windows), *map(ptr, out.arrays()))
+        out.invalid = rc == _lib.ERR_INVALID
+        if not (allow_invalid and out.invalid):
+            check(rc, "npr_align_quality", self)
         return out
 
     def align_indel_kmers(self, refs, reads, cigars, k=5, ref_index=None, start=None):
