@@ -668,7 +668,7 @@ int32_t npr_pileup_snp_calls(npr_pileup *pl, const uint8_t *ref_code, const uint
 /* ---- SNP variants on the device: the calls themselves and a consensus, from the same posteriors ----
  * The tables, the row layout, evolution16 and the posterior are those of the npr_*_snp_calls block above, for ONE error model
  * (error16 [candidate][observed], 16 entries) and without a truth.  Instead of histograms two things leave the device
- * (csrc/npr_snpcall.hip: k_snp_variants_count, _scan, _emit): a best base and its quality per row, and the list of calls.
+ * (csrc/npr_snpcall.hip: k_snp_variants_count, a scan, k_snp_variants_emit): a best base and its quality per row, and the list of calls.
  * A row is CALLABLE when it is seen, total = ((w0+w1)+w2)+w3 != 0 and its reference base is A/C/G/T.  For a callable row, in fp64:
  *   lp[c]  = log evolution[ref][c] + sum_o (w[o] / total) log error[c][o]     (o = 0..3 added in that order, starting from 0)
  *   e[c]   = exp(lp[c] - max_c lp[c]),   sum = ((e0+e1)+e2)+e3,   p[c] = e[c] / sum

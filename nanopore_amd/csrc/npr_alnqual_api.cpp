@@ -22,9 +22,7 @@ int32_t npr_pileup_coverage(npr_pileup *pl, const uint8_t *ref, const int64_t *r
     return guarded(ctx, "npr_pileup_coverage", [&](const Call &dev) -> int32_t {
         std::vector<int64_t> out(words, 0);
         if (T > 0) {
-            const int64_t n_slots = T + n_refs;
-            const PileupScanArgs scan{n_slots, n_refs, pileup_scan_tiles(n_slots), pl->dbase.p, pl->diff.p, pl->tile.p, pl->tab.p};
-            dev.launched(launch_pileup_scan(scan, ctx->stream), "k_pileup_scan");
+            pileup_scan(dev, pl);
             DevBuf<uint8_t> d_ref;
             DevBuf<unsigned long long> d_out;
             dev.upload(d_ref, ref + ref_off[0], static_cast<size_t>(T));

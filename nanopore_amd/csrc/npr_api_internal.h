@@ -641,7 +641,7 @@ struct PiecedFetch {
 int32_t fetch_pieced(npr_ctx *ctx, const PiecedFetch &f);
 int32_t fetch_device_words(npr_batch *b);                  // npr_cigtext_api.cpp: the packed words such a finish left on the device, while they are there
 // npr_seedchain_api.cpp: the chain kernels on rows and chain spans that lie on the device, wherever they came from (npr_seed_chains uploads
-// them, npr_seed_map_create made them there).  count: k_chain_dp, k_chain_trace<false>, k_chain_scan; `chains` and `n_ops` (the guides'
+// them, npr_seed_map_create made them there).  count: k_chain_dp, k_chain_trace<false>, the scan; `chains` and `n_ops` (the guides'
 // offsets) are final and `pairs` is on the host.  write: k_chain_trace<true> into `ops`; queued on the context's stream, not waited for.
 struct SeedChainRun {
     DevBuf<int32_t> node, back, run_end, chains, ops;
@@ -658,6 +658,7 @@ void seed_stage_reads(const Call &dev, int32_t strands, int64_t n_reads, const u
                       DevBuf<uint8_t> &fwd, DevBuf<uint8_t> &rev, DevBuf<int64_t> &d_off);
 SeedMatchArgs seed_match_args(const npr_seed_index *ix, int64_t min_len, const std::vector<int64_t> &off, const int64_t *d_off, uint32_t *d_count, const int64_t *d_hit_off);
 void seed_match_pass(const Call &dev, SeedMatchArgs &a, int32_t strands, const uint8_t *fwd, const uint8_t *rev, bool emit);
+void pileup_scan(const Call &dev, npr_pileup *pl);         // npr_pileup_api.cpp: word 5 of the pileup's table from its difference array
 // npr_stats_api.cpp: a set of reads' cigars packed on the device (one word per operation, off[n + 1]), with the upload it may own ...
 struct DeviceCigars {
     const uint32_t *ops = nullptr;

@@ -1,4 +1,4 @@
-// npr_cigtext.hip -- k_cigtext_len, k_cigtext_tile_sums / k_cigtext_tile_offsets / k_cigtext_scan, k_cigtext_write: the SAM CIGAR text of packed
+// npr_cigtext.hip -- k_cigtext_len, the scan of the lengths (npr_scan.h), k_cigtext_write: the SAM CIGAR text of packed
 // cigars (one word per operation, length << 2 | op) where the words lie in HBM -- the per-record text work of the reference's writer loop
 // (nanopore/analyses/utils.py:597-605: `aR.cigar = ...; outputSam.write(aR)`, pysam's cigarstring grammar: decimal length, then M / I / D, "*" for
 // an empty cigar).  Byte for byte what npr_format_cigars_packed (npr_text.cpp) writes on the host; include/nprealign.h: npr_cigar_text_packed,
@@ -7,8 +7,8 @@
 // Three steps, all integer work, ordinary vector stores only, no atomics: the output does not depend on the order anything runs in.
 //   lengths  k_cigtext_len: one wavefront per list, a lane per operation 64 at a time; the list's length is the sum of (decimal digits + 1), 1 for an
 //            empty list.  An operation code 3 sets *bad (every writer stores the same 1).
-//   offsets  the exclusive running sum of the n lengths, in place, as int64 (a batch's text can pass 2^31 bytes): the three-pass scan of
-//            npr_pileup.hip (tile sums; their running sum in one workgroup with a carry; every tile on top of its offset).  On the device and
+//   offsets  the exclusive running sum of the n lengths, in place, as int64 (a batch's text can pass 2^31 bytes): the tiled scan of
+//            npr_scan.h (tile sums; their running sum in one workgroup with a carry; every tile on top of its offset).  On the device and
 //            not on the host: the host has to wait for the total before it can size the text's buffers whichever side scans, and with the scan
 //            here that wait fetches what the caller is given anyway (the offsets, 8 bytes per list) and nothing goes back up -- a host scan would
 //            fetch the lengths and upload the offsets before the write pass could start.  The two were not timed against each other.
@@ -33,8 +33,6 @@ namespace {
 constexpr int WAVE = 64;
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / WAVE;
-constexpr int SCAN_PER_THREAD = 8;
-constexpr int SCAN_TILE = THREADS * SCAN_PER_THREAD;
 constexpr int OPS_PER_LANE = 4;
 constexpr int TILE_OPS = WAVE * OPS_PER_LANE;
 constexpr int TILE_BYTES = 3 + 11 * TILE_OPS;  // up to three bytes of misalignment, ten digits and a letter per operation
@@ -51,19 +49,10 @@ __device__ __forceinline__ int wave_scan(int v, int lane) {  // inclusive
     }
     return v;
 }
-__device__ __forceinline__ int64_t wave_scan64(int64_t v, int lane) {  // inclusive
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const int64_t t = __shfl_up(v, o, WAVE);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
 __device__ __forceinline__ int64_t list_ops(const CigTextArgs &a, int64_t i) { return a.n_ops ? a.n_ops[i] : a.word_off[i + 1] - a.word_off[i]; }
 
 __global__ void __launch_bounds__(THREADS) k_cigtext_len(CigTextArgs a) {
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.str_off[a.n] = 0;  // (the scan runs over n + 1 entries: the last one becomes the total)
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * WAVES + wv; i < a.n; i += static_cast<int64_t>(gridDim.x) * WAVES) {
         const int64_t m = list_ops(a, i);
         const uint32_t *src = a.words + a.word_off[i];
@@ -80,67 +69,6 @@ __global__ void __launch_bounds__(THREADS) k_cigtext_len(CigTextArgs a) {
             a.str_off[i] = k ? k : 1;  // an empty cigar is "*"
             if (other) *a.bad = 1;
         }
-    }
-}
-
-// ---- the exclusive running sum of str_off[0 .. n], in place ----
-__device__ __forceinline__ int64_t block_scan_exclusive(int64_t v, int64_t *lds, int64_t *total) {  // THREADS values, one per thread
-    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    const int64_t inc = wave_scan64(v, lane);
-    __syncthreads();
-    if (lane == WAVE - 1) lds[wv] = inc;
-    __syncthreads();
-    int64_t before = 0, all = 0;
-#pragma unroll
-    for (int q = 0; q < WAVES; ++q) {
-        const int64_t s = lds[q];
-        if (q < wv) before += s;
-        all += s;
-    }
-    *total = all;
-    return before + inc - v;
-}
-
-__global__ void __launch_bounds__(THREADS) k_cigtext_tile_sums(CigTextArgs a) {
-    __shared__ int64_t lds[WAVES];
-    const int64_t j0 = static_cast<int64_t>(blockIdx.x) * SCAN_TILE + static_cast<int64_t>(threadIdx.x) * SCAN_PER_THREAD;
-    int64_t s = 0;
-#pragma unroll
-    for (int q = 0; q < SCAN_PER_THREAD; ++q)
-        if (j0 + q <= a.n) s += a.str_off[j0 + q];
-    int64_t total;
-    (void)block_scan_exclusive(s, lds, &total);
-    if (threadIdx.x == 0) a.tile[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(THREADS) k_cigtext_tile_offsets(CigTextArgs a, int64_t n_tiles) {
-    __shared__ int64_t lds[WAVES];
-    int64_t carry = 0;
-    for (int64_t t0 = 0; t0 < n_tiles; t0 += THREADS) {
-        const int64_t t = t0 + threadIdx.x;
-        const int64_t v = t < n_tiles ? a.tile[t] : 0;
-        int64_t total;
-        const int64_t ex = block_scan_exclusive(v, lds, &total);
-        if (t < n_tiles) a.tile[t] = carry + ex;
-        carry += total;
-    }
-}
-
-__global__ void __launch_bounds__(THREADS) k_cigtext_scan(CigTextArgs a) {
-    __shared__ int64_t lds[WAVES];
-    const int64_t j0 = static_cast<int64_t>(blockIdx.x) * SCAN_TILE + static_cast<int64_t>(threadIdx.x) * SCAN_PER_THREAD;
-    int64_t v[SCAN_PER_THREAD], s = 0;
-#pragma unroll
-    for (int q = 0; q < SCAN_PER_THREAD; ++q) {
-        v[q] = j0 + q <= a.n ? a.str_off[j0 + q] : 0;
-        s += v[q];
-    }
-    int64_t total;
-    int64_t run = a.tile[blockIdx.x] + block_scan_exclusive(s, lds, &total);
-#pragma unroll
-    for (int q = 0; q < SCAN_PER_THREAD; ++q) {
-        if (j0 + q <= a.n) a.str_off[j0 + q] = run;  // (a thread reads its eight entries before it writes them, and nobody else touches them)
-        run += v[q];
     }
 }
 
@@ -196,19 +124,12 @@ __global__ void __launch_bounds__(WAVE) k_cigtext_write(CigTextArgs a) {
 
 }  // namespace
 
-int64_t cigtext_scan_tiles(int64_t entries) { return (entries + SCAN_TILE - 1) / SCAN_TILE; }
-
 int launch_cigtext_offsets(const CigTextArgs &a, void *stream) {
     if (a.n < 0) return static_cast<int>(hipErrorInvalidValue);
-    const int64_t n_tiles = cigtext_scan_tiles(a.n + 1);
-    if (n_tiles >= (int64_t(1) << 31)) return static_cast<int>(hipErrorInvalidValue);
     const int64_t groups = (a.n + WAVES - 1) / WAVES;
     const int grid = static_cast<int>(groups < 1 ? 1 : (groups < (1 << 20) ? groups : (1 << 20)));
     hipLaunchKernelGGL(k_cigtext_len, dim3(grid), dim3(THREADS), 0, static_cast<hipStream_t>(stream), a);
-    hipLaunchKernelGGL(k_cigtext_tile_sums, dim3(static_cast<unsigned>(n_tiles)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), a);
-    hipLaunchKernelGGL(k_cigtext_tile_offsets, dim3(1), dim3(THREADS), 0, static_cast<hipStream_t>(stream), a, n_tiles);
-    hipLaunchKernelGGL(k_cigtext_scan, dim3(static_cast<unsigned>(n_tiles)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), a);
-    return static_cast<int>(hipGetLastError());
+    return launch_scan_tiled<int64_t, int64_t>(a.str_off, a.str_off, a.n, a.tile, stream);
 }
 
 int launch_cigtext_write(const CigTextArgs &a, void *stream) {

@@ -20,7 +20,7 @@ struct TextBufs {
 bool run_cigtext(const Call &dev, int64_t n, const int64_t *d_word_off, const int64_t *d_n_ops, const uint32_t *d_words, bool want_text, int64_t cap, char *lend,
                  size_t lend_bytes, TextBufs &bufs, int64_t *str_off) {
     dev.alloc_cached(bufs.off, n + 1);
-    dev.alloc_cached(bufs.tile, cigtext_scan_tiles(n + 1));
+    dev.alloc_cached(bufs.tile, scan_tiles(n));
     dev.alloc_cached(bufs.bad, 1);
     dev.zero(bufs.bad.p, sizeof(int32_t));
     CigTextArgs a{n, d_word_off, d_n_ops, d_words, bufs.off.p, bufs.tile.p, bufs.bad.p, nullptr};

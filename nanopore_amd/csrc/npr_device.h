@@ -302,6 +302,14 @@ struct ReadQualArgs {
     unsigned long long *pos_qual, *pos_base, *len_hist, *meanq_hist, *gc_hist, *totals;
 };
 int launch_read_quality(const ReadQualArgs &a, void *stream);
+// the integer exclusive prefix sum the analysis units share (the contract and the kernels: npr_scan.h; compiled in npr_scan.hip): out[i] = in[0] + ...
+// + in[i - 1] for i in 0 .. n, in[n] is never read, in == out is allowed for types of one width.  _group: one workgroup, one launch; _tiled: three
+// launches over tiles, `tile` is scratch of scan_tiles(n) entries
+int64_t scan_tiles(int64_t n);
+template <typename In, typename Out>
+int launch_scan_group(const In *in, Out *out, int64_t n, void *stream);
+template <typename In, typename Out>
+int launch_scan_tiled(const In *in, Out *out, int64_t n, Out *tile, void *stream);
 // the device pileup (npr_pileup.hip): NPR_PILEUP_WORDS int32 per reference position, a difference array for the deletion columns
 struct PileupRec {
     int64_t row0;    // table row of the record's first reference position
@@ -322,14 +330,13 @@ struct PileupArgs {  // k_pileup_add
     int32_t *bad;            // set to 1 when a record's cigar runs past what it has (the record adds nothing)
 };
 struct PileupScanArgs {  // the running sum of diff into word 5 of tab
-    int64_t n_slots, n_refs, n_tiles;  // n_slots = rows + n_refs, n_tiles = pileup_scan_tiles(n_slots)
+    int64_t n_slots, n_refs;  // n_slots = rows + n_refs
     const int64_t *dbase;    // [n_refs + 1]: first slot of every sequence (first row + index)
     const int32_t *diff;
-    int32_t *tile;           // [n_tiles] scratch
+    int32_t *tile;           // [scan_tiles(n_slots)] scratch
     int32_t *tab;
 };
 int launch_pileup_add(const PileupArgs &a, void *stream);
-int64_t pileup_scan_tiles(int64_t n_slots);
 int launch_pileup_scan(const PileupScanArgs &a, void *stream);
 int launch_pileup_depth(const int32_t *tab, int64_t rows, int32_t *depth, uint8_t *covered, void *stream);
 // alignment-quality tables (npr_alnqual.hip; the definitions: include/nprealign.h, npr_pileup_coverage and npr_align_quality)
@@ -378,8 +385,8 @@ int launch_align_quality(const AlnQualArgs &a, void *stream);
 constexpr int NPR_SEED_MIN_K = 8, NPR_SEED_MAX_K = 32, NPR_SEED_MAX_KB = 12;
 constexpr int NPR_SEED_PAD = 48;  // a lane loads 32 bytes from its position, an extension step 8 bytes past a separator; rounded so that the buffer ends on 16 bytes
 constexpr uint8_t NPR_SEED_REF_OTHER = 4, NPR_SEED_READ_OTHER = 5, NPR_SEED_REF_SEP = 6, NPR_SEED_READ_SEP = 7;
-constexpr int NPR_SEED_SCAN_TILE = 4096;  // table entries a workgroup scans; the table is allocated in whole tiles
 NPR_HD constexpr int64_t seed_code_bytes(int64_t bases, int64_t n_seqs) { return (bases + n_seqs + 1 + NPR_SEED_PAD + 15) / 16 * 16; }
+constexpr int NPR_SEED_SCAN_TILE = 4096;  // table entries a workgroup of the seed unit's own scan takes; the table is allocated in whole tiles (no bounds check: npr_seed.hip)
 NPR_HD constexpr int64_t seed_table_entries(int kb) { return ((int64_t(1) << (2 * kb)) + 1 + NPR_SEED_SCAN_TILE - 1) / NPR_SEED_SCAN_TILE * NPR_SEED_SCAN_TILE; }
 struct SeedEncodeArgs {  // k_seed_encode: ASCII sequences lying back to back -> a code buffer, and (rc != nullptr) the buffer of their reverse complements
     const uint8_t *ascii;
@@ -434,23 +441,23 @@ struct SeedChainArgs {
     int32_t *back;           // [rows] scratch: the predecessor as an index into the run, -1 none
     int32_t *run_end;        // [2 * n_chains][2] scratch: the row (index into the run) the best chain of a run ends in, and its score
     int32_t *chains;         // [n_chains][4] = reference index, strand, score, rows in the chain
-    int64_t *n_ops;          // [n_chains + 1]: op pairs per chain, then (k_chain_scan) their exclusive prefix
+    int64_t *n_ops;          // [n_chains + 1]: op pairs per chain, then (launch_scan_group) their exclusive prefix
     int32_t *ops;            // [n_ops[n_chains]][2]
 };
-int launch_seed_chain_dp(const SeedChainArgs &a, void *stream);     // k_chain_dp, k_chain_trace<false>, k_chain_scan
+int launch_seed_chain_dp(const SeedChainArgs &a, void *stream);     // k_chain_dp, k_chain_trace<false>, the scan of n_ops
 int launch_seed_chain_write(const SeedChainArgs &a, void *stream);  // k_chain_trace<true>
 // from the rows k_seed_match emitted to the chain spans k_chain_dp takes, on the device (npr_seedmap.hip)
 // (the tier boundary of k_map_sort is NPR_SEED_MAP_LDS_ROWS of include/nprealign.h: a read of at most so many rows is sorted in LDS, one of more in global memory)
 struct SeedMapArgs {
     int64_t n_reads;
     const uint32_t *count;   // [n_reads] what k_seed_match<false> counted
-    int64_t *hit_off;        // [n_reads + 1]: k_map_scan<uint32_t> makes it of count
+    int64_t *hit_off;        // [n_reads + 1]: the exclusive prefix of count
     int32_t *hits;           // [hit_off[n_reads]][4]: k_map_sort sorts every read's rows by (strand, reference index, a, b) in place
-    int64_t *chain_off;      // [n_reads + 1]: k_map_spans<false> writes every read's number of chains, k_map_scan<int64_t> turns them into offsets in place
+    int64_t *chain_off;      // [n_reads + 1]: k_map_spans<false> writes every read's number of chains, the scan turns them into offsets in place
     SeedChainSpan *span;     // [chain_off[n_reads]]: k_map_spans<true>
 };
-int launch_seedmap_offsets(const SeedMapArgs &a, void *stream);  // k_map_scan<uint32_t>
-int launch_seedmap_chains(const SeedMapArgs &a, void *stream);   // k_map_sort, k_map_spans<false>, k_map_scan<int64_t>
+int launch_seedmap_offsets(const SeedMapArgs &a, void *stream);  // launch_scan_group: hit_off of count
+int launch_seedmap_chains(const SeedMapArgs &a, void *stream);   // k_map_sort, k_map_spans<false>, the scan of chain_off
 int launch_seedmap_spans(const SeedMapArgs &a, void *stream);    // k_map_spans<true>
 // SAM CIGAR text of packed cigars on the device (npr_cigtext.hip): list i = words[word_off[i] .. word_off[i] + n_ops[i])
 struct CigTextArgs {
@@ -459,11 +466,10 @@ struct CigTextArgs {
     const int64_t *n_ops;     // [n]; null: list i ends where list i + 1 begins
     const uint32_t *words;    // one word per cigar op: length << 2 | op
     int64_t *str_off;         // [n + 1]: the lengths pass writes every string's length, the scan turns them into offsets in place
-    int64_t *tile;            // [cigtext_scan_tiles(n + 1)] scratch of the scan
+    int64_t *tile;            // [scan_tiles(n)] scratch of the scan
     int32_t *bad;             // set to 1 when a list holds an operation outside M I D
     char *out;                // the write pass: string i at out[str_off[i] .. str_off[i + 1])
 };
-int64_t cigtext_scan_tiles(int64_t entries);
 int launch_cigtext_offsets(const CigTextArgs &a, void *stream);  // lengths + exclusive scan: str_off, *bad
 int launch_cigtext_write(const CigTextArgs &a, void *stream);
 constexpr float EXPECT_FIXED_ONE = 1099511627776.0f;  // 2^40

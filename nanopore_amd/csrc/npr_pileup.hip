@@ -1,4 +1,4 @@
-// npr_pileup.hip -- k_pileup_add, k_pileup_tile_sums / k_pileup_tile_offsets / k_pileup_scan, k_pileup_depth: the per-position table of a set of
+// npr_pileup.hip -- k_pileup_add, k_pileup_scan (on the tile offsets of npr_scan.h), k_pileup_depth: the per-position table of a set of
 // alignments (include/nprealign.h: npr_pileup_*), what the reference gets from `samtools depth` / `samtools mpileup` after writing, converting,
 // sorting and indexing the realigned SAM (nanopore/metaAnalyses/coverageDepth.py:49-65, analyses/consensus.py).
 //
@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "npr_device.h"
+#include "npr_scan.h"
 
 namespace npr {
 namespace {
@@ -31,8 +32,6 @@ namespace {
 constexpr int WAVE = 64;
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / WAVE;
-constexpr int SCAN_PER_THREAD = 8;
-constexpr int SCAN_TILE = THREADS * SCAN_PER_THREAD;
 
 __device__ __forceinline__ uint32_t code_of(uint32_t c) {
     c &= 0xdfu;  // upper case
@@ -121,62 +120,14 @@ __global__ void __launch_bounds__(THREADS) k_pileup_add(PileupArgs a) {
 }
 
 // ---- the running sum of the difference array into word 5 of the table ----
-// Three passes over tiles of SCAN_TILE slots: the tiles' sums; their exclusive running sum (one workgroup, a carry from piece to piece); every
-// tile's own running sum on top of its offset, written to word 5 of the slot's row.  Slot j of sequence k (dbase[k] <= j < dbase[k + 1], dbase[k]
-// = first row of k + k) is row j - k; the last slot of a sequence is the spare one and has no row.
-__device__ __forceinline__ int block_scan_exclusive(int v, int *lds, int *total) {  // THREADS values, one per thread
-    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    const int inc = wave_scan(v, lane);
-    __syncthreads();
-    if (lane == WAVE - 1) lds[wv] = inc;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int q = 0; q < WAVES; ++q) {
-        const int s = lds[q];
-        if (q < wv) before += s;
-        all += s;
-    }
-    *total = all;
-    return before + inc - v;
-}
-
-__global__ void __launch_bounds__(THREADS) k_pileup_tile_sums(PileupScanArgs a) {
-    __shared__ int lds[WAVES];
-    const int64_t j0 = static_cast<int64_t>(blockIdx.x) * SCAN_TILE + static_cast<int64_t>(threadIdx.x) * SCAN_PER_THREAD;
-    int s = 0;
-#pragma unroll
-    for (int q = 0; q < SCAN_PER_THREAD; ++q)
-        if (j0 + q < a.n_slots) s += a.diff[j0 + q];
-    int total;
-    (void)block_scan_exclusive(s, lds, &total);
-    if (threadIdx.x == 0) a.tile[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(THREADS) k_pileup_tile_offsets(PileupScanArgs a) {
-    __shared__ int lds[WAVES];
-    int carry = 0;
-    for (int64_t t0 = 0; t0 < a.n_tiles; t0 += THREADS) {
-        const int64_t t = t0 + threadIdx.x;
-        const int v = t < a.n_tiles ? a.tile[t] : 0;
-        int total;
-        const int ex = block_scan_exclusive(v, lds, &total);
-        if (t < a.n_tiles) a.tile[t] = carry + ex;
-        carry += total;
-    }
-}
-
-__global__ void __launch_bounds__(THREADS) k_pileup_scan(PileupScanArgs a) {
-    __shared__ int lds[WAVES];
-    const int64_t j0 = static_cast<int64_t>(blockIdx.x) * SCAN_TILE + static_cast<int64_t>(threadIdx.x) * SCAN_PER_THREAD;
-    int v[SCAN_PER_THREAD], s = 0;
-#pragma unroll
-    for (int q = 0; q < SCAN_PER_THREAD; ++q) {
-        v[q] = j0 + q < a.n_slots ? a.diff[j0 + q] : 0;
-        s += v[q];
-    }
-    int total;
-    int run = a.tile[blockIdx.x] + block_scan_exclusive(s, lds, &total);
+// The tiled scan of npr_scan.h with a last pass of its own: the tiles' sums, their exclusive running sum (k_scan_tile_sums, k_scan_group), then
+// every tile's INCLUSIVE running sum on top of its offset, written to word 5 of the slot's row.  Slot j of sequence k (dbase[k] <= j < dbase[k + 1],
+// dbase[k] = first row of k + k) is row j - k; the last slot of a sequence is the spare one and has no row.
+__global__ void __launch_bounds__(SCAN_THREADS) k_pileup_scan(PileupScanArgs a) {
+    __shared__ int32_t lds[SCAN_WAVES];
+    const int64_t j0 = scan_first_entry();
+    int32_t v[SCAN_PER_THREAD], total;
+    int32_t run = a.tile[blockIdx.x] + block_scan_exclusive(scan_load(a.diff, a.n_slots, j0, v), lds, &total);
     if (j0 >= a.n_slots) return;
     // the sequence of the thread's first slot: the last k with dbase[k] <= j0
     int64_t lo = 0, hi = a.n_refs - 1;
@@ -216,14 +167,14 @@ int launch_pileup_add(const PileupArgs &a, void *stream) {
     return static_cast<int>(hipGetLastError());
 }
 
-int64_t pileup_scan_tiles(int64_t n_slots) { return (n_slots + SCAN_TILE - 1) / SCAN_TILE; }
-
 int launch_pileup_scan(const PileupScanArgs &a, void *stream) {
     if (a.n_slots <= 0 || a.n_refs <= 0) return 0;
-    if (a.n_tiles >= (int64_t(1) << 31)) return static_cast<int>(hipErrorInvalidValue);
-    hipLaunchKernelGGL(k_pileup_tile_sums, dim3(static_cast<unsigned>(a.n_tiles)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), a);
-    hipLaunchKernelGGL(k_pileup_tile_offsets, dim3(1), dim3(THREADS), 0, static_cast<hipStream_t>(stream), a);
-    hipLaunchKernelGGL(k_pileup_scan, dim3(static_cast<unsigned>(a.n_tiles)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), a);
+    const int64_t tiles = scan_tiles(a.n_slots);
+    if (tiles >= (int64_t(1) << 31)) return static_cast<int>(hipErrorInvalidValue);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL((k_scan_tile_sums<int32_t, int32_t>), dim3(static_cast<unsigned>(tiles)), dim3(SCAN_THREADS), 0, st, a.diff, a.n_slots, a.tile);
+    hipLaunchKernelGGL((k_scan_group<int32_t, int32_t>), dim3(1), dim3(SCAN_THREADS), 0, st, a.tile, a.tile, tiles - 1);
+    hipLaunchKernelGGL(k_pileup_scan, dim3(static_cast<unsigned>(tiles)), dim3(SCAN_THREADS), 0, st, a);
     return static_cast<int>(hipGetLastError());
 }
 

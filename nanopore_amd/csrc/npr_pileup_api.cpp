@@ -18,14 +18,13 @@ int32_t run_pileup_add(const Call &dev, npr_pileup *pl, int64_t n, const DeviceC
     return bad;
 }
 
-// word 5 of the table from the difference array
-void pileup_scan(const Call &dev, npr_pileup *pl) {
+}  // namespace
+
+void npr_impl::pileup_scan(const Call &dev, npr_pileup *pl) {
     const int64_t n_refs = static_cast<int64_t>(pl->len.size()), n_slots = pl->rows + n_refs;
-    const PileupScanArgs a{n_slots, n_refs, pileup_scan_tiles(n_slots), pl->dbase.p, pl->diff.p, pl->tile.p, pl->tab.p};
+    const PileupScanArgs a{n_slots, n_refs, pl->dbase.p, pl->diff.p, pl->tile.p, pl->tab.p};
     dev.launched(launch_pileup_scan(a, dev.ctx->stream), "k_pileup_scan");
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -47,7 +46,7 @@ int32_t npr_pileup_create(npr_ctx *ctx, int64_t n_refs, const int64_t *ref_len, 
         const int64_t n_slots = pl->rows + n_refs;
         dev.alloc(pl->tab, static_cast<size_t>(pl->rows) * NPR_PILEUP_WORDS);
         dev.alloc(pl->diff, static_cast<size_t>(n_slots));
-        dev.alloc(pl->tile, static_cast<size_t>(pileup_scan_tiles(n_slots)));
+        dev.alloc(pl->tile, static_cast<size_t>(scan_tiles(n_slots)));
         dev.alloc(pl->bad, 1);
         dev.zero(pl->tab);
         dev.zero(pl->diff);

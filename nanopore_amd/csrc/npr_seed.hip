@@ -31,18 +31,20 @@
 //   k_seed_encode gives a lane 16 consecutive bytes of the buffer (one search for the first one's sequence, one 16-byte store); the bytes
 //   of the reverse complement leave one by one (they run backwards).
 //   The scan: 4096 entries per workgroup (16 per lane as four 16-byte loads), tile sums, one workgroup over the at most 4097 tile sums,
-//   then the tiles again.  Three launches over 64 MB: a few tens of microseconds at the HBM rate, once per reference.
+//   then the tiles again.  Three launches over 64 MB: a few tens of microseconds at the HBM rate, once per reference.  The unit keeps these
+//   kernels of its own on npr_scan.h's block_scan_exclusive: launch_scan_tiled (8 bounds-checked entries per lane) made npr_seed_index_create
+//   0.07 ms slower on a 4.6 Mb reference (profiles/scan_refactor_time.json), and the whole-tile padding of the table stays with them.
 #include <hip/hip_runtime.h>
 
 #include "npr_device.h"
+#include "npr_scan.h"
 
 namespace npr {
 namespace {
 
-constexpr int WAVE = 64;
 constexpr int THREADS = 256;
 constexpr int RUN = 16;  // bytes of the code buffer per lane of k_seed_encode
-static_assert(NPR_SEED_SCAN_TILE == THREADS * 16, "a lane of the scan holds four 16-byte pieces of the table");
+static_assert(NPR_SEED_SCAN_TILE == THREADS * 16 && THREADS == SCAN_THREADS, "a lane of the scan holds four 16-byte pieces of the table");
 static_assert(NPR_SEED_PAD >= 32 + 8, "a window load reads 32 bytes from a position, an extension step 8 bytes from a separator");
 
 __device__ __forceinline__ uint64_t load8(const uint8_t *p) {  // (any alignment)
@@ -123,28 +125,6 @@ __global__ void __launch_bounds__(THREADS) k_seed_bucket(SeedIndexArgs a) {  // 
     if (FILL) a.pos[slot] = static_cast<int32_t>(p);  // (slot < window starts <= bytes: the counts are those of the first pass)
 }
 
-// exclusive prefix of one value per thread over the workgroup, and the workgroup's total
-__device__ __forceinline__ int32_t block_scan(int32_t v, int32_t *wave_sum, int32_t &total) {
-    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    int32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const int32_t t = __shfl_up(inc, o, WAVE);
-        if (lane >= o) inc += t;
-    }
-    if (lane == WAVE - 1) wave_sum[wv] = inc;
-    __syncthreads();
-    int32_t base = 0;
-    total = 0;
-#pragma unroll
-    for (int q = 0; q < THREADS / WAVE; ++q) {
-        if (q < wv) base += wave_sum[q];
-        total += wave_sum[q];
-    }
-    __syncthreads();  // (the next call writes wave_sum again)
-    return base + inc - v;
-}
-
 __device__ __forceinline__ int32_t load_run(const int32_t *table, int32_t v[16]) {
     const uint4 *p = reinterpret_cast<const uint4 *>(table + (static_cast<int64_t>(blockIdx.x) * THREADS + threadIdx.x) * 16);
     int32_t sum = 0;
@@ -158,19 +138,19 @@ __device__ __forceinline__ int32_t load_run(const int32_t *table, int32_t v[16])
 }
 
 __global__ void __launch_bounds__(THREADS) k_seed_tile_sums(const int32_t *table, int32_t *tile) {
-    __shared__ int32_t wave_sum[THREADS / WAVE];
+    __shared__ int32_t wave_sum[SCAN_WAVES];
     int32_t v[16], total;
-    block_scan(load_run(table, v), wave_sum, total);
+    (void)block_scan_exclusive(load_run(table, v), wave_sum, &total);
     if (threadIdx.x == 0) tile[blockIdx.x] = total;
 }
 
 __global__ void __launch_bounds__(THREADS) k_seed_scan_tiles(int32_t *tile, int32_t n_tiles) {  // one workgroup
-    __shared__ int32_t wave_sum[THREADS / WAVE];
+    __shared__ int32_t wave_sum[SCAN_WAVES];
     const int32_t per = (n_tiles + THREADS - 1) / THREADS;
     const int32_t lo = min(static_cast<int32_t>(threadIdx.x) * per, n_tiles), hi = min(lo + per, n_tiles);
     int32_t sum = 0, total;
     for (int32_t q = lo; q < hi; ++q) sum += tile[q];
-    int32_t run = block_scan(sum, wave_sum, total);
+    int32_t run = block_scan_exclusive(sum, wave_sum, &total);
     for (int32_t q = lo; q < hi; ++q) {
         const int32_t t = tile[q];
         tile[q] = run;
@@ -179,9 +159,9 @@ __global__ void __launch_bounds__(THREADS) k_seed_scan_tiles(int32_t *tile, int3
 }
 
 __global__ void __launch_bounds__(THREADS) k_seed_scan_apply(int32_t *table, const int32_t *tile) {
-    __shared__ int32_t wave_sum[THREADS / WAVE];
+    __shared__ int32_t wave_sum[SCAN_WAVES];
     int32_t v[16], total;
-    int32_t run = block_scan(load_run(table, v), wave_sum, total) + tile[blockIdx.x];
+    int32_t run = block_scan_exclusive(load_run(table, v), wave_sum, &total) + tile[blockIdx.x];
     uint4 *p = reinterpret_cast<uint4 *>(table + (static_cast<int64_t>(blockIdx.x) * THREADS + threadIdx.x) * 16);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {

@@ -1,4 +1,4 @@
-// npr_seedchain.hip -- k_chain_dp, k_chain_trace<false> / k_chain_scan / k_chain_trace<true>: the co-linear chains of seed rows and the guide
+// npr_seedchain.hip -- k_chain_dp, k_chain_trace<false> / a scan / k_chain_trace<true>: the co-linear chains of seed rows and the guide
 // alignments they stand for, all (read, reference) pairs of a call at once (the definition: include/nprealign.h, "chaining of seed rows";
 // the host restatement of the same rule for one pair: npr_chain.cpp).
 //
@@ -24,7 +24,7 @@
 // backwards it meets the guide's operations last to first: after the last block the read's rest (I) and the reference's rest (D), then per
 // block its M and what lies before it (I, then D; forwards that is D then I as npr_chain_merge writes them); lengths of 0 dropped, equal
 // neighbours merged in a register before anything is counted or stored.  <false> counts (rows in the chain, op pairs) and writes the chain
-// row; k_chain_scan turns the counts into offsets (one workgroup: a lane sums a contiguous piece, the pieces' sums are scanned in LDS);
+// row; launch_scan_group (npr_scan.h) turns the counts into offsets in place;
 // <true> walks again and stores the pairs from the end of the chain's range backwards.  The walk is serial and its loads are dependent
 // (row, back pointer, row ...): it is latency-bound by construction, and the lanes of a wavefront walk chains of different lengths.  That
 // is accepted: a chain is tens of rows where the DP looked at thousands of pairs.
@@ -39,7 +39,6 @@ namespace {
 
 constexpr int WAVE = 64;
 constexpr int THREADS = 256;
-constexpr int SCAN_THREADS = 1024;
 
 struct Row {
     int32_t a, b, L;
@@ -169,31 +168,6 @@ __global__ void __launch_bounds__(THREADS) k_chain_trace(SeedChainArgs a) {
     }
 }
 
-// v[0 .. n) -> its exclusive prefix in place, the total in v[n]; one workgroup
-__global__ void __launch_bounds__(SCAN_THREADS) k_chain_scan(int64_t *v, int64_t n) {
-    __shared__ int64_t part[SCAN_THREADS];
-    const int64_t per = (n + SCAN_THREADS - 1) / SCAN_THREADS;
-    const int64_t lo = min(static_cast<int64_t>(threadIdx.x) * per, n), hi = min(lo + per, n);
-    int64_t sum = 0;
-    for (int64_t q = lo; q < hi; ++q) sum += v[q];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t run = 0;
-        for (int q = 0; q < SCAN_THREADS; ++q) {
-            const int64_t t = part[q];
-            part[q] = run, run += t;
-        }
-        v[n] = run;
-    }
-    __syncthreads();
-    int64_t run = part[threadIdx.x];
-    for (int64_t q = lo; q < hi; ++q) {
-        const int64_t t = v[q];
-        v[q] = run, run += t;
-    }
-}
-
 inline unsigned blocks_for(int64_t threads) { return static_cast<unsigned>((threads + THREADS - 1) / THREADS); }
 
 }  // namespace
@@ -202,8 +176,7 @@ int launch_seed_chain_dp(const SeedChainArgs &a, void *stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_chain_dp, dim3(blocks_for(2 * a.n_chains * WAVE)), dim3(THREADS), 0, st, a);
     hipLaunchKernelGGL(k_chain_trace<false>, dim3(blocks_for(a.n_chains)), dim3(THREADS), 0, st, a);
-    hipLaunchKernelGGL(k_chain_scan, dim3(1), dim3(SCAN_THREADS), 0, st, a.n_ops, a.n_chains);
-    return static_cast<int>(hipGetLastError());
+    return launch_scan_group<int64_t, int64_t>(a.n_ops, a.n_ops, a.n_chains, stream);
 }
 
 int launch_seed_chain_write(const SeedChainArgs &a, void *stream) {

@@ -1,13 +1,10 @@
-// npr_seedmap.hip -- k_map_scan, k_map_sort, k_map_spans: what lies between k_seed_match (npr_seed.hip) and k_chain_dp (npr_seedchain.hip)
+// npr_seedmap.hip -- two scans, k_map_sort, k_map_spans: what lies between k_seed_match (npr_seed.hip) and k_chain_dp (npr_seedchain.hip)
 // when the rows stay on the device (npr_seed_map_create, npr_seedmap_api.cpp; the definition: include/nprealign.h, "reads to rows, chains
 // and guides in one call").  npr_seed_matches and npr_seed_chains do the same three things on the host between their kernels: sum the
 // reads' row counts, std::sort every read's rows (HitLess), walk them for the (read, reference) spans (for_each_span).
-// k_map_scan<T>: counts of type T -> their exclusive prefix as int64, the total behind it; one workgroup, a lane sums a contiguous piece,
-// the pieces' sums are scanned in LDS (k_chain_scan's shape: the seed tile scan of npr_seed.hip is int32 in place over whole tiles of a
-// 64 MB table; this is one value per READ, or per read again, and 64 bits wide).  <uint32_t> makes hit_off of what k_seed_match<false>
-// counted, <int64_t> in place makes chain_off of what k_map_spans<false> counted.  One CU, lane 0 adds up the 1 024 piece sums one after
-// the other, and a lane's piece is contiguous so neighbouring lanes load far apart: nothing at the thousands of reads of a call today, a
-// serial stage on the critical path at millions of reads per chunk (then: a wavefront scan of the piece sums, strided pieces).
+// The scans: launch_scan_group of npr_scan.h (one workgroup, one launch: this is one value per READ, 64 bits wide), counts -> their
+// exclusive prefix as int64, the total behind it.  <uint32_t, int64_t> makes hit_off of what k_seed_match<false> counted, <int64_t, int64_t>
+// in place makes chain_off of what k_map_spans<false> counted.
 // k_map_sort: one workgroup per read sorts the read's rows by (strand, reference index, a, b) where k_seed_match<true> wrote them.  The
 // network is the bitonic one in its one-direction form: merging blocks of k, the first step compares row i with its mirror image in the
 // block (base + k - 1 - offset), the steps after it rows j apart, and EVERY exchange puts the smaller row at the lower index.  So rows
@@ -36,35 +33,8 @@ namespace npr {
 namespace {
 
 constexpr int THREADS = 256;
-constexpr int SCAN_THREADS = 1024;
 static_assert(NPR_SEED_MAP_LDS_ROWS * 16 <= 64 * 1024, "tier 1 of k_map_sort holds a read's rows in the LDS of one workgroup");
 static_assert(sizeof(SeedChainSpan) == 32, "a chain span is stored as one 32-byte struct");
-
-// in[0 .. n) -> its exclusive prefix out[0 .. n), the total in out[n]; one workgroup; in == out is allowed when T is int64_t
-template <typename T>
-__global__ void __launch_bounds__(SCAN_THREADS) k_map_scan(const T *in, int64_t *out, int64_t n) {
-    __shared__ int64_t part[SCAN_THREADS];
-    const int64_t per = (n + SCAN_THREADS - 1) / SCAN_THREADS;
-    const int64_t lo = min(static_cast<int64_t>(threadIdx.x) * per, n), hi = min(lo + per, n);
-    int64_t sum = 0;
-    for (int64_t q = lo; q < hi; ++q) sum += static_cast<int64_t>(in[q]);
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t run = 0;
-        for (int q = 0; q < SCAN_THREADS; ++q) {
-            const int64_t t = part[q];
-            part[q] = run, run += t;
-        }
-        out[n] = run;
-    }
-    __syncthreads();
-    int64_t run = part[threadIdx.x];
-    for (int64_t q = lo; q < hi; ++q) {
-        const int64_t t = static_cast<int64_t>(in[q]);
-        out[q] = run, run += t;
-    }
-}
 
 // HitLess of npr_seed_api.cpp: (strand, reference index, a, b)
 __device__ __forceinline__ bool row_less(const int4 &x, const int4 &y) {
@@ -147,16 +117,14 @@ inline unsigned blocks_for(int64_t threads) { return static_cast<unsigned>((thre
 }  // namespace
 
 int launch_seedmap_offsets(const SeedMapArgs &a, void *stream) {
-    hipLaunchKernelGGL(k_map_scan<uint32_t>, dim3(1), dim3(SCAN_THREADS), 0, static_cast<hipStream_t>(stream), a.count, a.hit_off, a.n_reads);
-    return static_cast<int>(hipGetLastError());
+    return launch_scan_group<uint32_t, int64_t>(a.count, a.hit_off, a.n_reads, stream);
 }
 
 int launch_seedmap_chains(const SeedMapArgs &a, void *stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_map_sort, dim3(static_cast<unsigned>(a.n_reads)), dim3(THREADS), 0, st, a);
     hipLaunchKernelGGL(k_map_spans<false>, dim3(blocks_for(a.n_reads)), dim3(THREADS), 0, st, a);
-    hipLaunchKernelGGL(k_map_scan<int64_t>, dim3(1), dim3(SCAN_THREADS), 0, st, a.chain_off, a.chain_off, a.n_reads);
-    return static_cast<int>(hipGetLastError());
+    return launch_scan_group<int64_t, int64_t>(a.chain_off, a.chain_off, a.n_reads, stream);
 }
 
 int launch_seedmap_spans(const SeedMapArgs &a, void *stream) {

@@ -1,6 +1,6 @@
 // npr_snpcall.hip -- the calling step of MarginAlignSnpCaller on the device (nanopore/analyses/marginAlignSnpCaller.py:18-23 and :163-197):
 // k_snp_calls counts the calls into histograms (include/nprealign.h: npr_snp_calls_table, npr_batch_snp_calls, npr_pileup_snp_calls),
-// k_snp_variants_count / _scan / _emit return them (npr_snp_variants_table, npr_batch_snp_variants, npr_pileup_snp_variants).
+// k_snp_variants_count / a scan / k_snp_variants_emit return them (npr_snp_variants_table, npr_batch_snp_variants, npr_pileup_snp_variants).
 //
 // The host path copies a [positions][4] fp64 table over PCIe, computes the posterior of the four candidate bases at every position and
 // appends one (probability, position) tuple per non-reference candidate to a Python list -- which is then reduced to two histograms of
@@ -13,7 +13,7 @@
 //
 // The variant kernels share the per-row arithmetic (row_frequencies, candidate_weights) and work on one error model.  A workgroup owns
 // tiles of SNP_VARIANT_TILE consecutive rows, one row per thread.  k_snp_variants_count reads the table once and writes three bytes per
-// row -- the best base, its quality, and which candidates are calls -- and one count per tile; k_snp_variants_scan, one workgroup, turns
+// row -- the best base, its quality, and which candidates are calls -- and one count per tile; launch_scan_group (npr_scan.h), one workgroup, turns
 // the counts into offsets and leaves the total for the host, which decides whether the calls fit; k_snp_variants_emit reads the mask
 // bytes, skips a tile without calls, and lets only the rows that call recompute their posteriors.  A call's place is its tile's offset
 // plus its rank in the tile (wavefront ballots, then the wavefronts before it): the arrays are in ascending (row, candidate) order
@@ -226,37 +226,6 @@ __global__ void __launch_bounds__(THREADS) k_snp_variants_count(SnpCallArgs a) {
 }
 static_assert(WAVES == 4, "k_snp_variants_count adds four wavefront counts");
 
-// tile_off[t] = the calls of the tiles before t, tile_off[tiles] = all of them: one workgroup, THREADS tiles a trip.  4.6 Mb of reference are
-// 18 k tiles, 71 trips.
-__global__ void __launch_bounds__(THREADS) k_snp_variants_scan(const uint32_t *__restrict__ tile_calls, int64_t tiles, int64_t *__restrict__ tile_off) {
-    __shared__ int64_t wave_total[WAVES];
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = uniform(tid >> 6);
-    int64_t carry = 0;
-    for (int64_t t0 = 0; t0 < tiles; t0 += THREADS) {
-        const int64_t t = t0 + tid;
-        const int64_t v = t < tiles ? static_cast<int64_t>(tile_calls[t]) : 0;
-        int64_t upto = v;  // inclusive, within the wavefront
-#pragma unroll
-        for (int o = 1; o < WAVE; o <<= 1) {
-            const int64_t u = __shfl_up(upto, o, WAVE);
-            if (lane >= o) upto += u;
-        }
-        if (lane == WAVE - 1) wave_total[wave] = upto;
-        __syncthreads();
-        int64_t before = carry, all = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) {
-            const int64_t n = wave_total[w];
-            if (w < wave) before += n;
-            all += n;
-        }
-        if (t < tiles) tile_off[t] = before + (upto - v);
-        carry += all;
-        __syncthreads();
-    }
-    if (tid == 0) tile_off[tiles] = carry;
-}
-
 template <int SRC>
 __global__ void __launch_bounds__(THREADS) k_snp_variants_emit(SnpCallArgs a) {
     __shared__ double evo[16];
@@ -342,8 +311,7 @@ int launch_snp_variants_count(const SnpCallArgs &a, void *stream) {
         hipLaunchKernelGGL(k_snp_variants_count<SNP_SRC_DOUBLE>, dim3(grid), dim3(THREADS), 0, s, a);
     else
         return static_cast<int>(hipErrorInvalidValue);
-    hipLaunchKernelGGL(k_snp_variants_scan, dim3(1), dim3(THREADS), 0, s, a.tile_calls, snp_variant_tiles(a.rows), a.tile_off);
-    return static_cast<int>(hipGetLastError());
+    return launch_scan_group<uint32_t, int64_t>(a.tile_calls, a.tile_off, snp_variant_tiles(a.rows), stream);
 }
 
 int launch_snp_variants_emit(const SnpCallArgs &a, void *stream) {

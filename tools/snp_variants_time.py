@@ -1,4 +1,4 @@
-"""Times the SNP-variant call on a pileup (csrc/npr_snpcall.hip: k_snp_variants_count / _scan / _emit) against the host route it replaces,
+"""Times the SNP-variant call on a pileup (csrc/npr_snpcall.hip: k_snp_variants_count / a scan / k_snp_variants_emit) against the host route it replaces,
 on one synthetic input: a random 4.6 Mb contig under reads of 5 000 bases at ten-fold depth (the depth of tools/snp_calls_time.py's
 defaults), every read a copy of its interval with 10 % of the bases substituted and one M run as its cigar, 1 % of the reference bases
 changed afterwards so that there is something to call.  Three figures, each one warm-up and then the median of seven repetitions:
