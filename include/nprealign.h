@@ -897,6 +897,107 @@ int32_t npr_fastq_qual_index(const char *text, int64_t len, const int64_t *rec, 
 int64_t npr_names_mark(const char *names_text, const int64_t *name_span /* [2 n] */, int64_t n, const char *sam_text,
                        const int64_t *span, const int64_t *fields, int64_t m, uint8_t *mark /* [n], OR-ed into */);
 
+/* ---- coordinate-sorted BAM and its BAI index from a SAM text (SAMv1 section 4 BAM, 4.1 BGZF, 5 indexing) ----
+ * What the reference gets from samToBamFile, pysam.sort and pysam.index (nanopore/metaAnalyses/customTrackAssemblyHub.py:56-62).  The
+ * BAM is BGZF with STORED deflate blocks (no compression: the file is about the size of the uncompressed stream).  The host parts
+ * (npr_sam_parse_tail, npr_bam_tags, npr_bam_header, npr_bai_write: csrc/npr_bam_host.cpp, threaded, no GPU needed) read what
+ * npr_sam_parse leaves aside and write the two small tables; the device parts (csrc/npr_bam.hip) order, measure, encode, frame and index.
+ *
+ * npr_sam_parse_tail: for the same n lines, tail[i * NPR_SAM_TAIL_COLS + c]:
+ *   0 RNEXT as a tid: "=" gives the record's own tid (column 10 of `fields`), "*" or a name not in the table gives -1
+ *   1 PNEXT - 1          2 TLEN          3, 4 QUAL [start, end)          5, 6 the optional fields [start, end): from the byte after the
+ *   tab that ends QUAL to the end of the line (a "\r" before the line end is not part of it: the span is npr_sam_index's); empty (both
+ *   the end of the line) when the line has 11 columns
+ *   7 NPR_OK; NPR_ERR_INVALID: fewer than 11 columns; FLAG, POS, MAPQ, PNEXT or TLEN is not a decimal number; FLAG outside 0..65535,
+ *     MAPQ outside 0..255, POS or PNEXT outside 0..2^29, TLEN outside -2^31+1..2^31-1; a QNAME of 0 or more than 254 bytes; a QUAL that
+ *     is neither "*" nor as long as SEQ (a QUAL beside SEQ "*" must be "*").
+ *   `fields` are the lines' rows as npr_sam_parse filled them (columns 5, 6 and 10 are read).  The cigar is not looked at here.
+ *
+ * npr_bam_tags: the optional fields of n lines as BAM auxiliary bytes; record i lands at out[tag_off[i] .. tag_off[i + 1]), tag_off[n + 1];
+ *   out == NULL: only the offsets.  Returns the total length, NPR_ERR_CAPACITY when cap is smaller, NPR_ERR_INVALID for a malformed field.
+ *   A line whose tail status is not NPR_OK has no bytes.  A field is TAG:TYPE:VALUE, TAG two bytes, fields separated by one tab; an empty
+ *   field (two tabs in a row, a tab at the end) is malformed.  Output per field: the two TAG bytes, a type byte, the value:
+ *   A one printable byte -> 'A' and the byte.    f a number strtof accepts whole -> 'f' and its 4 bytes.
+ *   i a decimal integer in -2^31 .. 2^32 - 1 -> the SMALLEST of the types c C s S i I that holds it, and for a value >= 0 the unsigned
+ *     type of a width before the signed one: 0..255 'C', 256..65535 'S', 65536..2^32-1 'I', -128..-1 'c', -32768..-129 's', below 'i'.
+ *   Z the bytes as they are (spaces allowed, no tab) and a NUL.    H an even number of hex digits, stored like Z.
+ *   B a subtype byte of c C s S i I f, then "," and a number for every element (none: an empty array): 'B', the subtype, the count as
+ *     uint32, the elements in the subtype's width, little endian; an integer element outside its subtype's range is malformed.
+ *
+ * npr_bam_header: the bytes before the first record: "BAM\1", l_text, the header text, n_ref, and per @SQ line l_name (with its NUL),
+ *   the name and its NUL, l_ref.  The text is the SAM header (`len` bytes, the @-lines as they stand in the file) with its @HD line
+ *   changed: the value of its SO: field becomes "coordinate" (sorted != 0) or "unsorted" (SO: is appended when @HD has none); without an
+ *   @HD line "@HD\tVN:1.0\tSO:coordinate\n" ("SO:unsorted") is put in front.  Names come from SN:, lengths from LN: (a decimal number
+ *   in 1 .. 2^31 - 1).  out == NULL: only the length; ref_len (cap_refs entries, may be NULL) receives the lengths.  Returns the length;
+ *   *n_refs the number of @SQ lines.  NPR_ERR_INVALID: no @SQ line, or one without SN: or a valid LN:; NPR_ERR_CAPACITY: cap or cap_refs.
+ *
+ * npr_bam_sort_order: the permutation that sorts n records by (tid, pos + 1, FLAG & 16 != 0): order[j] = the record at place j.  tid -1
+ *   sorts after every other tid; pos -1 (POS 0) first within its tid; equal keys keep their input order (the sort is STABLE).  An LSD
+ *   radix sort of 64-bit keys (tid' << 33 | (pos + 1) << 1 | reverse, tid' = largest tid + 1 for tid -1) with the record number as
+ *   payload, 8 bits a pass, only as many passes as the largest possible key has bits: per pass the digit histograms of every workgroup,
+ *   one prefix sum, one stable scatter whose ranks come from wavefront ballots and per-wavefront counts, never from the order in which
+ *   atomics land.  n < 2^31, tid in -1 .. 2^30 - 1, pos in -1 .. 2^31 - 2: NPR_ERR_INVALID otherwise, nothing written.
+ *
+ * npr_bgzf_frame: `len` bytes as a BGZF stream.  Block b holds the payload data[b * P .. min(len, (b + 1) * P)), P = NPR_BGZF_PAYLOAD;
+ *   a block of L payload bytes is, in order: 1f 8b 08 04, MTIME 0 (4 bytes), XFL 0, OS ff, XLEN 6 0, 'B' 'C' 2 0, BSIZE = L + 30 as
+ *   uint16 (the block's length - 1); 01, LEN = L, ~LEN (uint16 each: one stored deflate block, final); the payload; CRC-32 of the payload
+ *   (polynomial 0xEDB88320 reflected, initial value and final xor 0xFFFFFFFF) and ISIZE = L as uint32.  All little endian.  After the
+ *   last block the 28-byte end-of-file block: 1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 00 00 00 00 00 00 00 00.
+ *   len == 0 gives that block alone.  Returns the stream's length = len + 31 * ceil(len / P) + 28; out == NULL: only that;
+ *   NPR_ERR_CAPACITY when cap is smaller, and then nothing is written.  The VIRTUAL OFFSET of byte u of the data is therefore
+ *   ((u / P) * (P + 31)) << 16 | (u % P), in closed form; nothing below walks the blocks.
+ *
+ * npr_sam_bam: the whole conversion in one call; the text, the two parse tables and the tag bytes go up once, the BAM file image and the
+ *   index tables come back.  Record i is line i (span, fields, tail as the parsers filled them; tags / tag_off as npr_bam_tags did).
+ *   FAILS, with nothing written: a line whose tail status is not NPR_OK or whose `fields` status is NPR_SAM_UNKNOWN_REFERENCE; a tid
+ *   outside -1 .. n_refs - 1; a CIGAR that is neither "*" nor a list of <number><letter> with letters of MIDNSHP=X and numbers below 2^28
+ *   (NPR_ERR_INVALID).  Nothing is dropped: a record with RNAME "*" is kept with tid -1.  (That the cigar's read bases equal l_seq is not checked.)
+ *   MEASURE.  n_ops = the cigar's operations ("*": 0), consumed = the sum of its M D N = X lengths, end = pos + consumed, or pos + 1 when
+ *   consumed is 0 or FLAG has 4 set; bin = reg2bin(pos, end) of the specification (pos -1 is taken as 0; tid -1: 4680).  l_seq = the
+ *   length of SEQ, 0 for "*".
+ *   ORDER.  sorted != 0: npr_bam_sort_order on (tid, pos, FLAG); else the file's order.
+ *   RECORD.  block_size, refID, pos, l_read_name, mapq, bin, n_cigar_op, flag, l_seq, next_refID, next_pos, tlen (36 bytes); QNAME and a
+ *   NUL; the cigar, one uint32 per operation = length << 4 | op with MIDNSHP=X = 0..8; SEQ two bases a byte, first base in the high
+ *   nibble, through "=ACMGRSVTWYHKDBN" = 0..15 in either letter case, any other byte 15, an odd last nibble 0; QUAL bytes - 33, or l_seq
+ *   bytes 0xFF for "*"; the tag bytes.  A cigar of more than 65535 operations: n_cigar_op = 2, the cigar <l_seq>S<consumed>N, and after
+ *   the record's other tags 'C' 'G' 'B' 'I', n_ops as uint32 and the real operations.
+ *   The records follow the header in order; the stream is framed as npr_bgzf_frame does.  Returns the file's length; bam_out == NULL:
+ *   only that (the index is not made); NPR_ERR_CAPACITY when cap is smaller.
+ *   INDEX (sorted != 0 and bam_out != NULL; else the index arguments are not touched and may be NULL), over the records in sorted order,
+ *   with v(u) the virtual offset of stream byte u and [u0, u1) a record's bytes:
+ *   chunks: a maximal run of consecutive records of one (tid, bin) is one chunk [v(u0 of its first), v(u1 of its last)); the runs come
+ *     back ordered by (tid, bin), tid -1 last, file order among equals, as run_tid / run_bin / run_beg / run_end (room for n each);
+ *     *n_runs says how many.
+ *   linear: reference k has ((ref_len[k] - 1) >> 14) + 1 windows of 16384 positions (ref_len[k] >= 1), the references' windows back to
+ *     back; linear[w] = the smallest v(u0) of the records of tid k with max(pos, 0) >> 14 <= w' <= (end - 1) >> 14 (w' beyond the last
+ *     window counts as the last), or all ones when there is none.  (The backfill and the cut are npr_bai_write's.)
+ *   meta[k][4]: the smallest v(u0) and the largest v(u1) of the records of tid k (all ones and 0 without one), the number of those
+ *     with FLAG & 4 clear, and with it set.  *n_no_coor = the records of tid -1.
+ *
+ * npr_bai_write: the BAI file from those arrays: "BAI\1", n_ref; per reference n_bin, per bin: bin, n_chunk, the chunks' (beg, end) --
+ *   the runs of one (tid, bin) are the bin's chunks, in the order given; a reference with a record gets the pseudo-bin 37450 last, with
+ *   the two chunks (meta[k][0], meta[k][1]) and (meta[k][2], meta[k][3]) --; n_intv = the reference's windows up to the last one that
+ *   has a record (0 without one), and their values, a window without a record taking the value of the next one that has one; after the
+ *   last reference n_no_coor as uint64.  Runs of tid -1 are not written.  out == NULL: only the length.  NPR_ERR_INVALID for runs that
+ *   are not ordered by (tid, bin) or a tid outside -1 .. n_refs - 1; NPR_ERR_CAPACITY when cap is smaller. */
+#define NPR_SAM_TAIL_COLS 8
+#define NPR_BGZF_PAYLOAD 65280
+#define NPR_BAM_TILE 4096 /* bases of one record a workgroup of the encode kernel takes */
+int32_t npr_sam_parse_tail(const char *text, const int64_t *span, const int64_t *fields, int64_t n, const char *rnames,
+                           const int64_t *rname_off, int64_t n_refs, int64_t *tail);
+int64_t npr_bam_tags(const char *text, const int64_t *tail, int64_t n, int64_t *tag_off, uint8_t *out, int64_t cap);
+int64_t npr_bam_header(const char *sam_header, int64_t len, int32_t sorted, uint8_t *out, int64_t cap, int64_t *n_refs,
+                       int64_t *ref_len, int64_t cap_refs);
+int32_t npr_bam_sort_order(npr_ctx *ctx, int64_t n, const int32_t *tid, const int64_t *pos, const int32_t *flag, int32_t *order);
+int64_t npr_bgzf_frame(npr_ctx *ctx, const uint8_t *data, int64_t len, uint8_t *out, int64_t cap);
+int64_t npr_sam_bam(npr_ctx *ctx, const uint8_t *text, int64_t text_len, const int64_t *span, const int64_t *fields, const int64_t *tail,
+                    int64_t n, const int64_t *tag_off, const uint8_t *tags, const uint8_t *header, int64_t header_len, int64_t n_refs,
+                    const int64_t *ref_len, int32_t sorted, uint8_t *bam_out, int64_t cap, int64_t *n_runs, int32_t *run_tid,
+                    uint32_t *run_bin, uint64_t *run_beg, uint64_t *run_end, uint64_t *linear, uint64_t *meta, int64_t *n_no_coor);
+int64_t npr_bai_write(int64_t n_refs, const int64_t *ref_len, int64_t n_runs, const int32_t *run_tid, const uint32_t *run_bin,
+                      const uint64_t *run_beg, const uint64_t *run_end, const uint64_t *linear, const uint64_t *meta, int64_t n_no_coor,
+                      uint8_t *out, int64_t cap);
+
 /* npr_batch_create_at for reads that are NOT contiguous in memory: read i = read[read_begin[i] .. read_end[i]) -- e.g. the
  * aligned part of each record's SEQ inside the mapped SAM text (columns 11, 12 of npr_sam_parse), so the sequences go from
  * the file's bytes to the pinned staging buffer in one copy.  Everything else as npr_batch_create_at. */

@@ -54,6 +54,9 @@ RQ_MAX_GROUPS, RQ_TILE = 8, 2048  # NPR_RQ_MAX_GROUPS; NPR_RQ_TILE: positions of
 AQ_MAX_WINDOWS, AQ_WIN_WORDS, AQ_TOTALS, AQ_HOMOPOLYMER = 65536, 8, 8, 3  # NPR_AQ_*: the alignment-quality tables (npr_pileup_coverage, npr_align_quality)
 AQ_TILE = 2048    # NPR_AQ_TILE: consecutive rows a workgroup of the coverage kernel takes
 SAM_COLS = 16     # NPR_SAM_COLS
+SAM_TAIL_COLS = 8  # NPR_SAM_TAIL_COLS: what npr_sam_parse_tail fills per line
+BGZF_PAYLOAD = 65280  # NPR_BGZF_PAYLOAD: data bytes of a full BGZF block
+BAM_TILE = 4096   # NPR_BAM_TILE: bases of one record a workgroup of the BAM encode kernel takes
 SEED_MIN_K, SEED_MAX_K = 8, 32  # npr_seed_index_create: the k of a seed index
 SEED_MAP_LDS_ROWS = 4096  # NPR_SEED_MAP_LDS_ROWS: a read of at most so many rows is sorted in LDS by npr_seed_map_create, a longer one in global memory
 PILEUP_WORDS = 8  # NPR_PILEUP_WORDS: M columns by read base A C G T other, deletion columns, insertion runs, record starts
@@ -216,6 +219,13 @@ SIGNATURES = {
     "npr_fastq_index": (i64, [vp, i64, vp, i64]),
     "npr_fastq_qual_index": (i32, [vp, i64, vp, i64, vp]),
     "npr_names_mark": (i64, [vp, vp, i64, vp, vp, vp, i64, vp]),
+    "npr_sam_parse_tail": (i32, [vp, vp, vp, i64, vp, vp, i64, vp]),
+    "npr_bam_tags": (i64, [vp, vp, i64, vp, vp, i64]),
+    "npr_bam_header": (i64, [vp, i64, i32, vp, i64, C.POINTER(i64), vp, i64]),
+    "npr_bam_sort_order": (i32, [vp, i64, vp, vp, vp, vp]),
+    "npr_bgzf_frame": (i64, [vp, vp, i64, vp, i64]),
+    "npr_sam_bam": (i64, [vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i64, vp, i32, vp, i64, C.POINTER(i64)] + [vp] * 6 + [C.POINTER(i64)]),
+    "npr_bai_write": (i64, [i64, vp, i64] + [vp] * 6 + [i64, vp, i64]),
     "npr_batch_create_spans": (i32, [vp, _params, i64, i64] + [vp] * 10 + [_out]),
 }
 EXPORTS = list(SIGNATURES)

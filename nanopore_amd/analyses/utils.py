@@ -237,6 +237,17 @@ def _context(device=0):
     return _shared_ctx[device]
 
 
+def samToBamFile(samInputFile, bamOutputFile, ctx=None):
+    """samToBamFile of the reference (nanopore/analyses/utils.py: a pysam reader into a "wb" writer): the records in the file's order,
+    made on the device (realign.Context.sam_to_bam); no index."""
+    return (ctx or _context()).sam_to_bam(samInputFile, bamOutputFile, sort=False, index=False)
+
+
+def samToSortedBamFile(samFile, sortedBamFile, ctx=None):
+    """samToBamFile, pysam.sort and pysam.index in one: sortedBamFile coordinate-sorted and sortedBamFile + ".bai" beside it."""
+    return (ctx or _context()).sam_to_bam(samFile, sortedBamFile, sort=True, index=True)
+
+
 def _loadHmmInto(ctx, hmmFile, slot=0):
     ctx.set_hmm(None if hmmFile is None else Hmm.loadHmm(hmmFile), slot=slot)
 

@@ -43,6 +43,49 @@ def fastaWrite(fileHandleOrFile, name, seq, mode="w"):
             fh.close()
 
 
+def _runs(mask):
+    """(starts, sizes) of the runs of True in a boolean numpy array, as uint32."""
+    import numpy as np
+    edge = np.diff(np.concatenate(([0], mask.astype(np.int8), [0])))
+    starts, ends = np.nonzero(edge == 1)[0], np.nonzero(edge == -1)[0]
+    return starts.astype("<u4"), (ends - starts).astype("<u4")
+
+
+def faToTwoBit(fastaFile, twoBitFile):
+    """The UCSC .2bit file of a FASTA file (what the reference's track hub gets from /cluster/bin/x86_64/faToTwoBit,
+    nanopore/metaAnalyses/customTrackAssemblyHub.py:83), in numpy: the header (signature 0x1A412743, version 0, sequence count, 0), the
+    index (name size, name -- the first word of the header line --, offset of the record), and per sequence its size, the blocks of N / n
+    (count, starts, sizes), the mask blocks of lower-case runs (the same), a reserved 0 and the bases four to a byte, first base in the
+    two highest bits, T = 0, C = 1, A = 2, G = 3, N and anything else packed as T, the last byte filled with T.  Little endian."""
+    import numpy as np
+    records = []
+    for name, seq in fastaRead(fastaFile):
+        name = (name.split() or [""])[0].encode()
+        if not 0 < len(name) < 256:
+            raise ValueError("faToTwoBit: a sequence name of %d bytes" % len(name))
+        s = np.frombuffer(seq.encode(), dtype=np.uint8)
+        upper = s & 0xdf
+        n_starts, n_sizes = _runs(upper == ord("N"))
+        m_starts, m_sizes = _runs((s >= ord("a")) & (s <= ord("z")))
+        code = np.zeros(256, dtype=np.uint8)
+        code[ord("C")], code[ord("A")], code[ord("G")] = 1, 2, 3
+        two = np.zeros((len(s) + 3) // 4 * 4, dtype=np.uint8)
+        two[:len(s)] = code[upper]
+        two = two.reshape(-1, 4)
+        packed = (two[:, 0] << 6 | two[:, 1] << 4 | two[:, 2] << 2 | two[:, 3]).astype(np.uint8)
+        body = b"".join([np.array([len(s), len(n_starts)], dtype="<u4").tobytes(), n_starts.tobytes(), n_sizes.tobytes(),
+                         np.array([len(m_starts)], dtype="<u4").tobytes(), m_starts.tobytes(), m_sizes.tobytes(),
+                         np.array([0], dtype="<u4").tobytes(), packed.tobytes()])
+        records.append((name, body))
+    offset = 16 + sum(1 + len(name) + 4 for name, _ in records)
+    out = [np.array([0x1A412743, 0, len(records), 0], dtype="<u4").tobytes()]
+    for name, body in records:
+        out.append(bytes([len(name)]) + name + np.array([offset], dtype="<u4").tobytes())
+        offset += len(body)
+    with open(twoBitFile, "wb") as fh:
+        fh.write(b"".join(out + [body for _, body in records]))
+
+
 def fastqRead(fileHandleOrFile):
     """Yields (name, sequence, quality string or None); four-line records."""
     fh = open(fileHandleOrFile) if isinstance(fileHandleOrFile, str) else fileHandleOrFile

@@ -1,0 +1,275 @@
+// npr_bam_api.cpp -- npr_bam_sort_order, npr_bgzf_frame, npr_sam_bam: the checks, the records as the kernels take them, the launches of
+// npr_bam.hip and the tables as the header defines them ("coordinate-sorted BAM")
+// (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
+#include "npr_api_internal.h"
+
+static_assert(BGZF_PAYLOAD == NPR_BGZF_PAYLOAD && BAM_TILE == NPR_BAM_TILE, "the kernels' constants are the header's");
+
+namespace {
+
+constexpr uint32_t kCrcPoly = 0xEDB88320u;
+
+uint32_t gf_mul(uint32_t a, uint32_t b) {  // a * b modulo the CRC polynomial, reflected (bit 31 is x^0)
+    uint32_t p = 0;
+    for (int k = 0; k < 32; ++k) {
+        if (a & (0x80000000u >> k)) p ^= b;
+        b = (b & 1) ? (b >> 1) ^ kCrcPoly : b >> 1;
+    }
+    return p;
+}
+
+void bgzf_constants(BgzfArgs &a) {
+    a.x2n[0] = 0x40000000u;  // x^1
+    for (int k = 1; k < 32; ++k) a.x2n[k] = gf_mul(a.x2n[k - 1], a.x2n[k - 1]);
+    for (int lv = 0; lv < 8; ++lv) {  // x^(8 * BGZF_SLICE * 2^lv)
+        uint32_t p = 0x80000000u;
+        uint32_t bytes = static_cast<uint32_t>(BGZF_SLICE) << lv;
+        for (int k = 3; bytes; bytes >>= 1, ++k)
+            if (bytes & 1) p = gf_mul(a.x2n[k & 31], p);
+        a.level[lv] = p;
+    }
+}
+
+inline int64_t bgzf_length(int64_t len) { return len + BGZF_OVERHEAD * ((len + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD) + BGZF_EOF; }
+
+int bits_of(unsigned long long v) {
+    int b = 0;
+    while (v) ++b, v >>= 1;
+    return b;
+}
+
+// The stable order of n keys of at most `bits` bits that lie on the device: d_order[j] = index of the key at place j (the identity without a pass).
+// The keys are overwritten.
+void sort_order(const Call &dev, DevBuf<unsigned long long> &keys, int64_t n, int bits, DevBuf<uint32_t> &d_order) {
+    const int64_t blocks = bam_sort_blocks(n);
+    DevBuf<unsigned long long> keys2;
+    DevBuf<uint32_t> vals2, hist;
+    DevBuf<int32_t> tile;
+    dev.alloc(d_order, n), dev.alloc(vals2, n), dev.alloc(keys2, n);
+    dev.alloc(hist, BAM_SORT_DIGITS * blocks + 1);
+    dev.alloc(tile, scan_tiles(BAM_SORT_DIGITS * blocks));
+    const int passes = std::max(1, (bits + BAM_SORT_BITS - 1) / BAM_SORT_BITS);
+    // the last pass writes into d_order: with an odd number of passes the first one does too
+    unsigned long long *kin = keys.p, *kout = keys2.p;
+    uint32_t *vin = nullptr, *vout = (passes & 1) ? d_order.p : vals2.p;
+    for (int p = 0; p < passes; ++p) {
+        BamSortArgs a{n, p * BAM_SORT_BITS, kin, vin, kout, vout, hist.p, tile.p};
+        dev.launched(launch_bam_sort_pass(a, dev.ctx->stream), "k_sort_hist / scan / k_sort_scatter");
+        std::swap(kin, kout);
+        vin = vout, vout = vout == d_order.p ? vals2.p : d_order.p;
+    }
+    dev.sync();  // (the scratch of the passes goes out of scope)
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t npr_bam_sort_order(npr_ctx *ctx, int64_t n, const int32_t *tid, const int64_t *pos, const int32_t *flag, int32_t *order) {
+    if (!ctx || n < 0 || n >= (int64_t(1) << 31) || (n && (!tid || !pos || !flag || !order))) return NPR_ERR_INVALID;
+    return guarded(ctx, "npr_bam_sort_order", [&](const Call &dev) -> int32_t {
+        int64_t max_pos = 0;
+        int32_t max_tid = -1;
+        for (int64_t i = 0; i < n; ++i) {
+            if (tid[i] < -1 || tid[i] >= (1 << 30) || pos[i] < -1 || pos[i] > (int64_t(1) << 31) - 2) return fail(ctx, NPR_ERR_INVALID, "npr_bam_sort_order: a tid or pos out of range");
+            max_pos = std::max(max_pos, pos[i] + 1), max_tid = std::max(max_tid, tid[i]);
+        }
+        if (n == 0) return NPR_OK;
+        const int32_t no_tid = max_tid + 1;
+        const int bits = no_tid ? 33 + bits_of(static_cast<unsigned long long>(no_tid)) : bits_of(static_cast<unsigned long long>(max_pos) << 1 | 1);
+        DevBuf<int32_t> d_tid, d_flag;
+        DevBuf<int64_t> d_pos;
+        DevBuf<unsigned long long> keys;
+        DevBuf<uint32_t> d_order;
+        dev.upload(d_tid, tid, n), dev.upload(d_pos, pos, n), dev.upload(d_flag, flag, n);
+        dev.alloc(keys, n);
+        dev.launched(launch_bam_sort_keys(n, d_tid.p, d_pos.p, d_flag.p, no_tid, keys.p, ctx->stream), "k_sort_keys");
+        sort_order(dev, keys, n, bits, d_order);
+        dev.fetch(order, d_order.p, d_order.bytes());
+        dev.sync();
+        return NPR_OK;
+    });
+}
+
+int64_t npr_bgzf_frame(npr_ctx *ctx, const uint8_t *data, int64_t len, uint8_t *out, int64_t cap) {
+    if (!ctx || len < 0 || (len && !data) || cap < 0) return NPR_ERR_INVALID;
+    const int64_t total = bgzf_length(len);
+    if (!out) return total;
+    if (cap < total) return NPR_ERR_CAPACITY;
+    if ((len + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD + 1 >= (int64_t(1) << 31)) return NPR_ERR_INVALID;
+    return guarded(ctx, "npr_bgzf_frame", [&](const Call &dev) -> int64_t {
+        DevBuf<uint8_t> d_in, d_out;
+        dev.upload(d_in, data, static_cast<size_t>(len));
+        dev.alloc(d_out, static_cast<size_t>(total));
+        BgzfArgs a{};
+        a.data = d_in.p, a.len = len, a.out = d_out.p;
+        bgzf_constants(a);
+        dev.launched(launch_bgzf_frame(a, ctx->stream), "k_bgzf_frame");
+        dev.fetch(out, d_out.p, static_cast<size_t>(total));
+        dev.sync();
+        return total;
+    });
+}
+
+int64_t npr_sam_bam(npr_ctx *ctx, const uint8_t *text, int64_t text_len, const int64_t *span, const int64_t *fields, const int64_t *tail, int64_t n,
+                    const int64_t *tag_off, const uint8_t *tags, const uint8_t *header, int64_t header_len, int64_t n_refs, const int64_t *ref_len,
+                    int32_t sorted, uint8_t *bam_out, int64_t cap, int64_t *n_runs, int32_t *run_tid, uint32_t *run_bin, uint64_t *run_beg,
+                    uint64_t *run_end, uint64_t *linear, uint64_t *meta, int64_t *n_no_coor) {
+    const bool index = sorted && bam_out;
+    if (!ctx || n < 0 || n >= (int64_t(1) << 31) || text_len < 0 || header_len < 0 || n_refs < 0 || n_refs >= (1 << 30) || cap < 0 || (header_len && !header) ||
+        (n && (!text || !span || !fields || !tail || !tag_off)) || (n_refs && !ref_len) ||
+        (index && (!n_runs || !n_no_coor || (n && (!run_tid || !run_bin || !run_beg || !run_end)) || (n_refs && (!linear || !meta)))))
+        return NPR_ERR_INVALID;
+    return guarded(ctx, "npr_sam_bam", [&](const Call &dev) -> int64_t {
+        // the lines as records, every one checked before anything is launched
+        std::vector<BamRec> recs(static_cast<size_t>(n));
+        std::vector<int64_t> lin_off(static_cast<size_t>(n_refs) + 1, 0);
+        for (int64_t k = 0; k < n_refs; ++k) {
+            if (ref_len[k] < 1) return fail(ctx, NPR_ERR_INVALID, "npr_sam_bam: a reference length below 1");
+            lin_off[k + 1] = lin_off[k] + ((ref_len[k] - 1) >> 14) + 1;
+        }
+        std::atomic<int> bad{0};
+        std::vector<int64_t> tiles(static_cast<size_t>(n) + 1, 0);
+        parallel_for((n + 255) / 256, ctx->host_threads, [&](int64_t c) {
+            for (int64_t i = c * 256, hi = std::min(n, (c + 1) * 256); i < hi; ++i) {
+                const int64_t *f = fields + i * NPR_SAM_COLS, *t = tail + i * NPR_SAM_TAIL_COLS;
+                if (t[7] != NPR_OK || f[15] == NPR_SAM_UNKNOWN_REFERENCE) {
+                    bad = 1;
+                    continue;
+                }
+                BamRec &r = recs[i];
+                const bool no_seq = f[6] - f[5] == 1 && text[f[5]] == '*', no_qual = t[4] - t[3] == 1 && text[t[3]] == '*';
+                r.name = span[2 * i], r.l_name = static_cast<int32_t>(f[0] - span[2 * i]);
+                r.cigar_lo = f[3], r.cigar_hi = f[4];
+                r.seq = f[5], r.l_seq = no_seq ? 0 : static_cast<int32_t>(f[6] - f[5]);
+                r.qual = no_qual ? -1 : t[3];
+                r.tag_off = tag_off[i], r.tag_len = static_cast<int32_t>(tag_off[i + 1] - tag_off[i]);
+                r.tid = static_cast<int32_t>(f[10]), r.pos = static_cast<int32_t>(f[8]), r.flag = static_cast<int32_t>(f[7]), r.mapq = static_cast<int32_t>(f[9]);
+                r.next_tid = static_cast<int32_t>(t[0]), r.next_pos = static_cast<int32_t>(t[1]), r.tlen = static_cast<int32_t>(t[2]);
+                const bool inside = span[2 * i] >= 0 && span[2 * i] <= f[0] && f[0] <= f[3] && f[3] <= f[4] && f[4] <= f[5] && f[5] <= f[6] && f[6] <= t[3] && t[3] <= t[4] &&
+                                    t[4] <= span[2 * i + 1] && span[2 * i + 1] <= text_len;
+                if (!inside || f[6] - f[5] >= (int64_t(1) << 30) || r.tag_len < 0 || r.tid < -1 || r.tid >= n_refs || r.next_tid < -1 || r.next_tid >= n_refs ||
+                    r.l_name < 1 || r.l_name > 254 || r.pos < -1 || r.flag < 0 || r.flag > 65535 || r.mapq < 0 || r.mapq > 255 ||
+                    (!no_qual && t[4] - t[3] != r.l_seq))
+                    bad = 1;
+                tiles[i + 1] = std::max<int64_t>(1, (r.l_seq + BAM_TILE - 1) / BAM_TILE);
+            }
+        });
+        if (n && tag_off[n] > tag_off[0] && !tags) return NPR_ERR_INVALID;
+        if (bad) return fail(ctx, NPR_ERR_INVALID, "npr_sam_bam: a line that did not parse, names an unknown reference or lies outside the text");
+        for (int64_t i = 0; i < n; ++i) tiles[i + 1] += tiles[i];
+        const int64_t n_items = tiles[n];
+        if (n_items >= (int64_t(1) << 31)) return fail(ctx, NPR_ERR_INVALID, "npr_sam_bam: 2^31 tiles and more in one call");
+        std::vector<unsigned long long> items(static_cast<size_t>(n_items));
+        parallel_for((n + 255) / 256, ctx->host_threads, [&](int64_t c) {
+            for (int64_t i = c * 256, hi = std::min(n, (c + 1) * 256); i < hi; ++i)
+                for (int64_t k = tiles[i]; k < tiles[i + 1]; ++k) items[k] = static_cast<unsigned long long>(i) << 32 | static_cast<unsigned long long>(k - tiles[i]);
+        });
+
+        DevBuf<uint8_t> d_text, d_tags, d_raw, d_out;
+        DevBuf<BamRec> d_recs;
+        DevBuf<BamMeasure> d_meas;
+        DevBuf<int32_t> d_bad, d_tid, d_flag, d_head_tile;
+        DevBuf<int64_t> d_pos, d_size, d_tile, d_rec_off, d_lin_off;
+        DevBuf<uint32_t> d_order, d_head;
+        DevBuf<unsigned long long> d_items, d_keys;
+        BamArgs a{};
+        a.n = n, a.n_items = n_items, a.header_len = header_len, a.n_refs = n_refs;
+        if (n) {
+            dev.upload(d_text, text, static_cast<size_t>(text_len));
+            dev.upload(d_recs, recs);
+            dev.upload(d_tags, tags, static_cast<size_t>(tag_off[n]));
+            dev.alloc(d_meas, n);
+        }
+        dev.alloc(d_bad, 1), dev.zero(d_bad);
+        a.text = d_text.p, a.recs = d_recs.p, a.tags = d_tags.p, a.meas = d_meas.p, a.bad = d_bad.p;
+        dev.launched(launch_bam_measure(a, ctx->stream), "k_bam_measure");
+        if (sorted && n) {
+            std::vector<int32_t> tid(static_cast<size_t>(n)), flag(static_cast<size_t>(n));
+            std::vector<int64_t> pos(static_cast<size_t>(n));
+            int64_t max_pos = 0, max_tid = 0;  // the largest key's bits: from the largest tid' (n_refs for tid -1) and, when that is 0, the largest pos
+            for (int64_t i = 0; i < n; ++i) {
+                tid[i] = recs[i].tid, pos[i] = recs[i].pos, flag[i] = recs[i].flag;
+                max_pos = std::max<int64_t>(max_pos, pos[i] + 1), max_tid = std::max<int64_t>(max_tid, tid[i] < 0 ? n_refs : tid[i]);
+            }
+            dev.upload(d_tid, tid), dev.upload(d_pos, pos), dev.upload(d_flag, flag);
+            dev.alloc(d_keys, n);
+            dev.launched(launch_bam_sort_keys(n, d_tid.p, d_pos.p, d_flag.p, static_cast<int32_t>(n_refs), d_keys.p, ctx->stream), "k_sort_keys");
+            sort_order(dev, d_keys, n, max_tid ? 33 + bits_of(static_cast<unsigned long long>(max_tid)) : bits_of(static_cast<unsigned long long>(max_pos) << 1 | 1), d_order);
+            a.order = d_order.p;
+        }
+        dev.alloc(d_size, n + 1), dev.alloc(d_tile, scan_tiles(n)), dev.alloc(d_rec_off, std::max<int64_t>(n, 1));
+        a.size_sorted = d_size.p, a.tile = d_tile.p, a.rec_off = d_rec_off.p;
+        dev.launched(launch_bam_offsets(a, ctx->stream), "k_bam_gather_sizes / scan / k_bam_place");
+        int64_t records_bytes = 0;
+        int32_t bad_cigar = 0;
+        dev.fetch(&records_bytes, d_size.p + n, sizeof(int64_t));
+        dev.fetch(&bad_cigar, d_bad.p, sizeof(int32_t));
+        dev.sync();
+        if (bad_cigar) return fail(ctx, NPR_ERR_INVALID, "npr_sam_bam: a malformed CIGAR");
+        const int64_t stream_len = header_len + records_bytes, total = bgzf_length(stream_len);
+        if (!bam_out) return total;
+        if (cap < total) return NPR_ERR_CAPACITY;
+        if (total / BGZF_PAYLOAD + 2 >= (int64_t(1) << 31)) return fail(ctx, NPR_ERR_INVALID, "npr_sam_bam: 2^31 BGZF blocks and more");
+
+        dev.alloc(d_raw, static_cast<size_t>(std::max<int64_t>(stream_len, 1)));
+        dev.copy_up(d_raw.p, header, static_cast<size_t>(header_len));
+        dev.upload(d_items, items);
+        a.items = d_items.p, a.raw = d_raw.p;
+        dev.launched(launch_bam_encode(a, ctx->stream), "k_bam_cigar / k_bam_encode");
+        dev.alloc(d_out, static_cast<size_t>(total));
+        BgzfArgs z{};
+        z.data = d_raw.p, z.len = stream_len, z.out = d_out.p;
+        bgzf_constants(z);
+        dev.launched(launch_bgzf_frame(z, ctx->stream), "k_bgzf_frame");
+        dev.fetch(bam_out, d_out.p, static_cast<size_t>(total));
+        if (!index) {
+            dev.sync();
+            return total;
+        }
+
+        // the index
+        *n_runs = 0, *n_no_coor = 0;
+        const int64_t windows = lin_off[n_refs];
+        DevBuf<unsigned long long> d_linear, d_meta, d_no_coor, d_run_key, d_run_beg, d_run_end, d_out_beg, d_out_end;
+        DevBuf<int32_t> d_run_tid;
+        DevBuf<uint32_t> d_run_bin, d_perm;
+        std::vector<unsigned long long> meta0(4 * static_cast<size_t>(n_refs), 0);
+        for (int64_t k = 0; k < n_refs; ++k) meta0[4 * k] = ~0ull;
+        dev.upload(d_meta, meta0);
+        dev.alloc(d_linear, windows);
+        if (windows) dev.check(hipMemsetAsync(d_linear.p, 0xff, d_linear.bytes(), ctx->stream), "memset");
+        dev.alloc(d_no_coor, 1), dev.zero(d_no_coor);
+        if (n) {
+            dev.upload(d_lin_off, lin_off);
+            dev.alloc(d_head, n + 1), dev.alloc(d_head_tile, scan_tiles(n));
+            dev.alloc(d_run_key, n), dev.alloc(d_run_beg, n), dev.alloc(d_run_end, n);
+            a.lin_off = d_lin_off.p, a.head = d_head.p, a.head_tile = d_head_tile.p;
+            a.run_key = d_run_key.p, a.run_beg = d_run_beg.p, a.run_end = d_run_end.p;
+            a.linear = d_linear.p, a.meta = d_meta.p, a.no_coor = d_no_coor.p;
+            dev.launched(launch_bam_index_heads(a, ctx->stream), "k_bam_index_heads / scan");
+            dev.launched(launch_bam_index_runs(a, ctx->stream), "k_bam_index_runs");
+            int32_t runs = 0;
+            dev.fetch(&runs, d_head.p + n, sizeof(int32_t));
+            dev.sync();
+            sort_order(dev, d_run_key, runs, 16 + bits_of(static_cast<unsigned long long>(n_refs)), d_perm);
+            // (sort_order overwrote the keys' buffer or its twin: the keys are made again for the gather)
+            dev.launched(launch_bam_index_runs(a, ctx->stream), "k_bam_index_runs");
+            dev.alloc(d_run_tid, runs), dev.alloc(d_run_bin, runs), dev.alloc(d_out_beg, runs), dev.alloc(d_out_end, runs);
+            BamGatherArgs g{runs, d_perm.p, d_run_key.p, d_run_beg.p, d_run_end.p, static_cast<int32_t>(n_refs), d_run_tid.p, d_run_bin.p, d_out_beg.p, d_out_end.p};
+            dev.launched(launch_bam_gather_runs(g, ctx->stream), "k_bam_gather_runs");
+            dev.fetch(run_tid, d_run_tid.p, d_run_tid.bytes()), dev.fetch(run_bin, d_run_bin.p, d_run_bin.bytes());
+            dev.fetch(run_beg, d_out_beg.p, d_out_beg.bytes()), dev.fetch(run_end, d_out_end.p, d_out_end.bytes());
+            *n_runs = runs;
+        }
+        unsigned long long no_coor = 0;
+        dev.fetch(linear, d_linear.p, d_linear.bytes());
+        dev.fetch(meta, d_meta.p, d_meta.bytes());
+        dev.fetch(&no_coor, d_no_coor.p, sizeof(no_coor));
+        dev.sync();
+        *n_no_coor = static_cast<int64_t>(no_coor);
+        return total;
+    });
+}
+
+}  // extern "C"

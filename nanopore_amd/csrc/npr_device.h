@@ -472,6 +472,82 @@ struct CigTextArgs {
 };
 int launch_cigtext_offsets(const CigTextArgs &a, void *stream);  // lengths + exclusive scan: str_off, *bad
 int launch_cigtext_write(const CigTextArgs &a, void *stream);
+// SAM -> sorted BAM + BAI on the device (npr_bam.hip; the definitions: include/nprealign.h, "coordinate-sorted BAM")
+constexpr int BAM_SORT_BITS = 8, BAM_SORT_DIGITS = 1 << BAM_SORT_BITS;
+constexpr int BAM_SORT_ROUNDS = 8;                    // a workgroup of 256 threads takes this many rounds of 256 consecutive keys
+constexpr int BAM_SORT_TILE = 256 * BAM_SORT_ROUNDS;
+inline int64_t bam_sort_blocks(int64_t n) { return (n + BAM_SORT_TILE - 1) / BAM_SORT_TILE; }
+struct BamSortArgs {  // one pass: k_sort_hist, the scan of hist, k_sort_scatter
+    int64_t n;
+    int32_t shift;               // the pass's digit = (key >> shift) & 255
+    const unsigned long long *keys_in;
+    const uint32_t *vals_in;     // null: the values are the indices (the first pass)
+    unsigned long long *keys_out;
+    uint32_t *vals_out;
+    uint32_t *hist;              // [256][blocks] digit-major, then its exclusive scan in place (int32)
+    int32_t *tile;               // [scan_tiles(256 * blocks)] scratch of the scan
+};
+int launch_bam_sort_pass(const BamSortArgs &a, void *stream);
+int launch_bam_sort_keys(int64_t n, const int32_t *tid, const int64_t *pos, const int32_t *flag, int32_t no_tid, unsigned long long *keys, void *stream);
+constexpr int BGZF_PAYLOAD = 65280, BGZF_SLICE = 255, BGZF_OVERHEAD = 31, BGZF_EOF = 28;
+struct BgzfArgs {  // k_bgzf_frame: one workgroup of 256 threads per block, slices of BGZF_SLICE bytes
+    const uint8_t *data;
+    int64_t len;
+    uint8_t *out;
+    uint32_t x2n[32];            // x^(2^k) modulo the polynomial, reflected
+    uint32_t level[8];           // x^(8 * BGZF_SLICE * 2^k): the multiplier of level k of the combining tree when the right half is full
+};
+int launch_bgzf_frame(const BgzfArgs &a, void *stream);
+struct BamRec {  // one SAM line as the host's parsers found it
+    int64_t name, cigar_lo, cigar_hi, seq, qual;  // offsets in the text; qual < 0: "*"
+    int64_t tag_off;
+    int32_t l_name, l_seq, tag_len;
+    int32_t tid, pos, flag, mapq, next_tid, next_pos, tlen;
+};
+struct BamMeasure {  // what k_bam_measure finds
+    int64_t size;       // bytes of the record in the stream, block_size included
+    uint32_t n_ops, consumed;
+    int32_t end;
+    uint32_t bin;
+};
+constexpr int BAM_TILE = 4096;
+struct BamArgs {
+    int64_t n, n_items, header_len;
+    const uint8_t *text;
+    const BamRec *recs;
+    const uint8_t *tags;
+    BamMeasure *meas;
+    int32_t *bad;                // set to 1 by a malformed cigar
+    const uint32_t *order;       // [n] record at place j
+    int64_t *size_sorted;        // [n + 1]: the sizes in output order, then their exclusive scan in place
+    int64_t *tile;               // scratch of that scan
+    int64_t *rec_off;            // [n]: first stream byte of record i
+    const unsigned long long *items;  // [n_items] record << 32 | tile of SEQ / QUAL
+    uint8_t *raw;                // the uncompressed stream
+    // the index, over the places j
+    int64_t n_refs;
+    const int64_t *lin_off;      // [n_refs + 1] first window of every reference
+    uint32_t *head;              // [n + 1]: 1 where a run of one (tid, bin) begins, then its exclusive scan in place (int32)
+    int32_t *head_tile;
+    unsigned long long *run_key; // [runs] tid' << 16 | bin in file order
+    unsigned long long *run_beg, *run_end;  // [runs] in file order
+    unsigned long long *linear, *meta, *no_coor;
+};
+int launch_bam_measure(const BamArgs &a, void *stream);
+int launch_bam_offsets(const BamArgs &a, void *stream);   // sizes in output order, their scan, rec_off
+int launch_bam_encode(const BamArgs &a, void *stream);    // the cigars, then the (record, tile) items
+int launch_bam_index_heads(const BamArgs &a, void *stream);  // head flags + scan, linear, meta
+int launch_bam_index_runs(const BamArgs &a, void *stream);   // the runs in file order
+struct BamGatherArgs {
+    int64_t n_runs;
+    const uint32_t *perm;
+    const unsigned long long *key, *beg, *end;
+    int32_t no_tid;
+    int32_t *run_tid;
+    uint32_t *run_bin;
+    unsigned long long *out_beg, *out_end;
+};
+int launch_bam_gather_runs(const BamGatherArgs &a, void *stream);
 constexpr float EXPECT_FIXED_ONE = 1099511627776.0f;  // 2^40
 struct ExpectArgs {
     const Task *tasks;

@@ -725,6 +725,13 @@ class Context(object):
             check(rc, "npr_align_quality", self)
         return out
 
+    def sam_to_bam(self, samFile, bamFile, sort=True, index=True):
+        """samFile as a BAM file made on the device (include/nprealign.h: npr_sam_bam; nanopore_amd/bam.py): coordinate-sorted, with
+        bamFile + ".bai" beside it when index is set, or in the file's order without an index (sort=False).  BGZF with stored blocks: the
+        file is about the size of the uncompressed stream.  -> the counts (records, references, bytes, no_coordinate, mapped, unmapped)."""
+        from . import bam
+        return bam.sam_to_bam(self, samFile, bamFile, sort=sort, index=index)
+
     def align_indel_kmers(self, refs, reads, cigars, k=5, ref_index=None, start=None):
         """The k-mers that straddle a gap of arbitrary alignments (arguments as for align_stats), counted on the device
         (include/nprealign.h: npr_align_indel_kmers): (read-side table, reference-side table), int64 [4^k + 1] each."""
