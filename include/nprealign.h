@@ -899,7 +899,8 @@ int64_t npr_names_mark(const char *names_text, const int64_t *name_span /* [2 n]
 
 /* ---- coordinate-sorted BAM and its BAI index from a SAM text (SAMv1 section 4 BAM, 4.1 BGZF, 5 indexing) ----
  * What the reference gets from samToBamFile, pysam.sort and pysam.index (nanopore/metaAnalyses/customTrackAssemblyHub.py:56-62).  The
- * BAM is BGZF with STORED deflate blocks (no compression: the file is about the size of the uncompressed stream).  The host parts
+ * BAM is BGZF with STORED deflate blocks by default (the file is about the size of the uncompressed stream); npr_bgzf_deflate and
+ * npr_sam_bam_deflate write the same stream with every block COMPRESSED on the device (csrc/npr_deflate.hip).  The host parts
  * (npr_sam_parse_tail, npr_bam_tags, npr_bam_header, npr_bai_write: csrc/npr_bam_host.cpp, threaded, no GPU needed) read what
  * npr_sam_parse leaves aside and write the two small tables; the device parts (csrc/npr_bam.hip) order, measure, encode, frame and index.
  *
@@ -946,6 +947,35 @@ int64_t npr_names_mark(const char *names_text, const int64_t *name_span /* [2 n]
  *   len == 0 gives that block alone.  Returns the stream's length = len + 31 * ceil(len / P) + 28; out == NULL: only that;
  *   NPR_ERR_CAPACITY when cap is smaller, and then nothing is written.  The VIRTUAL OFFSET of byte u of the data is therefore
  *   ((u / P) * (P + 31)) << 16 | (u % P), in closed form; nothing below walks the blocks.
+ *
+ * npr_bgzf_deflate: the same stream in the same blocks (block b still holds data[b * P .. min(len, (b + 1) * P)), so the block of byte u is
+ *   still u / P), every block's deflate data compressed by one workgroup, independently of every other block.  A block of L payload bytes is
+ *   the 18 header bytes above with BSIZE = the block's length - 1; ONE FINAL BLOCK of raw DEFLATE (RFC 1951), the last byte filled with
+ *   zero bits; CRC-32 and ISIZE = L as above.  After the last block the same end-of-file block.
+ *   MATCHES are 3 .. 258 bytes long, 1 .. 32768 back, and never reach before the block's first byte.  The positions are taken in rounds of
+ *   256 consecutive ones; a position p with 3 bytes left has two candidates: p - 1, and the largest position of an earlier round whose three
+ *   bytes hash ((b0 | b1 << 8 | b2 << 16) * 0x9E3779B1 >> 20, 4096 entries) as p's do.  The longer match wins, the nearer on a tie.  The PARSE
+ *   is greedy from position 0: the match of a position that has one of 3 or more bytes, else a literal.
+ *   CODES.  The lengths of a Huffman code over the counts (literal/length: 286 symbols, distance: 30, code lengths: 19), ties broken by
+ *   symbol number (the used symbols are ordered by (count, symbol); of two the earlier never has the shorter code).  When a length would
+ *   exceed 15 bits (7 for the code-length alphabet), the codes per length are folded to the limit and, while the Kraft sum exceeds one, a
+ *   code of the largest shorter length moves one bit down: a complete prefix code again.  No distance symbol: HDIST = 0 and one code of
+ *   length zero; exactly one: one code of one bit.  The code lengths are sent one by one (symbols 16 / 17 / 18 are not used).
+ *   CHOICE.  From the counts, before anything is emitted, the exact bits of (a) one dynamic-Huffman block over the parse, (b) one over the
+ *   literals alone, (c) one stored block (8 L + 40).  The smallest is emitted; on a tie the later of a, b, c.  So no block exceeds L + 31
+ *   bytes, and the stream never exceeds what npr_bgzf_frame returns.  The output is the same bytes from run to run.
+ *   block_off (may be NULL) receives the file offset of every block and, last, of the end-of-file block: ceil(len / P) + 1 entries.  The
+ *   VIRTUAL OFFSET of byte u is block_off[u / P] << 16 | (u % P); for u == len on a full last block that is the end-of-file block's offset,
+ *   as in the stored layout.  out == NULL: returns an upper bound, the stored length (what npr_bgzf_frame returns).  NPR_ERR_CAPACITY when
+ *   cap is below that bound, and then nothing is written.  Else returns the stream's actual length; no byte at or after it is touched.
+ *
+ * npr_deflate_last: of the last stream this context compressed (npr_bgzf_deflate or npr_sam_bam_deflate that returned a length), out[0 .. 3]
+ *   = the blocks emitted as (a), (b), (c) and out[3] = the uncompressed stream's length; all 0 before the first.  NPR_ERR_INVALID for a
+ *   NULL argument.
+ *
+ * npr_sam_bam_deflate: npr_sam_bam (below; one body, the same checks and refusals) with the stream framed as npr_bgzf_deflate does and
+ *   every virtual offset of the index taken from its block table.  bam_out == NULL: the upper bound npr_sam_bam returns; cap is checked
+ *   against that bound; returns the file's actual length.
  *
  * npr_sam_bam: the whole conversion in one call; the text, the two parse tables and the tag bytes go up once, the BAM file image and the
  *   index tables come back.  Record i is line i (span, fields, tail as the parsers filled them; tags / tag_off as npr_bam_tags did).
@@ -994,6 +1024,14 @@ int64_t npr_sam_bam(npr_ctx *ctx, const uint8_t *text, int64_t text_len, const i
                     int64_t n, const int64_t *tag_off, const uint8_t *tags, const uint8_t *header, int64_t header_len, int64_t n_refs,
                     const int64_t *ref_len, int32_t sorted, uint8_t *bam_out, int64_t cap, int64_t *n_runs, int32_t *run_tid,
                     uint32_t *run_bin, uint64_t *run_beg, uint64_t *run_end, uint64_t *linear, uint64_t *meta, int64_t *n_no_coor);
+int64_t npr_bgzf_deflate(npr_ctx *ctx, const uint8_t *data, int64_t len, uint8_t *out, int64_t cap,
+                         int64_t *block_off /* [ceil(len / NPR_BGZF_PAYLOAD) + 1] or NULL */);
+int32_t npr_deflate_last(npr_ctx *ctx, int64_t *out /* [4] */);
+int64_t npr_sam_bam_deflate(npr_ctx *ctx, const uint8_t *text, int64_t text_len, const int64_t *span, const int64_t *fields,
+                            const int64_t *tail, int64_t n, const int64_t *tag_off, const uint8_t *tags, const uint8_t *header,
+                            int64_t header_len, int64_t n_refs, const int64_t *ref_len, int32_t sorted, uint8_t *bam_out, int64_t cap,
+                            int64_t *n_runs, int32_t *run_tid, uint32_t *run_bin, uint64_t *run_beg, uint64_t *run_end,
+                            uint64_t *linear, uint64_t *meta, int64_t *n_no_coor);
 int64_t npr_bai_write(int64_t n_refs, const int64_t *ref_len, int64_t n_runs, const int32_t *run_tid, const uint32_t *run_bin,
                       const uint64_t *run_beg, const uint64_t *run_end, const uint64_t *linear, const uint64_t *meta, int64_t n_no_coor,
                       uint8_t *out, int64_t cap);

@@ -225,6 +225,9 @@ SIGNATURES = {
     "npr_bam_sort_order": (i32, [vp, i64, vp, vp, vp, vp]),
     "npr_bgzf_frame": (i64, [vp, vp, i64, vp, i64]),
     "npr_sam_bam": (i64, [vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i64, vp, i32, vp, i64, C.POINTER(i64)] + [vp] * 6 + [C.POINTER(i64)]),
+    "npr_bgzf_deflate": (i64, [vp, vp, i64, vp, i64, vp]),
+    "npr_deflate_last": (i32, [vp, vp]),
+    "npr_sam_bam_deflate": (i64, [vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i64, vp, i32, vp, i64, C.POINTER(i64)] + [vp] * 6 + [C.POINTER(i64)]),
     "npr_bai_write": (i64, [i64, vp, i64] + [vp] * 6 + [i64, vp, i64]),
     "npr_batch_create_spans": (i32, [vp, _params, i64, i64] + [vp] * 10 + [_out]),
 }

@@ -237,15 +237,16 @@ def _context(device=0):
     return _shared_ctx[device]
 
 
-def samToBamFile(samInputFile, bamOutputFile, ctx=None):
+def samToBamFile(samInputFile, bamOutputFile, ctx=None, compress=False):
     """samToBamFile of the reference (nanopore/analyses/utils.py: a pysam reader into a "wb" writer): the records in the file's order,
-    made on the device (realign.Context.sam_to_bam); no index."""
-    return (ctx or _context()).sam_to_bam(samInputFile, bamOutputFile, sort=False, index=False)
+    made on the device (realign.Context.sam_to_bam); no index.  compress: compressed BGZF blocks instead of stored ones."""
+    return (ctx or _context()).sam_to_bam(samInputFile, bamOutputFile, sort=False, index=False, compress=compress)
 
 
-def samToSortedBamFile(samFile, sortedBamFile, ctx=None):
-    """samToBamFile, pysam.sort and pysam.index in one: sortedBamFile coordinate-sorted and sortedBamFile + ".bai" beside it."""
-    return (ctx or _context()).sam_to_bam(samFile, sortedBamFile, sort=True, index=True)
+def samToSortedBamFile(samFile, sortedBamFile, ctx=None, compress=False):
+    """samToBamFile, pysam.sort and pysam.index in one: sortedBamFile coordinate-sorted and sortedBamFile + ".bai" beside it.
+    compress: compressed BGZF blocks instead of stored ones."""
+    return (ctx or _context()).sam_to_bam(samFile, sortedBamFile, sort=True, index=True, compress=compress)
 
 
 def _loadHmmInto(ctx, hmmFile, slot=0):

@@ -1,7 +1,8 @@
 """SAM text to a coordinate-sorted BAM file and its BAI index through libnprealign.so (include/nprealign.h, "coordinate-sorted BAM";
 csrc/npr_bam_host.cpp, csrc/npr_bam.hip): what the reference gets from samToBamFile, pysam.sort and pysam.index
 (nanopore/metaAnalyses/customTrackAssemblyHub.py:56-62), without samtools.  The file is mapped and parsed as ingest.SamText does; the
-records are ordered, encoded, framed (BGZF with stored deflate blocks: no compression) and indexed on the device.  No CPU fallback.
+records are ordered, encoded, framed and indexed on the device: BGZF with stored deflate blocks by default (every byte as before), or,
+with compress=True, with every block compressed there (npr_sam_bam_deflate, csrc/npr_deflate.hip).  No CPU fallback.
 """
 import ctypes as C
 import os
@@ -75,7 +76,7 @@ def sort_order(ctx, tid, pos, flag):
 
 
 def bgzf_frame(ctx, data, cap=None):
-    """`data` (bytes or a uint8 array) as a BGZF stream of stored blocks, framed and checksummed on the device (npr_bgzf_frame): uint8 array.
+    """`data` (bytes or a uint8 array) as a BGZF stream of stored blocks (bgzf_deflate: compressed ones), framed and checksummed on the device (npr_bgzf_frame): uint8 array.
     cap: the size of the output buffer handed over (default: what the stream needs)."""
     data = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else _arr(data, np.uint8)
     total = check(ctx._L.npr_bgzf_frame(ctx._h, ptr(data), len(data), None, 0), "npr_bgzf_frame", ctx)
@@ -84,8 +85,28 @@ def bgzf_frame(ctx, data, cap=None):
     return out[:total]
 
 
-def convert(ctx, sam, fields, tail, tag_off, tags, header, ref_len, sort=True, index=True):
-    """The device call alone (npr_sam_bam) on a parsed ingest.SamText: (the BAM file image, the BAI file's bytes or None)."""
+def bgzf_deflate(ctx, data, cap=None):
+    """`data` as a BGZF stream whose blocks are compressed on the device (npr_bgzf_deflate): (uint8 array, block_off int64 [blocks + 1]: the
+    file offset of every block and of the end-of-file block).  cap: the size of the output buffer handed over (default: the stored length)."""
+    data = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else _arr(data, np.uint8)
+    bound = check(ctx._L.npr_bgzf_deflate(ctx._h, ptr(data), len(data), None, 0, None), "npr_bgzf_deflate", ctx)
+    out = np.zeros(bound if cap is None else max(int(cap), 1), dtype=np.uint8)
+    block_off = np.zeros((len(data) + _lib.BGZF_PAYLOAD - 1) // _lib.BGZF_PAYLOAD + 1, dtype=np.int64)
+    total = check(ctx._L.npr_bgzf_deflate(ctx._h, ptr(data), len(data), ptr(out), len(out) if cap is None else int(cap), ptr(block_off)), "npr_bgzf_deflate", ctx)
+    return out[:total], block_off
+
+
+def deflate_last(ctx):
+    """Of the last stream the context compressed (npr_deflate_last): {"a", "b", "c": the blocks emitted as dynamic Huffman over matches and
+    literals, over the literals alone, and stored; "stream_bytes": the uncompressed stream's length}."""
+    out = np.zeros(4, dtype=np.int64)
+    check(ctx._L.npr_deflate_last(ctx._h, ptr(out)), "npr_deflate_last", ctx)
+    return {"a": int(out[0]), "b": int(out[1]), "c": int(out[2]), "stream_bytes": int(out[3])}
+
+
+def convert(ctx, sam, fields, tail, tag_off, tags, header, ref_len, sort=True, index=True, compress=False):
+    """The device call alone (npr_sam_bam, or npr_sam_bam_deflate with compress) on a parsed ingest.SamText: (the BAM file image, the BAI
+    file's bytes or None)."""
     n, n_refs = len(sam), len(ref_len)
     want_index = bool(sort and index)
     run_tid, run_bin = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.uint32)
@@ -98,16 +119,19 @@ def convert(ctx, sam, fields, tail, tag_off, tags, header, ref_len, sort=True, i
     # a bound instead of a sizing call (pages nobody touches cost nothing): a record is at most twice its line plus its tag bytes
     stream = len(header) + 2 * int(sam.line_lengths().sum()) + int(tag_off[-1]) + 64 * n
     out = np.empty(stream + 31 * (stream // _lib.BGZF_PAYLOAD + 1) + 28, dtype=np.uint8)
-    total = int(check(ctx._L.npr_sam_bam(*head, ptr(out), len(out), *index_args), "npr_sam_bam", ctx))
+    entry = "npr_sam_bam_deflate" if compress else "npr_sam_bam"
+    total = int(check(getattr(ctx._L, entry)(*head, ptr(out), len(out), *index_args), entry, ctx))
     r = n_runs.value
     bai = bai_write(ref_len, run_tid[:r], run_bin[:r], run_beg[:r], run_end[:r], linear, meta[:n_refs], n_no_coor.value) if want_index else None
     return out[:total], bai
 
 
-def sam_to_bam(ctx, samFile, bamFile, sort=True, index=True):
+def sam_to_bam(ctx, samFile, bamFile, sort=True, index=True, compress=False):
     """samFile as a BAM file (npr_sam_bam): coordinate-sorted with bamFile + ".bai" beside it (sort and index), or in the file's order.
+    compress: the BGZF blocks are compressed on the device (npr_sam_bam_deflate) instead of stored; the records are the same bytes.
     A line that does not parse, an RNAME the header does not name or a malformed cigar raises and leaves no file; nothing is dropped.
-    -> {"records", "references", "bytes", "no_coordinate", "mapped", "unmapped"}."""
+    -> {"records", "references", "bytes", "no_coordinate", "mapped", "unmapped"}, with compress also "stream_bytes" (the uncompressed
+    stream's length)."""
     from .ingest import SamText
     sam = SamText(samFile)
     n = len(sam)
@@ -115,7 +139,7 @@ def sam_to_bam(ctx, samFile, bamFile, sort=True, index=True):
     tail = parse_tail(sam, fields)
     tag_off, tags = bam_tags(sam.text, tail)
     header, ref_len = bam_header(sam.header, sort)
-    out, bai = convert(ctx, sam, fields, tail, tag_off, tags, header, ref_len, sort, index)
+    out, bai = convert(ctx, sam, fields, tail, tag_off, tags, header, ref_len, sort, index, compress)
     tmp = bamFile + ".tmp"
     try:
         with open(tmp, "wb") as fh:
@@ -128,5 +152,8 @@ def sam_to_bam(ctx, samFile, bamFile, sort=True, index=True):
         with open(bamFile + ".bai", "wb") as fh:
             bai.tofile(fh)
     flag = fields[:, 7]
-    return {"records": n, "references": len(ref_len), "bytes": len(out), "no_coordinate": int((fields[:, 10] < 0).sum()),
-            "mapped": int(((flag & 4) == 0).sum()), "unmapped": int(((flag & 4) != 0).sum())}
+    counts = {"records": n, "references": len(ref_len), "bytes": len(out), "no_coordinate": int((fields[:, 10] < 0).sum()),
+              "mapped": int(((flag & 4) == 0).sum()), "unmapped": int(((flag & 4) != 0).sum())}
+    if compress:
+        counts["stream_bytes"] = int(deflate_last(ctx)["stream_bytes"])
+    return counts

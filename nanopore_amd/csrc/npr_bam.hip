@@ -22,13 +22,13 @@
 // block).  LDS: 1 KiB table + 256 x 8 bytes of tree = 3 KiB a workgroup.
 #include <hip/hip_runtime.h>
 
+#include "npr_bgzf.h"
 #include "npr_device.h"
 
 namespace npr {
 namespace {
 
 constexpr int THREADS = 256, WAVE = 64, WAVES = THREADS / WAVE;
-constexpr uint32_t CRC_POLY = 0xEDB88320u;
 
 // ------------------------------------------------------------------ the sort
 __global__ void __launch_bounds__(THREADS) k_sort_keys(int64_t n, const int32_t *tid, const int64_t *pos, const int32_t *flag, int32_t no_tid,
@@ -92,26 +92,6 @@ __global__ void __launch_bounds__(THREADS) k_sort_scatter(BamSortArgs a) {
 }
 
 // ------------------------------------------------------------------ BGZF
-__device__ __forceinline__ uint32_t gf_mul(uint32_t a, uint32_t b) {  // a * b modulo the polynomial, reflected: bit 31 is x^0
-    uint32_t p = 0;
-#pragma unroll 4
-    for (int k = 0; k < 32; ++k) {
-        if (a & (0x80000000u >> k)) p ^= b;
-        b = (b & 1) ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
-__device__ __forceinline__ uint32_t x_pow_bytes(const uint32_t *x2n, uint32_t bytes) {  // x^(8 * bytes)
-    uint32_t p = 0x80000000u;
-    for (int k = 3; bytes; bytes >>= 1, ++k)
-        if (bytes & 1) p = gf_mul(x2n[k & 31], p);
-    return p;
-}
-__device__ __forceinline__ void put16(uint8_t *p, uint32_t v) { p[0] = static_cast<uint8_t>(v), p[1] = static_cast<uint8_t>(v >> 8); }
-__device__ __forceinline__ void put32(uint8_t *p, uint32_t v) {
-    p[0] = static_cast<uint8_t>(v), p[1] = static_cast<uint8_t>(v >> 8), p[2] = static_cast<uint8_t>(v >> 16), p[3] = static_cast<uint8_t>(v >> 24);
-}
-
 __global__ void __launch_bounds__(THREADS) k_bgzf_frame(BgzfArgs a) {
     __shared__ uint32_t table[256];
     __shared__ uint32_t t_crc[THREADS], t_len[THREADS];
@@ -119,50 +99,19 @@ __global__ void __launch_bounds__(THREADS) k_bgzf_frame(BgzfArgs a) {
     const int64_t b = blockIdx.x;
     uint8_t *const out = a.out + b * (BGZF_PAYLOAD + BGZF_OVERHEAD);
     if (b >= blocks) {  // the end-of-file block, behind the last block (which may be short)
-        uint8_t *const out = a.out + a.len + blocks * BGZF_OVERHEAD;
-        if (threadIdx.x < BGZF_EOF) {
-            const uint8_t eof[BGZF_EOF] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            out[threadIdx.x] = eof[threadIdx.x];
-        }
+        bgzf_put_eof(a.out + a.len + blocks * BGZF_OVERHEAD, threadIdx.x);
         return;
     }
     const uint8_t *const in = a.data + b * BGZF_PAYLOAD;
     const uint32_t L = static_cast<uint32_t>(a.len - b * BGZF_PAYLOAD < BGZF_PAYLOAD ? a.len - b * BGZF_PAYLOAD : BGZF_PAYLOAD);
-    {
-        uint32_t c = threadIdx.x;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ CRC_POLY : c >> 1;
-        table[threadIdx.x] = c;
-    }
     if (threadIdx.x == 0) {
-        const uint8_t head[12] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0};
-        for (int k = 0; k < 12; ++k) out[k] = head[k];
-        out[12] = 'B', out[13] = 'C', out[14] = 2, out[15] = 0;
-        put16(out + 16, L + BGZF_OVERHEAD - 1);
+        bgzf_put_header(out, L + BGZF_OVERHEAD);
         out[18] = 1;
         put16(out + 19, L), put16(out + 21, ~L & 0xffffu);
     }
     for (uint32_t k = threadIdx.x; k < L; k += THREADS) out[23 + k] = in[k];
-    __syncthreads();
-    const uint32_t lo = min(L, threadIdx.x * BGZF_SLICE), hi = min(L, lo + BGZF_SLICE);
-    uint32_t c = threadIdx.x == 0 ? 0xFFFFFFFFu : 0u;
-    for (uint32_t k = lo; k < hi; ++k) c = table[(c ^ in[k]) & 0xff] ^ (c >> 8);
-    t_crc[threadIdx.x] = c, t_len[threadIdx.x] = hi - lo;
-    __syncthreads();
-#pragma unroll 1
-    for (int k = 0; k < 8; ++k) {
-        const uint32_t step = 1u << k;
-        if ((threadIdx.x & (2 * step - 1)) == 0) {
-            const uint32_t rl = t_len[threadIdx.x + step];
-            if (rl) {
-                const uint32_t m = rl == BGZF_SLICE * step ? a.level[k] : x_pow_bytes(a.x2n, rl);
-                t_crc[threadIdx.x] = gf_mul(t_crc[threadIdx.x], m) ^ t_crc[threadIdx.x + step];
-                t_len[threadIdx.x] += rl;
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) put32(out + 23 + L, ~t_crc[0]), put32(out + 27 + L, L);
+    const uint32_t crc = bgzf_crc(in, L, a, table, t_crc, t_len);
+    if (threadIdx.x == 0) put32(out + 23 + L, crc), put32(out + 27 + L, L);
 }
 
 // ------------------------------------------------------------------ the records
@@ -327,8 +276,10 @@ __global__ void __launch_bounds__(THREADS) k_bam_encode(BamArgs a) {
 }
 
 // ------------------------------------------------------------------ the index
-__device__ __forceinline__ unsigned long long voffset(int64_t u) {
-    return static_cast<unsigned long long>(u / BGZF_PAYLOAD * (BGZF_PAYLOAD + BGZF_OVERHEAD)) << 16 | static_cast<unsigned long long>(u % BGZF_PAYLOAD);
+// the virtual offset of stream byte u: the file offset of its block from the table of a compressed file, in closed form without one
+__device__ __forceinline__ unsigned long long voffset(const int64_t *block_off, int64_t u) {
+    const int64_t at = block_off ? block_off[u / BGZF_PAYLOAD] : u / BGZF_PAYLOAD * (BGZF_PAYLOAD + BGZF_OVERHEAD);
+    return static_cast<unsigned long long>(at) << 16 | static_cast<unsigned long long>(u % BGZF_PAYLOAD);
 }
 
 // size_sorted holds the scan: place j's record is the stream bytes [header_len + size_sorted[j], header_len + size_sorted[j + 1])
@@ -348,7 +299,7 @@ __global__ void __launch_bounds__(THREADS) k_bam_index_heads(BamArgs a) {
         atomicAdd(a.no_coor, 1ull);
         return;
     }
-    const unsigned long long v0 = voffset(a.header_len + a.size_sorted[j]), v1 = voffset(a.header_len + a.size_sorted[j + 1]);
+    const unsigned long long v0 = voffset(a.block_off, a.header_len + a.size_sorted[j]), v1 = voffset(a.block_off, a.header_len + a.size_sorted[j + 1]);
     unsigned long long *const mt = a.meta + 4 * static_cast<int64_t>(r.tid);
     atomicMin(mt, v0), atomicMax(mt + 1, v1), atomicAdd(mt + ((r.flag & 4) ? 3 : 2), 1ull);
     const int64_t w_first = a.lin_off[r.tid], windows = a.lin_off[r.tid + 1] - w_first;
@@ -366,11 +317,11 @@ __global__ void __launch_bounds__(THREADS) k_bam_index_runs(BamArgs a) {
     if (run[j + 1] == q) return;  // no head
     const uint32_t i = a.order[j];
     const unsigned long long t = a.recs[i].tid < 0 ? static_cast<unsigned long long>(a.n_refs) : static_cast<unsigned long long>(a.recs[i].tid);
-    const unsigned long long v0 = voffset(a.header_len + a.size_sorted[j]);
+    const unsigned long long v0 = voffset(a.block_off, a.header_len + a.size_sorted[j]);
     a.run_key[q] = t << 16 | a.meas[i].bin;
     a.run_beg[q] = v0;
     if (q > 0) a.run_end[q - 1] = v0;
-    if (q == run[a.n] - 1) a.run_end[q] = voffset(a.header_len + a.size_sorted[a.n]);
+    if (q == run[a.n] - 1) a.run_end[q] = voffset(a.block_off, a.header_len + a.size_sorted[a.n]);
 }
 
 __global__ void __launch_bounds__(THREADS) k_bam_gather_runs(BamGatherArgs a) {

@@ -1,5 +1,5 @@
-// npr_bam_api.cpp -- npr_bam_sort_order, npr_bgzf_frame, npr_sam_bam: the checks, the records as the kernels take them, the launches of
-// npr_bam.hip and the tables as the header defines them ("coordinate-sorted BAM")
+// npr_bam_api.cpp -- npr_bam_sort_order, npr_bgzf_frame, npr_bgzf_deflate, npr_deflate_last, npr_sam_bam, npr_sam_bam_deflate: the checks, the records as the kernels take them, the launches of
+// npr_bam.hip and npr_deflate.hip, and the tables as the header defines them ("coordinate-sorted BAM")
 // (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
 #include "npr_api_internal.h"
 
@@ -61,6 +61,45 @@ void sort_order(const Call &dev, DevBuf<unsigned long long> &keys, int64_t n, in
     dev.sync();  // (the scratch of the passes goes out of scope)
 }
 
+// The stream d_data[0, len) as compressed BGZF blocks: the buffers of one npr_deflate.hip run.  launch() queues the kernels; finish() fetches
+// the block table (block_off[0 .. blocks], host), waits, and returns the file's length; the image then lies in packed.
+struct DeflateRun {
+    DevBuf<uint8_t> slots, packed;
+    DevBuf<uint16_t> dist;
+    DevBuf<int64_t> block_len, tile;
+    DevBuf<uint32_t> chosen;
+    std::vector<int64_t> block_off;
+    int64_t blocks = 0, stream_len = 0;
+    void launch(const Call &dev, const uint8_t *d_data, int64_t len) {
+        blocks = (len + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD, stream_len = len;
+        dev.alloc(slots, static_cast<size_t>(blocks * DEFLATE_SLOT + 8)), dev.alloc(packed, static_cast<size_t>(bgzf_length(len)));
+        dev.alloc(dist, static_cast<size_t>(std::max<int64_t>(deflate_groups(blocks), 1) * BGZF_PAYLOAD));
+        dev.alloc(block_len, blocks + 1), dev.alloc(tile, scan_tiles(blocks));
+        dev.alloc(chosen, 4), dev.zero(chosen);
+        DeflateArgs d{};
+        d.z.data = d_data, d.z.len = len, d.z.out = slots.p;
+        bgzf_constants(d.z);
+        d.dist = dist.p, d.block_len = block_len.p, d.tile = tile.p, d.chosen = chosen.p, d.packed = packed.p;
+        dev.launched(launch_bgzf_deflate(d, dev.ctx->stream), "k_bgzf_deflate / scan / k_bgzf_pack");
+    }
+    int64_t finish(const Call &dev) {
+        uint32_t how[4] = {0, 0, 0, 0};
+        block_off.assign(static_cast<size_t>(blocks) + 1, 0);
+        dev.fetch(block_off.data(), block_len.p, block_len.bytes());
+        dev.fetch(how, chosen.p, sizeof(how));
+        dev.sync();
+        if (how[3]) dev.failed(NPR_ERR_STATE, "k_bgzf_deflate: the emitted bits of a block are not the measured ones", hipSuccess);
+        for (int k = 0; k < 3; ++k) dev.ctx->deflate_last[k] = how[k];
+        dev.ctx->deflate_last[3] = stream_len;
+        return block_off[blocks] + BGZF_EOF;
+    }
+};
+
+int64_t sam_bam(const char *entry, bool compress, npr_ctx *ctx, const uint8_t *text, int64_t text_len, const int64_t *span, const int64_t *fields, const int64_t *tail,
+                int64_t n, const int64_t *tag_off, const uint8_t *tags, const uint8_t *header, int64_t header_len, int64_t n_refs, const int64_t *ref_len,
+                int32_t sorted, uint8_t *bam_out, int64_t cap, int64_t *n_runs, int32_t *run_tid, uint32_t *run_bin, uint64_t *run_beg, uint64_t *run_end,
+                uint64_t *linear, uint64_t *meta, int64_t *n_no_coor);
+
 }  // namespace
 
 extern "C" {
@@ -111,21 +150,67 @@ int64_t npr_bgzf_frame(npr_ctx *ctx, const uint8_t *data, int64_t len, uint8_t *
     });
 }
 
+int64_t npr_bgzf_deflate(npr_ctx *ctx, const uint8_t *data, int64_t len, uint8_t *out, int64_t cap, int64_t *block_off) {
+    if (!ctx || len < 0 || (len && !data) || cap < 0) return NPR_ERR_INVALID;
+    const int64_t bound = bgzf_length(len);
+    if (!out) return bound;
+    if (cap < bound) return NPR_ERR_CAPACITY;
+    if ((len + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD + 1 >= (int64_t(1) << 31)) return NPR_ERR_INVALID;
+    return guarded(ctx, "npr_bgzf_deflate", [&](const Call &dev) -> int64_t {
+        DevBuf<uint8_t> d_in;
+        DeflateRun run;
+        dev.upload(d_in, data, static_cast<size_t>(len));
+        run.launch(dev, d_in.p, len);
+        const int64_t total = run.finish(dev);
+        dev.fetch(out, run.packed.p, static_cast<size_t>(total));
+        dev.sync();
+        if (block_off) std::copy(run.block_off.begin(), run.block_off.end(), block_off);
+        return total;
+    });
+}
+
+int32_t npr_deflate_last(npr_ctx *ctx, int64_t *out) {
+    if (!ctx || !out) return NPR_ERR_INVALID;
+    std::copy(ctx->deflate_last, ctx->deflate_last + 4, out);
+    return NPR_OK;
+}
+
 int64_t npr_sam_bam(npr_ctx *ctx, const uint8_t *text, int64_t text_len, const int64_t *span, const int64_t *fields, const int64_t *tail, int64_t n,
                     const int64_t *tag_off, const uint8_t *tags, const uint8_t *header, int64_t header_len, int64_t n_refs, const int64_t *ref_len,
                     int32_t sorted, uint8_t *bam_out, int64_t cap, int64_t *n_runs, int32_t *run_tid, uint32_t *run_bin, uint64_t *run_beg,
                     uint64_t *run_end, uint64_t *linear, uint64_t *meta, int64_t *n_no_coor) {
+    return sam_bam("npr_sam_bam", false, ctx, text, text_len, span, fields, tail, n, tag_off, tags, header, header_len, n_refs, ref_len, sorted, bam_out, cap, n_runs,
+                   run_tid, run_bin, run_beg, run_end, linear, meta, n_no_coor);
+}
+
+int64_t npr_sam_bam_deflate(npr_ctx *ctx, const uint8_t *text, int64_t text_len, const int64_t *span, const int64_t *fields, const int64_t *tail, int64_t n,
+                            const int64_t *tag_off, const uint8_t *tags, const uint8_t *header, int64_t header_len, int64_t n_refs, const int64_t *ref_len,
+                            int32_t sorted, uint8_t *bam_out, int64_t cap, int64_t *n_runs, int32_t *run_tid, uint32_t *run_bin, uint64_t *run_beg,
+                            uint64_t *run_end, uint64_t *linear, uint64_t *meta, int64_t *n_no_coor) {
+    return sam_bam("npr_sam_bam_deflate", true, ctx, text, text_len, span, fields, tail, n, tag_off, tags, header, header_len, n_refs, ref_len, sorted, bam_out, cap,
+                   n_runs, run_tid, run_bin, run_beg, run_end, linear, meta, n_no_coor);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the body of npr_sam_bam and npr_sam_bam_deflate: they differ in how the stream is framed and where the virtual offsets come from
+int64_t sam_bam(const char *entry, bool compress, npr_ctx *ctx, const uint8_t *text, int64_t text_len, const int64_t *span, const int64_t *fields, const int64_t *tail,
+                int64_t n, const int64_t *tag_off, const uint8_t *tags, const uint8_t *header, int64_t header_len, int64_t n_refs, const int64_t *ref_len,
+                int32_t sorted, uint8_t *bam_out, int64_t cap, int64_t *n_runs, int32_t *run_tid, uint32_t *run_bin, uint64_t *run_beg, uint64_t *run_end,
+                uint64_t *linear, uint64_t *meta, int64_t *n_no_coor) {
     const bool index = sorted && bam_out;
     if (!ctx || n < 0 || n >= (int64_t(1) << 31) || text_len < 0 || header_len < 0 || n_refs < 0 || n_refs >= (1 << 30) || cap < 0 || (header_len && !header) ||
         (n && (!text || !span || !fields || !tail || !tag_off)) || (n_refs && !ref_len) ||
         (index && (!n_runs || !n_no_coor || (n && (!run_tid || !run_bin || !run_beg || !run_end)) || (n_refs && (!linear || !meta)))))
         return NPR_ERR_INVALID;
-    return guarded(ctx, "npr_sam_bam", [&](const Call &dev) -> int64_t {
+    return guarded(ctx, entry, [&](const Call &dev) -> int64_t {
         // the lines as records, every one checked before anything is launched
         std::vector<BamRec> recs(static_cast<size_t>(n));
         std::vector<int64_t> lin_off(static_cast<size_t>(n_refs) + 1, 0);
         for (int64_t k = 0; k < n_refs; ++k) {
-            if (ref_len[k] < 1) return fail(ctx, NPR_ERR_INVALID, "npr_sam_bam: a reference length below 1");
+            if (ref_len[k] < 1) return fail(ctx, NPR_ERR_INVALID, (std::string(entry) + ": a reference length below 1").c_str());
             lin_off[k + 1] = lin_off[k] + ((ref_len[k] - 1) >> 14) + 1;
         }
         std::atomic<int> bad{0};
@@ -156,10 +241,10 @@ int64_t npr_sam_bam(npr_ctx *ctx, const uint8_t *text, int64_t text_len, const i
             }
         });
         if (n && tag_off[n] > tag_off[0] && !tags) return NPR_ERR_INVALID;
-        if (bad) return fail(ctx, NPR_ERR_INVALID, "npr_sam_bam: a line that did not parse, names an unknown reference or lies outside the text");
+        if (bad) return fail(ctx, NPR_ERR_INVALID, (std::string(entry) + ": a line that did not parse, names an unknown reference or lies outside the text").c_str());
         for (int64_t i = 0; i < n; ++i) tiles[i + 1] += tiles[i];
         const int64_t n_items = tiles[n];
-        if (n_items >= (int64_t(1) << 31)) return fail(ctx, NPR_ERR_INVALID, "npr_sam_bam: 2^31 tiles and more in one call");
+        if (n_items >= (int64_t(1) << 31)) return fail(ctx, NPR_ERR_INVALID, (std::string(entry) + ": 2^31 tiles and more in one call").c_str());
         std::vector<unsigned long long> items(static_cast<size_t>(n_items));
         parallel_for((n + 255) / 256, ctx->host_threads, [&](int64_t c) {
             for (int64_t i = c * 256, hi = std::min(n, (c + 1) * 256); i < hi; ++i)
@@ -206,26 +291,35 @@ int64_t npr_sam_bam(npr_ctx *ctx, const uint8_t *text, int64_t text_len, const i
         dev.fetch(&records_bytes, d_size.p + n, sizeof(int64_t));
         dev.fetch(&bad_cigar, d_bad.p, sizeof(int32_t));
         dev.sync();
-        if (bad_cigar) return fail(ctx, NPR_ERR_INVALID, "npr_sam_bam: a malformed CIGAR");
+        if (bad_cigar) return fail(ctx, NPR_ERR_INVALID, (std::string(entry) + ": a malformed CIGAR").c_str());
         const int64_t stream_len = header_len + records_bytes, total = bgzf_length(stream_len);
         if (!bam_out) return total;
         if (cap < total) return NPR_ERR_CAPACITY;
-        if (total / BGZF_PAYLOAD + 2 >= (int64_t(1) << 31)) return fail(ctx, NPR_ERR_INVALID, "npr_sam_bam: 2^31 BGZF blocks and more");
+        if (total / BGZF_PAYLOAD + 2 >= (int64_t(1) << 31)) return fail(ctx, NPR_ERR_INVALID, (std::string(entry) + ": 2^31 BGZF blocks and more").c_str());
 
         dev.alloc(d_raw, static_cast<size_t>(std::max<int64_t>(stream_len, 1)));
         dev.copy_up(d_raw.p, header, static_cast<size_t>(header_len));
         dev.upload(d_items, items);
         a.items = d_items.p, a.raw = d_raw.p;
         dev.launched(launch_bam_encode(a, ctx->stream), "k_bam_cigar / k_bam_encode");
-        dev.alloc(d_out, static_cast<size_t>(total));
-        BgzfArgs z{};
-        z.data = d_raw.p, z.len = stream_len, z.out = d_out.p;
-        bgzf_constants(z);
-        dev.launched(launch_bgzf_frame(z, ctx->stream), "k_bgzf_frame");
-        dev.fetch(bam_out, d_out.p, static_cast<size_t>(total));
+        DeflateRun deflate;
+        int64_t written = total;
+        if (compress) {
+            deflate.launch(dev, d_raw.p, stream_len);
+            written = deflate.finish(dev);
+            dev.fetch(bam_out, deflate.packed.p, static_cast<size_t>(written));
+            a.block_off = deflate.block_len.p;
+        } else {
+            dev.alloc(d_out, static_cast<size_t>(total));
+            BgzfArgs z{};
+            z.data = d_raw.p, z.len = stream_len, z.out = d_out.p;
+            bgzf_constants(z);
+            dev.launched(launch_bgzf_frame(z, ctx->stream), "k_bgzf_frame");
+            dev.fetch(bam_out, d_out.p, static_cast<size_t>(total));
+        }
         if (!index) {
             dev.sync();
-            return total;
+            return written;
         }
 
         // the index
@@ -268,8 +362,8 @@ int64_t npr_sam_bam(npr_ctx *ctx, const uint8_t *text, int64_t text_len, const i
         dev.fetch(&no_coor, d_no_coor.p, sizeof(no_coor));
         dev.sync();
         *n_no_coor = static_cast<int64_t>(no_coor);
-        return total;
+        return written;
     });
 }
 
-}  // extern "C"
+}  // namespace

@@ -498,6 +498,20 @@ struct BgzfArgs {  // k_bgzf_frame: one workgroup of 256 threads per block, slic
     uint32_t level[8];           // x^(8 * BGZF_SLICE * 2^k): the multiplier of level k of the combining tree when the right half is full
 };
 int launch_bgzf_frame(const BgzfArgs &a, void *stream);
+// BGZF blocks of compressed deflate data (npr_deflate.hip; the block layout and the choice rule: include/nprealign.h, npr_bgzf_deflate)
+constexpr int DEFLATE_SLOT = BGZF_PAYLOAD + BGZF_OVERHEAD;   // stride of the slots the blocks are compressed into
+constexpr int DEFLATE_MAX_GROUPS = 512;                      // workgroups of k_bgzf_deflate: each takes every DEFLATE_MAX_GROUPS-th block
+inline int64_t deflate_groups(int64_t blocks) { return blocks < DEFLATE_MAX_GROUPS ? blocks : DEFLATE_MAX_GROUPS; }
+struct DeflateArgs {
+    BgzfArgs z;                  // data, len, the CRC constants; out = the slots: [blocks * DEFLATE_SLOT + 8]
+    uint16_t *dist;              // [deflate_groups(blocks)][BGZF_PAYLOAD] scratch: distance - 1 of the match found at a position
+    int64_t *block_len;          // [blocks + 1]: every block's length, then their exclusive scan in place: block_off
+    int64_t *tile;               // [scan_tiles(blocks)] scratch of the scan
+    uint32_t *chosen;            // [4] zeroed, added to: blocks emitted as (a) matches and literals, (b) literals, (c) stored; [3] stays 0 unless the
+                                 // emitted bits disagree with the measured ones (a defect: the block is then stored and the call fails)
+    uint8_t *packed;             // the file image: block b at block_off[b], the end-of-file block at block_off[blocks]
+};
+int launch_bgzf_deflate(const DeflateArgs &a, void *stream);  // k_bgzf_deflate, the scan, k_bgzf_pack
 struct BamRec {  // one SAM line as the host's parsers found it
     int64_t name, cigar_lo, cigar_hi, seq, qual;  // offsets in the text; qual < 0: "*"
     int64_t tag_off;
@@ -532,6 +546,7 @@ struct BamArgs {
     unsigned long long *run_key; // [runs] tid' << 16 | bin in file order
     unsigned long long *run_beg, *run_end;  // [runs] in file order
     unsigned long long *linear, *meta, *no_coor;
+    const int64_t *block_off;    // file offset of every BGZF block of a compressed file, [blocks + 1]; null: stored blocks, the closed form
 };
 int launch_bam_measure(const BamArgs &a, void *stream);
 int launch_bam_offsets(const BamArgs &a, void *stream);   // sizes in output order, their scan, rec_off

@@ -12,7 +12,8 @@ comes from the experiment's own reference file, the same thing for such names.  
 run repeats every stanza; here they are written anew.  The reference swallows a failed conversion (`except: continue`); here the other
 experiments are still converted and the failures are raised together afterwards, which the pipeline driver reports as a failed
 meta-analysis.  The reference does its work in __init__; here it is run().  Not in the pipeline's default list (the reference has it
-commented out there): `--metaAnalyses CustomTrackAssemblyHub`.
+commented out there): `--metaAnalyses CustomTrackAssemblyHub`.  CustomTrackAssemblyHubCompressed lays out the same hub with BAM files
+whose BGZF blocks are compressed on the device (csrc/npr_deflate.hip), as the reference's are: a browser fetches them over HTTP.
 """
 import os
 import shutil
@@ -45,6 +46,8 @@ def genomesText(header, sequenceId, length):
 class CustomTrackAssemblyHub(AbstractMetaAnalysis):
     """mapping.sam of every experiment as <reference>/bamFiles/<experiment>.sorted.bam + .bai, with trackDb.txt, genomes.txt, groups.txt"""
 
+    compress = False   # stored BGZF blocks; the subclass below compresses them
+
     def run(self, ctx=None):
         from ..analyses.utils import samToSortedBamFile
         failed, tracks = [], {}
@@ -54,8 +57,8 @@ class CustomTrackAssemblyHub(AbstractMetaAnalysis):
             hubDir = os.path.join(self.outputDir, referenceHeader(referenceFastaFile))
             bamDir = os.path.join(hubDir, "bamFiles")
             os.makedirs(bamDir, exist_ok=True)
-            try:
-                samToSortedBamFile(os.path.join(resultsDir, "mapping.sam"), os.path.join(bamDir, experiment + ".sorted.bam"), ctx=ctx)
+            try:   # (the keyword only when set: a converter put in this one's place with the plain signature keeps working)
+                samToSortedBamFile(os.path.join(resultsDir, "mapping.sam"), os.path.join(bamDir, experiment + ".sorted.bam"), ctx=ctx, **({"compress": True} if self.compress else {}))
             except Exception as e:  # the other experiments still get their files
                 failed.append((experiment, e))
                 continue
@@ -84,3 +87,8 @@ class CustomTrackAssemblyHub(AbstractMetaAnalysis):
             fh.write(GROUPS_TEXT)
         if failed:
             raise RuntimeError("CustomTrackAssemblyHub: no sorted BAM for %s" % ", ".join("%s (%s: %s)" % (x, type(e).__name__, e) for x, e in failed)) from failed[0][1]
+
+
+class CustomTrackAssemblyHubCompressed(CustomTrackAssemblyHub):
+    """The same hub with compressed BAM files (`--metaAnalyses CustomTrackAssemblyHubCompressed`; not in the default list either)"""
+    compress = True

@@ -725,12 +725,13 @@ class Context(object):
             check(rc, "npr_align_quality", self)
         return out
 
-    def sam_to_bam(self, samFile, bamFile, sort=True, index=True):
+    def sam_to_bam(self, samFile, bamFile, sort=True, index=True, compress=False):
         """samFile as a BAM file made on the device (include/nprealign.h: npr_sam_bam; nanopore_amd/bam.py): coordinate-sorted, with
-        bamFile + ".bai" beside it when index is set, or in the file's order without an index (sort=False).  BGZF with stored blocks: the
-        file is about the size of the uncompressed stream.  -> the counts (records, references, bytes, no_coordinate, mapped, unmapped)."""
+        bamFile + ".bai" beside it when index is set, or in the file's order without an index (sort=False).  BGZF with stored blocks (the
+        file is about the size of the uncompressed stream), or with compress=True with blocks compressed on the device
+        (npr_sam_bam_deflate).  -> the counts (records, references, bytes, no_coordinate, mapped, unmapped; with compress stream_bytes)."""
         from . import bam
-        return bam.sam_to_bam(self, samFile, bamFile, sort=sort, index=index)
+        return bam.sam_to_bam(self, samFile, bamFile, sort=sort, index=index, compress=compress)
 
     def align_indel_kmers(self, refs, reads, cigars, k=5, ref_index=None, start=None):
         """The k-mers that straddle a gap of arbitrary alignments (arguments as for align_stats), counted on the device
