@@ -1036,6 +1036,69 @@ int64_t npr_bai_write(int64_t n_refs, const int64_t *ref_len, int64_t n_runs, co
                       const uint64_t *run_beg, const uint64_t *run_end, const uint64_t *linear, const uint64_t *meta, int64_t n_no_coor,
                       uint8_t *out, int64_t cap);
 
+/* ---- reading BGZF: the blocks of a file inflated on the device (SAMv1 section 4.1, RFC 1951, RFC 1952) ----
+ * The inverse of npr_bgzf_frame / npr_bgzf_deflate, for the files of any writer (htslib, zlib): csrc/npr_inflate.h is the decoder, one body
+ * for host and device, csrc/npr_inflate.hip the kernel, one workgroup a block.
+ *
+ * npr_bgzf_scan (host, no GPU): walks the blocks of file[0, len).  A block is: 1f 8b 08, FLG with FEXTRA (bit 2) set, MTIME, XFL, OS, XLEN,
+ *   the extra subfields (SI1, SI2, SLEN, data), among them -- anywhere, not only first -- 'B' 'C' of SLEN 2 whose value is BSIZE = the
+ *   block's length - 1; the deflate data; CRC-32 and ISIZE (uint32 each).  The block must lie inside the file, hold its extra field and its
+ *   trailer, and ISIZE must be at most 65536.  A block of ISIZE 0 is a block like any other.  The file must end with the 28-byte end-of-file
+ *   block of npr_bgzf_frame and the blocks before it must fill the file exactly: otherwise it is truncated, NPR_ERR_INVALID.
+ *   *n_blocks = the blocks before that last end-of-file block.  block_off / stream_off (either may be NULL; cap_blocks entries each): the
+ *   file offset of every block and the stream offset of its first payload byte (the sum of the ISIZEs before it), and at index *n_blocks
+ *   the end-of-file block's offset and the stream's length; NPR_ERR_CAPACITY when cap_blocks < *n_blocks + 1 (*n_blocks is set).  Returns
+ *   the stream's length.  The deflate data is not looked at.
+ *
+ * npr_bgzf_inflate: the payloads of all blocks of the file, in order, in out[0, returned length).  out == NULL: only the stream's length
+ *   (the scan alone).  NPR_ERR_CAPACITY when cap is smaller.  Every block's deflate data is decoded by one workgroup, independently of
+ *   every other block, as RFC 1951 in full: any number of deflate blocks up to the one with BFINAL, stored, fixed and dynamic ones, code
+ *   length symbols 16 / 17 / 18, lengths 3 .. 258, distances 1 .. 32768, matches that overlap their own output.  A block is ACCEPTED
+ *   exactly when a fresh raw inflater of zlib (no history) accepts its deflate data and ends on its last byte, the output has ISIZE bytes
+ *   and their CRC-32 is the trailer's.  The refusals, a status per block (csrc/npr_inflate.h INF_*): 1 BTYPE 3; 2 a stored block's LEN is
+ *   not ~NLEN; 3 over-subscribed code lengths; 4 incomplete code lengths (zlib's rule: a literal/length or distance code whose longest
+ *   code has one bit may be incomplete, and there may be no distance code at all; the code-length code must be complete); 5 a repeat code
+ *   with no length before it or running past HLIT + HDIST; 6 no code for symbol 256; 7 HLIT above 286, HDIST above 30, literal/length
+ *   symbols 286 / 287, distance symbols 30 / 31, bits that are no code; 8 a distance that reaches before the block's first byte; 9 output
+ *   past ISIZE; 10 input past the deflate data's end; 11 bytes of deflate data left after the final block; 12 a produced length that is
+ *   not ISIZE; 13 a CRC-32 that is not the trailer's; 14 the decoder's step bound (unreachable).  When any block is refused the call
+ *   returns NPR_ERR_INVALID and NO byte of out is touched.  A refused block costs bounded time: every read is checked against the block,
+ *   every write against ISIZE, and every loop of the decoder is bounded.
+ *
+ * npr_inflate_last: of the last file this context inflated (a call that reached the device), out[0 .. 3] = the blocks, the first refused
+ *   block (-1: none), its status (above; 0: none), the stream's length.  Before the first: 0, -1, 0, 0.  NPR_ERR_INVALID for a NULL argument. */
+int64_t npr_bgzf_scan(const uint8_t *file, int64_t len, int64_t *block_off, int64_t *stream_off, int64_t cap_blocks, int64_t *n_blocks);
+int64_t npr_bgzf_inflate(npr_ctx *ctx, const uint8_t *file, int64_t len, uint8_t *out, int64_t cap);
+int32_t npr_inflate_last(npr_ctx *ctx, int64_t *out /* [4] */);
+
+/* ---- reading BAM: a BAM file as SAM text (SAMv1 section 4.2), the records walked and written on the device (csrc/npr_bamread.hip) ----
+ * npr_bam_aux_text (host, threaded, no GPU): the inverse of npr_bam_tags.  The auxiliary bytes of n records, record i =
+ *   aux[aux_off[i] .. aux_off[i + 1]), as text, record i at out[text_off[i] .. text_off[i + 1]), text_off[n + 1]: its fields as
+ *   TAG:TYPE:VALUE separated by one tab (no tab before the first or after the last).  A one byte; c C s S i I all print as type i, in
+ *   decimal; f as C's %g; Z and H the bytes up to their NUL; B the subtype letter, then "," and a value per element (integers in decimal, f
+ *   as %g).  placeholder (may be NULL): where placeholder[i] is not 0, the first CG:B:I field of record i is left out of the text and
+ *   cg[2 i], cg[2 i + 1] receive the offset of its elements from the record's first auxiliary byte and their number (cg[2 n], both -1
+ *   for a record without one); an element whose low four bits exceed 8 is malformed.  out == NULL: only the offsets and cg.  Returns the
+ *   total length; NPR_ERR_CAPACITY when cap is smaller; NPR_ERR_INVALID, with nothing written to out, for an unknown type, a field cut by the
+ *   record's end, a Z or H without NUL, or an array that runs past the record.
+ *
+ * npr_bam_sam: file[0, len), a BAM file image, as SAM text in sam_out: the header text (l_text bytes as they stand), then one line per
+ *   record in the file's order.  The blocks are inflated as npr_bgzf_inflate does (the same refusals; npr_inflate_last tells).  One
+ *   wavefront checks the header (magic "BAM\1", l_text, n_ref, every l_name with its NUL and l_ref inside the stream); one wavefront
+ *   follows the block_size chain, in rounds into a table of fixed size, and checks per record: block_size at least 33, the record inside
+ *   the stream (the last one ends with it), l_read_name at least 1 with a NUL at its end, the 32 fixed bytes, name, cigar, SEQ and QUAL
+ *   inside block_size, refID and next_refID in -1 .. n_ref - 1; a cigar operation above 8 is refused too.  THE LINE, columns separated by
+ *   one tab: QNAME; FLAG; RNAME, "*" for refID -1; POS + 1; MAPQ; CIGAR: "*" for no operation, else <length><MIDNSHP=X> per operation --
+ *   when the stored cigar is <l_seq>S<n>N and the record has a CG:B:I field, that field's operations, and the field is dropped --; RNEXT:
+ *   "*" for next_refID -1, "=" when it equals refID, else the name; PNEXT + 1; TLEN; SEQ through "=ACMGRSVTWYHKDBN", "*" for l_seq 0; QUAL
+ *   + 33, "*" when l_seq is 0 or the first byte is 0xFF; the auxiliary fields as npr_bam_aux_text writes them, each after a tab; "\n".
+ *   Returns the text's length and sets *n_records (may be NULL); sam_out == NULL: only that.  NPR_ERR_CAPACITY when cap is smaller (cap may
+ *   be a generous bound: only the returned length is written).  NPR_ERR_INVALID for every refusal above.  Nothing is written to sam_out
+ *   unless the call succeeds. */
+int64_t npr_bam_aux_text(const uint8_t *aux, const int64_t *aux_off /* [n + 1] */, int64_t n, const uint8_t *placeholder /* [n] or NULL */,
+                         int64_t *text_off /* [n + 1] */, int64_t *cg /* [2 n] */, uint8_t *out, int64_t cap);
+int64_t npr_bam_sam(npr_ctx *ctx, const uint8_t *file, int64_t len, uint8_t *sam_out, int64_t cap, int64_t *n_records);
+
 /* npr_batch_create_at for reads that are NOT contiguous in memory: read i = read[read_begin[i] .. read_end[i]) -- e.g. the
  * aligned part of each record's SEQ inside the mapped SAM text (columns 11, 12 of npr_sam_parse), so the sequences go from
  * the file's bytes to the pinned staging buffer in one copy.  Everything else as npr_batch_create_at. */

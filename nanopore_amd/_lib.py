@@ -229,6 +229,11 @@ SIGNATURES = {
     "npr_deflate_last": (i32, [vp, vp]),
     "npr_sam_bam_deflate": (i64, [vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i64, vp, i32, vp, i64, C.POINTER(i64)] + [vp] * 6 + [C.POINTER(i64)]),
     "npr_bai_write": (i64, [i64, vp, i64] + [vp] * 6 + [i64, vp, i64]),
+    "npr_bgzf_scan": (i64, [vp, i64, vp, vp, i64, C.POINTER(i64)]),
+    "npr_bgzf_inflate": (i64, [vp, vp, i64, vp, i64]),
+    "npr_inflate_last": (i32, [vp, vp]),
+    "npr_bam_aux_text": (i64, [vp, vp, i64, vp, vp, vp, vp, i64]),
+    "npr_bam_sam": (i64, [vp, vp, i64, vp, i64, C.POINTER(i64)]),
     "npr_batch_create_spans": (i32, [vp, _params, i64, i64] + [vp] * 10 + [_out]),
 }
 EXPORTS = list(SIGNATURES)

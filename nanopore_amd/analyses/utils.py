@@ -243,6 +243,11 @@ def samToBamFile(samInputFile, bamOutputFile, ctx=None, compress=False):
     return (ctx or _context()).sam_to_bam(samInputFile, bamOutputFile, sort=False, index=False, compress=compress)
 
 
+def bamToSamFile(bamFile, samFile, ctx=None):
+    """The way back: bamFile (of any BGZF writer) as SAM text in samFile, made on the device (realign.Context.bam_to_sam); no samtools."""
+    return (ctx or _context()).bam_to_sam(bamFile, samFile)
+
+
 def samToSortedBamFile(samFile, sortedBamFile, ctx=None, compress=False):
     """samToBamFile, pysam.sort and pysam.index in one: sortedBamFile coordinate-sorted and sortedBamFile + ".bai" beside it.
     compress: compressed BGZF blocks instead of stored ones."""

@@ -6,6 +6,7 @@ with compress=True, with every block compressed there (npr_sam_bam_deflate, csrc
 """
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -102,6 +103,95 @@ def deflate_last(ctx):
     out = np.zeros(4, dtype=np.int64)
     check(ctx._L.npr_deflate_last(ctx._h, ptr(out)), "npr_deflate_last", ctx)
     return {"a": int(out[0]), "b": int(out[1]), "c": int(out[2]), "stream_bytes": int(out[3])}
+
+
+INFLATE_STATUS = ("ok", "BTYPE 3", "a stored block's LEN is not ~NLEN", "over-subscribed code lengths", "incomplete code lengths",
+                  "a repeat code with no length before it or past HLIT + HDIST", "no code for symbol 256", "a symbol or code that does not exist",
+                  "a distance that reaches before the block's first byte", "output past ISIZE", "input past the deflate data's end",
+                  "deflate data left after the final block", "the produced length is not ISIZE", "the CRC-32 is not the trailer's",
+                  "the decoder's step bound")   # csrc/npr_inflate.h INF_*
+
+
+def bgzf_scan(data):
+    """The block table of a BGZF file image (npr_bgzf_scan, host code): (block_off, stream_off), int64 [blocks + 1] each: the file offset of
+    every block and the stream offset of its payload; last the end-of-file block's offset and the stream's length.  A file that does not
+    end with the end-of-file block, or whose blocks do not chain to it, raises."""
+    data = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else _arr(data, np.uint8)
+    L, n = _lib.load(), C.c_int64(0)
+    check(L.npr_bgzf_scan(ptr(data), len(data), None, None, 0, C.byref(n)), "npr_bgzf_scan")
+    block_off, stream_off = np.zeros(n.value + 1, dtype=np.int64), np.zeros(n.value + 1, dtype=np.int64)
+    check(L.npr_bgzf_scan(ptr(data), len(data), ptr(block_off), ptr(stream_off), n.value + 1, C.byref(n)), "npr_bgzf_scan")
+    return block_off, stream_off
+
+
+def bgzf_inflate(ctx, data, out=None):
+    """The payloads of a BGZF file image (bytes or a uint8 array), every block inflated on the device (npr_bgzf_inflate): uint8 array.  The
+    blocks may come from any writer.  A block that is refused raises NprError and nothing is written; inflate_last(ctx) says which and why.
+    out: a uint8 array to write into (default: a new one)."""
+    data = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else _arr(data, np.uint8)
+    total = check(ctx._L.npr_bgzf_inflate(ctx._h, ptr(data), len(data), None, 0), "npr_bgzf_inflate", ctx)
+    if out is None:
+        out = np.empty(max(total, 1), dtype=np.uint8)
+    check(ctx._L.npr_bgzf_inflate(ctx._h, ptr(data), len(data), ptr(out), len(out)), "npr_bgzf_inflate", ctx)
+    return out[:total]
+
+
+def inflate_last(ctx):
+    """Of the last file the context inflated (npr_inflate_last): {"blocks", "failed_block" (-1: none), "status", "reason", "stream_bytes"}."""
+    out = np.zeros(4, dtype=np.int64)
+    check(ctx._L.npr_inflate_last(ctx._h, ptr(out)), "npr_inflate_last", ctx)
+    status = int(out[2])
+    return {"blocks": int(out[0]), "failed_block": int(out[1]), "status": status,
+            "reason": INFLATE_STATUS[status] if 0 <= status < len(INFLATE_STATUS) else "unknown", "stream_bytes": int(out[3])}
+
+
+def bam_aux_text(aux, aux_off, placeholder=None):
+    """The auxiliary bytes of records as TAG:TYPE:VALUE text (npr_bam_aux_text, host code, the inverse of bam_tags): (text_off int64 [n + 1],
+    text uint8, cg int64 [n, 2]: with placeholder[i] set, where the elements of record i's CG:B:I field lie and how many; -1 without one)."""
+    aux, aux_off = _arr(aux, np.uint8), _arr(aux_off, np.int64)
+    n = len(aux_off) - 1
+    placeholder = None if placeholder is None else _arr(placeholder, np.uint8)
+    text_off, cg = np.zeros(n + 1, dtype=np.int64), np.full((max(n, 1), 2), -1, dtype=np.int64)
+    out = _sized(_lib.load().npr_bam_aux_text, "npr_bam_aux_text", [ptr(aux), ptr(aux_off), n, ptr(placeholder), ptr(text_off), ptr(cg)])
+    return text_off, out, cg[:n]
+
+
+def bam_sam(ctx, data):
+    """A BAM file image as SAM text (npr_bam_sam): (uint8 array: the header text, then a line per record; the number of records)."""
+    data = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else _arr(data, np.uint8)
+    stream = check(ctx._L.npr_bgzf_inflate(ctx._h, ptr(data), len(data), None, 0), "npr_bgzf_inflate", ctx)
+    # a bound instead of a sizing call (pages nobody touches cost nothing): a stream byte becomes at most 5 text bytes (an element of a B:c array:
+    # "-128,"), a 4-byte number at most 12 with its tab
+    out = np.empty(6 * stream + 64, dtype=np.uint8)
+    n = C.c_int64(0)
+    total = int(check(ctx._L.npr_bam_sam(ctx._h, ptr(data), len(data), ptr(out), len(out), C.byref(n)), "npr_bam_sam", ctx))
+    return out[:total], n.value
+
+
+def bam_to_sam(ctx, bamFile, samFile):
+    """bamFile as SAM text in samFile (npr_bam_sam): the blocks inflated, the records walked and the lines written on the device, the
+    auxiliary fields turned to text on the host.  A file that is not BGZF, a block that does not inflate, a bad BAM magic or a malformed
+    record raises and leaves no file.  -> {"records", "references", "bytes", "stream_bytes", "blocks"}."""
+    data = np.fromfile(bamFile, dtype=np.uint8)
+    text, n = bam_sam(ctx, data)
+    last = inflate_last(ctx)
+    tmp = samFile + ".tmp"
+    try:
+        with open(tmp, "wb") as fh:
+            text.tofile(fh)
+        os.replace(tmp, samFile)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    k = 1 << 16   # the header's @SQ lines: the header comes first, and is looked for in a prefix that grows until it ends
+    while True:
+        head = text[:k].tobytes()
+        m = re.search(rb"(?m)^[^@]", head)
+        if m or k >= len(text):
+            break
+        k *= 4
+    references = len(re.findall(rb"(?m)^@SQ\t", head[:m.start()] if m else head))
+    return {"records": int(n), "references": references, "bytes": int(len(text)), "stream_bytes": last["stream_bytes"], "blocks": last["blocks"]}
 
 
 def convert(ctx, sam, fields, tail, tag_off, tags, header, ref_len, sort=True, index=True, compress=False):

@@ -90,6 +90,7 @@ struct npr_ctx {
     DeviceArena *arena = nullptr;  // the device's forward scratch (shared with the other contexts on this device)
     int overlap = 0;               // NPR_OPT_OVERLAP: see include/nprealign.h (1: own MEA tables + half of every SIMD left free by the DP launches; 2: own MEA tables only)
     int64_t deflate_last[4] = {};  // npr_deflate_last: blocks emitted as (a), (b), (c) and the stream's length, of the last compressed stream
+    int64_t inflate_last[4] = {0, -1, 0, 0};  // npr_inflate_last: blocks, the first refused one (-1: none), its status and the stream's length, of the last file inflated
     int64_t opt[NPR_OPT_COUNT] = {};  // npr_ctx_option: the test / bring-up switches (all 0 by default)
     static constexpr size_t kArenaPad = DeviceArena::kPad;
     float *arena_Fx = nullptr;  // E-step only: four more forward planes (per context)

@@ -1,5 +1,5 @@
-// npr_bam_api.cpp -- npr_bam_sort_order, npr_bgzf_frame, npr_bgzf_deflate, npr_deflate_last, npr_sam_bam, npr_sam_bam_deflate: the checks, the records as the kernels take them, the launches of
-// npr_bam.hip and npr_deflate.hip, and the tables as the header defines them ("coordinate-sorted BAM")
+// npr_bam_api.cpp -- npr_bam_sort_order, npr_bgzf_frame, npr_bgzf_deflate, npr_deflate_last, npr_bgzf_inflate, npr_inflate_last, npr_sam_bam, npr_sam_bam_deflate: the checks, the records as the
+// kernels take them, the launches of npr_bam.hip, npr_deflate.hip and npr_inflate.hip, and the tables as the header defines them ("coordinate-sorted BAM")
 // (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
 #include "npr_api_internal.h"
 
@@ -100,6 +100,63 @@ int64_t sam_bam(const char *entry, bool compress, npr_ctx *ctx, const uint8_t *t
                 int32_t sorted, uint8_t *bam_out, int64_t cap, int64_t *n_runs, int32_t *run_tid, uint32_t *run_bin, uint64_t *run_beg, uint64_t *run_end,
                 uint64_t *linear, uint64_t *meta, int64_t *n_no_coor);
 
+// npr_bgzf_scan into vectors of blocks + 1 entries: one pass over the file as a rule (room for a block per 16 KiB of file: a block of 64 KiB
+// of payload seldom compresses below a quarter), a second one when there are more.  Returns what the scan returns.
+int64_t scan_table(const uint8_t *file, int64_t len, std::vector<int64_t> &block_off, std::vector<int64_t> &stream_off) {
+    int64_t blocks = 0, cap = len / 16384 + 64;
+    for (int pass = 0;; ++pass) {
+        block_off.resize(static_cast<size_t>(cap)), stream_off.resize(static_cast<size_t>(cap));
+        const int64_t total = npr_bgzf_scan(file, len, block_off.data(), stream_off.data(), cap, &blocks);
+        if (total == NPR_ERR_CAPACITY && pass == 0) {
+            cap = blocks + 1;
+            continue;
+        }
+        if (total >= 0) block_off.resize(static_cast<size_t>(blocks) + 1), stream_off.resize(static_cast<size_t>(blocks) + 1);
+        return total;
+    }
+}
+
+int dec_digits(uint32_t v) {
+    int k = 1;
+    while (v >= 10u) v /= 10u, ++k;
+    return k;
+}
+
+// A BGZF file image inflated on the device: the buffers of one npr_inflate.hip run.  launch() takes the block table npr_bgzf_scan made and
+// queues the kernel; finish() fetches the blocks' statuses, waits, fills the context's inflate_last and refuses the file when a block was
+// refused; the payloads then lie in stream.
+struct InflateRun {
+    DevBuf<uint8_t> file, stream;
+    DevBuf<int64_t> block_off, stream_off;
+    DevBuf<int32_t> status;
+    int64_t blocks = 0, stream_len = 0;
+    void launch(const Call &dev, const uint8_t *image, int64_t len, const std::vector<int64_t> &b_off, const std::vector<int64_t> &s_off) {
+        blocks = static_cast<int64_t>(b_off.size()) - 1, stream_len = s_off.back();
+        dev.upload(file, image, static_cast<size_t>(len));
+        dev.upload(block_off, b_off), dev.upload(stream_off, s_off);
+        dev.alloc(stream, static_cast<size_t>(std::max<int64_t>(stream_len, 1)));
+        dev.alloc(status, static_cast<size_t>(std::max<int64_t>(blocks, 1)));
+        InflateArgs a{};
+        bgzf_constants(a.z);
+        a.file = file.p, a.block_off = block_off.p, a.stream_off = stream_off.p, a.blocks = blocks, a.stream = stream.p, a.status = status.p;
+        dev.launched(launch_bgzf_inflate(a, dev.ctx->stream), "k_bgzf_inflate");
+    }
+    void finish(const Call &dev) {
+        std::vector<int32_t> st(static_cast<size_t>(blocks), 0);
+        dev.fetch(st.data(), status.p, st.size() * sizeof(int32_t));
+        dev.sync();
+        int64_t *last = dev.ctx->inflate_last;
+        last[0] = blocks, last[1] = -1, last[2] = 0, last[3] = stream_len;
+        for (int64_t b = 0; b < blocks; ++b)
+            if (st[b] != 0) {
+                last[1] = b, last[2] = st[b];
+                char text[160];
+                std::snprintf(text, sizeof(text), "%s: BGZF block %lld is refused (inflate status %d)", dev.entry, static_cast<long long>(b), st[b]);
+                dev.refuse(NPR_ERR_INVALID, text);
+            }
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -172,6 +229,169 @@ int64_t npr_bgzf_deflate(npr_ctx *ctx, const uint8_t *data, int64_t len, uint8_t
 int32_t npr_deflate_last(npr_ctx *ctx, int64_t *out) {
     if (!ctx || !out) return NPR_ERR_INVALID;
     std::copy(ctx->deflate_last, ctx->deflate_last + 4, out);
+    return NPR_OK;
+}
+
+int64_t npr_bgzf_inflate(npr_ctx *ctx, const uint8_t *file, int64_t len, uint8_t *out, int64_t cap) {
+    if (!ctx || !file || len < 0 || cap < 0) return NPR_ERR_INVALID;
+    return guarded(ctx, "npr_bgzf_inflate", [&](const Call &dev) -> int64_t {
+        std::vector<int64_t> block_off, stream_off;
+        const int64_t total = scan_table(file, len, block_off, stream_off);
+        if (total < 0) dev.refuse(NPR_ERR_INVALID, "npr_bgzf_inflate: not a BGZF file that ends with the end-of-file block");
+        if (!out) return total;
+        if (cap < total) return NPR_ERR_CAPACITY;
+        if (block_off.size() >= (size_t(1) << 31)) return NPR_ERR_INVALID;
+        InflateRun run;
+        run.launch(dev, file, len, block_off, stream_off);
+        run.finish(dev);
+        dev.fetch(out, run.stream.p, static_cast<size_t>(total));
+        dev.sync();
+        return total;
+    });
+}
+
+int64_t npr_bam_sam(npr_ctx *ctx, const uint8_t *file, int64_t len, uint8_t *sam_out, int64_t cap, int64_t *n_records) {
+    if (!ctx || !file || len < 0 || cap < 0) return NPR_ERR_INVALID;
+    return guarded(ctx, "npr_bam_sam", [&](const Call &dev) -> int64_t {
+        std::vector<int64_t> block_off, stream_off;
+        if (scan_table(file, len, block_off, stream_off) < 0) dev.refuse(NPR_ERR_INVALID, "npr_bam_sam: not a BGZF file that ends with the end-of-file block");
+        if (block_off.size() >= (size_t(1) << 31)) return NPR_ERR_INVALID;
+        InflateRun run;
+        run.launch(dev, file, len, block_off, stream_off);
+        run.finish(dev);
+        const int64_t stream_len = run.stream_len;
+        const uint8_t *const d_stream = run.stream.p;
+
+        // the header: its end from the device, its bytes once to the host for the names
+        DevBuf<int64_t> d_head;
+        int64_t head[4] = {0, 0, 0, 0};
+        dev.alloc(d_head, 4);
+        dev.launched(launch_bam_head(d_stream, stream_len, d_head.p, ctx->stream), "k_bam_head");
+        dev.fetch(head, d_head.p, sizeof(head));
+        dev.sync();
+        if (head[0] != 0) dev.refuse(NPR_ERR_INVALID, "npr_bam_sam: no BAM magic, or a header that runs past the stream");
+        const int64_t header_end = head[1], l_text = head[2], n_ref = head[3];
+        std::vector<uint8_t> header(static_cast<size_t>(header_end));
+        dev.fetch(header.data(), d_stream, header.size());
+        dev.sync();
+        std::vector<uint8_t> names;
+        std::vector<int64_t> name_off(static_cast<size_t>(n_ref) + 1, 0);
+        for (int64_t k = 0, at = 8 + l_text + 4; k < n_ref; ++k) {  // (k_bam_head checked every l_name against the header's end)
+            int32_t l_name;
+            std::memcpy(&l_name, header.data() + at, 4);
+            names.insert(names.end(), header.begin() + at + 4, header.begin() + at + 4 + l_name - 1);
+            name_off[k + 1] = static_cast<int64_t>(names.size());
+            at += 8 + l_name;
+        }
+
+        // the records: the block_size chain in rounds into a table of fixed size
+        constexpr int64_t kWalk = int64_t(1) << 18;
+        DevBuf<int64_t> d_table, d_walk;
+        dev.alloc(d_table, kWalk), dev.alloc(d_walk, 3);
+        std::vector<int64_t> rec_off;
+        for (int64_t at = header_end; at < stream_len;) {
+            int64_t w[3] = {0, 0, 0};
+            dev.launched(launch_bam_walk(d_stream, stream_len, at, static_cast<int32_t>(n_ref), d_table.p, kWalk, d_walk.p, ctx->stream), "k_bam_walk");
+            dev.fetch(w, d_walk.p, sizeof(w));
+            dev.sync();
+            if (w[2] != 0 || w[0] <= 0) {
+                char text[160];
+                std::snprintf(text, sizeof(text), "npr_bam_sam: record %lld at stream byte %lld is refused (walk status %lld)", static_cast<long long>(rec_off.size() + w[0]),
+                              static_cast<long long>(w[1]), static_cast<long long>(w[2]));
+                dev.refuse(NPR_ERR_INVALID, text);
+            }
+            const size_t had = rec_off.size();
+            rec_off.resize(had + static_cast<size_t>(w[0]));
+            dev.fetch(rec_off.data() + had, d_table.p, static_cast<size_t>(w[0]) * sizeof(int64_t));
+            dev.sync();
+            at = w[1];
+        }
+        const int64_t n = static_cast<int64_t>(rec_off.size());
+        if (n >= (int64_t(1) << 31)) dev.refuse(NPR_ERR_INVALID, "npr_bam_sam: 2^31 records and more");
+
+        DevBuf<uint8_t> d_names, d_aux, d_text, d_out;
+        DevBuf<int64_t> d_name_off, d_rec_off, d_aux_off, d_cg, d_text_off, d_line_off, d_tile;
+        DevBuf<BamReadRec> d_meas;
+        DevBuf<int32_t> d_bad;
+        DevBuf<unsigned long long> d_items;
+        BamReadArgs a{};
+        a.stream = d_stream, a.len = stream_len, a.n_ref = static_cast<int32_t>(n_ref), a.n = n;
+        dev.upload(d_names, names), dev.upload(d_name_off, name_off), dev.upload(d_rec_off, rec_off);
+        dev.alloc(d_meas, n), dev.alloc(d_bad, 1), dev.zero(d_bad);
+        a.names = d_names.p, a.name_off = d_name_off.p, a.rec_off = d_rec_off.p, a.meas = d_meas.p, a.bad = d_bad.p;
+        dev.launched(launch_bam_read_measure(a, ctx->stream), "k_bam_measure");
+        std::vector<BamReadRec> meas(static_cast<size_t>(n));
+        int32_t bad = 0;
+        dev.fetch(meas.data(), d_meas.p, d_meas.bytes());
+        dev.fetch(&bad, d_bad.p, sizeof(bad));
+        dev.sync();
+        if (bad) dev.refuse(NPR_ERR_INVALID, "npr_bam_sam: a cigar operation above 8");
+
+        // the auxiliary bytes: packed, down once, to text on the host, up again
+        std::vector<int64_t> aux_off(static_cast<size_t>(n) + 1, 0), text_off(static_cast<size_t>(n) + 1, 0), cg(2 * static_cast<size_t>(n) + 2, -1);
+        std::vector<uint8_t> placeholder(static_cast<size_t>(n) + 1, 0);
+        for (int64_t i = 0; i < n; ++i) aux_off[i + 1] = aux_off[i] + meas[i].aux_len, placeholder[i] = meas[i].placeholder != 0;
+        std::vector<uint8_t> aux(static_cast<size_t>(aux_off[n]) + 1);
+        dev.upload(d_aux_off, aux_off), dev.alloc(d_aux, aux.size());
+        a.aux_pack_off = d_aux_off.p, a.aux_pack = d_aux.p;
+        dev.launched(launch_bam_gather_aux(a, ctx->stream), "k_bam_gather_aux");
+        dev.fetch(aux.data(), d_aux.p, static_cast<size_t>(aux_off[n]));
+        dev.sync();
+        const int64_t text_len = npr_bam_aux_text(aux.data(), aux_off.data(), n, placeholder.data(), text_off.data(), cg.data(), nullptr, 0);
+        if (text_len < 0) dev.refuse(static_cast<int32_t>(text_len), "npr_bam_sam: a malformed auxiliary field");
+        std::vector<uint8_t> text(static_cast<size_t>(text_len) + 1);
+        if (npr_bam_aux_text(aux.data(), aux_off.data(), n, placeholder.data(), text_off.data(), cg.data(), text.data(), text_len) != text_len)
+            dev.refuse(NPR_ERR_STATE, "npr_bam_sam: the auxiliary text changed its length");
+
+        // the lines' lengths, their offsets by the device's scan, the (record, tile) items
+        std::vector<int64_t> line_len(static_cast<size_t>(n) + 1, 0);
+        std::vector<unsigned long long> items;
+        int64_t lines = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            int64_t cig = meas[i].cig_len;
+            if (cg[2 * i] >= 0) {
+                cig = cg[2 * i + 1] ? 0 : 1;
+                const uint8_t *ops = aux.data() + aux_off[i] + cg[2 * i];
+                for (int64_t q = 0; q < cg[2 * i + 1]; ++q) {
+                    uint32_t v;
+                    std::memcpy(&v, ops + 4 * q, 4);
+                    cig += dec_digits(v >> 4) + 1;
+                }
+            }
+            const int64_t tl = text_off[i + 1] - text_off[i];
+            line_len[i] = meas[i].fixed_len - meas[i].cig_len + cig + (tl ? 1 + tl : 0) + 1;
+            lines += line_len[i];
+            const int64_t tiles = std::max<int64_t>(1, (static_cast<int64_t>(meas[i].l_seq) + BAM_TILE - 1) / BAM_TILE);
+            for (int64_t k = 0; k < tiles; ++k) items.push_back(static_cast<unsigned long long>(i) << 32 | static_cast<unsigned long long>(k));
+        }
+        if (items.size() >= (size_t(1) << 31)) dev.refuse(NPR_ERR_INVALID, "npr_bam_sam: 2^31 tiles and more in one call");
+        const int64_t total = l_text + lines;
+        if (!sam_out) {
+            if (n_records) *n_records = n;
+            return total;
+        }
+        if (cap < total) return NPR_ERR_CAPACITY;
+        dev.upload(d_line_off, line_len), dev.alloc(d_tile, scan_tiles(n));
+        dev.launched(launch_scan_tiled<int64_t, int64_t>(d_line_off.p, d_line_off.p, n, d_tile.p, ctx->stream), "scan");
+        dev.upload(d_cg, cg), dev.upload(d_text, text), dev.upload(d_text_off, text_off), dev.upload(d_items, items);
+        dev.alloc(d_out, static_cast<size_t>(std::max<int64_t>(total, 1)));
+        if (l_text) dev.check(hipMemcpyAsync(d_out.p, d_stream + 8, static_cast<size_t>(l_text), hipMemcpyDeviceToDevice, ctx->stream), "D2D");
+        a.cg = d_cg.p, a.aux_text = d_text.p, a.aux_text_off = d_text_off.p, a.line_off = d_line_off.p, a.items = d_items.p;
+        a.n_items = static_cast<int64_t>(items.size()), a.out = d_out.p + l_text;
+        dev.launched(launch_bam_emit(a, ctx->stream), "k_bam_emit");
+        dev.fetch(&bad, d_bad.p, sizeof(bad));
+        dev.sync();
+        if (bad) dev.failed(NPR_ERR_STATE, "k_bam_emit: a line's columns do not add up to its measured length", hipSuccess);
+        dev.fetch(sam_out, d_out.p, static_cast<size_t>(total));
+        dev.sync();
+        if (n_records) *n_records = n;
+        return total;
+    });
+}
+
+int32_t npr_inflate_last(npr_ctx *ctx, int64_t *out) {
+    if (!ctx || !out) return NPR_ERR_INVALID;
+    std::copy(ctx->inflate_last, ctx->inflate_last + 4, out);
     return NPR_OK;
 }
 

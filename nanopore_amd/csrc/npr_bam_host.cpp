@@ -1,10 +1,12 @@
 // npr_bam_host.cpp -- the host side of the SAM -> sorted BAM + BAI conversion (include/nprealign.h, "coordinate-sorted BAM"): the columns
 // npr_sam_parse leaves aside (npr_sam_parse_tail), the optional fields as BAM auxiliary bytes (npr_bam_tags), the bytes before the first
-// record (npr_bam_header) and the index file from the tables the device made (npr_bai_write).  Host code, threaded, no HIP.
+// record (npr_bam_header) and the index file from the tables the device made (npr_bai_write); and, for the way back, the block table of a
+// BGZF file (npr_bgzf_scan; "reading BGZF").  Host code, threaded, no HIP.
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -158,6 +160,73 @@ int64_t aux_line(const char *p, const char *e, uint8_t *out) {
     return s.n;
 }
 
+// the way back: the auxiliary bytes [p, e) of one record as tab-separated TAG:TYPE:VALUE text into the sink; false: malformed.  With
+// `placeholder` a CG:B:I field is left out of the text and cg[0 .. 1] say where its elements lie (offset from p) and how many they are.
+bool aux_text_line(const uint8_t *p, const uint8_t *e, bool placeholder, Sink &s, int64_t *cg) {
+    const uint8_t *const p0 = p;
+    char num[48];
+    bool first = true;
+    cg[0] = cg[1] = -1;
+    auto number = [&](const char *fmt, auto v) { s.bytes(num, std::snprintf(num, sizeof(num), fmt, v)); };
+    auto element = [&](char t, const uint8_t *q) {  // one value of an integer type or 'f' at q
+        uint32_t u = 0;
+        for (int k = 0; k < width_of(t); ++k) u |= static_cast<uint32_t>(q[k]) << (8 * k);
+        if (t == 'f') {
+            float f;
+            std::memcpy(&f, &u, 4);
+            number("%g", static_cast<double>(f));
+        } else if (t == 'c') number("%d", static_cast<int>(static_cast<int8_t>(u)));
+        else if (t == 's') number("%d", static_cast<int>(static_cast<int16_t>(u)));
+        else if (t == 'i') number("%d", static_cast<int>(static_cast<int32_t>(u)));
+        else number("%u", u);
+    };
+    while (p < e) {
+        if (e - p < 3) return false;
+        const uint8_t t0 = p[0], t1 = p[1];
+        const char type = static_cast<char>(p[2]);
+        p += 3;
+        if (placeholder && cg[0] < 0 && t0 == 'C' && t1 == 'G' && type == 'B' && e - p >= 5 && p[0] == 'I') {
+            const int64_t count = p[1] | static_cast<int64_t>(p[2]) << 8 | static_cast<int64_t>(p[3]) << 16 | static_cast<int64_t>(p[4]) << 24;
+            if (count >= (int64_t(1) << 31) || 4 * count > e - (p + 5)) return false;
+            for (int64_t k = 0; k < count; ++k)
+                if ((p[5 + 4 * k] & 15) > 8) return false;
+            cg[0] = p + 5 - p0, cg[1] = count;
+            p += 5 + 4 * count;
+            continue;
+        }
+        if (!first) s.byte('\t');
+        first = false;
+        s.byte(t0), s.byte(t1), s.byte(':');
+        const int w = width_of(type);
+        if (type == 'A') {
+            if (e - p < 1) return false;
+            s.byte('A'), s.byte(':'), s.byte(*p++);
+        } else if (w) {
+            if (e - p < w) return false;
+            s.byte(type == 'f' ? 'f' : 'i'), s.byte(':'), element(type, p);
+            p += w;
+        } else if (type == 'Z' || type == 'H') {
+            const void *nul = std::memchr(p, 0, static_cast<size_t>(e - p));
+            if (!nul) return false;
+            const uint8_t *z = static_cast<const uint8_t *>(nul);
+            s.byte(static_cast<uint8_t>(type)), s.byte(':'), s.bytes(p, z - p);
+            p = z + 1;
+        } else if (type == 'B') {
+            if (e - p < 5) return false;
+            const char sub = static_cast<char>(p[0]);
+            const int sw = width_of(sub);
+            const int64_t count = p[1] | static_cast<int64_t>(p[2]) << 8 | static_cast<int64_t>(p[3]) << 16 | static_cast<int64_t>(p[4]) << 24;
+            if (!sw || sw * count > e - (p + 5)) return false;
+            s.byte('B'), s.byte(':'), s.byte(static_cast<uint8_t>(sub));
+            for (int64_t k = 0; k < count; ++k) s.byte(','), element(sub, p + 5 + sw * k);
+            p += 5 + sw * count;
+        } else {
+            return false;
+        }
+    }
+    return true;
+}
+
 // the value of FIELD: in a tab-separated header line [p, e): its span, or (e, e)
 std::string_view header_field(const char *p, const char *e, const char *key) {
     for (const char *q = find(p, e, '\t'); q < e;) {
@@ -221,6 +290,74 @@ int32_t npr_sam_parse_tail(const char *text, const int64_t *span, const int64_t 
             }
         });
         return NPR_OK;
+    } catch (const std::exception &) {
+        return NPR_ERR_NOMEM;
+    }
+}
+
+int64_t npr_bgzf_scan(const uint8_t *file, int64_t len, int64_t *block_off, int64_t *stream_off, int64_t cap_blocks, int64_t *n_blocks) {
+    static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (!file || len < 28 || cap_blocks < 0 || !n_blocks || std::memcmp(file + len - 28, eof, 28) != 0) return NPR_ERR_INVALID;
+    const int64_t end = len - 28;  // the blocks fill [0, end) exactly
+    int64_t at = 0, stream = 0, n = 0;
+    while (at < end) {
+        if (end - at < 12 + 6 + 8) return NPR_ERR_INVALID;
+        const uint8_t *b = file + at;
+        if (b[0] != 0x1f || b[1] != 0x8b || b[2] != 8 || !(b[3] & 4)) return NPR_ERR_INVALID;
+        const int64_t xlen = b[10] | static_cast<int64_t>(b[11]) << 8;
+        if (12 + xlen + 8 > end - at) return NPR_ERR_INVALID;
+        int64_t size = -1;
+        for (int64_t x = 12; x < 12 + xlen;) {  // the extra subfields: SI1, SI2, SLEN, the data; BC may stand anywhere among them
+            if (x + 4 > 12 + xlen) return NPR_ERR_INVALID;
+            const int64_t slen = b[x + 2] | static_cast<int64_t>(b[x + 3]) << 8;
+            if (x + 4 + slen > 12 + xlen) return NPR_ERR_INVALID;
+            if (b[x] == 'B' && b[x + 1] == 'C' && slen == 2 && size < 0) size = (b[x + 4] | static_cast<int64_t>(b[x + 5]) << 8) + 1;
+            x += 4 + slen;
+        }
+        if (size < 12 + xlen + 8 || size > end - at) return NPR_ERR_INVALID;
+        const int64_t isize = b[size - 4] | static_cast<int64_t>(b[size - 3]) << 8 | static_cast<int64_t>(b[size - 2]) << 16 | static_cast<int64_t>(b[size - 1]) << 24;
+        if (isize > 65536) return NPR_ERR_INVALID;
+        if (n < cap_blocks) {
+            if (block_off) block_off[n] = at;
+            if (stream_off) stream_off[n] = stream;
+        }
+        ++n, at += size, stream += isize;
+    }
+    *n_blocks = n;
+    if (block_off || stream_off) {
+        if (n + 1 > cap_blocks) return NPR_ERR_CAPACITY;
+        if (block_off) block_off[n] = end;
+        if (stream_off) stream_off[n] = stream;
+    }
+    return stream;
+}
+
+int64_t npr_bam_aux_text(const uint8_t *aux, const int64_t *aux_off, int64_t n, const uint8_t *placeholder, int64_t *text_off, int64_t *cg, uint8_t *out,
+                         int64_t cap) {
+    if (n < 0 || !aux_off || !text_off || !cg || cap < 0 || (n && aux_off[n] > aux_off[0] && !aux)) return NPR_ERR_INVALID;
+    try {
+        std::atomic<bool> bad{false};
+        const int64_t chunks = (n + 127) / 128;
+        parallel_for(chunks, usable_cpus(), [&](int64_t c) {
+            for (int64_t i = c * 128, hi = std::min(n, (c + 1) * 128); i < hi; ++i) {
+                Sink s{nullptr};
+                if (aux_off[i + 1] < aux_off[i] || !aux_text_line(aux + aux_off[i], aux + aux_off[i + 1], placeholder && placeholder[i], s, cg + 2 * i)) bad = true;
+                text_off[i + 1] = s.n;
+            }
+        });
+        if (bad) return NPR_ERR_INVALID;
+        text_off[0] = 0;
+        for (int64_t i = 0; i < n; ++i) text_off[i + 1] += text_off[i];
+        const int64_t total = text_off[n];
+        if (!out) return total;
+        if (cap < total) return NPR_ERR_CAPACITY;
+        parallel_for(chunks, usable_cpus(), [&](int64_t c) {
+            for (int64_t i = c * 128, hi = std::min(n, (c + 1) * 128); i < hi; ++i) {
+                Sink s{out + text_off[i]};
+                (void)aux_text_line(aux + aux_off[i], aux + aux_off[i + 1], placeholder && placeholder[i], s, cg + 2 * i);
+            }
+        });
+        return total;
     } catch (const std::exception &) {
         return NPR_ERR_NOMEM;
     }

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "npr_device.h"
+#include "npr_devtext.h"
 
 namespace npr {
 namespace {
@@ -37,10 +38,6 @@ constexpr int OPS_PER_LANE = 4;
 constexpr int TILE_OPS = WAVE * OPS_PER_LANE;
 constexpr int TILE_BYTES = 3 + 11 * TILE_OPS;  // up to three bytes of misalignment, ten digits and a letter per operation
 
-__device__ __forceinline__ int digits30(uint32_t v) {  // decimal digits of v < 2^30
-    return 1 + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) + (v >= 10000000u) +
-           (v >= 100000000u) + (v >= 1000000000u);
-}
 __device__ __forceinline__ int wave_scan(int v, int lane) {  // inclusive
 #pragma unroll
     for (int o = 1; o < WAVE; o <<= 1) {

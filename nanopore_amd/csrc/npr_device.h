@@ -512,6 +512,53 @@ struct DeflateArgs {
     uint8_t *packed;             // the file image: block b at block_off[b], the end-of-file block at block_off[blocks]
 };
 int launch_bgzf_deflate(const DeflateArgs &a, void *stream);  // k_bgzf_deflate, the scan, k_bgzf_pack
+// BGZF blocks inflated (npr_inflate.hip; the decoder and its statuses: npr_inflate.h)
+constexpr int INFLATE_MAX_GROUPS = 1024;                     // workgroups of k_bgzf_inflate: each takes every INFLATE_MAX_GROUPS-th block
+struct InflateArgs {
+    BgzfArgs z;                  // the CRC constants (data, len, out are not used)
+    const uint8_t *file;         // the file image
+    const int64_t *block_off;    // [blocks + 1] file offset of every block, then of the end-of-file block (npr_bgzf_scan)
+    const int64_t *stream_off;   // [blocks + 1] stream offset of every block's payload, then the stream's length
+    int64_t blocks;
+    uint8_t *stream;             // [stream_off[blocks]] the payloads; a block that is refused leaves its bytes as they were
+    int32_t *status;             // [blocks] INF_OK or why a block was refused
+};
+int launch_bgzf_inflate(const InflateArgs &a, void *stream);
+// BAM records as SAM lines (npr_bamread.hip; the line format: its head and include/nprealign.h, npr_bam_sam)
+struct BamReadRec {  // what k_bam_measure finds
+    int64_t aux_off;             // first auxiliary byte in the stream
+    int32_t aux_len, l_seq;
+    int32_t fixed_len;           // text bytes of the eleven mandatory columns with their ten tabs, the CIGAR as the record stores it
+    int32_t cig_len;             // ... of which the CIGAR
+    int32_t placeholder;         // the stored cigar is <l_seq>S<n>N: a CG:B:I tag, when there is one, holds the real operations
+    int32_t pad;
+};
+struct BamReadArgs {
+    const uint8_t *stream;       // the uncompressed BAM stream
+    int64_t len;
+    int32_t n_ref;
+    const uint8_t *names;        // the reference names back to back, name k = names[name_off[k] .. name_off[k + 1])
+    const int64_t *name_off;
+    int64_t n;                   // records
+    const int64_t *rec_off;      // [n] stream offset of every record's block_size
+    BamReadRec *meas;            // [n]
+    int32_t *bad;                // set to 1 by a cigar operation above 8
+    const int64_t *aux_pack_off; // [n + 1] where a record's auxiliary bytes go in aux_pack (k_bam_gather_aux)
+    uint8_t *aux_pack;
+    const int64_t *cg;           // [2 n] the real operations of a folded cigar: byte offset within the record's auxiliary bytes and count; -1: none
+    const uint8_t *aux_text;     // the auxiliary fields as text (npr_bam_aux_text), record i = [aux_text_off[i], aux_text_off[i + 1])
+    const int64_t *aux_text_off;
+    const int64_t *line_off;     // [n + 1] first byte of every line in out
+    const unsigned long long *items;  // [n_items] record << 32 | tile of SEQ / QUAL
+    int64_t n_items;
+    uint8_t *out;                // the lines
+};
+int launch_bam_head(const uint8_t *stream, int64_t len, int64_t *out4, void *hip_stream);  // out: status (0 ok), the header's end, l_text, n_ref
+// up to cap record offsets from `start` on into table; out: how many, where the next record begins (len: the stream is done), status (0 ok)
+int launch_bam_walk(const uint8_t *stream, int64_t len, int64_t start, int32_t n_ref, int64_t *table, int64_t cap, int64_t *out3, void *hip_stream);
+int launch_bam_read_measure(const BamReadArgs &a, void *stream);
+int launch_bam_gather_aux(const BamReadArgs &a, void *stream);
+int launch_bam_emit(const BamReadArgs &a, void *stream);
 struct BamRec {  // one SAM line as the host's parsers found it
     int64_t name, cigar_lo, cigar_hi, seq, qual;  // offsets in the text; qual < 0: "*"
     int64_t tag_off;

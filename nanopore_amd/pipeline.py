@@ -232,8 +232,11 @@ def main(argv=None):
     parser.add_argument("--device", type=int, default=0, help="the GPU everything runs on (default 0)")
     parser.add_argument("--mutateReferences", action="store_true", help="also map to copies of every reference with 1, 5, 10 and 20 percent of the "
                         "bases substituted, written with their truth files next to the processed references (default: off)")
+    parser.add_argument("--bamDir", help="where the BamFile mappers look for <readType>/<fastq stem>.<reference stem>.bam (default: workingDir/alignmentBamFiles)")
     options = parser.parse_args(argv)
     workingDir = options.workingDir
+    from .mappers.bamFileMapper import BamFile
+    BamFile.bamDir = options.bamDir or os.path.join(workingDir, "alignmentBamFiles")
     chosenMappers = mappers if options.mappers is None else resolveClasses(options.mappers, "nanopore_amd.mappers", AbstractMapper)
     chosenAnalyses = analyses if options.analyses is None else resolveClasses(options.analyses, "nanopore_amd.analyses", AbstractAnalysis)
     chosenMetaAnalyses = metaAnalyses if options.metaAnalyses is None else resolveClasses(options.metaAnalyses, "nanopore_amd.metaAnalyses", AbstractMetaAnalysis)

@@ -733,6 +733,12 @@ class Context(object):
         from . import bam
         return bam.sam_to_bam(self, samFile, bamFile, sort=sort, index=index, compress=compress)
 
+    def bam_to_sam(self, bamFile, samFile):
+        """bamFile as SAM text in samFile, inflated, walked and written on the device (include/nprealign.h: npr_bam_sam; nanopore_amd/bam.py).
+        -> the counts (records, references, bytes, stream_bytes, blocks).  A malformed file raises and leaves no file."""
+        from . import bam
+        return bam.bam_to_sam(self, bamFile, samFile)
+
     def align_indel_kmers(self, refs, reads, cigars, k=5, ref_index=None, start=None):
         """The k-mers that straddle a gap of arbitrary alignments (arguments as for align_stats), counted on the device
         (include/nprealign.h: npr_align_indel_kmers): (read-side table, reference-side table), int64 [4^k + 1] each."""
