@@ -1099,6 +1099,46 @@ int64_t npr_bam_aux_text(const uint8_t *aux, const int64_t *aux_off /* [n + 1] *
                          int64_t *text_off /* [n + 1] */, int64_t *cg /* [2 n] */, uint8_t *out, int64_t cap);
 int64_t npr_bam_sam(npr_ctx *ctx, const uint8_t *file, int64_t len, uint8_t *sam_out, int64_t cap, int64_t *n_records);
 
+/* ---- a BAM file into a pileup without SAM text: the records added where they lie on the device (csrc/npr_bampile.hip, csrc/npr_bamrec.h) ----
+ * What the reference runs on a sorted BAM file -- `samtools depth x.bam` (nanopore/metaAnalyses/coverageDepth.py:49-65), `samtools mpileup`
+ * (analyses/consensus.py:56-64) -- without turning the file into SAM text, parsing it on the host and uploading cigars and bases again.
+ *
+ * npr_bam_open: file[0, len), a BAM file image, as an object on the device: the blocks are inflated as npr_bgzf_inflate does (the same
+ *   refusals; npr_inflate_last tells), the header is checked and the block_size chain followed by the kernels of npr_bam_sam (the same
+ *   refusals, NPR_ERR_INVALID; a cigar operation above 8 is a matter of npr_pileup_add_bam).  The stream and the table of record offsets stay
+ *   on the device; the header's names and lengths are kept on the host.  No object is returned unless the call succeeds.  The object belongs
+ *   to its context and must be closed before it; calls on it count as calls on the context.
+ * npr_bam_stream_info: out[0 .. 3] = the records, n_ref, l_text, the stream's length; returns the number of records.
+ * npr_bam_stream_refs: ref_len[k] = l_ref of sequence k, its name = names[name_off[k] .. name_off[k + 1]) (back to back, without NULs).
+ *   Returns the names' total length; names == NULL: only that, nothing is written; NPR_ERR_CAPACITY when cap is smaller.  ref_len and name_off
+ *   may be NULL.
+ *
+ * npr_pileup_add_bam: the records of `bs` into the table of `pl`.  First the header: n_ref must be the pileup's n_refs, every l_ref its
+ *   ref_len[k], and both objects of one context -- else NPR_ERR_INVALID, nothing is added and counts is all zero.
+ *   SELECTED is a record with refID >= 0, (flag & flag_mask) == 0, l_seq > 0 and a cigar of at least one operation.  THE CIGAR, by the rule
+ *   of npr_bam_sam: the stored operations -- unless they are exactly <l_seq>S<n>N: then the record's auxiliary fields are walked on the device
+ *   (types A c C s S i I f Z H B, every step checked against the record's end) and the elements of the first CG:B:I field, when there is one,
+ *   are the operations (of no element: the record is not selected).
+ *   COLUMNS.  M, = and X runs are columns: word 0-3 of the row by the read's nibble 1, 2, 4, 8 (A, C, G, T), word 4 for every other code
+ *   ("=" and N among them).  D runs are deletion columns (word 5, through the difference array).  Words 6 and 7 by the rules of
+ *   npr_pileup_add: an I run is attached to the last column (M = X or D) the record consumed before it, however many N, S, H, P runs or runs
+ *   of length 0 lie between; I runs not separated by a column count once; an I run before the first column counts not at all; word 7 is
+ *   set at the record's first column.  N advances the reference and counts nothing, S advances the read and counts nothing, H and P do
+ *   nothing, a run of length 0 does nothing.
+ *   REFUSED is a selected record with pos < 0, with pos + the reference bases its cigar consumes (M D N = X) above l_ref, with read bases
+ *   consumed (M I S = X) other than l_seq, with an operation code above 8, or -- under a placeholder cigar -- with malformed auxiliary fields
+ *   (a field cut by the record's end, an unknown type or array subtype, a Z or H without NUL, an array past the record's end).  Sums are
+ *   taken in 64 bits.  A refused record adds NOTHING -- every cigar is checked before the first add --, the other records are counted, and
+ *   the call returns NPR_ERR_INVALID.
+ *   counts[0 .. 3] = the records, the selected ones, the added ones, the refused ones (selected = added + refused); written whenever the
+ *   kernels ran.  Counts are integers: the table does not depend on the order.  Nothing but the counts crosses to the host. */
+typedef struct npr_bam_stream npr_bam_stream;
+int32_t npr_bam_open(npr_ctx *ctx, const uint8_t *file, int64_t len, npr_bam_stream **out);
+void npr_bam_close(npr_bam_stream *bs);
+int64_t npr_bam_stream_info(npr_bam_stream *bs, int64_t *out /* [4] */);
+int64_t npr_bam_stream_refs(npr_bam_stream *bs, int64_t *ref_len /* [n_ref] */, int64_t *name_off /* [n_ref + 1] */, uint8_t *names, int64_t cap);
+int32_t npr_pileup_add_bam(npr_pileup *pl, npr_bam_stream *bs, int32_t flag_mask, int64_t *counts /* [4] */);
+
 /* npr_batch_create_at for reads that are NOT contiguous in memory: read i = read[read_begin[i] .. read_end[i]) -- e.g. the
  * aligned part of each record's SEQ inside the mapped SAM text (columns 11, 12 of npr_sam_parse), so the sequences go from
  * the file's bytes to the pinned staging buffer in one copy.  Everything else as npr_batch_create_at. */

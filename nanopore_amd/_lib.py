@@ -234,6 +234,11 @@ SIGNATURES = {
     "npr_inflate_last": (i32, [vp, vp]),
     "npr_bam_aux_text": (i64, [vp, vp, i64, vp, vp, vp, vp, i64]),
     "npr_bam_sam": (i64, [vp, vp, i64, vp, i64, C.POINTER(i64)]),
+    "npr_bam_open": (i32, [vp, vp, i64, _out]),
+    "npr_bam_close": (None, [vp]),
+    "npr_bam_stream_info": (i64, [vp, vp]),
+    "npr_bam_stream_refs": (i64, [vp, vp, vp, vp, i64]),
+    "npr_pileup_add_bam": (i32, [vp, vp, i32, vp]),
     "npr_batch_create_spans": (i32, [vp, _params, i64, i64] + [vp] * 10 + [_out]),
 }
 EXPORTS = list(SIGNATURES)

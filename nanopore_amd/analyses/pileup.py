@@ -4,7 +4,8 @@ The reference gets these numbers from samtools after converting the SAM to BAM, 
 (`samtools depth`, nanopore/metaAnalyses/coverageDepth.py:49-65; `samtools mpileup`, analyses/consensus.py).  Here the
 records go from the file's bytes through the whole-file scanners (ingest.py / csrc/npr_io.cpp) to `Pileup.add_csr`
 (include/nprealign.h: npr_pileup_add; csrc/npr_pileup.hip) without a Python object per record, and the table comes
-back from the device.  No CPU fallback.
+back from the device.  A BAM file does not become text first: `pileup_of_bam` opens it on the device and its records
+are added where they lie (`Pileup.add_bam`; npr_bam_open, npr_pileup_add_bam; csrc/npr_bampile.hip).  No CPU fallback.
 
 Not reproduced: samtools 0.1.19 admits at most 8000 records to a position's pileup (bam_pileup.c, maxcnt), which
 depends on the order of the file; the device table has no cap.
@@ -50,6 +51,32 @@ def pileup_of_sam(ctx, samFile, referenceFastaFile):
     except Exception:
         pileup.close()
         raise
+    return names, lengths, pileup
+
+
+def pileup_of_bam(ctx, bamFile, referenceFastaFile=None):
+    """-> (names, ref_lengths, Pileup): the table of the records of `bamFile` that samtools' pileup would keep, rows in the order
+    of the BAM header's reference sequences, whose names and lengths are the ones returned.  The file is inflated and walked on
+    the device and its records are added where they lie (Pileup.add_bam; include/nprealign.h: npr_pileup_add_bam): no SAM text,
+    no parse on the host.  With `referenceFastaFile`, its sequences must be the ones the header names (their lengths are
+    compared, as pileup_of_sam compares them); the caller closes the Pileup."""
+    data = np.fromfile(bamFile, dtype=np.uint8)
+    with ctx.bam_open(data) as stream:
+        names, lengths = list(stream.references), np.asarray(stream.lengths, dtype=np.int64)
+        if referenceFastaFile is not None:
+            fasta = ingest.FastaTable(referenceFastaFile)
+            for name, length in zip(names, lengths):
+                if name not in fasta.index:
+                    raise KeyError("%s: reference sequence %r is not in %s" % (bamFile, name, referenceFastaFile))
+                k = fasta.index[name]
+                if int(fasta.off[k + 1] - fasta.off[k]) != int(length):
+                    raise ValueError("%s: reference sequence %r has length %d, %s holds %d bases" % (bamFile, name, length, referenceFastaFile, fasta.off[k + 1] - fasta.off[k]))
+        pileup = ctx.pileup(lengths)
+        try:
+            pileup.add_bam(stream, FLAG_MASK)
+        except Exception:
+            pileup.close()
+            raise
     return names, lengths, pileup
 
 

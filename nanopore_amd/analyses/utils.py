@@ -248,6 +248,21 @@ def bamToSamFile(bamFile, samFile, ctx=None):
     return (ctx or _context()).bam_to_sam(bamFile, samFile)
 
 
+def bamDepthFile(bamFile, depthFile, ctx=None):
+    """The text of `samtools depth bamFile` (the reference's metaAnalyses/coverageDepth.py:49-65) in depthFile, from the pileup of the
+    file's records made on the device without SAM text (analyses/pileup.py: pileup_of_bam, depth_text).  -> the text's length."""
+    from .pileup import depth_text, pileup_of_bam
+    names, lengths, pileup = pileup_of_bam(ctx or _context(), bamFile)
+    try:
+        depth, covered = pileup.depth()
+    finally:
+        pileup.close()
+    text = depth_text(names, lengths, depth, covered)
+    with open(depthFile, "w") as fh:
+        fh.write(text)
+    return len(text)
+
+
 def samToSortedBamFile(samFile, sortedBamFile, ctx=None, compress=False):
     """samToBamFile, pysam.sort and pysam.index in one: sortedBamFile coordinate-sorted and sortedBamFile + ".bai" beside it.
     compress: compressed BGZF blocks instead of stored ones."""

@@ -479,6 +479,18 @@ struct npr_pileup {
     DevBuf<int32_t> bad;         // one word: a record of the current call ran past what it has
 };
 
+// an inflated BAM stream and the offsets of its records (npr_bam_api.cpp, npr_bam_open): on the device from npr_bam_open to npr_bam_close; the
+// header's fields on the host
+struct npr_bam_stream {
+    npr_ctx *ctx = nullptr;
+    int64_t stream_len = 0, l_text = 0, n = 0;  // n: records
+    DevBuf<uint8_t> stream;
+    DevBuf<int64_t> rec_off;        // [n] stream offset of every record's block_size
+    std::vector<int64_t> ref_len;   // [n_ref] l_ref
+    std::vector<int64_t> name_off;  // [n_ref + 1]
+    std::vector<uint8_t> names;     // back to back, without NULs
+};
+
 // the index of one reference set (npr_seed_api.cpp): lives on the device from npr_seed_index_create to npr_seed_index_destroy
 struct npr_seed_index {
     npr_ctx *ctx = nullptr;

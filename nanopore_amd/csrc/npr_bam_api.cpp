@@ -1,5 +1,6 @@
-// npr_bam_api.cpp -- npr_bam_sort_order, npr_bgzf_frame, npr_bgzf_deflate, npr_deflate_last, npr_bgzf_inflate, npr_inflate_last, npr_sam_bam, npr_sam_bam_deflate: the checks, the records as the
-// kernels take them, the launches of npr_bam.hip, npr_deflate.hip and npr_inflate.hip, and the tables as the header defines them ("coordinate-sorted BAM")
+// npr_bam_api.cpp -- npr_bam_sort_order, npr_bgzf_frame, npr_bgzf_deflate, npr_deflate_last, npr_bgzf_inflate, npr_inflate_last, npr_sam_bam, npr_sam_bam_deflate,
+// npr_bam_sam, npr_bam_open / _close / _stream_info / _stream_refs, npr_pileup_add_bam: the checks, the records as the
+// kernels take them, the launches of npr_bam.hip, npr_deflate.hip, npr_inflate.hip, npr_bamread.hip and npr_bampile.hip, and the tables as the header defines them ("coordinate-sorted BAM")
 // (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
 #include "npr_api_internal.h"
 
@@ -157,6 +158,37 @@ struct InflateRun {
     }
 };
 
+// The header of a BAM stream on the device (npr_bam_sam, npr_bam_open): k_bam_head checks it and gives its end, its bytes cross once for the names
+// (back to back, without NULs) and, when asked for, every l_ref.  Refuses a stream without the magic or with a header that runs past it.
+struct BamHeader {
+    int64_t end, l_text, n_ref;
+};
+BamHeader bam_header(const Call &dev, const uint8_t *d_stream, int64_t stream_len, std::vector<uint8_t> &names, std::vector<int64_t> &name_off, std::vector<int64_t> *ref_len) {
+    DevBuf<int64_t> d_head;
+    int64_t head[4] = {0, 0, 0, 0};
+    dev.alloc(d_head, 4);
+    dev.launched(launch_bam_head(d_stream, stream_len, d_head.p, dev.ctx->stream), "k_bam_head");
+    dev.fetch(head, d_head.p, sizeof(head));
+    dev.sync();
+    if (head[0] != 0) dev.refuse(NPR_ERR_INVALID, (std::string(dev.entry) + ": no BAM magic, or a header that runs past the stream").c_str());
+    const BamHeader h{head[1], head[2], head[3]};
+    std::vector<uint8_t> header(static_cast<size_t>(h.end));
+    dev.fetch(header.data(), d_stream, header.size());
+    dev.sync();
+    names.clear(), name_off.assign(static_cast<size_t>(h.n_ref) + 1, 0);
+    if (ref_len) ref_len->assign(static_cast<size_t>(h.n_ref), 0);
+    for (int64_t k = 0, at = 8 + h.l_text + 4; k < h.n_ref; ++k) {  // (k_bam_head checked every l_name against the header's end)
+        int32_t l_name, l_ref;
+        std::memcpy(&l_name, header.data() + at, 4);
+        std::memcpy(&l_ref, header.data() + at + 4 + l_name, 4);
+        names.insert(names.end(), header.begin() + at + 4, header.begin() + at + 4 + l_name - 1);
+        name_off[k + 1] = static_cast<int64_t>(names.size());
+        if (ref_len) (*ref_len)[k] = l_ref;
+        at += 8 + l_name;
+    }
+    return h;
+}
+
 }  // namespace
 
 extern "C" {
@@ -262,27 +294,10 @@ int64_t npr_bam_sam(npr_ctx *ctx, const uint8_t *file, int64_t len, uint8_t *sam
         const int64_t stream_len = run.stream_len;
         const uint8_t *const d_stream = run.stream.p;
 
-        // the header: its end from the device, its bytes once to the host for the names
-        DevBuf<int64_t> d_head;
-        int64_t head[4] = {0, 0, 0, 0};
-        dev.alloc(d_head, 4);
-        dev.launched(launch_bam_head(d_stream, stream_len, d_head.p, ctx->stream), "k_bam_head");
-        dev.fetch(head, d_head.p, sizeof(head));
-        dev.sync();
-        if (head[0] != 0) dev.refuse(NPR_ERR_INVALID, "npr_bam_sam: no BAM magic, or a header that runs past the stream");
-        const int64_t header_end = head[1], l_text = head[2], n_ref = head[3];
-        std::vector<uint8_t> header(static_cast<size_t>(header_end));
-        dev.fetch(header.data(), d_stream, header.size());
-        dev.sync();
         std::vector<uint8_t> names;
-        std::vector<int64_t> name_off(static_cast<size_t>(n_ref) + 1, 0);
-        for (int64_t k = 0, at = 8 + l_text + 4; k < n_ref; ++k) {  // (k_bam_head checked every l_name against the header's end)
-            int32_t l_name;
-            std::memcpy(&l_name, header.data() + at, 4);
-            names.insert(names.end(), header.begin() + at + 4, header.begin() + at + 4 + l_name - 1);
-            name_off[k + 1] = static_cast<int64_t>(names.size());
-            at += 8 + l_name;
-        }
+        std::vector<int64_t> name_off;
+        const BamHeader h = bam_header(dev, d_stream, stream_len, names, name_off, nullptr);
+        const int64_t header_end = h.end, l_text = h.l_text, n_ref = h.n_ref;
 
         // the records: the block_size chain in rounds into a table of fixed size
         constexpr int64_t kWalk = int64_t(1) << 18;
@@ -393,6 +408,109 @@ int32_t npr_inflate_last(npr_ctx *ctx, int64_t *out) {
     if (!ctx || !out) return NPR_ERR_INVALID;
     std::copy(ctx->inflate_last, ctx->inflate_last + 4, out);
     return NPR_OK;
+}
+
+int32_t npr_bam_open(npr_ctx *ctx, const uint8_t *file, int64_t len, npr_bam_stream **out) {
+    if (!ctx || !file || len < 0 || !out) return NPR_ERR_INVALID;
+    *out = nullptr;
+    return guarded(ctx, "npr_bam_open", [&](const Call &dev) -> int32_t {
+        std::vector<int64_t> block_off, stream_off;
+        if (scan_table(file, len, block_off, stream_off) < 0) dev.refuse(NPR_ERR_INVALID, "npr_bam_open: not a BGZF file that ends with the end-of-file block");
+        if (block_off.size() >= (size_t(1) << 31)) return NPR_ERR_INVALID;
+        std::unique_ptr<npr_bam_stream> bs(new npr_bam_stream);
+        bs->ctx = ctx;
+        {
+            InflateRun run;  // (the file image and the block tables go when the stream is made)
+            run.launch(dev, file, len, block_off, stream_off);
+            run.finish(dev);
+            bs->stream_len = run.stream_len;
+            bs->stream.take(run.stream);
+        }
+        const uint8_t *const d_stream = bs->stream.p;
+        const BamHeader h = bam_header(dev, d_stream, bs->stream_len, bs->names, bs->name_off, &bs->ref_len);
+        bs->l_text = h.l_text;
+
+        // the records: the block_size chain in rounds of fixed size into a table that stays on the device and doubles when it is full
+        constexpr int64_t kWalk = int64_t(1) << 18;
+        DevBuf<int64_t> d_walk;
+        int64_t cap = kWalk, n = 0;
+        dev.alloc(bs->rec_off, cap), dev.alloc(d_walk, 3);
+        for (int64_t at = h.end; at < bs->stream_len;) {
+            if (n + kWalk > cap) {
+                DevBuf<int64_t> wider;
+                dev.alloc(wider, 2 * cap);
+                dev.check(hipMemcpyAsync(wider.p, bs->rec_off.p, static_cast<size_t>(n) * sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream), "D2D");
+                dev.sync();
+                bs->rec_off.take(wider);
+                cap *= 2;
+            }
+            int64_t w[3] = {0, 0, 0};
+            dev.launched(launch_bam_walk(d_stream, bs->stream_len, at, static_cast<int32_t>(h.n_ref), bs->rec_off.p + n, kWalk, d_walk.p, ctx->stream), "k_bam_walk");
+            dev.fetch(w, d_walk.p, sizeof(w));
+            dev.sync();
+            if (w[2] != 0 || w[0] <= 0) {
+                char text[160];
+                std::snprintf(text, sizeof(text), "npr_bam_open: record %lld at stream byte %lld is refused (walk status %lld)", static_cast<long long>(n + w[0]),
+                              static_cast<long long>(w[1]), static_cast<long long>(w[2]));
+                dev.refuse(NPR_ERR_INVALID, text);
+            }
+            n += w[0], at = w[1];
+        }
+        if (n >= (int64_t(1) << 31)) dev.refuse(NPR_ERR_INVALID, "npr_bam_open: 2^31 records and more");
+        bs->n = n;
+        *out = bs.release();
+        return NPR_OK;
+    });
+}
+
+void npr_bam_close(npr_bam_stream *bs) {
+    if (!bs) return;
+    (void)hipSetDevice(bs->ctx->device);
+    delete bs;
+}
+
+int64_t npr_bam_stream_info(npr_bam_stream *bs, int64_t *out) {
+    if (!bs || !out) return NPR_ERR_INVALID;
+    out[0] = bs->n, out[1] = static_cast<int64_t>(bs->ref_len.size()), out[2] = bs->l_text, out[3] = bs->stream_len;
+    return bs->n;
+}
+
+int64_t npr_bam_stream_refs(npr_bam_stream *bs, int64_t *ref_len, int64_t *name_off, uint8_t *names, int64_t cap) {
+    if (!bs || cap < 0) return NPR_ERR_INVALID;
+    const int64_t total = static_cast<int64_t>(bs->names.size());
+    if (!names) return total;
+    if (cap < total) return NPR_ERR_CAPACITY;
+    if (ref_len) std::copy(bs->ref_len.begin(), bs->ref_len.end(), ref_len);
+    if (name_off) std::copy(bs->name_off.begin(), bs->name_off.end(), name_off);
+    std::copy(bs->names.begin(), bs->names.end(), names);
+    return total;
+}
+
+int32_t npr_pileup_add_bam(npr_pileup *pl, npr_bam_stream *bs, int32_t flag_mask, int64_t *counts) {
+    if (!pl || !bs || !counts) return NPR_ERR_INVALID;
+    std::fill(counts, counts + 4, int64_t(0));
+    npr_ctx *ctx = pl->ctx;
+    if (bs->ctx != ctx) return fail(ctx, NPR_ERR_INVALID, "npr_pileup_add_bam: the stream and the pileup are of two contexts");
+    if (bs->ref_len != pl->len) return fail(ctx, NPR_ERR_INVALID, "npr_pileup_add_bam: the file's reference sequences are not the pileup's (their number or a length)");
+    if (bs->n == 0) return NPR_OK;
+    return guarded(ctx, "npr_pileup_add_bam", [&](const Call &dev) -> int32_t {
+        DevBuf<BamPileRec> d_recs;
+        DevBuf<int64_t> d_len;
+        DevBuf<unsigned long long> d_counts;
+        dev.alloc(d_recs, static_cast<size_t>(bs->n)), dev.upload(d_len, bs->ref_len);
+        dev.alloc(d_counts, 4), dev.zero(d_counts);
+        const BamPileArgs a{bs->stream.p, bs->stream_len, bs->n, bs->rec_off.p, static_cast<int64_t>(bs->ref_len.size()), d_len.p, pl->dbase.p, flag_mask,
+                            d_recs.p, d_counts.p, pl->tab.p, pl->diff.p};
+        dev.launched(launch_bampile_check(a, ctx->stream), "k_bampile_check");
+        dev.launched(launch_bampile_add(a, ctx->stream), "k_bampile_add");
+        unsigned long long got[4] = {0, 0, 0, 0};
+        dev.fetch(got, d_counts.p, sizeof(got));
+        dev.sync();
+        counts[0] = bs->n;
+        for (int k = 1; k < 4; ++k) counts[k] = static_cast<int64_t>(got[k]);
+        return counts[3] ? fail(ctx, NPR_ERR_INVALID, "npr_pileup_add_bam: a record's cigar does not fit its reference sequence or its read, or its auxiliary fields are malformed (the record was left out)")
+                         : NPR_OK;
+    });
 }
 
 int64_t npr_sam_bam(npr_ctx *ctx, const uint8_t *text, int64_t text_len, const int64_t *span, const int64_t *fields, const int64_t *tail, int64_t n,

@@ -1,0 +1,121 @@
+// npr_bamrec.h -- the checks of ONE BAM record before it may be added to a pileup (include/nprealign.h, npr_pileup_add_bam): whether it is
+// selected, which cigar applies, what that cigar consumes, the verdict.  Plain C++ on a byte pointer and lengths, one body for host and device
+// (the kernel: k_bampile_check, npr_bampile.hip; the host program under AddressSanitizer: tests/native/bamrec_check.cpp).  No intrinsics.
+// r points at the record's block_size, `avail` bytes of the stream lie from there on.  In this order:
+//   the parts      block_size at least 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq with l_read_name at least 1 and l_seq at least 0,
+//                  the record inside `avail`, refID below n_ref: else BR_REFUSED / BR_WHY_PARTS (k_bam_walk has refused such a file already)
+//   selection      refID >= 0, (flag & flag_mask) == 0, l_seq > 0, n_cigar_op > 0: else BR_SKIP
+//   the cigar      the stored operations -- unless they are exactly <l_seq>S<n>N: then the auxiliary fields are walked (types A c C s S i I f Z H B,
+//                  every step checked against the record's end; a field cut by the end, an unknown type or array subtype, a Z or H without NUL, an
+//                  array past the end: BR_REFUSED / BR_WHY_AUX) and the elements of the FIRST CG:B:I field are the operations, when there is one;
+//                  such a field of no element: BR_SKIP
+//   the sums       in 64 bits over all operations: reference bases (M D N = X), read bases (M I S = X); a code above 8: BR_REFUSED / BR_WHY_OP
+//   the verdict    pos < 0: BR_WHY_POS; pos + reference bases > l_ref: BR_WHY_REF; read bases != l_seq: BR_WHY_READ; else BR_ADD
+// Every read index is checked against the record's end, which lies inside `avail`, before it happens.
+#ifndef NPR_BAMREC_H
+#define NPR_BAMREC_H
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define NPR_BR_FN __host__ __device__ inline
+#else
+#define NPR_BR_FN inline
+#endif
+
+namespace npr {
+
+enum { BR_SKIP = 0, BR_ADD = 1, BR_REFUSED = 2 };
+enum { BR_WHY_NONE = 0, BR_WHY_PARTS, BR_WHY_AUX, BR_WHY_OP, BR_WHY_POS, BR_WHY_REF, BR_WHY_READ };
+
+struct BamRecVerdict {
+    int32_t verdict, why;
+    int32_t from_cg;           // the operations are a CG:B:I field's elements
+    int32_t tid, pos, l_seq;
+    int64_t ops_at, n_ops;     // the operations: 4-byte words from r + ops_at on (any alignment)
+    int64_t seq_at;            // the packed bases from r + seq_at on
+    int64_t ref_sum, read_sum;
+};
+
+NPR_BR_FN uint32_t br_ld32(const uint8_t *p) {
+    return p[0] | static_cast<uint32_t>(p[1]) << 8 | static_cast<uint32_t>(p[2]) << 16 | static_cast<uint32_t>(p[3]) << 24;
+}
+NPR_BR_FN int br_width(uint8_t t) { return (t == 'c' || t == 'C') ? 1 : ((t == 's' || t == 'S') ? 2 : ((t == 'i' || t == 'I' || t == 'f') ? 4 : 0)); }
+
+// The auxiliary fields r[at, end): false when one is malformed.  *cg_at / *cg_n: where the elements of the first CG:B:I field lie (from r) and
+// how many; -1 / 0 without one.
+NPR_BR_FN bool bamrec_aux_walk(const uint8_t *r, int64_t at, int64_t end, int64_t *cg_at, int64_t *cg_n) {
+    *cg_at = -1, *cg_n = 0;
+    while (at < end) {
+        if (end - at < 3) return false;
+        const uint8_t t0 = r[at], t1 = r[at + 1], type = r[at + 2];
+        at += 3;
+        const int w = br_width(type);
+        if (type == 'A') {
+            if (end - at < 1) return false;
+            at += 1;
+        } else if (w) {
+            if (end - at < w) return false;
+            at += w;
+        } else if (type == 'Z' || type == 'H') {
+            while (at < end && r[at] != 0) ++at;
+            if (at >= end) return false;
+            at += 1;
+        } else if (type == 'B') {
+            if (end - at < 5) return false;
+            const uint8_t sub = r[at];
+            const int sw = br_width(sub);
+            const int64_t count = br_ld32(r + at + 1);
+            if (!sw || sw * count > end - (at + 5)) return false;
+            if (*cg_at < 0 && t0 == 'C' && t1 == 'G' && sub == 'I') *cg_at = at + 5, *cg_n = count;
+            at += 5 + sw * count;
+        } else {
+            return false;
+        }
+    }
+    return true;
+}
+
+NPR_BR_FN void bamrec_check(const uint8_t *r, int64_t avail, const int64_t *ref_len, int64_t n_ref, int32_t flag_mask, BamRecVerdict &v) {
+    v.verdict = BR_REFUSED, v.why = BR_WHY_PARTS, v.from_cg = 0, v.tid = -1, v.pos = 0, v.l_seq = 0;
+    v.ops_at = 0, v.n_ops = 0, v.seq_at = 0, v.ref_sum = 0, v.read_sum = 0;
+    if (avail < 36) return;
+    const int64_t size = static_cast<int32_t>(br_ld32(r));
+    const int64_t l_name = r[12], n_cig = r[16] | static_cast<int64_t>(r[17]) << 8, l_seq = static_cast<int32_t>(br_ld32(r + 20));
+    const int32_t tid = static_cast<int32_t>(br_ld32(r + 4)), pos = static_cast<int32_t>(br_ld32(r + 8)), flag = r[18] | r[19] << 8;
+    if (size < 32 || 4 + size > avail || l_name < 1 || l_seq < 0 || 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq > size || tid >= n_ref) return;
+    const int64_t end = 4 + size, cigar_at = 36 + l_name, seq_at = cigar_at + 4 * n_cig, aux_at = seq_at + (l_seq + 1) / 2 + l_seq;
+    v.tid = tid, v.pos = pos, v.l_seq = static_cast<int32_t>(l_seq), v.seq_at = seq_at;
+    v.verdict = BR_SKIP, v.why = BR_WHY_NONE;
+    if (tid < 0 || (flag & flag_mask) != 0 || l_seq <= 0 || n_cig == 0) return;
+    v.ops_at = cigar_at, v.n_ops = n_cig;
+    if (n_cig == 2 && br_ld32(r + cigar_at) == (static_cast<uint32_t>(l_seq) << 4 | 4u) && (br_ld32(r + cigar_at + 4) & 15u) == 3u) {
+        int64_t cg_at, cg_n;
+        if (!bamrec_aux_walk(r, aux_at, end, &cg_at, &cg_n)) {
+            v.verdict = BR_REFUSED, v.why = BR_WHY_AUX;
+            return;
+        }
+        if (cg_at >= 0) {
+            v.from_cg = 1, v.ops_at = cg_at, v.n_ops = cg_n;
+            if (cg_n == 0) return;
+        }
+    }
+    int64_t ref_sum = 0, read_sum = 0;
+    bool other = false;
+    for (int64_t q = 0; q < v.n_ops; ++q) {
+        const uint32_t w = br_ld32(r + v.ops_at + 4 * q), op = w & 15u;
+        const int64_t len = w >> 4;
+        other |= op > 8u;
+        if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) ref_sum += len;
+        if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) read_sum += len;
+    }
+    v.ref_sum = ref_sum, v.read_sum = read_sum;
+    v.verdict = BR_REFUSED;
+    if (other) v.why = BR_WHY_OP;
+    else if (pos < 0) v.why = BR_WHY_POS;
+    else if (pos + ref_sum > ref_len[tid]) v.why = BR_WHY_REF;
+    else if (read_sum != l_seq) v.why = BR_WHY_READ;
+    else v.verdict = BR_ADD;
+}
+
+}  // namespace npr
+#endif

@@ -559,6 +559,32 @@ int launch_bam_walk(const uint8_t *stream, int64_t len, int64_t start, int32_t n
 int launch_bam_read_measure(const BamReadArgs &a, void *stream);
 int launch_bam_gather_aux(const BamReadArgs &a, void *stream);
 int launch_bam_emit(const BamReadArgs &a, void *stream);
+// the records of a BAM stream into a pileup where they lie (npr_bampile.hip; the rules: npr_bamrec.h and include/nprealign.h, npr_pileup_add_bam)
+struct BamPileRec {  // what k_bampile_check finds
+    int64_t ops_at;              // first cigar word in the stream (the stored ones or a CG:B:I field's; any alignment)
+    int64_t n_ops;
+    int64_t seq_at;              // first byte of the packed bases in the stream
+    int64_t row0;                // table row of POS
+    int64_t d0;                  // slot of POS in the difference array (row0 + refID)
+    int32_t verdict;             // BR_SKIP, BR_ADD, BR_REFUSED
+    int32_t pad;
+};
+struct BamPileArgs {
+    const uint8_t *stream;       // the uncompressed BAM stream
+    int64_t len;
+    int64_t n;                   // records
+    const int64_t *rec_off;      // [n] stream offset of every record's block_size
+    int64_t n_ref;
+    const int64_t *ref_len;      // [n_ref]
+    const int64_t *dbase;        // [n_ref + 1] first slot of every sequence in the difference array (first row + index)
+    int32_t flag_mask;
+    BamPileRec *recs;            // [n]
+    unsigned long long *counts;  // [4], added to: (unused), selected, added, refused
+    int32_t *tab;                // [rows][NPR_PILEUP_WORDS], added to
+    int32_t *diff;               // [rows + n_ref], added to
+};
+int launch_bampile_check(const BamPileArgs &a, void *stream);
+int launch_bampile_add(const BamPileArgs &a, void *stream);
 struct BamRec {  // one SAM line as the host's parsers found it
     int64_t name, cigar_lo, cigar_hi, seq, qual;  // offsets in the text; qual < 0: "*"
     int64_t tag_off;

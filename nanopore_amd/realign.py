@@ -432,6 +432,18 @@ class Pileup(_Handle):
         check(self._L.npr_pileup_add(self._h, n, ptr(ri), ptr(read), ptr(read_begin), ptr(read_end), ptr(ops), ptr(ops_off), ptr(st), ptr(u)),
               "npr_pileup_add", self.ctx)
 
+    def add_bam(self, stream, flag_mask=0x4 | 0x100 | 0x200 | 0x400):
+        """The records of a BamStream (Context.bam_open) where they lie on the device (include/nprealign.h: npr_pileup_add_bam, which states
+        what is selected, which cigar applies and what is refused): no SAM text, nothing parsed on the host.  flag_mask: records with one of
+        these FLAG bits are left out (default: samtools' pileup mask, analyses/pileup.py FLAG_MASK).  -> {"records", "selected", "added",
+        "refused"}, kept in self.last_bam_counts too.  A refused record adds nothing and raises NprError (ERR_INVALID) as add_csr does, after
+        the other records were counted; a file whose reference sequences are not the pileup's raises too, and nothing is added."""
+        out = np.zeros(4, dtype=np.int64)
+        rc = self._L.npr_pileup_add_bam(self._h, stream._h, int(flag_mask), ptr(out))
+        self.last_bam_counts = dict(zip(("records", "selected", "added", "refused"), (int(v) for v in out)))
+        check(rc, "npr_pileup_add_bam", self.ctx)
+        return self.last_bam_counts
+
     def counts(self):
         """The table so far: int32 [rows, PILEUP_WORDS]."""
         out = np.zeros((self.rows, _lib.PILEUP_WORDS), dtype=np.int32)
@@ -468,6 +480,34 @@ class Pileup(_Handle):
             out = Coverage.zeros(n_windows if 1 <= n_windows <= _lib.AQ_MAX_WINDOWS else 1)
         check(self._L.npr_pileup_coverage(self._h, ptr(ref_text), ptr(ref_off), int(n_windows), *map(ptr, out.arrays())), "npr_pileup_coverage", self.ctx)
         return out
+
+
+class BamStream(_Handle):
+    """A BAM file image inflated and walked on the device (include/nprealign.h: npr_bam_open): the uncompressed stream and the table of its
+    records' offsets stay there until close(); .references / .lengths are the header's names and l_ref values, .n_records the records,
+    .l_text the header text's length, .stream_bytes the stream's.  `data`: bytes or a uint8 array.  A file that is not BGZF, a block that
+    does not inflate, a bad BAM magic or a malformed record raises, and there is no object.  Pileup.add_bam takes it; it may be added any
+    number of times, to any pileup of its context.  A context manager: closed on exit."""
+    _destroy = "npr_bam_close"
+
+    def __init__(self, ctx, data):
+        data = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else _arr(data, np.uint8)
+        self._create(ctx, "npr_bam_open", "npr_bam_open", ptr(data), len(data))
+        info = np.zeros(4, dtype=np.int64)
+        check(self._L.npr_bam_stream_info(self._h, ptr(info)), "npr_bam_stream_info", ctx)
+        self.n_records, n_ref, self.l_text, self.stream_bytes = (int(v) for v in info)
+        total = int(check(self._L.npr_bam_stream_refs(self._h, None, None, None, 0), "npr_bam_stream_refs", ctx))
+        self.lengths, name_off, names = np.zeros(n_ref, dtype=np.int64), np.zeros(n_ref + 1, dtype=np.int64), np.zeros(max(total, 1), dtype=np.uint8)
+        check(self._L.npr_bam_stream_refs(self._h, ptr(self.lengths), ptr(name_off), ptr(names), len(names)), "npr_bam_stream_refs", ctx)
+        text = names.tobytes()
+        self.references = [text[name_off[k]:name_off[k + 1]].decode() for k in range(n_ref)]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 class SeedIndex(_Handle):
@@ -738,6 +778,11 @@ class Context(object):
         -> the counts (records, references, bytes, stream_bytes, blocks).  A malformed file raises and leaves no file."""
         from . import bam
         return bam.bam_to_sam(self, bamFile, samFile)
+
+    def bam_open(self, data):
+        """A BAM file image (bytes or a uint8 array) inflated and walked on the device, kept there (BamStream; include/nprealign.h:
+        npr_bam_open): what Pileup.add_bam takes."""
+        return BamStream(self, data)
 
     def align_indel_kmers(self, refs, reads, cigars, k=5, ref_index=None, start=None):
         """The k-mers that straddle a gap of arbitrary alignments (arguments as for align_stats), counted on the device
