@@ -1087,7 +1087,8 @@ int32_t npr_inflate_last(npr_ctx *ctx, int64_t *out /* [4] */);
  *   wavefront checks the header (magic "BAM\1", l_text, n_ref, every l_name with its NUL and l_ref inside the stream); one wavefront
  *   follows the block_size chain, in rounds into a table of fixed size, and checks per record: block_size at least 33, the record inside
  *   the stream (the last one ends with it), l_read_name at least 1 with a NUL at its end, the 32 fixed bytes, name, cigar, SEQ and QUAL
- *   inside block_size, refID and next_refID in -1 .. n_ref - 1; a cigar operation above 8 is refused too.  THE LINE, columns separated by
+ *   inside block_size, refID and next_refID in -1 .. n_ref - 1, pos and next_pos at most 2^31 - 2 (walk status 6: POS and PNEXT, one more,
+ *   end at 2^31 - 1 in SAM); a cigar operation above 8 is refused too.  THE LINE, columns separated by
  *   one tab: QNAME; FLAG; RNAME, "*" for refID -1; POS + 1; MAPQ; CIGAR: "*" for no operation, else <length><MIDNSHP=X> per operation --
  *   when the stored cigar is <l_seq>S<n>N and the record has a CG:B:I field, that field's operations, and the field is dropped --; RNEXT:
  *   "*" for next_refID -1, "=" when it equals refID, else the name; PNEXT + 1; TLEN; SEQ through "=ACMGRSVTWYHKDBN", "*" for l_seq 0; QUAL

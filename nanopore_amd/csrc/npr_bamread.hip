@@ -5,7 +5,8 @@
 //   k_bam_walk     one wavefront follows the block_size chain from there and writes record offsets into a table of fixed size; the host calls
 //                  it in rounds, resuming where the last one stopped.  One dependent load a record: serial by the format.  Per record:
 //                  block_size at least 33, the record inside the stream, l_read_name at least 1 with a NUL at its end, the fixed parts (32
-//                  bytes, name, cigar, SEQ, QUAL) inside block_size, refID and next_refID in -1 .. n_ref - 1.
+//                  bytes, name, cigar, SEQ, QUAL) inside block_size, refID and next_refID in -1 .. n_ref - 1, pos and next_pos at most
+//                  2^31 - 2 (SAM's POS and PNEXT end at 2^31 - 1; pos + 1 stays an int32 in the kernels below).
 //   k_bam_measure  a thread a record: the text length of the eleven mandatory columns (the stored cigar's apart), the span of the auxiliary
 //                  bytes, whether the stored cigar is the placeholder <l_seq>S<n>N.
 //   k_bam_gather_aux  the auxiliary bytes of all records packed back to back: they go to the host once.
@@ -34,7 +35,7 @@ __device__ __forceinline__ uint32_t ld32(const uint8_t *p) {
 __device__ __forceinline__ int32_t ld32s(const uint8_t *p) { return static_cast<int32_t>(ld32(p)); }
 
 enum { HEAD_OK = 0, HEAD_MAGIC = 1, HEAD_TEXT = 2, HEAD_REFS = 3 };
-enum { WALK_OK = 0, WALK_SIZE = 1, WALK_PAST = 2, WALK_NAME = 3, WALK_PARTS = 4, WALK_REF = 5 };
+enum { WALK_OK = 0, WALK_SIZE = 1, WALK_PAST = 2, WALK_NAME = 3, WALK_PARTS = 4, WALK_REF = 5, WALK_POS = 6 };
 
 __global__ void __launch_bounds__(64) k_bam_head(const uint8_t *s, int64_t len, int64_t *out) {
     if (threadIdx.x != 0) return;
@@ -92,6 +93,10 @@ __global__ void __launch_bounds__(64) k_bam_walk(const uint8_t *s, int64_t len, 
         }
         if (tid < -1 || tid >= n_ref || ntid < -1 || ntid >= n_ref) {
             status = WALK_REF;
+            break;
+        }
+        if (ld32s(r + 8) > 0x7ffffffe || ld32s(r + 28) > 0x7ffffffe) {  // POS / PNEXT = pos + 1 would not fit SAM's 2^31 - 1 (nor an int32)
+            status = WALK_POS;
             break;
         }
         table[n++] = at;

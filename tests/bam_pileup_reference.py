@@ -40,20 +40,22 @@ def pack_seq(nibbles):
     return bytes(nib[k] << 4 | nib[k + 1] for k in range(0, len(nib), 2))
 
 
-def record(name, flag, tid, pos, words, nibbles, aux=b"", l_seq=None, mapq=30):
-    """One BAM record.  l_seq: what the record says (default: the nibbles given); the bin field is left 0."""
+def record(name, flag, tid, pos, words, nibbles, aux=b"", l_seq=None, mapq=30, bin=0, next_tid=-1, next_pos=-1, tlen=0, qual=None):
+    """One BAM record.  l_seq: what the record says (default: the nibbles given); qual: the quality bytes as they are stored (default: 0xFF per
+    nibble given, "no qualities").  With an odd l_seq and one nibble more given, that nibble lands in the unused low half of the last byte."""
     name = name.encode() + b"\0"
     l_seq = len(nibbles) if l_seq is None else l_seq
-    body = struct.pack("<iiBBHHHiiii", tid, pos, len(name), mapq, 0, len(words), flag, l_seq, -1, -1, 0) + name
-    body += struct.pack("<%dI" % len(words), *words) + pack_seq(nibbles) + b"\xff" * len(nibbles) + aux
+    qual = b"\xff" * len(nibbles) if qual is None else bytes(qual)
+    body = struct.pack("<iiBBHHHiiii", tid, pos, len(name), mapq, bin, len(words), flag, l_seq, next_tid, next_pos, tlen) + name
+    body += struct.pack("<%dI" % len(words), *words) + pack_seq(nibbles) + qual + aux
     return struct.pack("<i", len(body)) + body
 
 
-def cg_record(name, flag, tid, pos, words, nibbles, aux_before=b"", aux_after=b"", with_cg=True):
-    """The record of a long cigar: <l_seq>S<n>N stored, the operations in a CG:B:I field between the other auxiliary bytes."""
+def cg_record(name, flag, tid, pos, words, nibbles, aux_before=b"", aux_after=b"", with_cg=True, **kw):
+    """The record of a long cigar: <l_seq>S<n>N stored, the operations in a CG:B:I field between the other auxiliary bytes.  kw: record()'s."""
     stored = [len(nibbles) << 4 | 4, consumed(words, REF_OPS) << 4 | 3]
     cg = b"CGBI" + struct.pack("<I%dI" % len(words), len(words), *words) if with_cg else b""
-    return record(name, flag, tid, pos, stored, nibbles, aux=aux_before + cg + aux_after)
+    return record(name, flag, tid, pos, stored, nibbles, aux=aux_before + cg + aux_after, **kw)
 
 
 def header(refs, text=None):

@@ -117,9 +117,15 @@ def _aux_text(b):
     return out
 
 
-def bam_decode(stream):
+def bam_decode(stream, any_writer=False):
     """-> (header text, [(name, length)], [record dict]); a record has the SAM columns as text (`line`, with a CG tag folded back into
-    CIGAR), and tid, pos, end, flag, bin, n_cigar_op, u0, u1 (its bytes in the stream)."""
+    CIGAR), and tid, pos, end, flag, bin, n_cigar_op, u0, u1 (its bytes in the stream).
+    Two assertions hold this project's writer to more than the specification asks: the unused low nibble of an odd l_seq is 0 (section
+    4.2.3 only recommends it: "the bottom 4 bits of the last byte are undefined"), and a CG tag is the record's last (section 4.2.2 says
+    the tag "CG:B:I" holds the real cigar, not where it stands).  any_writer=True lifts both and keeps the specification's rule: the
+    nibble is ignored, and the FIRST CG:B:I field is folded wherever it stands among the other tags -- of a record whose stored cigar is
+    <l_seq>S<n>N; beside any other stored cigar a CG field is printed as the tag it is, where the default asserts.  (POS is pos + 1 for every pos,
+    so pos -1 prints 0 on a real refID too: section 4.2, "0-based leftmost coordinate", -1 + 1 = SAM's 0 for "unavailable".)"""
     assert stream[:4] == b"BAM\1"
     l_text = struct.unpack_from("<i", stream, 4)[0]
     text = stream[8:8 + l_text].decode()
@@ -146,7 +152,7 @@ def bam_decode(stream):
         q += 4 * n_cig
         packed = np.frombuffer(body[q:q + (l_seq + 1) // 2], dtype=np.uint8)
         nib = np.stack([packed >> 4, packed & 15], axis=1).reshape(-1)
-        if l_seq & 1:
+        if l_seq & 1 and not any_writer:
             assert nib[-1] == 0
         seq = "".join(BASES[v] for v in nib[:l_seq]) or "*"
         q += (l_seq + 1) // 2
@@ -156,12 +162,15 @@ def bam_decode(stream):
         aux = _aux_text(body[q:])
         stored = list(cig)
         cg = [a for a in aux if a.startswith("CG:B:I")]
+        if cg and any_writer and not (n_cig == 2 and stored[0] == (l_seq << 4 | 4) and stored[1] & 15 == 3):
+            cg = []   # (section 4.2.2: CG holds the cigar only of a record whose stored cigar is kSmN; elsewhere it is a tag like any other)
         if cg:
             real = [int(v) for v in cg[0].split(",")[1:]]
             consumed = sum(v >> 4 for v in real if (v & 15) in (0, 2, 3, 7, 8))
             assert n_cig == 2 and stored == [l_seq << 4 | 4, consumed << 4 | 3], "the placeholder of a long cigar"
-            assert aux[-1] == cg[0], "CG comes after the record's other tags"
-            cig, aux = real, aux[:-1]
+            assert any_writer or aux[-1] == cg[0], "CG comes after the record's other tags"
+            at_cg = aux.index(cg[0])
+            cig, aux = real, aux[:at_cg] + aux[at_cg + 1:]
         cigar = "".join("%d%s" % (v >> 4, OPS[v & 15]) for v in cig) or "*"
         consumed = sum(v >> 4 for v in cig if (v & 15) in (0, 2, 3, 7, 8))
         end = pos + 1 if (consumed == 0 or flag & 4) else pos + consumed
