@@ -1140,6 +1140,53 @@ int64_t npr_bam_stream_info(npr_bam_stream *bs, int64_t *out /* [4] */);
 int64_t npr_bam_stream_refs(npr_bam_stream *bs, int64_t *ref_len /* [n_ref] */, int64_t *name_off /* [n_ref + 1] */, uint8_t *names, int64_t cap);
 int32_t npr_pileup_add_bam(npr_pileup *pl, npr_bam_stream *bs, int32_t flag_mask, int64_t *counts /* [4] */);
 
+/* ---- region queries on an indexed BAM file: the BAI read, only the blocks it names inflated (SAMv1 section 5; csrc/npr_bamregion.hip) ----
+ * What the reference's users get from pysam.index: `samtools view x.bam chr:a-b`, `samtools depth -r`, `mpileup -r`.  A region is
+ * [beg, end) of reference sequence tid, 0-based and half-open.  A record's interval is [rb, re): rb = max(pos, 0), re = max(pos + the
+ * reference bases of its cigar (M D N = X), rb + 1); with FLAG 4 set or without a cigar re = rb + 1 (the MEASURE rule of npr_sam_bam); under
+ * the placeholder cigar <l_seq>S<n>N the operations are those of the first CG:B:I field, when there is one.  A record OVERLAPS the region
+ * when its refID is tid and rb < end && re > beg.
+ *
+ * npr_bai_chunks (host, no GPU): the chunks a reader has to visit for the region, from bai[0, bai_len), the BAI file image of any writer
+ *   ("BAI\1", n_ref; per reference n_bin, per bin: bin, n_chunk, the chunks' (beg, end); n_intv, ioffset[n_intv]; optionally n_no_coor).
+ *   The bins are those of the specification's reg2bins(beg, end): bin 0 and, for the shifts 26, 23, 20, 17, 14 with first bins 1, 9, 73,
+ *   585, 4681, first + (beg >> shift) .. first + ((end - 1) >> shift); the pseudo-bin 37450 is never one of them.  The lower bound is
+ *   low = ioffset[min(beg >> 14, n_intv - 1)], 0 when n_intv is 0 (htslib's rule: safe for every writer).  A chunk with end <= low is
+ *   dropped; the rest are sorted by beg and a chunk whose beg is less than or equal to the running end is merged into its predecessor:
+ *   the result is disjoint, ascending chunks, chunk_beg[i] / chunk_end[i] (virtual offsets).  Returns their number; chunk_beg == NULL:
+ *   only that; NPR_ERR_CAPACITY when cap is smaller.  *n_ref is set once the header has been read.  NPR_ERR_INVALID, with nothing written
+ *   to the chunks, for a wrong magic, a count (n_ref, n_bin, n_chunk, n_intv) that is negative or runs past bai_len -- every read is checked
+ *   against bai_len first, so a malformed image costs bounded time --, a chunk with end < beg (in any bin but the pseudo-bin, of any
+ *   reference), a tid outside 0 .. n_ref - 1, a region that does not satisfy 0 <= beg < end <= 2^29, or bytes after the last reference
+ *   that are not the 8 of n_no_coor (which is optional).
+ *
+ * npr_bam_open_region: npr_bam_open for the records that overlap the region, found through the index.  The block headers are scanned
+ *   (npr_bgzf_scan); the blocks that hold the BAM header are inflated (block 0, and more while the header runs on) and the header is
+ *   checked as npr_bam_open checks it; the index's n_ref must be the file's.  A chunk [vb, ve) of npr_bai_chunks needs the blocks whose
+ *   file offset lies in [vb >> 16, ve >> 16], the last one only when ve & 0xffff > 0; vb >> 16 and ve >> 16 must be block offsets of the
+ *   scan (ve >> 16 may be the end-of-file block's) and the low 16 bits may not exceed that block's ISIZE.  The union of the header's and
+ *   the chunks' blocks, in file order, is inflated into ONE COMPACT STREAM (the same decoder, statuses and refusals; npr_inflate_last
+ *   reports the blocks and the length of this stream: how a caller sees that the file was not inflated whole).  Every chunk is walked by
+ *   one wavefront with the per-record checks of npr_bam_sam, from its first byte until the record offset reaches its end; a chunk that
+ *   does not end on a record boundary is refused with walk status 7.  The records of all chunks, in file order, are then filtered: a
+ *   record is kept when it overlaps the region.  A kept candidate (refID tid, FLAG 4 clear) under a placeholder cigar whose auxiliary
+ *   fields are malformed (npr_pileup_add_bam states when) is not kept and makes the call fail.  NPR_ERR_INVALID for every refusal above
+ *   and of npr_bai_chunks; no object is returned unless the call succeeds.  The object is an ordinary npr_bam_stream: its records are the
+ *   overlapping ones in file order, its header fields the file's, npr_bam_stream_info out[3] the compact stream's length; whole records
+ *   are kept, so npr_pileup_add_bam on it gives a table that is complete inside [beg, end) and partial outside.
+ * npr_bam_stream_restrict: narrows the object's record table in place to the records that overlap the region, order preserved, by the same
+ *   filter; needs no index and works on a file in any order; restricting twice gives the intersection.  Returns the number of records
+ *   left.  NPR_ERR_INVALID (the table stays as it was) for a tid outside 0 .. n_ref - 1, a region that does not satisfy 0 <= beg < end,
+ *   or malformed auxiliary fields as above.
+ * npr_bam_stream_sam: the header text and one line per record of the object, exactly the lines npr_bam_sam writes (one body); arguments,
+ *   return value and refusals as npr_bam_sam.  After npr_bam_open_region or npr_bam_stream_restrict: `samtools view -h x.bam region`. */
+int64_t npr_bai_chunks(const uint8_t *bai, int64_t bai_len, int32_t tid, int64_t beg, int64_t end, uint64_t *chunk_beg, uint64_t *chunk_end,
+                       int64_t cap, int64_t *n_ref);
+int32_t npr_bam_open_region(npr_ctx *ctx, const uint8_t *file, int64_t len, const uint8_t *bai, int64_t bai_len, int32_t tid, int64_t beg,
+                            int64_t end, npr_bam_stream **out);
+int64_t npr_bam_stream_restrict(npr_bam_stream *bs, int32_t tid, int64_t beg, int64_t end);
+int64_t npr_bam_stream_sam(npr_bam_stream *bs, uint8_t *sam_out, int64_t cap, int64_t *n_records);
+
 /* npr_batch_create_at for reads that are NOT contiguous in memory: read i = read[read_begin[i] .. read_end[i]) -- e.g. the
  * aligned part of each record's SEQ inside the mapped SAM text (columns 11, 12 of npr_sam_parse), so the sequences go from
  * the file's bytes to the pinned staging buffer in one copy.  Everything else as npr_batch_create_at. */

@@ -239,6 +239,10 @@ SIGNATURES = {
     "npr_bam_stream_info": (i64, [vp, vp]),
     "npr_bam_stream_refs": (i64, [vp, vp, vp, vp, i64]),
     "npr_pileup_add_bam": (i32, [vp, vp, i32, vp]),
+    "npr_bai_chunks": (i64, [vp, i64, i32, i64, i64, vp, vp, i64, C.POINTER(i64)]),
+    "npr_bam_open_region": (i32, [vp, vp, i64, vp, i64, i32, i64, i64, _out]),
+    "npr_bam_stream_restrict": (i64, [vp, i32, i64, i64]),
+    "npr_bam_stream_sam": (i64, [vp, vp, i64, C.POINTER(i64)]),
     "npr_batch_create_spans": (i32, [vp, _params, i64, i64] + [vp] * 10 + [_out]),
 }
 EXPORTS = list(SIGNATURES)

@@ -10,6 +10,8 @@ are added where they lie (`Pileup.add_bam`; npr_bam_open, npr_pileup_add_bam; cs
 Not reproduced: samtools 0.1.19 admits at most 8000 records to a position's pileup (bam_pileup.c, maxcnt), which
 depends on the order of the file; the device table has no cap.
 """
+import os
+
 import numpy as np
 
 from .. import ingest
@@ -54,14 +56,28 @@ def pileup_of_sam(ctx, samFile, referenceFastaFile):
     return names, lengths, pileup
 
 
-def pileup_of_bam(ctx, bamFile, referenceFastaFile=None):
+def region_index(bamFile, region, index=None):
+    """The bytes of the BAI file that serves a region query on bamFile, or None: `index` (a path) when given, else bamFile + ".bai" when
+    there is a region and that file exists."""
+    if region is None:
+        return None
+    if index is None and os.path.exists(bamFile + ".bai"):
+        index = bamFile + ".bai"
+    return None if index is None else np.fromfile(index, dtype=np.uint8)
+
+
+def pileup_of_bam(ctx, bamFile, referenceFastaFile=None, region=None, index=None):
     """-> (names, ref_lengths, Pileup): the table of the records of `bamFile` that samtools' pileup would keep, rows in the order
     of the BAM header's reference sequences, whose names and lengths are the ones returned.  The file is inflated and walked on
     the device and its records are added where they lie (Pileup.add_bam; include/nprealign.h: npr_pileup_add_bam): no SAM text,
     no parse on the host.  With `referenceFastaFile`, its sequences must be the ones the header names (their lengths are
-    compared, as pileup_of_sam compares them); the caller closes the Pileup."""
+    compared, as pileup_of_sam compares them); the caller closes the Pileup.
+    region (Context.bam_open says how one is written; `samtools mpileup -r`): only the records that overlap it are added -- found
+    through the BAI file `index` (default: bamFile + ".bai" when it exists), so that only the blocks it names are inflated, else by
+    restricting the whole file on the device.  WHOLE records are added: the table still has all rows, and it is complete inside
+    [beg, end) of the region's sequence and partial outside it (a record that reaches out of the region adds its columns there too)."""
     data = np.fromfile(bamFile, dtype=np.uint8)
-    with ctx.bam_open(data) as stream:
+    with ctx.bam_open(data, index=region_index(bamFile, region, index), region=region) as stream:
         names, lengths = list(stream.references), np.asarray(stream.lengths, dtype=np.int64)
         if referenceFastaFile is not None:
             fasta = ingest.FastaTable(referenceFastaFile)

@@ -248,15 +248,24 @@ def bamToSamFile(bamFile, samFile, ctx=None):
     return (ctx or _context()).bam_to_sam(bamFile, samFile)
 
 
-def bamDepthFile(bamFile, depthFile, ctx=None):
+def bamDepthFile(bamFile, depthFile, ctx=None, region=None):
     """The text of `samtools depth bamFile` (the reference's metaAnalyses/coverageDepth.py:49-65) in depthFile, from the pileup of the
-    file's records made on the device without SAM text (analyses/pileup.py: pileup_of_bam, depth_text).  -> the text's length."""
+    file's records made on the device without SAM text (analyses/pileup.py: pileup_of_bam, depth_text).  -> the text's length.
+    region (`samtools depth -r`; Context.bam_open says how one is written): only the lines of the positions inside it.  The pileup is
+    made of the whole records that overlap the region (pileup_of_bam, through bamFile + ".bai" when it exists): it is complete inside
+    [beg, end) and partial outside, and what lies outside is not written."""
     from .pileup import depth_text, pileup_of_bam
-    names, lengths, pileup = pileup_of_bam(ctx or _context(), bamFile)
+    names, lengths, pileup = pileup_of_bam(ctx or _context(), bamFile, region=region)
     try:
         depth, covered = pileup.depth()
     finally:
         pileup.close()
+    if region is not None:
+        from ..realign import parse_region
+        tid, beg, end = parse_region(names, lengths, region)
+        row, inside = int(np.sum(lengths[:tid])), np.zeros(len(covered), dtype=bool)
+        inside[row + beg:row + min(end, int(lengths[tid]))] = True
+        covered = covered & inside
     text = depth_text(names, lengths, depth, covered)
     with open(depthFile, "w") as fh:
         fh.write(text)

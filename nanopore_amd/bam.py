@@ -194,6 +194,79 @@ def bam_to_sam(ctx, bamFile, samFile):
     return {"records": int(n), "references": references, "bytes": int(len(text)), "stream_bytes": last["stream_bytes"], "blocks": last["blocks"]}
 
 
+def bam_references(data):
+    """The reference names and lengths of a BAM file image, read on the host from as many of its first blocks as the header fills (bgzf_scan
+    for where they lie, zlib for their few kilobytes): (names, lengths).  What turns a region's name into the refID an indexed query needs
+    before anything is on the device; the device checks the header itself."""
+    import struct
+    import zlib
+    data = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else _arr(data, np.uint8)
+    block_off, _ = bgzf_scan(data)
+    head, used = b"", 0
+
+    def have(n):   # the first n bytes of the stream, when the file has them
+        nonlocal head, used
+        while len(head) < n and used < len(block_off) - 1:
+            block = data[block_off[used]:block_off[used + 1]].tobytes()
+            xlen = struct.unpack_from("<H", block, 10)[0]
+            head += zlib.decompress(block[12 + xlen:-8], -15)
+            used += 1
+        if len(head) < n:
+            raise _lib.NprError(_lib.ERR_INVALID, "bam_references", "the BAM header runs past the file")
+    have(12)
+    if head[:4] != b"BAM\1":
+        raise _lib.NprError(_lib.ERR_INVALID, "bam_references", "no BAM magic")
+    at = 8 + struct.unpack_from("<i", head, 4)[0]
+    have(at + 4)
+    n_ref = struct.unpack_from("<i", head, at)[0]
+    at += 4
+    names, lengths = [], np.zeros(max(n_ref, 0), dtype=np.int64)
+    for k in range(n_ref):
+        have(at + 4)
+        l_name = struct.unpack_from("<i", head, at)[0]
+        have(at + 8 + l_name)
+        names.append(head[at + 4:at + 4 + l_name - 1].decode())
+        lengths[k] = struct.unpack_from("<i", head, at + 4 + l_name)[0]
+        at += 8 + l_name
+    return names, lengths
+
+
+def bai_chunks(bai, tid, beg, end):
+    """The chunks of a BAM file a reader has to visit for [beg, end) of reference tid, 0-based and half-open, from the bytes of its BAI
+    index (npr_bai_chunks, host code, which states the rule): (uint64 [n, 2] of virtual offsets (beg, end), disjoint and ascending; the
+    index's n_ref)."""
+    bai = np.frombuffer(bytes(bai), dtype=np.uint8) if isinstance(bai, (bytes, bytearray)) else _arr(bai, np.uint8)
+    L, n_ref = _lib.load(), C.c_int64(-1)
+    n = int(check(L.npr_bai_chunks(ptr(bai), len(bai), int(tid), int(beg), int(end), None, None, 0, C.byref(n_ref)), "npr_bai_chunks"))
+    cb, ce = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+    check(L.npr_bai_chunks(ptr(bai), len(bai), int(tid), int(beg), int(end), ptr(cb), ptr(ce), n, C.byref(n_ref)), "npr_bai_chunks")
+    return np.stack([cb[:n], ce[:n]], axis=1), int(n_ref.value)
+
+
+def bam_region_to_sam(ctx, bamFile, region, samFile, index=None):
+    """The records of bamFile that overlap `region` (Context.bam_open says how one is written) as SAM text in samFile, under the file's
+    header: `samtools view -h bamFile region`.  index: the path of the BAI file; by default bamFile + ".bai" when that file exists --
+    then only the blocks it names are inflated (npr_bam_open_region) --, else the file is opened whole and restricted on the device
+    (npr_bam_stream_restrict).  A malformed file or index raises and leaves no file.
+    -> {"records", "bytes", "stream_bytes", "blocks", "indexed"}: blocks and stream_bytes are what was inflated."""
+    data = np.fromfile(bamFile, dtype=np.uint8)
+    if index is None and os.path.exists(bamFile + ".bai"):
+        index = bamFile + ".bai"
+    bai = None if index is None else np.fromfile(index, dtype=np.uint8)
+    with ctx.bam_open(data, index=bai, region=region) as stream:
+        last = inflate_last(ctx)
+        text, n = stream.sam_text(), stream.n_records
+    tmp = samFile + ".tmp"
+    try:
+        with open(tmp, "wb") as fh:
+            text.tofile(fh)
+        os.replace(tmp, samFile)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return {"records": int(n), "bytes": int(len(text)), "stream_bytes": last["stream_bytes"], "blocks": last["blocks"], "indexed": bai is not None}
+
+
 def convert(ctx, sam, fields, tail, tag_off, tags, header, ref_len, sort=True, index=True, compress=False):
     """The device call alone (npr_sam_bam, or npr_sam_bam_deflate with compress) on a parsed ingest.SamText: (the BAM file image, the BAI
     file's bytes or None)."""

@@ -1,6 +1,6 @@
 // npr_bam_api.cpp -- npr_bam_sort_order, npr_bgzf_frame, npr_bgzf_deflate, npr_deflate_last, npr_bgzf_inflate, npr_inflate_last, npr_sam_bam, npr_sam_bam_deflate,
-// npr_bam_sam, npr_bam_open / _close / _stream_info / _stream_refs, npr_pileup_add_bam: the checks, the records as the
-// kernels take them, the launches of npr_bam.hip, npr_deflate.hip, npr_inflate.hip, npr_bamread.hip and npr_bampile.hip, and the tables as the header defines them ("coordinate-sorted BAM")
+// npr_bam_sam, npr_bam_open / _close / _stream_info / _stream_refs, npr_pileup_add_bam, npr_bam_open_region, npr_bam_stream_restrict, npr_bam_stream_sam: the checks, the records as the
+// kernels take them, the launches of npr_bam.hip, npr_deflate.hip, npr_inflate.hip, npr_bamread.hip, npr_bampile.hip and npr_bamregion.hip, and the tables as the header defines them ("coordinate-sorted BAM")
 // (one of the translation units of the C ABI, include/nprealign.h; what they share: npr_api_internal.h)
 #include "npr_api_internal.h"
 
@@ -131,9 +131,33 @@ struct InflateRun {
     DevBuf<int64_t> block_off, stream_off;
     DevBuf<int32_t> status;
     int64_t blocks = 0, stream_len = 0;
+    std::vector<int64_t> b_sub;
     void launch(const Call &dev, const uint8_t *image, int64_t len, const std::vector<int64_t> &b_off, const std::vector<int64_t> &s_off) {
-        blocks = static_cast<int64_t>(b_off.size()) - 1, stream_len = s_off.back();
         dev.upload(file, image, static_cast<size_t>(len));
+        queue(dev, b_off, s_off);
+    }
+    // The blocks pick[0 ..] of the scan's table alone (ascending indices): only their bytes cross, back to back, a run of neighbours in one copy,
+    // and their payloads make a COMPACT stream; s_sub[j] = where the payload of block pick[j] begins in it, last its length.  (k_bgzf_inflate
+    // takes a block's size from the next entry of the table: the picked blocks get a table of their own, re-based on the bytes that crossed.)
+    void launch_picked(const Call &dev, const uint8_t *image, const std::vector<int64_t> &b_off, const std::vector<int64_t> &s_off, const std::vector<int64_t> &pick,
+                       std::vector<int64_t> &s_sub) {
+        b_sub.assign(pick.size() + 1, 0);  // (a member: the upload is queued, and waited for in finish())
+        s_sub.assign(pick.size() + 1, 0);
+        for (size_t j = 0; j < pick.size(); ++j) {
+            b_sub[j + 1] = b_sub[j] + (b_off[pick[j] + 1] - b_off[pick[j]]);
+            s_sub[j + 1] = s_sub[j] + (s_off[pick[j] + 1] - s_off[pick[j]]);
+        }
+        dev.alloc(file, static_cast<size_t>(std::max<int64_t>(b_sub.back(), 1)));
+        for (size_t j = 0; j < pick.size();) {
+            size_t k = j + 1;
+            while (k < pick.size() && pick[k] == pick[k - 1] + 1) ++k;
+            dev.copy_up(file.p + b_sub[j], image + b_off[pick[j]], static_cast<size_t>(b_sub[k] - b_sub[j]));
+            j = k;
+        }
+        queue(dev, b_sub, s_sub);
+    }
+    void queue(const Call &dev, const std::vector<int64_t> &b_off, const std::vector<int64_t> &s_off) {
+        blocks = static_cast<int64_t>(b_off.size()) - 1, stream_len = s_off.back();
         dev.upload(block_off, b_off), dev.upload(stream_off, s_off);
         dev.alloc(stream, static_cast<size_t>(std::max<int64_t>(stream_len, 1)));
         dev.alloc(status, static_cast<size_t>(std::max<int64_t>(blocks, 1)));
@@ -187,6 +211,115 @@ BamHeader bam_header(const Call &dev, const uint8_t *d_stream, int64_t stream_le
         at += 8 + l_name;
     }
     return h;
+}
+
+// The records rec_off[0, n) (on the device) of a BAM stream there as SAM text: the header text and a line per record -- what npr_bam_sam and
+// npr_bam_stream_sam do once they know where the records lie.  Returns the text's length; sam_out == NULL: only that.
+int64_t sam_lines(const Call &dev, const uint8_t *d_stream, int64_t stream_len, int64_t l_text, int64_t n_ref, const std::vector<uint8_t> &names,
+                  const std::vector<int64_t> &name_off, const int64_t *d_rec_off, int64_t n, uint8_t *sam_out, int64_t cap, int64_t *n_records) {
+    const std::string entry(dev.entry);
+    DevBuf<uint8_t> d_names, d_aux, d_text, d_out;
+    DevBuf<int64_t> d_name_off, d_aux_off, d_cg, d_text_off, d_line_off, d_tile;
+    DevBuf<BamReadRec> d_meas;
+    DevBuf<int32_t> d_bad;
+    DevBuf<unsigned long long> d_items;
+    BamReadArgs a{};
+    a.stream = d_stream, a.len = stream_len, a.n_ref = static_cast<int32_t>(n_ref), a.n = n;
+    dev.upload(d_names, names), dev.upload(d_name_off, name_off);
+    dev.alloc(d_meas, n), dev.alloc(d_bad, 1), dev.zero(d_bad);
+    a.names = d_names.p, a.name_off = d_name_off.p, a.rec_off = d_rec_off, a.meas = d_meas.p, a.bad = d_bad.p;
+    dev.launched(launch_bam_read_measure(a, dev.ctx->stream), "k_bam_measure");
+    std::vector<BamReadRec> meas(static_cast<size_t>(n));
+    int32_t bad = 0;
+    dev.fetch(meas.data(), d_meas.p, d_meas.bytes());
+    dev.fetch(&bad, d_bad.p, sizeof(bad));
+    dev.sync();
+    if (bad) dev.refuse(NPR_ERR_INVALID, (entry + ": a cigar operation above 8").c_str());
+
+    // the auxiliary bytes: packed, down once, to text on the host, up again
+    std::vector<int64_t> aux_off(static_cast<size_t>(n) + 1, 0), text_off(static_cast<size_t>(n) + 1, 0), cg(2 * static_cast<size_t>(n) + 2, -1);
+    std::vector<uint8_t> placeholder(static_cast<size_t>(n) + 1, 0);
+    for (int64_t i = 0; i < n; ++i) aux_off[i + 1] = aux_off[i] + meas[i].aux_len, placeholder[i] = meas[i].placeholder != 0;
+    std::vector<uint8_t> aux(static_cast<size_t>(aux_off[n]) + 1);
+    dev.upload(d_aux_off, aux_off), dev.alloc(d_aux, aux.size());
+    a.aux_pack_off = d_aux_off.p, a.aux_pack = d_aux.p;
+    dev.launched(launch_bam_gather_aux(a, dev.ctx->stream), "k_bam_gather_aux");
+    dev.fetch(aux.data(), d_aux.p, static_cast<size_t>(aux_off[n]));
+    dev.sync();
+    const int64_t text_len = npr_bam_aux_text(aux.data(), aux_off.data(), n, placeholder.data(), text_off.data(), cg.data(), nullptr, 0);
+    if (text_len < 0) dev.refuse(static_cast<int32_t>(text_len), (entry + ": a malformed auxiliary field").c_str());
+    std::vector<uint8_t> text(static_cast<size_t>(text_len) + 1);
+    if (npr_bam_aux_text(aux.data(), aux_off.data(), n, placeholder.data(), text_off.data(), cg.data(), text.data(), text_len) != text_len)
+        dev.refuse(NPR_ERR_STATE, (entry + ": the auxiliary text changed its length").c_str());
+
+    // the lines' lengths, their offsets by the device's scan, the (record, tile) items
+    std::vector<int64_t> line_len(static_cast<size_t>(n) + 1, 0);
+    std::vector<unsigned long long> items;
+    int64_t lines = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        int64_t cig = meas[i].cig_len;
+        if (cg[2 * i] >= 0) {
+            cig = cg[2 * i + 1] ? 0 : 1;
+            const uint8_t *ops = aux.data() + aux_off[i] + cg[2 * i];
+            for (int64_t q = 0; q < cg[2 * i + 1]; ++q) {
+                uint32_t v;
+                std::memcpy(&v, ops + 4 * q, 4);
+                cig += dec_digits(v >> 4) + 1;
+            }
+        }
+        const int64_t tl = text_off[i + 1] - text_off[i];
+        line_len[i] = meas[i].fixed_len - meas[i].cig_len + cig + (tl ? 1 + tl : 0) + 1;
+        lines += line_len[i];
+        const int64_t tiles = std::max<int64_t>(1, (static_cast<int64_t>(meas[i].l_seq) + BAM_TILE - 1) / BAM_TILE);
+        for (int64_t k = 0; k < tiles; ++k) items.push_back(static_cast<unsigned long long>(i) << 32 | static_cast<unsigned long long>(k));
+    }
+    if (items.size() >= (size_t(1) << 31)) dev.refuse(NPR_ERR_INVALID, (entry + ": 2^31 tiles and more in one call").c_str());
+    const int64_t total = l_text + lines;
+    if (!sam_out) {
+        if (n_records) *n_records = n;
+        return total;
+    }
+    if (cap < total) return NPR_ERR_CAPACITY;
+    dev.upload(d_line_off, line_len), dev.alloc(d_tile, scan_tiles(n));
+    dev.launched(launch_scan_tiled<int64_t, int64_t>(d_line_off.p, d_line_off.p, n, d_tile.p, dev.ctx->stream), "scan");
+    dev.upload(d_cg, cg), dev.upload(d_text, text), dev.upload(d_text_off, text_off), dev.upload(d_items, items);
+    dev.alloc(d_out, static_cast<size_t>(std::max<int64_t>(total, 1)));
+    if (l_text) dev.check(hipMemcpyAsync(d_out.p, d_stream + 8, static_cast<size_t>(l_text), hipMemcpyDeviceToDevice, dev.ctx->stream), "D2D");
+    a.cg = d_cg.p, a.aux_text = d_text.p, a.aux_text_off = d_text_off.p, a.line_off = d_line_off.p, a.items = d_items.p;
+    a.n_items = static_cast<int64_t>(items.size()), a.out = d_out.p + l_text;
+    dev.launched(launch_bam_emit(a, dev.ctx->stream), "k_bam_emit");
+    dev.fetch(&bad, d_bad.p, sizeof(bad));
+    dev.sync();
+    if (bad) dev.failed(NPR_ERR_STATE, "k_bam_emit: a line's columns do not add up to its measured length", hipSuccess);
+    dev.fetch(sam_out, d_out.p, static_cast<size_t>(total));
+    dev.sync();
+    if (n_records) *n_records = n;
+    return total;
+}
+
+// The records d_rec[0, n) of a stream that overlap [beg, end) of reference tid, order preserved, into `kept` (k_bam_overlap, the scan,
+// k_bam_gather of npr_bamregion.hip): how many.  Refuses malformed auxiliary fields under a placeholder cigar; `kept` is then not made.
+int64_t overlap_filter(const Call &dev, const uint8_t *d_stream, const int64_t *d_rec, int64_t n, int32_t tid, int64_t beg, int64_t end, DevBuf<int64_t> &kept) {
+    DevBuf<int64_t> d_keep, d_tile;
+    DevBuf<int32_t> d_bad;
+    dev.alloc(d_keep, static_cast<size_t>(n) + 1), dev.alloc(d_tile, static_cast<size_t>(scan_tiles(n)));
+    dev.alloc(d_bad, 1), dev.zero(d_bad);
+    BamOverlapArgs a{d_stream, n, d_rec, tid, beg, end, d_keep.p, d_bad.p, nullptr};
+    dev.launched(launch_bam_overlap_flags(a, dev.ctx->stream), "k_bam_overlap");
+    dev.launched(launch_scan_tiled<int64_t, int64_t>(d_keep.p, d_keep.p, n, d_tile.p, dev.ctx->stream), "scan");
+    int64_t total = 0;
+    int32_t bad = 0;
+    dev.fetch(&total, d_keep.p + n, sizeof(total));
+    dev.fetch(&bad, d_bad.p, sizeof(bad));
+    dev.sync();
+    if (bad) dev.refuse(NPR_ERR_INVALID, (std::string(dev.entry) + ": malformed auxiliary fields under a placeholder cigar").c_str());
+    DevBuf<int64_t> out;
+    dev.alloc(out, static_cast<size_t>(std::max<int64_t>(total, 1)));
+    a.kept = out.p;
+    dev.launched(launch_bam_overlap_gather(a, dev.ctx->stream), "k_bam_gather");
+    dev.sync();  // (the flags go out of scope)
+    kept.take(out);
+    return total;
 }
 
 }  // namespace
@@ -324,83 +457,9 @@ int64_t npr_bam_sam(npr_ctx *ctx, const uint8_t *file, int64_t len, uint8_t *sam
         const int64_t n = static_cast<int64_t>(rec_off.size());
         if (n >= (int64_t(1) << 31)) dev.refuse(NPR_ERR_INVALID, "npr_bam_sam: 2^31 records and more");
 
-        DevBuf<uint8_t> d_names, d_aux, d_text, d_out;
-        DevBuf<int64_t> d_name_off, d_rec_off, d_aux_off, d_cg, d_text_off, d_line_off, d_tile;
-        DevBuf<BamReadRec> d_meas;
-        DevBuf<int32_t> d_bad;
-        DevBuf<unsigned long long> d_items;
-        BamReadArgs a{};
-        a.stream = d_stream, a.len = stream_len, a.n_ref = static_cast<int32_t>(n_ref), a.n = n;
-        dev.upload(d_names, names), dev.upload(d_name_off, name_off), dev.upload(d_rec_off, rec_off);
-        dev.alloc(d_meas, n), dev.alloc(d_bad, 1), dev.zero(d_bad);
-        a.names = d_names.p, a.name_off = d_name_off.p, a.rec_off = d_rec_off.p, a.meas = d_meas.p, a.bad = d_bad.p;
-        dev.launched(launch_bam_read_measure(a, ctx->stream), "k_bam_measure");
-        std::vector<BamReadRec> meas(static_cast<size_t>(n));
-        int32_t bad = 0;
-        dev.fetch(meas.data(), d_meas.p, d_meas.bytes());
-        dev.fetch(&bad, d_bad.p, sizeof(bad));
-        dev.sync();
-        if (bad) dev.refuse(NPR_ERR_INVALID, "npr_bam_sam: a cigar operation above 8");
-
-        // the auxiliary bytes: packed, down once, to text on the host, up again
-        std::vector<int64_t> aux_off(static_cast<size_t>(n) + 1, 0), text_off(static_cast<size_t>(n) + 1, 0), cg(2 * static_cast<size_t>(n) + 2, -1);
-        std::vector<uint8_t> placeholder(static_cast<size_t>(n) + 1, 0);
-        for (int64_t i = 0; i < n; ++i) aux_off[i + 1] = aux_off[i] + meas[i].aux_len, placeholder[i] = meas[i].placeholder != 0;
-        std::vector<uint8_t> aux(static_cast<size_t>(aux_off[n]) + 1);
-        dev.upload(d_aux_off, aux_off), dev.alloc(d_aux, aux.size());
-        a.aux_pack_off = d_aux_off.p, a.aux_pack = d_aux.p;
-        dev.launched(launch_bam_gather_aux(a, ctx->stream), "k_bam_gather_aux");
-        dev.fetch(aux.data(), d_aux.p, static_cast<size_t>(aux_off[n]));
-        dev.sync();
-        const int64_t text_len = npr_bam_aux_text(aux.data(), aux_off.data(), n, placeholder.data(), text_off.data(), cg.data(), nullptr, 0);
-        if (text_len < 0) dev.refuse(static_cast<int32_t>(text_len), "npr_bam_sam: a malformed auxiliary field");
-        std::vector<uint8_t> text(static_cast<size_t>(text_len) + 1);
-        if (npr_bam_aux_text(aux.data(), aux_off.data(), n, placeholder.data(), text_off.data(), cg.data(), text.data(), text_len) != text_len)
-            dev.refuse(NPR_ERR_STATE, "npr_bam_sam: the auxiliary text changed its length");
-
-        // the lines' lengths, their offsets by the device's scan, the (record, tile) items
-        std::vector<int64_t> line_len(static_cast<size_t>(n) + 1, 0);
-        std::vector<unsigned long long> items;
-        int64_t lines = 0;
-        for (int64_t i = 0; i < n; ++i) {
-            int64_t cig = meas[i].cig_len;
-            if (cg[2 * i] >= 0) {
-                cig = cg[2 * i + 1] ? 0 : 1;
-                const uint8_t *ops = aux.data() + aux_off[i] + cg[2 * i];
-                for (int64_t q = 0; q < cg[2 * i + 1]; ++q) {
-                    uint32_t v;
-                    std::memcpy(&v, ops + 4 * q, 4);
-                    cig += dec_digits(v >> 4) + 1;
-                }
-            }
-            const int64_t tl = text_off[i + 1] - text_off[i];
-            line_len[i] = meas[i].fixed_len - meas[i].cig_len + cig + (tl ? 1 + tl : 0) + 1;
-            lines += line_len[i];
-            const int64_t tiles = std::max<int64_t>(1, (static_cast<int64_t>(meas[i].l_seq) + BAM_TILE - 1) / BAM_TILE);
-            for (int64_t k = 0; k < tiles; ++k) items.push_back(static_cast<unsigned long long>(i) << 32 | static_cast<unsigned long long>(k));
-        }
-        if (items.size() >= (size_t(1) << 31)) dev.refuse(NPR_ERR_INVALID, "npr_bam_sam: 2^31 tiles and more in one call");
-        const int64_t total = l_text + lines;
-        if (!sam_out) {
-            if (n_records) *n_records = n;
-            return total;
-        }
-        if (cap < total) return NPR_ERR_CAPACITY;
-        dev.upload(d_line_off, line_len), dev.alloc(d_tile, scan_tiles(n));
-        dev.launched(launch_scan_tiled<int64_t, int64_t>(d_line_off.p, d_line_off.p, n, d_tile.p, ctx->stream), "scan");
-        dev.upload(d_cg, cg), dev.upload(d_text, text), dev.upload(d_text_off, text_off), dev.upload(d_items, items);
-        dev.alloc(d_out, static_cast<size_t>(std::max<int64_t>(total, 1)));
-        if (l_text) dev.check(hipMemcpyAsync(d_out.p, d_stream + 8, static_cast<size_t>(l_text), hipMemcpyDeviceToDevice, ctx->stream), "D2D");
-        a.cg = d_cg.p, a.aux_text = d_text.p, a.aux_text_off = d_text_off.p, a.line_off = d_line_off.p, a.items = d_items.p;
-        a.n_items = static_cast<int64_t>(items.size()), a.out = d_out.p + l_text;
-        dev.launched(launch_bam_emit(a, ctx->stream), "k_bam_emit");
-        dev.fetch(&bad, d_bad.p, sizeof(bad));
-        dev.sync();
-        if (bad) dev.failed(NPR_ERR_STATE, "k_bam_emit: a line's columns do not add up to its measured length", hipSuccess);
-        dev.fetch(sam_out, d_out.p, static_cast<size_t>(total));
-        dev.sync();
-        if (n_records) *n_records = n;
-        return total;
+        DevBuf<int64_t> d_rec_off;
+        dev.upload(d_rec_off, rec_off);
+        return sam_lines(dev, d_stream, stream_len, l_text, n_ref, names, name_off, d_rec_off.p, n, sam_out, cap, n_records);
     });
 }
 
@@ -510,6 +569,140 @@ int32_t npr_pileup_add_bam(npr_pileup *pl, npr_bam_stream *bs, int32_t flag_mask
         for (int k = 1; k < 4; ++k) counts[k] = static_cast<int64_t>(got[k]);
         return counts[3] ? fail(ctx, NPR_ERR_INVALID, "npr_pileup_add_bam: a record's cigar does not fit its reference sequence or its read, or its auxiliary fields are malformed (the record was left out)")
                          : NPR_OK;
+    });
+}
+
+int32_t npr_bam_open_region(npr_ctx *ctx, const uint8_t *file, int64_t len, const uint8_t *bai, int64_t bai_len, int32_t tid, int64_t beg, int64_t end,
+                            npr_bam_stream **out) {
+    if (!ctx || !file || len < 0 || !bai || bai_len < 0 || !out) return NPR_ERR_INVALID;
+    *out = nullptr;
+    return guarded(ctx, "npr_bam_open_region", [&](const Call &dev) -> int32_t {
+        // the chunks of the query (host)
+        int64_t index_refs = -1;
+        const int64_t n_chunks = npr_bai_chunks(bai, bai_len, tid, beg, end, nullptr, nullptr, 0, &index_refs);
+        if (n_chunks < 0)
+            dev.refuse(static_cast<int32_t>(n_chunks), "npr_bam_open_region: a malformed index, a reference sequence it does not have, or a region that is not 0 <= beg < end <= 2^29");
+        std::vector<uint64_t> vbeg(static_cast<size_t>(n_chunks) + 1), vend(static_cast<size_t>(n_chunks) + 1);
+        if (npr_bai_chunks(bai, bai_len, tid, beg, end, vbeg.data(), vend.data(), n_chunks, &index_refs) != n_chunks)
+            dev.refuse(NPR_ERR_STATE, "npr_bam_open_region: the index changed its chunks");
+        std::vector<int64_t> block_off, stream_off;
+        if (scan_table(file, len, block_off, stream_off) < 0) dev.refuse(NPR_ERR_INVALID, "npr_bam_open_region: not a BGZF file that ends with the end-of-file block");
+        if (block_off.size() >= (size_t(1) << 31)) return NPR_ERR_INVALID;
+        const int64_t blocks = static_cast<int64_t>(block_off.size()) - 1;
+
+        // the header's blocks: block 0, and twice as many while the header runs on
+        int64_t head[4] = {1, 0, 0, 0};
+        std::vector<int64_t> pick, s_sub;
+        {
+            DevBuf<int64_t> d_head;
+            dev.alloc(d_head, 4);
+            for (int64_t hb = std::min<int64_t>(blocks, 1);; hb = std::min(blocks, 2 * hb)) {
+                InflateRun run;
+                pick.resize(static_cast<size_t>(hb));
+                for (int64_t b = 0; b < hb; ++b) pick[b] = b;
+                run.launch_picked(dev, file, block_off, stream_off, pick, s_sub);
+                run.finish(dev);
+                dev.launched(launch_bam_head(run.stream.p, run.stream_len, d_head.p, ctx->stream), "k_bam_head");
+                dev.fetch(head, d_head.p, sizeof(head));
+                dev.sync();
+                if (head[0] == 0) break;
+                if (head[0] == 1 || hb == blocks) dev.refuse(NPR_ERR_INVALID, "npr_bam_open_region: no BAM magic, or a header that runs past the stream");  // (1: k_bam_head saw no magic)
+            }
+        }
+        if (head[3] != index_refs) dev.refuse(NPR_ERR_INVALID, "npr_bam_open_region: the index is of a file with another number of reference sequences");
+        const int64_t head_blocks = std::lower_bound(stream_off.begin(), stream_off.begin() + blocks, head[1]) - stream_off.begin();  // those that begin before the header's end
+
+        // the chunks' blocks, and the chunks as spans [u0, u1) of the whole stream
+        std::vector<uint8_t> need(static_cast<size_t>(blocks) + 1, 0);
+        std::fill(need.begin(), need.begin() + head_blocks, uint8_t(1));
+        std::vector<int64_t> u0, u1, first;
+        for (int64_t c = 0; c < n_chunks; ++c) {
+            const int64_t fb = static_cast<int64_t>(vbeg[c] >> 16), fe = static_cast<int64_t>(vend[c] >> 16), lb = static_cast<int64_t>(vbeg[c] & 0xffffu), le = static_cast<int64_t>(vend[c] & 0xffffu);
+            const int64_t ib = std::lower_bound(block_off.begin(), block_off.begin() + blocks, fb) - block_off.begin();
+            const int64_t ie = std::lower_bound(block_off.begin(), block_off.end(), fe) - block_off.begin();
+            if (ib >= blocks || block_off[ib] != fb || ie > blocks || block_off[ie] != fe)
+                dev.refuse(NPR_ERR_INVALID, "npr_bam_open_region: a chunk of the index does not begin or end in a block of the file");
+            if (lb > stream_off[ib + 1] - stream_off[ib] || le > (ie < blocks ? stream_off[ie + 1] - stream_off[ie] : 0))
+                dev.refuse(NPR_ERR_INVALID, "npr_bam_open_region: a chunk of the index begins or ends past its block's ISIZE");
+            for (int64_t b = ib; b < ie; ++b) need[b] = 1;
+            if (le > 0) need[ie] = 1;
+            if (stream_off[ie] + le > stream_off[ib] + lb) u0.push_back(stream_off[ib] + lb), u1.push_back(stream_off[ie] + le), first.push_back(ib);
+        }
+        pick.clear();
+        std::vector<int64_t> where(static_cast<size_t>(blocks) + 1, -1);
+        for (int64_t b = 0; b < blocks; ++b)
+            if (need[b]) where[b] = static_cast<int64_t>(pick.size()), pick.push_back(b);
+
+        std::unique_ptr<npr_bam_stream> bs(new npr_bam_stream);
+        bs->ctx = ctx;
+        {
+            InflateRun run;  // (the blocks' bytes and tables go when the stream is made)
+            run.launch_picked(dev, file, block_off, stream_off, pick, s_sub);
+            run.finish(dev);
+            bs->stream_len = run.stream_len;
+            bs->stream.take(run.stream);
+        }
+        const uint8_t *const d_stream = bs->stream.p;
+        const BamHeader h = bam_header(dev, d_stream, bs->stream_len, bs->names, bs->name_off, &bs->ref_len);
+        bs->l_text = h.l_text;
+
+        // the chunks in the compact stream: a chunk's blocks are neighbours in the file, so they are neighbours there and one shift serves it
+        const int64_t walks = static_cast<int64_t>(u0.size());
+        DevBuf<int64_t> d_table;
+        int64_t n = 0;
+        if (walks) {
+            for (int64_t c = 0; c < walks; ++c) {
+                const int64_t shift = s_sub[where[first[c]]] - stream_off[first[c]];
+                u0[c] += shift, u1[c] += shift;
+            }
+            DevBuf<int64_t> d_beg, d_end, d_count, d_stop, d_tile;
+            DevBuf<int32_t> d_status;
+            dev.upload(d_beg, u0), dev.upload(d_end, u1);
+            dev.alloc(d_count, static_cast<size_t>(walks) + 1), dev.alloc(d_stop, static_cast<size_t>(walks)), dev.alloc(d_status, static_cast<size_t>(walks));
+            dev.alloc(d_tile, static_cast<size_t>(scan_tiles(walks)));
+            BamChunkArgs a{d_stream, bs->stream_len, static_cast<int32_t>(h.n_ref), walks, d_beg.p, d_end.p, d_count.p, d_stop.p, d_status.p, nullptr};
+            dev.launched(launch_bam_chunk_count(a, ctx->stream), "k_bam_chunk_walk");
+            dev.launched(launch_scan_tiled<int64_t, int64_t>(d_count.p, d_count.p, walks, d_tile.p, ctx->stream), "scan");
+            std::vector<int64_t> stop(static_cast<size_t>(walks));
+            std::vector<int32_t> status(static_cast<size_t>(walks));
+            dev.fetch(stop.data(), d_stop.p, d_stop.bytes()), dev.fetch(status.data(), d_status.p, d_status.bytes());
+            dev.fetch(&n, d_count.p + walks, sizeof(n));
+            dev.sync();
+            for (int64_t c = 0; c < walks; ++c)
+                if (status[c] != 0) {
+                    char text[200];
+                    std::snprintf(text, sizeof(text), "npr_bam_open_region: chunk %lld of the index: the record at byte %lld of the inflated blocks is refused (walk status %d)",
+                                  static_cast<long long>(c), static_cast<long long>(stop[c]), status[c]);
+                    dev.refuse(NPR_ERR_INVALID, text);
+                }
+            if (n >= (int64_t(1) << 31)) dev.refuse(NPR_ERR_INVALID, "npr_bam_open_region: 2^31 records and more");
+            dev.alloc(d_table, static_cast<size_t>(std::max<int64_t>(n, 1)));
+            a.table = d_table.p;
+            dev.launched(launch_bam_chunk_write(a, ctx->stream), "k_bam_chunk_walk");
+            dev.sync();  // (the chunks' tables go out of scope)
+        }
+        bs->n = overlap_filter(dev, d_stream, d_table.p, n, tid, beg, end, bs->rec_off);
+        *out = bs.release();
+        return NPR_OK;
+    });
+}
+
+int64_t npr_bam_stream_restrict(npr_bam_stream *bs, int32_t tid, int64_t beg, int64_t end) {
+    if (!bs) return NPR_ERR_INVALID;
+    npr_ctx *ctx = bs->ctx;
+    if (tid < 0 || tid >= static_cast<int64_t>(bs->ref_len.size()) || beg < 0 || beg >= end)
+        return fail(ctx, NPR_ERR_INVALID, "npr_bam_stream_restrict: a reference sequence the file does not have, or a region that is not 0 <= beg < end");
+    return guarded(ctx, "npr_bam_stream_restrict", [&](const Call &dev) -> int64_t {
+        bs->n = overlap_filter(dev, bs->stream.p, bs->rec_off.p, bs->n, tid, beg, end, bs->rec_off);
+        return bs->n;
+    });
+}
+
+int64_t npr_bam_stream_sam(npr_bam_stream *bs, uint8_t *sam_out, int64_t cap, int64_t *n_records) {
+    if (!bs || cap < 0) return NPR_ERR_INVALID;
+    return guarded(bs->ctx, "npr_bam_stream_sam", [&](const Call &dev) -> int64_t {
+        return sam_lines(dev, bs->stream.p, bs->stream_len, bs->l_text, static_cast<int64_t>(bs->ref_len.size()), bs->names, bs->name_off, bs->rec_off.p, bs->n, sam_out, cap,
+                         n_records);
     });
 }
 

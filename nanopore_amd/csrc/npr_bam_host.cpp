@@ -1,7 +1,8 @@
 // npr_bam_host.cpp -- the host side of the SAM -> sorted BAM + BAI conversion (include/nprealign.h, "coordinate-sorted BAM"): the columns
 // npr_sam_parse leaves aside (npr_sam_parse_tail), the optional fields as BAM auxiliary bytes (npr_bam_tags), the bytes before the first
 // record (npr_bam_header) and the index file from the tables the device made (npr_bai_write); and, for the way back, the block table of a
-// BGZF file (npr_bgzf_scan; "reading BGZF").  Host code, threaded, no HIP.
+// BGZF file (npr_bgzf_scan; "reading BGZF") and the chunks of a region from a BAI file (npr_bai_chunks; "region queries").  Host code,
+// threaded, no HIP.
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
@@ -330,6 +331,86 @@ int64_t npr_bgzf_scan(const uint8_t *file, int64_t len, int64_t *block_off, int6
         if (stream_off) stream_off[n] = stream;
     }
     return stream;
+}
+
+int64_t npr_bai_chunks(const uint8_t *bai, int64_t bai_len, int32_t tid, int64_t beg, int64_t end, uint64_t *chunk_beg, uint64_t *chunk_end, int64_t cap,
+                       int64_t *n_ref) {
+    if (!bai || bai_len < 8 || cap < 0 || !n_ref || (chunk_beg && !chunk_end)) return NPR_ERR_INVALID;
+    try {
+        int64_t at = 0;
+        // a little-endian value of `width` bytes at `at`, which moves on; false: it runs past the image
+        auto take = [&](int width, uint64_t &v) {
+            if (bai_len - at < width) return false;
+            v = 0;
+            for (int k = 0; k < width; ++k) v |= static_cast<uint64_t>(bai[at + k]) << (8 * k);
+            at += width;
+            return true;
+        };
+        auto count = [&](int64_t &v) {  // an int32 count: not negative
+            uint64_t u;
+            if (!take(4, u)) return false;
+            v = static_cast<int32_t>(static_cast<uint32_t>(u));
+            return v >= 0;
+        };
+        if (std::memcmp(bai, "BAI\1", 4) != 0) return NPR_ERR_INVALID;
+        at = 4;
+        int64_t refs = 0;
+        if (!count(refs)) return NPR_ERR_INVALID;
+        *n_ref = refs;
+        if (tid < 0 || tid >= refs || beg < 0 || beg >= end || end > (int64_t(1) << 29)) return NPR_ERR_INVALID;
+        // reg2bins(beg, end): bin 0 and, per level, the bins of beg >> shift .. (end - 1) >> shift
+        auto wanted = [&](uint64_t bin) {
+            if (bin == 0) return true;
+            static const int shift[5] = {26, 23, 20, 17, 14};
+            static const int64_t first[5] = {1, 9, 73, 585, 4681};
+            for (int lv = 0; lv < 5; ++lv) {
+                const int64_t b = static_cast<int64_t>(bin) - first[lv];
+                if (b >= (beg >> shift[lv]) && b <= ((end - 1) >> shift[lv]) && static_cast<int64_t>(bin) < (lv < 4 ? first[lv + 1] : 37449)) return true;
+            }
+            return false;
+        };
+        std::vector<std::pair<uint64_t, uint64_t>> found;
+        uint64_t low = 0;
+        for (int64_t k = 0; k < refs; ++k) {
+            int64_t n_bin = 0, n_intv = 0;
+            if (!count(n_bin)) return NPR_ERR_INVALID;
+            for (int64_t b = 0; b < n_bin; ++b) {
+                uint64_t bin;
+                int64_t n_chunk = 0;
+                if (!take(4, bin) || !count(n_chunk) || n_chunk > (bai_len - at) / 16) return NPR_ERR_INVALID;
+                const bool use = k == tid && bin != 37450 && wanted(bin);
+                for (int64_t c = 0; c < n_chunk; ++c) {
+                    uint64_t cb, ce;
+                    (void)take(8, cb), (void)take(8, ce);  // (n_chunk was checked against what is left)
+                    if (bin == 37450) continue;            // (the pseudo-bin's pairs are an interval and two counts)
+                    if (ce < cb) return NPR_ERR_INVALID;
+                    if (use) found.emplace_back(cb, ce);
+                }
+            }
+            if (!count(n_intv) || n_intv > (bai_len - at) / 8) return NPR_ERR_INVALID;
+            if (k == tid && n_intv) {
+                int64_t keep = at;
+                at += 8 * std::min<int64_t>(beg >> 14, n_intv - 1);
+                (void)take(8, low);
+                at = keep;
+            }
+            at += 8 * n_intv;
+        }
+        if (bai_len - at != 0 && bai_len - at != 8) return NPR_ERR_INVALID;  // n_no_coor, or nothing
+        found.erase(std::remove_if(found.begin(), found.end(), [&](const std::pair<uint64_t, uint64_t> &c) { return c.second <= low; }), found.end());
+        std::sort(found.begin(), found.end());
+        size_t n = 0;
+        for (size_t i = 0; i < found.size(); ++i) {
+            if (n && found[i].first <= found[n - 1].second) found[n - 1].second = std::max(found[n - 1].second, found[i].second);
+            else found[n++] = found[i];
+        }
+        if (!chunk_beg) return static_cast<int64_t>(n);
+        if (cap < static_cast<int64_t>(n)) return NPR_ERR_CAPACITY;
+        for (size_t i = 0; i < n; ++i) chunk_beg[i] = found[i].first, chunk_end[i] = found[i].second;
+        return static_cast<int64_t>(n);
+    } catch (const std::exception &) {
+        return NPR_ERR_NOMEM;
+    }
 }
 
 int64_t npr_bam_aux_text(const uint8_t *aux, const int64_t *aux_off, int64_t n, const uint8_t *placeholder, int64_t *text_off, int64_t *cg, uint8_t *out,

@@ -20,6 +20,7 @@
 // as TAG:TYPE:VALUE (npr_bam_aux_text); "\n".  Columns are separated by one tab.
 #include <hip/hip_runtime.h>
 
+#include "npr_bamrec.h"
 #include "npr_device.h"
 #include "npr_devtext.h"
 #include "npr_scan.h"
@@ -35,7 +36,6 @@ __device__ __forceinline__ uint32_t ld32(const uint8_t *p) {
 __device__ __forceinline__ int32_t ld32s(const uint8_t *p) { return static_cast<int32_t>(ld32(p)); }
 
 enum { HEAD_OK = 0, HEAD_MAGIC = 1, HEAD_TEXT = 2, HEAD_REFS = 3 };
-enum { WALK_OK = 0, WALK_SIZE = 1, WALK_PAST = 2, WALK_NAME = 3, WALK_PARTS = 4, WALK_REF = 5, WALK_POS = 6 };
 
 __global__ void __launch_bounds__(64) k_bam_head(const uint8_t *s, int64_t len, int64_t *out) {
     if (threadIdx.x != 0) return;
@@ -63,44 +63,11 @@ __global__ void __launch_bounds__(64) k_bam_walk(const uint8_t *s, int64_t len, 
     int64_t at = start, n = 0;
     int status = WALK_OK;
     while (at < len && n < cap) {
-        if (at + 4 > len) {
-            status = WALK_PAST;
-            break;
-        }
-        const int64_t size = ld32s(s + at);
-        if (size < 33) {
-            status = WALK_SIZE;
-            break;
-        }
-        if (at + 4 + size > len) {
-            status = WALK_PAST;
-            break;
-        }
-        const uint8_t *r = s + at;
-        const int32_t tid = ld32s(r + 4), ntid = ld32s(r + 24);
-        const int64_t l_name = r[12], n_cig = r[16] | static_cast<int64_t>(r[17]) << 8, l_seq = ld32s(r + 20);
-        if (l_name < 1) {
-            status = WALK_NAME;
-            break;
-        }
-        if (l_seq < 0 || 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq > size) {
-            status = WALK_PARTS;
-            break;
-        }
-        if (r[36 + l_name - 1] != 0) {  // (inside the record: the parts fit)
-            status = WALK_NAME;
-            break;
-        }
-        if (tid < -1 || tid >= n_ref || ntid < -1 || ntid >= n_ref) {
-            status = WALK_REF;
-            break;
-        }
-        if (ld32s(r + 8) > 0x7ffffffe || ld32s(r + 28) > 0x7ffffffe) {  // POS / PNEXT = pos + 1 would not fit SAM's 2^31 - 1 (nor an int32)
-            status = WALK_POS;
-            break;
-        }
+        int64_t next = at;
+        status = bam_walk_step(s, len, at, n_ref, &next);  // (npr_bamrec.h: the checks named above)
+        if (status != WALK_OK) break;
         table[n++] = at;
-        at += 4 + size;
+        at = next;
     }
     out[0] = n, out[1] = at, out[2] = status;
 }

@@ -12,6 +12,8 @@
 //   the sums       in 64 bits over all operations: reference bases (M D N = X), read bases (M I S = X); a code above 8: BR_REFUSED / BR_WHY_OP
 //   the verdict    pos < 0: BR_WHY_POS; pos + reference bases > l_ref: BR_WHY_REF; read bases != l_seq: BR_WHY_READ; else BR_ADD
 // Every read index is checked against the record's end, which lies inside `avail`, before it happens.
+// Also here, for the same reason (one body wherever a record is looked at): bam_walk_step, a step of the block_size chain with the checks of
+// npr_bam_sam (k_bam_walk, k_bam_chunk_walk), and bamrec_interval, the reference interval of a record for a region query (k_bam_overlap).
 #ifndef NPR_BAMREC_H
 #define NPR_BAMREC_H
 #include <stdint.h>
@@ -72,6 +74,57 @@ NPR_BR_FN bool bamrec_aux_walk(const uint8_t *r, int64_t at, int64_t end, int64_
             return false;
         }
     }
+    return true;
+}
+
+// One step of the block_size chain (k_bam_walk, npr_bamread.hip; k_bam_chunk_walk, npr_bamregion.hip): the record at s + at of a stream of
+// len bytes, at < len.  In this order: block_size inside the stream (WALK_PAST) and at least 33 (WALK_SIZE), the record inside the stream
+// (WALK_PAST), l_read_name at least 1 (WALK_NAME), l_seq at least 0 and the fixed parts inside block_size (WALK_PARTS), a NUL at the name's end
+// (WALK_NAME), refID and next_refID in -1 .. n_ref - 1 (WALK_REF), pos and next_pos at most 2^31 - 2 (WALK_POS: POS / PNEXT = pos + 1 would
+// not fit SAM's 2^31 - 1, nor an int32).  WALK_OK: *next = where the next record begins.  WALK_CHUNK is the chunk walk's: a chunk of an
+// index that does not end on a record boundary.
+enum { WALK_OK = 0, WALK_SIZE = 1, WALK_PAST = 2, WALK_NAME = 3, WALK_PARTS = 4, WALK_REF = 5, WALK_POS = 6, WALK_CHUNK = 7 };
+
+NPR_BR_FN int bam_walk_step(const uint8_t *s, int64_t len, int64_t at, int32_t n_ref, int64_t *next) {
+    if (at + 4 > len) return WALK_PAST;
+    const int64_t size = static_cast<int32_t>(br_ld32(s + at));
+    if (size < 33) return WALK_SIZE;
+    if (at + 4 + size > len) return WALK_PAST;
+    const uint8_t *r = s + at;
+    const int32_t tid = static_cast<int32_t>(br_ld32(r + 4)), ntid = static_cast<int32_t>(br_ld32(r + 24));
+    const int64_t l_name = r[12], n_cig = r[16] | static_cast<int64_t>(r[17]) << 8, l_seq = static_cast<int32_t>(br_ld32(r + 20));
+    if (l_name < 1) return WALK_NAME;
+    if (l_seq < 0 || 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq > size) return WALK_PARTS;
+    if (r[36 + l_name - 1] != 0) return WALK_NAME;  // (inside the record: the parts fit)
+    if (tid < -1 || tid >= n_ref || ntid < -1 || ntid >= n_ref) return WALK_REF;
+    if (static_cast<int32_t>(br_ld32(r + 8)) > 0x7ffffffe || static_cast<int32_t>(br_ld32(r + 28)) > 0x7ffffffe) return WALK_POS;
+    *next = at + 4 + size;
+    return WALK_OK;
+}
+
+// The interval of a record the walk has accepted, for a region query (include/nprealign.h, "region queries"): rb = max(pos, 0), re = max(pos +
+// the reference bases of its cigar, rb + 1), re = rb + 1 with FLAG 4 or without a cigar; under the placeholder <l_seq>S<n>N the operations of
+// the first CG:B:I field, when there is one.  r points at block_size; the record lies inside the stream and its parts inside block_size
+// (bam_walk_step).  false: malformed auxiliary fields under a placeholder cigar (the interval is then [rb, rb + 1)).
+NPR_BR_FN bool bamrec_interval(const uint8_t *r, int64_t *rb, int64_t *re) {
+    const int64_t size = static_cast<int32_t>(br_ld32(r)), pos = static_cast<int32_t>(br_ld32(r + 8));
+    const int64_t l_name = r[12], n_cig = r[16] | static_cast<int64_t>(r[17]) << 8, l_seq = static_cast<int32_t>(br_ld32(r + 20));
+    const int32_t flag = r[18] | r[19] << 8;
+    *rb = pos > 0 ? pos : 0, *re = *rb + 1;
+    if ((flag & 4) != 0 || n_cig == 0) return true;
+    const int64_t end = 4 + size, cigar_at = 36 + l_name, aux_at = cigar_at + 4 * n_cig + (l_seq + 1) / 2 + l_seq;
+    int64_t ops_at = cigar_at, n_ops = n_cig;
+    if (n_cig == 2 && br_ld32(r + cigar_at) == (static_cast<uint32_t>(l_seq) << 4 | 4u) && (br_ld32(r + cigar_at + 4) & 15u) == 3u) {
+        int64_t cg_at, cg_n;
+        if (!bamrec_aux_walk(r, aux_at, end, &cg_at, &cg_n)) return false;
+        if (cg_at >= 0) ops_at = cg_at, n_ops = cg_n;
+    }
+    int64_t ref_sum = 0;
+    for (int64_t q = 0; q < n_ops; ++q) {  // (the stored words lie inside the parts, a CG field's inside the record: bamrec_aux_walk)
+        const uint32_t w = br_ld32(r + ops_at + 4 * q), op = w & 15u;
+        if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) ref_sum += w >> 4;
+    }
+    if (pos + ref_sum > *re) *re = pos + ref_sum;
     return true;
 }
 

@@ -585,6 +585,33 @@ struct BamPileArgs {
 };
 int launch_bampile_check(const BamPileArgs &a, void *stream);
 int launch_bampile_add(const BamPileArgs &a, void *stream);
+// the records of the chunks of an index, and the records that overlap a region (npr_bamregion.hip; the rules: include/nprealign.h, "region queries")
+struct BamChunkArgs {
+    const uint8_t *stream;       // the compact stream: the payloads of the inflated blocks back to back
+    int64_t len;
+    int32_t n_ref;
+    int64_t n_chunks;
+    const int64_t *chunk_beg;    // [n_chunks] first byte of every chunk in the stream
+    const int64_t *chunk_end;    // [n_chunks] one past its last record
+    int64_t *count;              // [n_chunks + 1] the count pass: records of every chunk; the write pass: their exclusive scan
+    int64_t *stop;               // [n_chunks] the count pass: where the walk of the chunk ended
+    int32_t *status;             // [n_chunks] the count pass: WALK_OK or why it ended there (npr_bamrec.h)
+    int64_t *table;              // the write pass: [count[n_chunks]] the record offsets, chunk after chunk
+};
+int launch_bam_chunk_count(const BamChunkArgs &a, void *stream);
+int launch_bam_chunk_write(const BamChunkArgs &a, void *stream);
+struct BamOverlapArgs {
+    const uint8_t *stream;
+    int64_t n;                   // records
+    const int64_t *rec_off;      // [n]
+    int32_t tid;
+    int64_t beg, end;            // the region
+    int64_t *keep;               // [n + 1] the flag pass: 1 for a record that overlaps; the gather pass: their exclusive scan
+    int32_t *bad;                // set to 1 by malformed auxiliary fields under a placeholder cigar
+    int64_t *kept;               // the gather pass: [keep[n]] the offsets of the kept records, order preserved
+};
+int launch_bam_overlap_flags(const BamOverlapArgs &a, void *stream);
+int launch_bam_overlap_gather(const BamOverlapArgs &a, void *stream);
 struct BamRec {  // one SAM line as the host's parsers found it
     int64_t name, cigar_lo, cigar_hi, seq, qual;  // offsets in the text; qual < 0: "*"
     int64_t tag_off;

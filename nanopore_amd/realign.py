@@ -482,6 +482,34 @@ class Pileup(_Handle):
         return out
 
 
+def parse_region(references, lengths, region):
+    """A region of a file with these reference names and lengths -> (tid, beg, end), 0-based and half-open.  `region`: (name or tid, beg,
+    end), 0-based and half-open as it stands, or a samtools string: "name" is the whole sequence, "name:a-b" positions a to b, 1-based and
+    inclusive ("name:a": from a to the sequence's end; commas in the numbers are skipped).  A string that is wholly a reference name wins
+    over splitting it at its last colon."""
+    def tid_of(name):
+        if isinstance(name, (int, np.integer)):
+            if not 0 <= int(name) < len(references):
+                raise ValueError("region %r: the file has %d reference sequences" % (region, len(references)))
+            return int(name)
+        if name not in references:
+            raise KeyError("region %r: no reference sequence %r" % (region, name))
+        return list(references).index(name)
+    if not isinstance(region, str):
+        name, beg, end = region
+        return tid_of(name), int(beg), int(end)
+    if region in references or ":" not in region:
+        tid = tid_of(region)
+        return tid, 0, int(lengths[tid])
+    name, _, span = region.rpartition(":")
+    tid = tid_of(name)
+    a, dash, b = span.replace(",", "").partition("-")
+    try:
+        return tid, int(a) - 1, int(b) if dash else int(lengths[tid])
+    except ValueError:
+        raise ValueError("region %r: not name, name:a or name:a-b" % (region,))
+
+
 class BamStream(_Handle):
     """A BAM file image inflated and walked on the device (include/nprealign.h: npr_bam_open): the uncompressed stream and the table of its
     records' offsets stay there until close(); .references / .lengths are the header's names and l_ref values, .n_records the records,
@@ -490,9 +518,18 @@ class BamStream(_Handle):
     number of times, to any pileup of its context.  A context manager: closed on exit."""
     _destroy = "npr_bam_close"
 
-    def __init__(self, ctx, data):
+    def __init__(self, ctx, data, index=None, region=None):
+        """index, region: Context.bam_open."""
         data = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else _arr(data, np.uint8)
-        self._create(ctx, "npr_bam_open", "npr_bam_open", ptr(data), len(data))
+        if index is not None and region is None:
+            raise ValueError("an index serves a region: give one, or leave the index out")
+        if index is not None:
+            from . import bam
+            index = np.frombuffer(bytes(index), dtype=np.uint8) if isinstance(index, (bytes, bytearray)) else _arr(index, np.uint8)
+            tid, beg, end = parse_region(*bam.bam_references(data), region)
+            self._create(ctx, "npr_bam_open_region", "npr_bam_open_region", ptr(data), len(data), ptr(index), len(index), tid, beg, end)
+        else:
+            self._create(ctx, "npr_bam_open", "npr_bam_open", ptr(data), len(data))
         info = np.zeros(4, dtype=np.int64)
         check(self._L.npr_bam_stream_info(self._h, ptr(info)), "npr_bam_stream_info", ctx)
         self.n_records, n_ref, self.l_text, self.stream_bytes = (int(v) for v in info)
@@ -501,6 +538,28 @@ class BamStream(_Handle):
         check(self._L.npr_bam_stream_refs(self._h, ptr(self.lengths), ptr(name_off), ptr(names), len(names)), "npr_bam_stream_refs", ctx)
         text = names.tobytes()
         self.references = [text[name_off[k]:name_off[k + 1]].decode() for k in range(n_ref)]
+        if region is not None and index is None:
+            try:
+                self.restrict(region)
+            except Exception:
+                self.close()
+                raise
+
+    def restrict(self, region):
+        """Narrows the object to the records that overlap `region` (Context.bam_open says how one is written; include/nprealign.h:
+        npr_bam_stream_restrict, which states when a record overlaps), order preserved, on the device: no index, a file in any order.
+        Restricting twice gives the intersection.  -> the number of records left, .n_records too."""
+        tid, beg, end = parse_region(self.references, self.lengths, region)
+        self.n_records = int(check(self._L.npr_bam_stream_restrict(self._h, tid, beg, end), "npr_bam_stream_restrict", self.ctx))
+        return self.n_records
+
+    def sam_text(self):
+        """The header text and one line per record of the object, the lines Context.bam_to_sam writes (include/nprealign.h:
+        npr_bam_stream_sam): a uint8 array.  After a region query: `samtools view -h x.bam region`."""
+        out = np.empty(6 * self.stream_bytes + 64, dtype=np.uint8)   # a bound instead of a sizing call, as bam.bam_sam's
+        n = C.c_int64(0)
+        total = int(check(self._L.npr_bam_stream_sam(self._h, ptr(out), len(out), C.byref(n)), "npr_bam_stream_sam", self.ctx))
+        return out[:total]
 
     def __enter__(self):
         return self
@@ -779,10 +838,13 @@ class Context(object):
         from . import bam
         return bam.bam_to_sam(self, bamFile, samFile)
 
-    def bam_open(self, data):
+    def bam_open(self, data, index=None, region=None):
         """A BAM file image (bytes or a uint8 array) inflated and walked on the device, kept there (BamStream; include/nprealign.h:
-        npr_bam_open): what Pileup.add_bam takes."""
-        return BamStream(self, data)
+        npr_bam_open): what Pileup.add_bam takes.  region: only the records that overlap it -- (name or tid, beg, end), 0-based and
+        half-open, or a samtools string ("name", "name:a-b" 1-based and inclusive; parse_region).  With `index` (the bytes of the file's
+        .bai) only the blocks the index names for the region are inflated and walked (npr_bam_open_region: the file must be the sorted one
+        the index was made of); without it the file is opened whole and restricted (BamStream.restrict)."""
+        return BamStream(self, data, index=index, region=region)
 
     def align_indel_kmers(self, refs, reads, cigars, k=5, ref_index=None, start=None):
         """The k-mers that straddle a gap of arbitrary alignments (arguments as for align_stats), counted on the device
