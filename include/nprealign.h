@@ -984,7 +984,9 @@ int64_t npr_names_mark(const char *names_text, const int64_t *name_span /* [2 n]
  *   (NPR_ERR_INVALID).  Nothing is dropped: a record with RNAME "*" is kept with tid -1.  (That the cigar's read bases equal l_seq is not checked.)
  *   MEASURE.  n_ops = the cigar's operations ("*": 0), consumed = the sum of its M D N = X lengths, end = pos + consumed, or pos + 1 when
  *   consumed is 0 or FLAG has 4 set; bin = reg2bin(pos, end) of the specification (pos -1 is taken as 0; tid -1: 4680).  l_seq = the
- *   length of SEQ, 0 for "*".
+ *   length of SEQ, 0 for "*".  Nothing here looks at ref_len, and no record is refused for where it ends: a record that ends past 2^29
+ *   (POS is at most 2^29, so it never begins there) fits no level and gets reg2bin's last answer, bin 0; a record that begins at or past
+ *   its reference's end keeps the bin of its position.
  *   ORDER.  sorted != 0: npr_bam_sort_order on (tid, pos, FLAG); else the file's order.
  *   RECORD.  block_size, refID, pos, l_read_name, mapq, bin, n_cigar_op, flag, l_seq, next_refID, next_pos, tlen (36 bytes); QNAME and a
  *   NUL; the cigar, one uint32 per operation = length << 4 | op with MIDNSHP=X = 0..8; SEQ two bases a byte, first base in the high
@@ -1000,7 +1002,11 @@ int64_t npr_names_mark(const char *names_text, const int64_t *name_span /* [2 n]
  *     *n_runs says how many.
  *   linear: reference k has ((ref_len[k] - 1) >> 14) + 1 windows of 16384 positions (ref_len[k] >= 1), the references' windows back to
  *     back; linear[w] = the smallest v(u0) of the records of tid k with max(pos, 0) >> 14 <= w' <= (end - 1) >> 14 (w' beyond the last
- *     window counts as the last), or all ones when there is none.  (The backfill and the cut are npr_bai_write's.)
+ *     window counts as the last: a record past its reference's end, or past 2^29 on a reference of 2^29 bases, lies in the last window),
+ *     or all ones when there is none.  (The backfill and the cut are npr_bai_write's.)  A ref_len above 2^29 is accepted, because the
+ *     parser keeps POS at or below 2^29: every record begins where a BAI can address it.  Such a reference has windows from the 32 768th
+ *     on; they hold the records that reach past 2^29 (which lie in bin 0), npr_bai_write writes them like the others, and no query
+ *     consults them (npr_bai_chunks takes regions up to 2^29): positions past 2^29 are covered by no index.
  *   meta[k][4]: the smallest v(u0) and the largest v(u1) of the records of tid k (all ones and 0 without one), the number of those
  *     with FLAG & 4 clear, and with it set.  *n_no_coor = the records of tid -1.
  *

@@ -1,5 +1,6 @@
 """BGZF, BAM, BAI and .2bit as the specifications state them (SAMv1 sections 4, 4.1 and 5; UCSC's twoBit description), in plain Python
 and numpy: the readers and the restated index rules the BAM tests compare the product against.  Imports nothing from the product."""
+import bisect
 import gzip
 import struct
 import zlib
@@ -291,6 +292,38 @@ def bai_query(index, records, tid, beg, end):
     for i, r in enumerate(records):
         v0 = voffset(r["u0"])
         if r["tid"] == tid and any(c[0] <= v0 < c[1] for c in chunks):
+            rb = max(r["pos"], 0)
+            if rb < end and max(r["end"], rb + 1) > beg:
+                found.append(i)
+    return found
+
+
+def records_of_tid(records):
+    """-> {tid: [place of every record of that tid, ascending]}: what bai_query_tid scans instead of the whole file"""
+    out = {}
+    for i, r in enumerate(records):
+        out.setdefault(r["tid"], []).append(i)
+    return out
+
+
+def bai_query_tid(index, records, of_tid, tid, beg, end, vo=voffset):
+    """bai_query for a file of many records and references: only the records of `tid` are looked at (of_tid = records_of_tid(records)),
+    and a record's chunk is found by bisection -- the chunks of one reference are disjoint, every record lying in one run of one bin.
+    vo: stream offset -> virtual offset (the closed form of the stored writer by default)."""
+    bins, linear = index[tid]
+    low = 0
+    if linear:
+        w = beg >> 14
+        low = linear[w] if w < len(linear) else NONE
+    chunks = sorted(c for b in reg2bins(beg, end) if b in bins for c in bins[b] if c[1] > low)
+    assert all(a[1] <= b[0] for a, b in zip(chunks, chunks[1:])), "chunks of one reference overlap"
+    begs = [c[0] for c in chunks]
+    found = []
+    for i in of_tid.get(tid, []):
+        r = records[i]
+        v0 = vo(r["u0"])
+        k = bisect.bisect_right(begs, v0) - 1
+        if k >= 0 and v0 < chunks[k][1]:
             rb = max(r["pos"], 0)
             if rb < end and max(r["end"], rb + 1) > beg:
                 found.append(i)

@@ -82,3 +82,66 @@ def test_out_of_range_is_refused(ctx):
         bam.sort_order(ctx, [-2], [0], [0])
     with pytest.raises(_lib.NprError):
         bam.sort_order(ctx, [0], [-2], [0])
+
+
+# ---------------------------------------------------------------- wide tids, every pass count, the contract's ends
+def _bits_of(v):
+    return int(v).bit_length()
+
+
+def _passes(tid, pos):
+    """the passes npr_bam_sort_order takes, by the rule of csrc/npr_bam_api.cpp: the key tid' << 33 | (pos + 1) << 1 | reverse has
+    33 + bits_of(no_tid) bits with no_tid = the largest tid + 1 (the tid' of tid -1), or, when that is 0, the bits of the largest
+    (pos + 1) << 1 | 1; 8 bits a pass, one pass at least"""
+    no_tid = max([int(t) for t in tid] + [-1]) + 1
+    max_pos = max([int(p) + 1 for p in pos] + [0])
+    bits = 33 + _bits_of(no_tid) if no_tid else _bits_of(max_pos << 1 | 1)
+    return max(1, (bits + 7) // 8)
+
+
+@pytest.mark.parametrize("n", (257, 2049))
+def test_wide_tids(ctx, n):
+    rng = np.random.default_rng(n)
+    tids, poss = [-1, 0, 127, 128, 255, 256, 32767, 32768, (1 << 30) - 1], [-1, 0, (1 << 29) - 1, 1 << 29, (1 << 31) - 2]
+    keys = [(t, p, f) for t in tids for p in poss for f in (0, 16)]
+    pick = np.concatenate([np.arange(len(keys)), rng.integers(0, len(keys), n - len(keys))])    # every key once at least, the rest drawn: ties
+    rng.shuffle(pick)
+    tid = np.array([keys[k][0] for k in pick], dtype=np.int32)
+    pos = np.array([keys[k][1] for k in pick], dtype=np.int64)
+    flag = (np.array([keys[k][2] for k in pick]) + rng.integers(0, 2, n) * 4).astype(np.int32)
+    assert _passes(tid, pos) == 8 and len(tid) == n
+    _check(ctx, tid, pos, flag)
+
+
+# passes -> (the largest tid, the largest pos) with which the key just fills them; -1: every record without a reference
+PASS_CASES = {1: (-1, 126), 2: (-1, 32766), 3: (-1, (1 << 23) - 2), 4: (-1, (1 << 31) - 2), 5: (126, (1 << 31) - 2), 6: (32766, (1 << 29) - 1),
+              7: ((1 << 23) - 2, (1 << 31) - 2), 8: ((1 << 30) - 1, (1 << 31) - 2)}
+
+
+@pytest.mark.parametrize("passes", sorted(PASS_CASES))
+def test_every_pass_count(ctx, passes):
+    """n = 2049: two tiles.  The values drawn lie at both ends of the top digit of the last pass, around the digit edges below it, and
+    repeat: ties in every pass."""
+    max_tid, max_pos = PASS_CASES[passes]
+    n, rng = 2049, np.random.default_rng(passes)
+
+    def around(top):
+        vals = {0, 1, top, top - 1, top // 2, top // 255} | {(1 << b) - d for b in range(7, 31, 8) for d in (0, 1)}
+        return np.array(sorted(v for v in vals if 0 <= v <= top))
+    tid = np.full(n, -1, dtype=np.int32) if max_tid < 0 else rng.choice(np.append(around(max_tid), -1), n).astype(np.int32)
+    pos = rng.choice(np.append(around(max_pos), -1), n).astype(np.int64)
+    flag = (rng.integers(0, 2, n) * 16).astype(np.int32)
+    tid[5], pos[7] = max_tid, max_pos
+    assert _passes(tid, pos) == passes
+    largest = max((max_tid + 1) << 33, (max_pos + 1) << 1 | 1)      # (tid -1 is drawn in every case, so max_tid + 1 is a key's tid')
+    assert 0 < largest >> (8 * (passes - 1)) < 256, "the last pass has a digit that is not 0, and there is no digit above it"
+    _check(ctx, tid, pos, flag)
+
+
+def test_the_contracts_upper_ends_are_refused(ctx):
+    from nanopore_amd import _lib, bam
+    for tid, pos in (([1 << 30], [0]), ([0], [(1 << 31) - 1]), ([0, 1 << 30], [5, 5]), ([0, 0], [5, (1 << 31) - 1])):
+        with pytest.raises(_lib.NprError) as e:
+            bam.sort_order(ctx, tid, pos, [0] * len(tid))
+        assert e.value.code == _lib.ERR_INVALID
+    assert bam.sort_order(ctx, [(1 << 30) - 1, 0], [(1 << 31) - 2, (1 << 31) - 2], [0, 0]).tolist() == [1, 0]
