@@ -1193,6 +1193,60 @@ int32_t npr_bam_open_region(npr_ctx *ctx, const uint8_t *file, int64_t len, cons
 int64_t npr_bam_stream_restrict(npr_bam_stream *bs, int32_t tid, int64_t beg, int64_t end);
 int64_t npr_bam_stream_sam(npr_bam_stream *bs, uint8_t *sam_out, int64_t cap, int64_t *n_records);
 
+/* ---- BAM streams to BAM files: sorted, merged and region files without SAM text, the index of any sorted file (csrc/npr_bammerge.hip) ----
+ * What the reference's users get from `samtools sort`, `samtools merge` / `cat`, `samtools view -b x.bam chr:a-b` and `samtools index`
+ * (the reference joins its mappers' files with combineSamFiles): the records are measured, ordered and moved where they lie on the device;
+ * only the file image and the index arrays cross to the host.  Every record's bytes pass as they stand, whatever wrote them.
+ *
+ * npr_bam_streams_bam: the records of streams[0 .. n_streams) -- as their record tables stand now, that is after any npr_bam_open_region or
+ *   npr_bam_stream_restrict -- as ONE BAM file image.  n_streams >= 1; all streams belong to ctx and have the same n_ref, the same l_ref values
+ *   and the same names in the same order (reference ids are not remapped), else NPR_ERR_INVALID.  A stream may appear twice, and may have no
+ *   record; the total must be below 2^31; the streams are not changed.  header[0, header_len) is the complete BAM header of the output as
+ *   npr_bam_header writes it (magic, l_text, the text, n_ref, the names and lengths), ending exactly at header_len, with the streams' n_ref
+ *   and l_ref values, else NPR_ERR_INVALID.
+ *   MEASURE, per record from its bytes (csrc/npr_bamrec.h bamrec_measure, one body with the region queries' interval): the MEASURE rule of
+ *   npr_sam_bam restated on BAM fields.  The operations are the stored ones, or under the placeholder cigar <l_seq>S<n>N those of the first
+ *   CG:B:I field when there is one; consumed = the sum of their M D N = X lengths (64 bits); end = pos + consumed, or pos + 1 when consumed
+ *   is 0 or FLAG has 4 set; bin = reg2bin(max(pos, 0), max(end, max(pos, 0) + 1)), 4680 for refID -1: the bin of the interval [rb, re) of
+ *   "region queries".  A record with an operation code above 8 among those operations makes the call fail with NPR_ERR_INVALID, and so does
+ *   a record with refID >= 0 and FLAG 4 clear whose auxiliary fields under a placeholder cigar are malformed (npr_pileup_add_bam states
+ *   when); nothing is written then.  (With refID -1 or FLAG 4 such fields are not needed: the stored operations count.)
+ *   ORDER.  The records are concatenated in argument order, each stream's in its table's order.  sorted != 0: the stable order of
+ *   npr_bam_sort_order on (refID, pos, FLAG) -- ties keep the concatenation's order; a pos below -1 sorts as -1 --; else the concatenation
+ *   as it stands (`samtools cat`).
+ *   BYTES.  Every record is copied as it stands, block_size through its last auxiliary byte, with exactly one change: the two bytes of
+ *   `bin` are the measured bin.  The stream is header, then the records; compress == 0 frames it as npr_bgzf_frame does, else as
+ *   npr_bgzf_deflate does (npr_deflate_last tells).
+ *   INDEX (sorted != 0 and bam_out != NULL; else the index arguments are not touched and may be NULL): exactly the INDEX paragraph of
+ *   npr_sam_bam -- the same arrays with room for the total record count, the same order of runs, the same linear (the windows of the
+ *   streams' l_ref values, each at least 1) and meta.
+ *   Returns the file's length and sets *n_records (may be NULL) to the total; bam_out == NULL: the length with stored blocks, an upper
+ *   bound of the compressed one, and nothing else is made.  NPR_ERR_CAPACITY when cap is smaller than that bound, as npr_sam_bam_deflate.
+ *   Nothing is written to bam_out unless the call succeeds.
+ * npr_bam_merge_last: of the last image npr_bam_streams_bam wrote on this context, out[0 .. 3] = the records, the stream's length, the
+ *   bytes the gather kernel moved (the stream without its header; it reads and writes each once) and that kernel's time in nanoseconds
+ *   between two events.  Before the first: zeros.
+ *
+ * npr_bam_index: the index of file[0, len), a BAM file image of any writer, as it stands.  The file is opened as npr_bam_open opens it (the
+ *   same refusals).  The records must be in coordinate order already: (refID, pos) never decreases from a record to the next, refID -1
+ *   counting as last; FLAG is not looked at (writers break ties differently).  A file out of order is NPR_ERR_INVALID and no array is
+ *   touched.  MEASURE and its refusals as above.  The arrays are those of the INDEX paragraph of npr_sam_bam, with v(u) taken from THIS
+ *   file's blocks (npr_bgzf_scan's tables): the block that holds stream byte u is the last one whose first byte lies at or before u -- a
+ *   block of ISIZE 0 holds no byte and is passed over --, v(u) = block_off << 16 | (u - stream_off); u == the stream's length is one past
+ *   the payload of a short last block (block_off << 16 | ISIZE), and the end-of-file block's offset << 16 after a last block of 65 280
+ *   bytes.  *n_refs = the header's n_ref and ref_len[k] its l_ref values (each at least 1, else NPR_ERR_INVALID), what npr_bai_write needs;
+ *   meta has room for cap_refs x 4, linear for cap_linear windows, the run arrays for cap_runs each (there are at most as many runs as
+ *   records).  A count above its cap is NPR_ERR_CAPACITY: *n_refs and *n_runs are set and no array is written.  Returns the number of
+ *   records. */
+int64_t npr_bam_streams_bam(npr_ctx *ctx, npr_bam_stream *const *streams, int64_t n_streams, const uint8_t *header, int64_t header_len,
+                            int32_t sorted, int32_t compress, uint8_t *bam_out, int64_t cap, int64_t *n_records, int64_t *n_runs,
+                            int32_t *run_tid, uint32_t *run_bin, uint64_t *run_beg, uint64_t *run_end, uint64_t *linear, uint64_t *meta,
+                            int64_t *n_no_coor);
+int32_t npr_bam_merge_last(npr_ctx *ctx, int64_t *out /* [4] */);
+int64_t npr_bam_index(npr_ctx *ctx, const uint8_t *file, int64_t len, int64_t *n_refs, int64_t *ref_len, int64_t cap_refs, int64_t *n_runs,
+                      int32_t *run_tid, uint32_t *run_bin, uint64_t *run_beg, uint64_t *run_end, int64_t cap_runs, uint64_t *linear,
+                      int64_t cap_linear, uint64_t *meta, int64_t *n_no_coor);
+
 /* npr_batch_create_at for reads that are NOT contiguous in memory: read i = read[read_begin[i] .. read_end[i]) -- e.g. the
  * aligned part of each record's SEQ inside the mapped SAM text (columns 11, 12 of npr_sam_parse), so the sequences go from
  * the file's bytes to the pinned staging buffer in one copy.  Everything else as npr_batch_create_at. */

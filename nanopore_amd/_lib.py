@@ -243,6 +243,9 @@ SIGNATURES = {
     "npr_bam_open_region": (i32, [vp, vp, i64, vp, i64, i32, i64, i64, _out]),
     "npr_bam_stream_restrict": (i64, [vp, i32, i64, i64]),
     "npr_bam_stream_sam": (i64, [vp, vp, i64, C.POINTER(i64)]),
+    "npr_bam_streams_bam": (i64, [vp, vp, i64, vp, i64, i32, i32, vp, i64, C.POINTER(i64), C.POINTER(i64)] + [vp] * 6 + [C.POINTER(i64)]),
+    "npr_bam_merge_last": (i32, [vp, vp]),
+    "npr_bam_index": (i64, [vp, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), vp, vp, vp, vp, i64, vp, i64, vp, C.POINTER(i64)]),
     "npr_batch_create_spans": (i32, [vp, _params, i64, i64] + [vp] * 10 + [_out]),
 }
 EXPORTS = list(SIGNATURES)

@@ -56,14 +56,26 @@ def pileup_of_sam(ctx, samFile, referenceFastaFile):
     return names, lengths, pileup
 
 
-def region_index(bamFile, region, index=None):
+def region_index(bamFile, region, index=None, ctx=None, data=None):
     """The bytes of the BAI file that serves a region query on bamFile, or None: `index` (a path) when given, else bamFile + ".bai" when
-    there is a region and that file exists."""
+    there is a region and that file exists; else, with a context, the index of the file as it stands, made in memory on the device
+    (Context.bam_index; data: the file image when the caller has read it) -- a file the indexer refuses because its records are not in
+    coordinate order has no index: None, and the caller restricts the whole file, which works in any order.  Any other refusal raises."""
     if region is None:
         return None
     if index is None and os.path.exists(bamFile + ".bai"):
         index = bamFile + ".bai"
-    return None if index is None else np.fromfile(index, dtype=np.uint8)
+    if index is not None:
+        return np.fromfile(index, dtype=np.uint8)
+    if ctx is None:
+        return None
+    from .._lib import NprError
+    try:
+        return ctx.bam_index(np.fromfile(bamFile, dtype=np.uint8) if data is None else data)
+    except NprError as e:
+        if "coordinate order" in str(e):
+            return None
+        raise
 
 
 def pileup_of_bam(ctx, bamFile, referenceFastaFile=None, region=None, index=None):
@@ -73,11 +85,11 @@ def pileup_of_bam(ctx, bamFile, referenceFastaFile=None, region=None, index=None
     no parse on the host.  With `referenceFastaFile`, its sequences must be the ones the header names (their lengths are
     compared, as pileup_of_sam compares them); the caller closes the Pileup.
     region (Context.bam_open says how one is written; `samtools mpileup -r`): only the records that overlap it are added -- found
-    through the BAI file `index` (default: bamFile + ".bai" when it exists), so that only the blocks it names are inflated, else by
-    restricting the whole file on the device.  WHOLE records are added: the table still has all rows, and it is complete inside
+    through the BAI file `index` (default: bamFile + ".bai" when it exists, else an index made in memory: region_index), so that only
+    the blocks it names are inflated; a file that is not coordinate-sorted is restricted whole on the device.  WHOLE records are added: the table still has all rows, and it is complete inside
     [beg, end) of the region's sequence and partial outside it (a record that reaches out of the region adds its columns there too)."""
     data = np.fromfile(bamFile, dtype=np.uint8)
-    with ctx.bam_open(data, index=region_index(bamFile, region, index), region=region) as stream:
+    with ctx.bam_open(data, index=region_index(bamFile, region, index, ctx=ctx, data=data), region=region) as stream:
         names, lengths = list(stream.references), np.asarray(stream.lengths, dtype=np.int64)
         if referenceFastaFile is not None:
             fasta = ingest.FastaTable(referenceFastaFile)

@@ -272,6 +272,26 @@ def bamDepthFile(bamFile, depthFile, ctx=None, region=None):
     return len(text)
 
 
+def sortBamFile(bamFile, sortedBamFile, ctx=None, compress=False):
+    """pysam.sort and pysam.index on a BAM file: sortedBamFile coordinate-sorted and sortedBamFile + ".bai" beside it, made on the device
+    without SAM text (bam.bam_sort); every record's bytes pass as they stand."""
+    from .. import bam
+    return bam.bam_sort(ctx or _context(), bamFile, sortedBamFile, index=True, compress=compress)
+
+
+def mergeBamFiles(bamFiles, mergedBamFile, ctx=None, sort=True, compress=False):
+    """The records of bamFiles in one file (bam.bam_merge): coordinate-sorted and indexed (`samtools merge`), or with sort=False one file
+    after the other, the order of the reference's combineSamFiles.  The header is the first file's."""
+    from .. import bam
+    return bam.bam_merge(ctx or _context(), list(bamFiles), mergedBamFile, sort=sort, index=sort, compress=compress)
+
+
+def indexBamFile(bamFile, baiFile=None, ctx=None):
+    """pysam.index: the BAI file of a coordinate-sorted BAM file of any writer (bam.bam_index); default bamFile + ".bai"."""
+    from .. import bam
+    return bam.bam_index(ctx or _context(), bamFile, baiFile)
+
+
 def samToSortedBamFile(samFile, sortedBamFile, ctx=None, compress=False):
     """samToBamFile, pysam.sort and pysam.index in one: sortedBamFile coordinate-sorted and sortedBamFile + ".bai" beside it.
     compress: compressed BGZF blocks instead of stored ones."""

@@ -198,6 +198,11 @@ def bam_references(data):
     """The reference names and lengths of a BAM file image, read on the host from as many of its first blocks as the header fills (bgzf_scan
     for where they lie, zlib for their few kilobytes): (names, lengths).  What turns a region's name into the refID an indexed query needs
     before anything is on the device; the device checks the header itself."""
+    return bam_head(data)[1:]
+
+
+def bam_head(data):
+    """bam_references with the header text before them: (text as bytes, names, lengths)."""
     import struct
     import zlib
     data = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else _arr(data, np.uint8)
@@ -218,6 +223,7 @@ def bam_references(data):
         raise _lib.NprError(_lib.ERR_INVALID, "bam_references", "no BAM magic")
     at = 8 + struct.unpack_from("<i", head, 4)[0]
     have(at + 4)
+    text = head[8:at]
     n_ref = struct.unpack_from("<i", head, at)[0]
     at += 4
     names, lengths = [], np.zeros(max(n_ref, 0), dtype=np.int64)
@@ -228,7 +234,7 @@ def bam_references(data):
         names.append(head[at + 4:at + 4 + l_name - 1].decode())
         lengths[k] = struct.unpack_from("<i", head, at + 4 + l_name)[0]
         at += 8 + l_name
-    return names, lengths
+    return text, names, lengths
 
 
 def bai_chunks(bai, tid, beg, end):
@@ -265,6 +271,72 @@ def bam_region_to_sam(ctx, bamFile, region, samFile, index=None):
         if os.path.exists(tmp):
             os.remove(tmp)
     return {"records": int(n), "bytes": int(len(text)), "stream_bytes": last["stream_bytes"], "blocks": last["blocks"], "indexed": bai is not None}
+
+
+def _write_bam(out, bai, bamOut):
+    """the image to bamOut through a temporary name, and the index beside it"""
+    tmp = bamOut + ".tmp"
+    try:
+        with open(tmp, "wb") as fh:
+            out.tofile(fh)
+        os.replace(tmp, bamOut)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    if bai is not None:
+        with open(bamOut + ".bai", "wb") as fh:
+            bai.tofile(fh)
+
+
+def bam_merge(ctx, bamIns, bamOut, sort=True, index=True, compress=False):
+    """The records of the BAM files bamIns as one BAM file, made on the device without SAM text (Context.bam_merge; include/nprealign.h:
+    npr_bam_streams_bam): coordinate-sorted with bamOut + ".bai" beside it (`samtools merge`; ties keep the order of bamIns), or with
+    sort=False one file after the other (`samtools cat`).  The header is the first file's; all files must have its reference sequences.
+    Every record's bytes pass as they stand but for its bin.  A malformed file raises and leaves no file.
+    -> {"records", "references", "bytes", "stream_bytes", "files"}."""
+    streams = []
+    try:
+        for path in bamIns:
+            streams.append(ctx.bam_open(np.fromfile(path, dtype=np.uint8)))
+        out, bai = ctx.bam_merge(streams, sort=sort, index=index, compress=compress)
+        references = len(streams[0].references) if streams else 0
+    finally:
+        for s in streams:
+            s.close()
+    _write_bam(out, bai, bamOut)
+    last = ctx.bam_merge_last()
+    return {"records": last["records"], "references": references, "bytes": int(len(out)), "stream_bytes": last["stream_bytes"], "files": len(streams)}
+
+
+def bam_sort(ctx, bamIn, bamOut, index=True, compress=False):
+    """bamIn coordinate-sorted as bamOut, with bamOut + ".bai" beside it (index): `samtools sort` and `samtools index`, on the device without
+    SAM text (bam_merge of one file)."""
+    return bam_merge(ctx, [bamIn], bamOut, sort=True, index=index, compress=compress)
+
+
+def bam_region_to_bam(ctx, bamFile, region, bamOut, index=None, compress=False):
+    """The records of bamFile that overlap `region` as a sorted BAM file bamOut with its own index beside it: `samtools view -b bamFile
+    region`.  The file is opened as bam_region_to_sam opens it (index: the BAI file's path; by default bamFile + ".bai" when it exists,
+    else the file is opened whole and restricted).  -> {"records", "bytes", "stream_bytes", "blocks", "indexed"}."""
+    data = np.fromfile(bamFile, dtype=np.uint8)
+    if index is None and os.path.exists(bamFile + ".bai"):
+        index = bamFile + ".bai"
+    bai_in = None if index is None else np.fromfile(index, dtype=np.uint8)
+    with ctx.bam_open(data, index=bai_in, region=region) as stream:
+        last = inflate_last(ctx)
+        n = stream.n_records
+        out, bai = ctx.bam_merge([stream], sort=True, index=True, compress=compress)
+    _write_bam(out, bai, bamOut)
+    return {"records": int(n), "bytes": int(len(out)), "stream_bytes": last["stream_bytes"], "blocks": last["blocks"], "indexed": bai_in is not None}
+
+
+def bam_index(ctx, bamFile, baiFile=None):
+    """The BAI index of a coordinate-sorted BAM file of any writer, made on the device (Context.bam_index; npr_bam_index): `samtools index`.
+    baiFile: where it goes (default bamFile + ".bai").  A file out of order raises and leaves no file.  -> {"bytes"}."""
+    bai = ctx.bam_index(np.fromfile(bamFile, dtype=np.uint8))
+    with open(bamFile + ".bai" if baiFile is None else baiFile, "wb") as fh:
+        bai.tofile(fh)
+    return {"bytes": int(len(bai))}
 
 
 def convert(ctx, sam, fields, tail, tag_off, tags, header, ref_len, sort=True, index=True, compress=False):

@@ -11,6 +11,8 @@
 //   npr_seed_api.cpp  exact-match seeding (npr_seed.hip): the index, the matches, their SAM records
 //   npr_seedchain_api.cpp  the chains of seed rows given on the host as guides (npr_seedchain.hip), their SAM records
 //   npr_seedmap_api.cpp  reads -> rows, chains and guides in one device-resident object (npr_seedmap.hip between the two above)
+//   npr_bam_api.cpp  SAM text to sorted BAM and BAI, BGZF both ways, BAM to SAM text, BAM streams into a pileup, region queries (npr_bam.hip, npr_deflate.hip, npr_inflate.hip, npr_bamread.hip, npr_bampile.hip, npr_bamregion.hip)
+//   npr_bammerge_api.cpp  BAM streams to sorted, merged BAM files, the index of a file as it stands (npr_bammerge.hip)
 //   npr_cigtext_api.cpp  cigar text made on the device (npr_cigtext.hip): npr_cigar_text_packed, npr_batch_cigar_text, NPR_OPT_FINISH_TEXT
 #pragma once
 #include <hip/hip_runtime.h>
@@ -91,6 +93,7 @@ struct npr_ctx {
     int overlap = 0;               // NPR_OPT_OVERLAP: see include/nprealign.h (1: own MEA tables + half of every SIMD left free by the DP launches; 2: own MEA tables only)
     int64_t deflate_last[4] = {};  // npr_deflate_last: blocks emitted as (a), (b), (c) and the stream's length, of the last compressed stream
     int64_t inflate_last[4] = {0, -1, 0, 0};  // npr_inflate_last: blocks, the first refused one (-1: none), its status and the stream's length, of the last file inflated
+    int64_t merge_last[4] = {};    // npr_bam_merge_last: records, stream bytes, bytes k_merge_gather moved and its nanoseconds, of the last BAM image written from streams
     int64_t opt[NPR_OPT_COUNT] = {};  // npr_ctx_option: the test / bring-up switches (all 0 by default)
     static constexpr size_t kArenaPad = DeviceArena::kPad;
     float *arena_Fx = nullptr;  // E-step only: four more forward planes (per context)
@@ -489,6 +492,7 @@ struct npr_bam_stream {
     std::vector<int64_t> ref_len;   // [n_ref] l_ref
     std::vector<int64_t> name_off;  // [n_ref + 1]
     std::vector<uint8_t> names;     // back to back, without NULs
+    std::vector<int64_t> block_off, stream_off;  // npr_bam_open only: the file's block tables (npr_bgzf_scan), [blocks + 1] each, what npr_bam_index searches
 };
 
 // the index of one reference set (npr_seed_api.cpp): lives on the device from npr_seed_index_create to npr_seed_index_destroy
@@ -685,4 +689,49 @@ void cigars_from_host(const Call &dev, const uint32_t *ops, const std::vector<in
 // ... and the ones npr_batch_finish produced handed to `run`: where the device MEA stage left them (in the arena, whose lock is held until `run`
 // returns: it waits for its kernels), else uploaded from the batch's packed host form
 void with_batch_cigars(const Call &dev, npr_batch *b, const std::function<void(const DeviceCigars &)> &run);
+// npr_bam_api.cpp: what the SAM -> BAM writer there and the BAM -> BAM writer of npr_bammerge_api.cpp share
+void bgzf_constants(BgzfArgs &a);   // the CRC constants of the BGZF kernels
+int64_t bgzf_length(int64_t len);   // a stream's length as stored blocks with the end-of-file block
+int bits_of(unsigned long long v);
+// The stable order of n keys of at most `bits` bits that lie on the device: d_order[j] = index of the key at place j (the identity without a pass).
+// The keys are overwritten.
+void sort_order(const Call &dev, DevBuf<unsigned long long> &keys, int64_t n, int bits, DevBuf<uint32_t> &d_order);
+// The stream d_data[0, len) as compressed BGZF blocks: the buffers of one npr_deflate.hip run.  launch() queues the kernels; finish() fetches
+// the block table (block_off[0 .. blocks], host), waits, and returns the file's length; the image then lies in packed.
+struct DeflateRun {
+    DevBuf<uint8_t> slots, packed;
+    DevBuf<uint16_t> dist;
+    DevBuf<int64_t> block_len, tile;
+    DevBuf<uint32_t> chosen;
+    std::vector<int64_t> block_off;
+    int64_t blocks = 0, stream_len = 0;
+    void launch(const Call &dev, const uint8_t *d_data, int64_t len) {
+        blocks = (len + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD, stream_len = len;
+        dev.alloc(slots, static_cast<size_t>(blocks * DEFLATE_SLOT + 8)), dev.alloc(packed, static_cast<size_t>(bgzf_length(len)));
+        dev.alloc(dist, static_cast<size_t>(std::max<int64_t>(deflate_groups(blocks), 1) * BGZF_PAYLOAD));
+        dev.alloc(block_len, blocks + 1), dev.alloc(tile, scan_tiles(blocks));
+        dev.alloc(chosen, 4), dev.zero(chosen);
+        DeflateArgs d{};
+        d.z.data = d_data, d.z.len = len, d.z.out = slots.p;
+        bgzf_constants(d.z);
+        d.dist = dist.p, d.block_len = block_len.p, d.tile = tile.p, d.chosen = chosen.p, d.packed = packed.p;
+        dev.launched(launch_bgzf_deflate(d, dev.ctx->stream), "k_bgzf_deflate / scan / k_bgzf_pack");
+    }
+    int64_t finish(const Call &dev) {
+        uint32_t how[4] = {0, 0, 0, 0};
+        block_off.assign(static_cast<size_t>(blocks) + 1, 0);
+        dev.fetch(block_off.data(), block_len.p, block_len.bytes());
+        dev.fetch(how, chosen.p, sizeof(how));
+        dev.sync();
+        if (how[3]) dev.failed(NPR_ERR_STATE, "k_bgzf_deflate: the emitted bits of a block are not the measured ones", hipSuccess);
+        for (int k = 0; k < 3; ++k) dev.ctx->deflate_last[k] = how[k];
+        dev.ctx->deflate_last[3] = stream_len;
+        return block_off[blocks] + BGZF_EOF;
+    }
+};
+// The index tables of n records in sorted order from what a measure pass left in `a` (recs, meas, order, size_sorted scanned, header_len, n_refs and
+// the blocks' tables), by the INDEX paragraph of npr_sam_bam: k_bam_index_heads, the scan, k_bam_index_runs, the sort over (tid, bin),
+// k_bam_gather_runs.  lin_off: [n_refs + 1] first window of every reference.  The outputs are host arrays; waits for the stream.
+void bam_index_tables(const Call &dev, BamArgs &a, const std::vector<int64_t> &lin_off, int64_t *n_runs, int32_t *run_tid, uint32_t *run_bin, uint64_t *run_beg,
+                      uint64_t *run_end, uint64_t *linear, uint64_t *meta, int64_t *n_no_coor);
 }  // namespace npr_impl

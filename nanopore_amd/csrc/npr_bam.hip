@@ -22,6 +22,7 @@
 // block).  LDS: 1 KiB table + 256 x 8 bytes of tree = 3 KiB a workgroup.
 #include <hip/hip_runtime.h>
 
+#include "npr_bamrec.h"
 #include "npr_bgzf.h"
 #include "npr_device.h"
 
@@ -276,22 +277,25 @@ __global__ void __launch_bounds__(THREADS) k_bam_encode(BamArgs a) {
 }
 
 // ------------------------------------------------------------------ the index
-// the virtual offset of stream byte u: the file offset of its block from the table of a compressed file, in closed form without one
-__device__ __forceinline__ unsigned long long voffset(const int64_t *block_off, int64_t u) {
-    const int64_t at = block_off ? block_off[u / BGZF_PAYLOAD] : u / BGZF_PAYLOAD * (BGZF_PAYLOAD + BGZF_OVERHEAD);
+// the virtual offset of stream byte u: in blocks of BGZF_PAYLOAD bytes the file offset of its block from the table of a compressed file, in
+// closed form without one; in the blocks of any writer (a.stream_off) by a search in the scan's tables (bgzf_voffset_search, npr_bamrec.h)
+__device__ __forceinline__ unsigned long long voffset(const BamArgs &a, int64_t u) {
+    if (a.stream_off) return bgzf_voffset_search(a.stream_off, a.block_off, a.n_blocks, u);
+    const int64_t at = a.block_off ? a.block_off[u / BGZF_PAYLOAD] : u / BGZF_PAYLOAD * (BGZF_PAYLOAD + BGZF_OVERHEAD);
     return static_cast<unsigned long long>(at) << 16 | static_cast<unsigned long long>(u % BGZF_PAYLOAD);
 }
 
-// size_sorted holds the scan: place j's record is the stream bytes [header_len + size_sorted[j], header_len + size_sorted[j + 1])
+// size_sorted holds the scan: place j's record is the stream bytes [header_len + size_sorted[j], header_len + size_sorted[j + 1]); without
+// an order the records lie in their places (npr_bam_index)
 __global__ void __launch_bounds__(THREADS) k_bam_index_heads(BamArgs a) {
     const int64_t j = static_cast<int64_t>(blockIdx.x) * THREADS + threadIdx.x;
     if (j >= a.n) return;
-    const uint32_t i = a.order[j];
+    const int64_t i = a.order ? a.order[j] : j;
     const BamRec r = a.recs[i];
     const BamMeasure m = a.meas[i];
     bool head = j == 0;
     if (!head) {
-        const uint32_t ip = a.order[j - 1];
+        const int64_t ip = a.order ? a.order[j - 1] : j - 1;
         head = a.recs[ip].tid != r.tid || a.meas[ip].bin != m.bin;
     }
     a.head[j] = head;
@@ -299,7 +303,7 @@ __global__ void __launch_bounds__(THREADS) k_bam_index_heads(BamArgs a) {
         atomicAdd(a.no_coor, 1ull);
         return;
     }
-    const unsigned long long v0 = voffset(a.block_off, a.header_len + a.size_sorted[j]), v1 = voffset(a.block_off, a.header_len + a.size_sorted[j + 1]);
+    const unsigned long long v0 = voffset(a, a.header_len + a.size_sorted[j]), v1 = voffset(a, a.header_len + a.size_sorted[j + 1]);
     unsigned long long *const mt = a.meta + 4 * static_cast<int64_t>(r.tid);
     atomicMin(mt, v0), atomicMax(mt + 1, v1), atomicAdd(mt + ((r.flag & 4) ? 3 : 2), 1ull);
     const int64_t w_first = a.lin_off[r.tid], windows = a.lin_off[r.tid + 1] - w_first;
@@ -315,13 +319,13 @@ __global__ void __launch_bounds__(THREADS) k_bam_index_runs(BamArgs a) {
     const int32_t *const run = reinterpret_cast<const int32_t *>(a.head);
     const int32_t q = run[j];
     if (run[j + 1] == q) return;  // no head
-    const uint32_t i = a.order[j];
+    const int64_t i = a.order ? a.order[j] : j;
     const unsigned long long t = a.recs[i].tid < 0 ? static_cast<unsigned long long>(a.n_refs) : static_cast<unsigned long long>(a.recs[i].tid);
-    const unsigned long long v0 = voffset(a.block_off, a.header_len + a.size_sorted[j]);
+    const unsigned long long v0 = voffset(a, a.header_len + a.size_sorted[j]);
     a.run_key[q] = t << 16 | a.meas[i].bin;
     a.run_beg[q] = v0;
     if (q > 0) a.run_end[q - 1] = v0;
-    if (q == run[a.n] - 1) a.run_end[q] = voffset(a.block_off, a.header_len + a.size_sorted[a.n]);
+    if (q == run[a.n] - 1) a.run_end[q] = voffset(a, a.header_len + a.size_sorted[a.n]);
 }
 
 __global__ void __launch_bounds__(THREADS) k_bam_gather_runs(BamGatherArgs a) {

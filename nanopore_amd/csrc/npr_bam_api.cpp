@@ -6,11 +6,12 @@
 
 static_assert(BGZF_PAYLOAD == NPR_BGZF_PAYLOAD && BAM_TILE == NPR_BAM_TILE, "the kernels' constants are the header's");
 
-namespace {
+// ---- what npr_bammerge_api.cpp shares with the writer here (declared in npr_api_internal.h, with DeflateRun) ----
+namespace npr_impl {
 
 constexpr uint32_t kCrcPoly = 0xEDB88320u;
 
-uint32_t gf_mul(uint32_t a, uint32_t b) {  // a * b modulo the CRC polynomial, reflected (bit 31 is x^0)
+static uint32_t gf_mul(uint32_t a, uint32_t b) {  // a * b modulo the CRC polynomial, reflected (bit 31 is x^0)
     uint32_t p = 0;
     for (int k = 0; k < 32; ++k) {
         if (a & (0x80000000u >> k)) p ^= b;
@@ -31,7 +32,7 @@ void bgzf_constants(BgzfArgs &a) {
     }
 }
 
-inline int64_t bgzf_length(int64_t len) { return len + BGZF_OVERHEAD * ((len + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD) + BGZF_EOF; }
+int64_t bgzf_length(int64_t len) { return len + BGZF_OVERHEAD * ((len + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD) + BGZF_EOF; }
 
 int bits_of(unsigned long long v) {
     int b = 0;
@@ -62,39 +63,9 @@ void sort_order(const Call &dev, DevBuf<unsigned long long> &keys, int64_t n, in
     dev.sync();  // (the scratch of the passes goes out of scope)
 }
 
-// The stream d_data[0, len) as compressed BGZF blocks: the buffers of one npr_deflate.hip run.  launch() queues the kernels; finish() fetches
-// the block table (block_off[0 .. blocks], host), waits, and returns the file's length; the image then lies in packed.
-struct DeflateRun {
-    DevBuf<uint8_t> slots, packed;
-    DevBuf<uint16_t> dist;
-    DevBuf<int64_t> block_len, tile;
-    DevBuf<uint32_t> chosen;
-    std::vector<int64_t> block_off;
-    int64_t blocks = 0, stream_len = 0;
-    void launch(const Call &dev, const uint8_t *d_data, int64_t len) {
-        blocks = (len + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD, stream_len = len;
-        dev.alloc(slots, static_cast<size_t>(blocks * DEFLATE_SLOT + 8)), dev.alloc(packed, static_cast<size_t>(bgzf_length(len)));
-        dev.alloc(dist, static_cast<size_t>(std::max<int64_t>(deflate_groups(blocks), 1) * BGZF_PAYLOAD));
-        dev.alloc(block_len, blocks + 1), dev.alloc(tile, scan_tiles(blocks));
-        dev.alloc(chosen, 4), dev.zero(chosen);
-        DeflateArgs d{};
-        d.z.data = d_data, d.z.len = len, d.z.out = slots.p;
-        bgzf_constants(d.z);
-        d.dist = dist.p, d.block_len = block_len.p, d.tile = tile.p, d.chosen = chosen.p, d.packed = packed.p;
-        dev.launched(launch_bgzf_deflate(d, dev.ctx->stream), "k_bgzf_deflate / scan / k_bgzf_pack");
-    }
-    int64_t finish(const Call &dev) {
-        uint32_t how[4] = {0, 0, 0, 0};
-        block_off.assign(static_cast<size_t>(blocks) + 1, 0);
-        dev.fetch(block_off.data(), block_len.p, block_len.bytes());
-        dev.fetch(how, chosen.p, sizeof(how));
-        dev.sync();
-        if (how[3]) dev.failed(NPR_ERR_STATE, "k_bgzf_deflate: the emitted bits of a block are not the measured ones", hipSuccess);
-        for (int k = 0; k < 3; ++k) dev.ctx->deflate_last[k] = how[k];
-        dev.ctx->deflate_last[3] = stream_len;
-        return block_off[blocks] + BGZF_EOF;
-    }
-};
+}  // namespace npr_impl
+
+namespace {
 
 int64_t sam_bam(const char *entry, bool compress, npr_ctx *ctx, const uint8_t *text, int64_t text_len, const int64_t *span, const int64_t *fields, const int64_t *tail,
                 int64_t n, const int64_t *tag_off, const uint8_t *tags, const uint8_t *header, int64_t header_len, int64_t n_refs, const int64_t *ref_len,
@@ -517,6 +488,7 @@ int32_t npr_bam_open(npr_ctx *ctx, const uint8_t *file, int64_t len, npr_bam_str
         }
         if (n >= (int64_t(1) << 31)) dev.refuse(NPR_ERR_INVALID, "npr_bam_open: 2^31 records and more");
         bs->n = n;
+        bs->block_off.swap(block_off), bs->stream_off.swap(stream_off);
         *out = bs.release();
         return NPR_OK;
     });
@@ -785,9 +757,9 @@ int64_t sam_bam(const char *entry, bool compress, npr_ctx *ctx, const uint8_t *t
         DevBuf<uint8_t> d_text, d_tags, d_raw, d_out;
         DevBuf<BamRec> d_recs;
         DevBuf<BamMeasure> d_meas;
-        DevBuf<int32_t> d_bad, d_tid, d_flag, d_head_tile;
-        DevBuf<int64_t> d_pos, d_size, d_tile, d_rec_off, d_lin_off;
-        DevBuf<uint32_t> d_order, d_head;
+        DevBuf<int32_t> d_bad, d_tid, d_flag;
+        DevBuf<int64_t> d_pos, d_size, d_tile, d_rec_off;
+        DevBuf<uint32_t> d_order;
         DevBuf<unsigned long long> d_items, d_keys;
         BamArgs a{};
         a.n = n, a.n_items = n_items, a.header_len = header_len, a.n_refs = n_refs;
@@ -854,47 +826,59 @@ int64_t sam_bam(const char *entry, bool compress, npr_ctx *ctx, const uint8_t *t
         }
 
         // the index
-        *n_runs = 0, *n_no_coor = 0;
-        const int64_t windows = lin_off[n_refs];
-        DevBuf<unsigned long long> d_linear, d_meta, d_no_coor, d_run_key, d_run_beg, d_run_end, d_out_beg, d_out_end;
-        DevBuf<int32_t> d_run_tid;
-        DevBuf<uint32_t> d_run_bin, d_perm;
-        std::vector<unsigned long long> meta0(4 * static_cast<size_t>(n_refs), 0);
-        for (int64_t k = 0; k < n_refs; ++k) meta0[4 * k] = ~0ull;
-        dev.upload(d_meta, meta0);
-        dev.alloc(d_linear, windows);
-        if (windows) dev.check(hipMemsetAsync(d_linear.p, 0xff, d_linear.bytes(), ctx->stream), "memset");
-        dev.alloc(d_no_coor, 1), dev.zero(d_no_coor);
-        if (n) {
-            dev.upload(d_lin_off, lin_off);
-            dev.alloc(d_head, n + 1), dev.alloc(d_head_tile, scan_tiles(n));
-            dev.alloc(d_run_key, n), dev.alloc(d_run_beg, n), dev.alloc(d_run_end, n);
-            a.lin_off = d_lin_off.p, a.head = d_head.p, a.head_tile = d_head_tile.p;
-            a.run_key = d_run_key.p, a.run_beg = d_run_beg.p, a.run_end = d_run_end.p;
-            a.linear = d_linear.p, a.meta = d_meta.p, a.no_coor = d_no_coor.p;
-            dev.launched(launch_bam_index_heads(a, ctx->stream), "k_bam_index_heads / scan");
-            dev.launched(launch_bam_index_runs(a, ctx->stream), "k_bam_index_runs");
-            int32_t runs = 0;
-            dev.fetch(&runs, d_head.p + n, sizeof(int32_t));
-            dev.sync();
-            sort_order(dev, d_run_key, runs, 16 + bits_of(static_cast<unsigned long long>(n_refs)), d_perm);
-            // (sort_order overwrote the keys' buffer or its twin: the keys are made again for the gather)
-            dev.launched(launch_bam_index_runs(a, ctx->stream), "k_bam_index_runs");
-            dev.alloc(d_run_tid, runs), dev.alloc(d_run_bin, runs), dev.alloc(d_out_beg, runs), dev.alloc(d_out_end, runs);
-            BamGatherArgs g{runs, d_perm.p, d_run_key.p, d_run_beg.p, d_run_end.p, static_cast<int32_t>(n_refs), d_run_tid.p, d_run_bin.p, d_out_beg.p, d_out_end.p};
-            dev.launched(launch_bam_gather_runs(g, ctx->stream), "k_bam_gather_runs");
-            dev.fetch(run_tid, d_run_tid.p, d_run_tid.bytes()), dev.fetch(run_bin, d_run_bin.p, d_run_bin.bytes());
-            dev.fetch(run_beg, d_out_beg.p, d_out_beg.bytes()), dev.fetch(run_end, d_out_end.p, d_out_end.bytes());
-            *n_runs = runs;
-        }
-        unsigned long long no_coor = 0;
-        dev.fetch(linear, d_linear.p, d_linear.bytes());
-        dev.fetch(meta, d_meta.p, d_meta.bytes());
-        dev.fetch(&no_coor, d_no_coor.p, sizeof(no_coor));
-        dev.sync();
-        *n_no_coor = static_cast<int64_t>(no_coor);
+        bam_index_tables(dev, a, lin_off, n_runs, run_tid, run_bin, run_beg, run_end, linear, meta, n_no_coor);
         return written;
     });
 }
 
 }  // namespace
+
+namespace npr_impl {
+
+void bam_index_tables(const Call &dev, BamArgs &a, const std::vector<int64_t> &lin_off, int64_t *n_runs, int32_t *run_tid, uint32_t *run_bin, uint64_t *run_beg,
+                      uint64_t *run_end, uint64_t *linear, uint64_t *meta, int64_t *n_no_coor) {
+    npr_ctx *const ctx = dev.ctx;
+    const int64_t n = a.n, n_refs = a.n_refs;
+    *n_runs = 0, *n_no_coor = 0;
+    const int64_t windows = lin_off[n_refs];
+    DevBuf<unsigned long long> d_linear, d_meta, d_no_coor, d_run_key, d_run_beg, d_run_end, d_out_beg, d_out_end;
+    DevBuf<int32_t> d_run_tid, d_head_tile;
+    DevBuf<uint32_t> d_run_bin, d_perm, d_head;
+    DevBuf<int64_t> d_lin_off;
+    std::vector<unsigned long long> meta0(4 * static_cast<size_t>(n_refs), 0);
+    for (int64_t k = 0; k < n_refs; ++k) meta0[4 * k] = ~0ull;
+    dev.upload(d_meta, meta0);
+    dev.alloc(d_linear, windows);
+    if (windows) dev.check(hipMemsetAsync(d_linear.p, 0xff, d_linear.bytes(), ctx->stream), "memset");
+    dev.alloc(d_no_coor, 1), dev.zero(d_no_coor);
+    if (n) {
+        dev.upload(d_lin_off, lin_off);
+        dev.alloc(d_head, n + 1), dev.alloc(d_head_tile, scan_tiles(n));
+        dev.alloc(d_run_key, n), dev.alloc(d_run_beg, n), dev.alloc(d_run_end, n);
+        a.lin_off = d_lin_off.p, a.head = d_head.p, a.head_tile = d_head_tile.p;
+        a.run_key = d_run_key.p, a.run_beg = d_run_beg.p, a.run_end = d_run_end.p;
+        a.linear = d_linear.p, a.meta = d_meta.p, a.no_coor = d_no_coor.p;
+        dev.launched(launch_bam_index_heads(a, ctx->stream), "k_bam_index_heads / scan");
+        dev.launched(launch_bam_index_runs(a, ctx->stream), "k_bam_index_runs");
+        int32_t runs = 0;
+        dev.fetch(&runs, d_head.p + n, sizeof(int32_t));
+        dev.sync();
+        sort_order(dev, d_run_key, runs, 16 + bits_of(static_cast<unsigned long long>(n_refs)), d_perm);
+        // (sort_order overwrote the keys' buffer or its twin: the keys are made again for the gather)
+        dev.launched(launch_bam_index_runs(a, ctx->stream), "k_bam_index_runs");
+        dev.alloc(d_run_tid, runs), dev.alloc(d_run_bin, runs), dev.alloc(d_out_beg, runs), dev.alloc(d_out_end, runs);
+        BamGatherArgs g{runs, d_perm.p, d_run_key.p, d_run_beg.p, d_run_end.p, static_cast<int32_t>(n_refs), d_run_tid.p, d_run_bin.p, d_out_beg.p, d_out_end.p};
+        dev.launched(launch_bam_gather_runs(g, ctx->stream), "k_bam_gather_runs");
+        dev.fetch(run_tid, d_run_tid.p, d_run_tid.bytes()), dev.fetch(run_bin, d_run_bin.p, d_run_bin.bytes());
+        dev.fetch(run_beg, d_out_beg.p, d_out_beg.bytes()), dev.fetch(run_end, d_out_end.p, d_out_end.bytes());
+        *n_runs = runs;
+    }
+    unsigned long long no_coor = 0;
+    dev.fetch(linear, d_linear.p, d_linear.bytes());
+    dev.fetch(meta, d_meta.p, d_meta.bytes());
+    dev.fetch(&no_coor, d_no_coor.p, sizeof(no_coor));
+    dev.sync();
+    *n_no_coor = static_cast<int64_t>(no_coor);
+}
+
+}  // namespace npr_impl

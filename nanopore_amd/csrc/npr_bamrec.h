@@ -13,7 +13,9 @@
 //   the verdict    pos < 0: BR_WHY_POS; pos + reference bases > l_ref: BR_WHY_REF; read bases != l_seq: BR_WHY_READ; else BR_ADD
 // Every read index is checked against the record's end, which lies inside `avail`, before it happens.
 // Also here, for the same reason (one body wherever a record is looked at): bam_walk_step, a step of the block_size chain with the checks of
-// npr_bam_sam (k_bam_walk, k_bam_chunk_walk), and bamrec_interval, the reference interval of a record for a region query (k_bam_overlap).
+// npr_bam_sam (k_bam_walk, k_bam_chunk_walk), bamrec_interval, the reference interval of a record for a region query (k_bam_overlap), bamrec_measure,
+// what a writer of sorted BAM needs of a record (k_merge_measure, npr_bammerge.hip), and bgzf_voffset_search, a virtual offset in any writer's blocks
+// (the index kernels of npr_bam.hip; both under AddressSanitizer: tests/native/bammerge_check.cpp).
 #ifndef NPR_BAMREC_H
 #define NPR_BAMREC_H
 #include <stdint.h>
@@ -106,26 +108,92 @@ NPR_BR_FN int bam_walk_step(const uint8_t *s, int64_t len, int64_t at, int32_t n
 // the reference bases of its cigar, rb + 1), re = rb + 1 with FLAG 4 or without a cigar; under the placeholder <l_seq>S<n>N the operations of
 // the first CG:B:I field, when there is one.  r points at block_size; the record lies inside the stream and its parts inside block_size
 // (bam_walk_step).  false: malformed auxiliary fields under a placeholder cigar (the interval is then [rb, rb + 1)).
+NPR_BR_FN bool bamrec_ref_bases(const uint8_t *r, int64_t *ref_sum, bool *op_above_8);
 NPR_BR_FN bool bamrec_interval(const uint8_t *r, int64_t *rb, int64_t *re) {
-    const int64_t size = static_cast<int32_t>(br_ld32(r)), pos = static_cast<int32_t>(br_ld32(r + 8));
-    const int64_t l_name = r[12], n_cig = r[16] | static_cast<int64_t>(r[17]) << 8, l_seq = static_cast<int32_t>(br_ld32(r + 20));
+    const int64_t pos = static_cast<int32_t>(br_ld32(r + 8)), n_cig = r[16] | static_cast<int64_t>(r[17]) << 8;
     const int32_t flag = r[18] | r[19] << 8;
     *rb = pos > 0 ? pos : 0, *re = *rb + 1;
     if ((flag & 4) != 0 || n_cig == 0) return true;
-    const int64_t end = 4 + size, cigar_at = 36 + l_name, aux_at = cigar_at + 4 * n_cig + (l_seq + 1) / 2 + l_seq;
-    int64_t ops_at = cigar_at, n_ops = n_cig;
-    if (n_cig == 2 && br_ld32(r + cigar_at) == (static_cast<uint32_t>(l_seq) << 4 | 4u) && (br_ld32(r + cigar_at + 4) & 15u) == 3u) {
-        int64_t cg_at, cg_n;
-        if (!bamrec_aux_walk(r, aux_at, end, &cg_at, &cg_n)) return false;
-        if (cg_at >= 0) ops_at = cg_at, n_ops = cg_n;
-    }
     int64_t ref_sum = 0;
-    for (int64_t q = 0; q < n_ops; ++q) {  // (the stored words lie inside the parts, a CG field's inside the record: bamrec_aux_walk)
-        const uint32_t w = br_ld32(r + ops_at + 4 * q), op = w & 15u;
-        if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) ref_sum += w >> 4;
-    }
+    bool other = false;
+    if (!bamrec_ref_bases(r, &ref_sum, &other)) return false;
     if (pos + ref_sum > *re) *re = pos + ref_sum;
     return true;
+}
+
+// THE cigar walk of a record the block_size chain has accepted: the reference bases (M D N = X) of the operations that apply -- the stored
+// ones, or, under the placeholder <l_seq>S<n>N, those of the first CG:B:I field when there is one -- and whether one of them has a code
+// above 8.  false: malformed auxiliary fields under a placeholder cigar (the sums are then the stored operations').
+NPR_BR_FN bool bamrec_ref_bases(const uint8_t *r, int64_t *ref_sum, bool *op_above_8) {
+    const int64_t size = static_cast<int32_t>(br_ld32(r));
+    const int64_t l_name = r[12], n_cig = r[16] | static_cast<int64_t>(r[17]) << 8, l_seq = static_cast<int32_t>(br_ld32(r + 20));
+    const int64_t end = 4 + size, cigar_at = 36 + l_name, aux_at = cigar_at + 4 * n_cig + (l_seq + 1) / 2 + l_seq;
+    int64_t ops_at = cigar_at, n_ops = n_cig;
+    bool fine = true;
+    if (n_cig == 2 && br_ld32(r + cigar_at) == (static_cast<uint32_t>(l_seq) << 4 | 4u) && (br_ld32(r + cigar_at + 4) & 15u) == 3u) {
+        int64_t cg_at, cg_n;
+        fine = bamrec_aux_walk(r, aux_at, end, &cg_at, &cg_n);
+        if (fine && cg_at >= 0) ops_at = cg_at, n_ops = cg_n;
+    }
+    int64_t sum = 0;
+    bool other = false;
+    for (int64_t q = 0; q < n_ops; ++q) {  // (the stored words lie inside the parts, a CG field's inside the record: bamrec_aux_walk)
+        const uint32_t w = br_ld32(r + ops_at + 4 * q), op = w & 15u;
+        other |= op > 8u;
+        if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) sum += w >> 4;
+    }
+    *ref_sum = sum, *op_above_8 = other;
+    return fine;
+}
+
+// What a writer of sorted BAM needs of a record the walk has accepted (include/nprealign.h, "BAM streams to BAM files", MEASURE): the sort
+// key's parts, the record's bytes with block_size, end = pos + the reference bases of its cigar (pos + 1 without any, or with FLAG 4), its
+// bin = reg2bin(max(pos, 0), max(end, max(pos, 0) + 1)) (4680 for refID -1), and why it is refused: BR_WHY_OP for an operation above 8,
+// BR_WHY_AUX for malformed auxiliary fields under a placeholder cigar on a record with refID >= 0 and FLAG 4 clear, else BR_WHY_NONE.
+struct BamRecMeasure {
+    int32_t tid, pos, flag, refused;
+    int64_t size, end;
+    uint32_t bin;
+};
+NPR_BR_FN uint32_t bamrec_reg2bin(int64_t beg, int64_t end) {
+    --end;
+    if (beg >> 14 == end >> 14) return static_cast<uint32_t>(4681 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return static_cast<uint32_t>(585 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return static_cast<uint32_t>(73 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return static_cast<uint32_t>(9 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return static_cast<uint32_t>(1 + (beg >> 26));
+    return 0;
+}
+NPR_BR_FN void bamrec_measure(const uint8_t *r, BamRecMeasure &m) {
+    m.tid = static_cast<int32_t>(br_ld32(r + 4)), m.pos = static_cast<int32_t>(br_ld32(r + 8)), m.flag = r[18] | r[19] << 8;
+    m.size = 4 + static_cast<int64_t>(static_cast<int32_t>(br_ld32(r)));
+    int64_t ref_sum = 0;
+    bool other = false;
+    const bool fine = bamrec_ref_bases(r, &ref_sum, &other);
+    m.refused = other ? BR_WHY_OP : ((!fine && m.tid >= 0 && (m.flag & 4) == 0) ? BR_WHY_AUX : BR_WHY_NONE);
+    m.end = static_cast<int64_t>(m.pos) + ((ref_sum == 0 || (m.flag & 4) != 0) ? 1 : ref_sum);
+    const int64_t beg = m.pos > 0 ? m.pos : 0;
+    m.bin = m.tid < 0 ? 4680u : bamrec_reg2bin(beg, m.end < beg + 1 ? beg + 1 : m.end);
+}
+
+// The virtual offset of byte u of a stream of `blocks` BGZF blocks (npr_bgzf_scan's tables: block b holds the stream bytes [stream_off[b],
+// stream_off[b + 1]) and begins at file byte block_off[b]; entry `blocks` is the stream's length and the end-of-file block's offset): the
+// LAST block whose first byte is at or before u -- a block of ISIZE 0 holds no byte and is passed over -- and u's place in it.  u == the
+// stream's length lies one past the payload of a short last block, and at the end-of-file block after a full one (65 280 bytes).
+NPR_BR_FN unsigned long long bgzf_voffset_search(const int64_t *stream_off, const int64_t *block_off, int64_t blocks, int64_t u) {
+    if (blocks <= 0) return 0;
+    if (u >= stream_off[blocks]) {
+        const int64_t ln = stream_off[blocks] - stream_off[blocks - 1];
+        return ln < 65280 ? static_cast<unsigned long long>(block_off[blocks - 1]) << 16 | static_cast<unsigned long long>(ln)
+                          : static_cast<unsigned long long>(block_off[blocks]) << 16;
+    }
+    int64_t lo = 0, hi = blocks;  // the first block that begins after u lies in (lo, hi]
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (stream_off[mid] <= u) lo = mid;
+        else hi = mid;
+    }
+    return static_cast<unsigned long long>(block_off[lo]) << 16 | static_cast<unsigned long long>(u - stream_off[lo]);
 }
 
 NPR_BR_FN void bamrec_check(const uint8_t *r, int64_t avail, const int64_t *ref_len, int64_t n_ref, int32_t flag_mask, BamRecVerdict &v) {

@@ -647,6 +647,8 @@ struct BamArgs {
     unsigned long long *run_beg, *run_end;  // [runs] in file order
     unsigned long long *linear, *meta, *no_coor;
     const int64_t *block_off;    // file offset of every BGZF block of a compressed file, [blocks + 1]; null: stored blocks, the closed form
+    const int64_t *stream_off;   // null: blocks of BGZF_PAYLOAD bytes.  Else the blocks of any writer: stream offset of every block's payload, [n_blocks + 1],
+    int64_t n_blocks;            // beside block_off [n_blocks + 1] (npr_bgzf_scan's tables); a virtual offset is then searched for (npr_bamrec.h)
 };
 int launch_bam_measure(const BamArgs &a, void *stream);
 int launch_bam_offsets(const BamArgs &a, void *stream);   // sizes in output order, their scan, rec_off
@@ -663,6 +665,28 @@ struct BamGatherArgs {
     unsigned long long *out_beg, *out_end;
 };
 int launch_bam_gather_runs(const BamGatherArgs &a, void *stream);
+// BAM records to a BAM stream where they lie on the device (npr_bammerge.hip; the rules: include/nprealign.h, "BAM streams to BAM files")
+constexpr int MERGE_PIECE = 4096;  // bytes of the output stream one wavefront of k_merge_gather writes: 64 lanes x 16 bytes x 4 rounds
+struct MergeArgs {
+    int64_t n;                   // records, the streams' tables back to back
+    const uint8_t *const *src;   // [n] where record i's block_size lies (k_merge_sources: its stream + its table entry)
+    BamRec *recs;                // [n] k_merge_measure: tid, pos, flag (what the index kernels of npr_bam.hip read; the rest stays 0)
+    BamMeasure *meas;            // [n] k_merge_measure: size, end, bin
+    int32_t *tid, *flag;         // [n] the sort key's parts
+    int64_t *pos;
+    int32_t *bad;                // set to BR_WHY_OP / BR_WHY_AUX by a refused record, to -1 by a pair of records out of coordinate order (k_merge_ordered)
+    const uint32_t *order;       // [n] record at place j; null: the identity
+    int64_t *size_sorted;        // [n + 1] k_merge_place: the sizes in output order; then their exclusive scan in place
+    const uint8_t **place_src;   // [n] k_merge_place: src of the record at place j
+    uint32_t *place_bin;         // [n] ... and its measured bin
+    int64_t header_len, stream_len;  // the output stream: header_len bytes of header, then the records
+    uint8_t *raw;                // [stream_len], 16-byte aligned
+};
+int launch_merge_sources(const uint8_t *stream, const int64_t *rec_off, int64_t n, const uint8_t **src, void *hip_stream);
+int launch_merge_measure(const MergeArgs &a, void *stream);
+int launch_merge_ordered(const MergeArgs &a, void *stream);
+int launch_merge_place(const MergeArgs &a, void *stream);
+int launch_merge_gather(const MergeArgs &a, void *stream);
 constexpr float EXPECT_FIXED_ONE = 1099511627776.0f;  // 2^40
 struct ExpectArgs {
     const Task *tasks;

@@ -538,6 +538,7 @@ class BamStream(_Handle):
         check(self._L.npr_bam_stream_refs(self._h, ptr(self.lengths), ptr(name_off), ptr(names), len(names)), "npr_bam_stream_refs", ctx)
         text = names.tobytes()
         self.references = [text[name_off[k]:name_off[k + 1]].decode() for k in range(n_ref)]
+        self._image, self._header_text = data, None   # (the file image is kept until header_text() has read the header from it, or close())
         if region is not None and index is None:
             try:
                 self.restrict(region)
@@ -560,6 +561,18 @@ class BamStream(_Handle):
         n = C.c_int64(0)
         total = int(check(self._L.npr_bam_stream_sam(self._h, ptr(out), len(out), C.byref(n)), "npr_bam_stream_sam", self.ctx))
         return out[:total]
+
+    def header_text(self):
+        """The header text alone (the first l_text bytes of sam_text()), read on the host from the file image the first time it is
+        asked for (bam.bam_head)."""
+        if self._header_text is None:
+            from . import bam
+            self._header_text, self._image = bam.bam_head(self._image)[0], None
+        return self._header_text
+
+    def close(self):
+        self._image = None
+        _Handle.close(self)
 
     def __enter__(self):
         return self
@@ -845,6 +858,61 @@ class Context(object):
         .bai) only the blocks the index names for the region are inflated and walked (npr_bam_open_region: the file must be the sorted one
         the index was made of); without it the file is opened whole and restricted (BamStream.restrict)."""
         return BamStream(self, data, index=index, region=region)
+
+    def bam_merge(self, streams, sort=True, index=True, compress=False):
+        """The records of BamStreams of this context -- as they stand, after any region query or restrict -- as one BAM file image made on
+        the device without SAM text (include/nprealign.h: npr_bam_streams_bam; csrc/npr_bammerge.hip): coordinate-sorted (stable: ties keep
+        the order of `streams`, then the file's) or, with sort=False, one stream after the other (`samtools cat`).  Every record's bytes pass
+        as they stand but for its bin, which is measured.  The header is stream 0's text through bam.bam_header(text, sort=sort); all
+        streams must have stream 0's reference sequences.  compress: the BGZF blocks are compressed on the device.
+        -> (the image as a uint8 array, the BAI file's bytes (bam.bai_write) or None without sort and index)."""
+        from . import bam
+        streams = list(streams)
+        if not streams:
+            raise _lib.NprError(_lib.ERR_INVALID, "npr_bam_streams_bam", "no stream")
+        first = streams[0]
+        header, ref_len = bam.bam_header(first.header_text(), sort=sort)
+        n, n_refs = sum(s.n_records for s in streams), len(ref_len)
+        want_index = bool(sort and index)
+        handles = (C.c_void_p * len(streams))(*[s._h for s in streams])
+        run_tid, run_bin = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.uint32)
+        run_beg, run_end = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        linear, meta = np.zeros(max(int(bam.linear_windows(ref_len)[-1]), 1), dtype=np.uint64), np.zeros((max(n_refs, 1), 4), dtype=np.uint64)
+        n_runs, n_no_coor, n_records = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        # a bound instead of a sizing call (pages nobody touches cost nothing): the records are bytes of the streams
+        stream = len(header) + sum(s.stream_bytes for s in streams)
+        room = stream + 31 * (stream // _lib.BGZF_PAYLOAD + 1) + 28
+        out = np.empty(room, dtype=np.uint8)
+        total = int(check(self._L.npr_bam_streams_bam(self._h, handles, len(streams), ptr(header), len(header), int(bool(sort)), int(bool(compress)), ptr(out),
+                                                      room, C.byref(n_records), C.byref(n_runs), ptr(run_tid), ptr(run_bin),
+                                                      ptr(run_beg), ptr(run_end), ptr(linear), ptr(meta), C.byref(n_no_coor)), "npr_bam_streams_bam", self))
+        r = n_runs.value
+        bai = bam.bai_write(ref_len, run_tid[:r], run_bin[:r], run_beg[:r], run_end[:r], linear, meta[:n_refs], n_no_coor.value) if want_index else None
+        return out[:total], bai
+
+    def bam_merge_last(self):
+        """Of the last image bam_merge wrote (npr_bam_merge_last): {"records", "stream_bytes", "gather_bytes": what the gather kernel moved,
+        "gather_ns": its time between two events}."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self._L.npr_bam_merge_last(self._h, ptr(out)), "npr_bam_merge_last", self)
+        return dict(zip(("records", "stream_bytes", "gather_bytes", "gather_ns"), (int(v) for v in out)))
+
+    def bam_index(self, data):
+        """The BAI file's bytes for a coordinate-sorted BAM file image of any writer, made on the device from the file as it stands
+        (include/nprealign.h: npr_bam_index): `samtools index`.  A file whose records are out of order raises NprError (ERR_INVALID)."""
+        from . import bam
+        data = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else _arr(data, np.uint8)
+        _, lengths = bam.bam_references(data)
+        _, stream_off = bam.bgzf_scan(data)
+        n_refs, windows = len(lengths), int(bam.linear_windows(np.maximum(lengths, 1))[-1])
+        room = int(stream_off[-1]) // 36 + 1   # a record has 36 bytes and more; pages nobody touches cost nothing
+        ref_len, meta, linear = np.zeros(max(n_refs, 1), dtype=np.int64), np.zeros((max(n_refs, 1), 4), dtype=np.uint64), np.zeros(max(windows, 1), dtype=np.uint64)
+        run_tid, run_bin, run_beg, run_end = np.empty(room, dtype=np.int32), np.empty(room, dtype=np.uint32), np.empty(room, dtype=np.uint64), np.empty(room, dtype=np.uint64)
+        got_refs, n_runs, n_no_coor = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(self._L.npr_bam_index(self._h, ptr(data), len(data), C.byref(got_refs), ptr(ref_len), n_refs, C.byref(n_runs), ptr(run_tid), ptr(run_bin), ptr(run_beg),
+                                    ptr(run_end), room, ptr(linear), windows, ptr(meta), C.byref(n_no_coor)), "npr_bam_index", self)
+        r = n_runs.value
+        return bam.bai_write(ref_len[:n_refs], run_tid[:r], run_bin[:r], run_beg[:r], run_end[:r], linear, meta[:n_refs], n_no_coor.value)
 
     def align_indel_kmers(self, refs, reads, cigars, k=5, ref_index=None, start=None):
         """The k-mers that straddle a gap of arbitrary alignments (arguments as for align_stats), counted on the device
